@@ -3,6 +3,11 @@
 512x4096 sequences).
 
   python bench.py [--gpus N --steps K --warmup W]        (N > 1: launched by torch.distributed.run)
+  python bench.py ... --full                             (+ per-kernel roofline, probes, opt-in arithmetics, CPU baseline)
+  python bench.py ... --dump-outputs DIR                 (what the last timed step computed, as DIR/<name>.npy)
+
+A plain run sets up, warms up, times exactly K steps once and prints the result line; everything else the benchmark
+measures or checks runs only with --full.
 
 A "step" = one synthetic 512x4096 radargram per GPU = 8 non-overlapping items [T=32, N=63, 16x16]
 (patch 16x16, overlap (8,0), reference defaults) -> encoder fwd, normalise+affinity, dual softmax,
@@ -41,16 +46,24 @@ def parse():
     ap.add_argument("--convs", default="bf16x3", choices=["bf16x3", "mixed", "bf16", "torch"],
                     help="conv2-5 of the CNN: bf16x3 = HIP kernels, hi/lo bf16 operand pairs (fp32-grade, default); mixed = that forward, "
                          "backward on plain bf16 operands; bf16 = HIP kernels, plain bf16 operands; torch = PyTorch-ROCm (MIOpen) fp32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="skip the per-kernel roofline probes")
-    ap.add_argument("--repeats", type=int, default=0,
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run what else the benchmark measures and checks: the per-kernel roofline "
+                         "(HIP events around the kernels of the timed steps), the stand-alone probes, the opt-in conv arithmetics and "
+                         "the CPU baseline (radargram); the bf16x3-chain option (dense); labelprop alone, the CPU oracle and the "
+                         "label audit (labelprop); the item-wise comparison (shared).  --repeats then defaults to 0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (what a caller of the timed path receives) "
+                         "as DIR/<name>.npy, float32 (float64 kept), at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-probe", action="store_true", help="with --full: skip the per-kernel roofline probes")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region of --steps steps is run this many times; value / ms_per_step = the MEDIAN repeat "
-                         "(min / max on the line); every repeat is bracketed by barrier + synchronize like a single one.  0 (default): "
-                         "as many repeats as keep the GPU busy for about --gpu-seconds (at least 5), so that an outside sampler of GPU "
-                         "activity sees the run")
+                         "(min / max on the line); every repeat is bracketed by barrier + synchronize like a single one.  Default 1 "
+                         "(0 with --full).  0: as many repeats as keep the GPU busy for about --gpu-seconds (at least 5), so that an "
+                         "outside sampler of GPU activity sees the run")
     ap.add_argument("--gpu-seconds", type=float, default=10.0, help="target duration of all timed repeats together when --repeats is 0")
     ap.add_argument("--no-events", action="store_true",
-                    help="do not bracket the conv kernels of the timed steps with HIP events (A/B of their overhead)")
+                    help="with --full: do not bracket the conv kernels of the timed steps with HIP events (A/B of their overhead)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline's all-threads leg (a 1-thread step follows)")
     ap.add_argument("--workload", default="radargram", choices=["radargram", "chain", "labelprop", "shared", "dense", "train32"],
                     help="radargram: the BASELINE metric (default); chain: kernel-only stress shape K of SURVEY "
@@ -63,7 +76,36 @@ def parse():
     ap.add_argument("--nodes", type=int, default=4096, help="N of the chain workload")
     ap.add_argument("--walk", type=int, default=32, help="T (frames) of the chain workload")
     ap.add_argument("--modes", default="f32,bf16x3,bf16", help="chain arithmetics the chain workload runs (profiling one at a time)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 0 if args.full else 1
+    if not args.full:  # a plain run: the headline figure only
+        args.no_probe = args.no_cpu_baseline = args.no_events = True
+    return args
+
+
+DUMP_BYTES = 60 << 20  # array data: with the .npy headers under 64 MB, decimal or binary
+
+
+def dump_outputs(path, arrays):
+    """arrays {name: tensor} -> path/<name>.npy in float32 (float64 stays float64), DUMP_BYTES in all.  Where the arrays together
+    are larger, the budget is shared out smallest first, and an array larger than its share is written as a fixed sample of its
+    flattened elements (numpy default_rng(0), indices in ascending order): the same elements on every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    left = DUMP_BYTES
+    for i, name in enumerate(sorted(out, key=lambda k: out[k].nbytes)):
+        a = out[name]
+        share = left // (len(out) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def make_batch(rank, device):
@@ -355,7 +397,7 @@ def bench_chain(args):
     base = torch.randn(1, 1, N, C, generator=g)
     emb0 = (base + 0.5 * torch.randn(1, T, N, C, generator=g)).cuda()
     nprod = 9 * (T - 3) + 3
-    res, ref_loss = {}, None
+    res, ref_loss, outputs = {}, None, {}
     for name, chain, mult in (("f32", crw_hip.CHAIN_F32, 1), ("bf16x3", crw_hip.CHAIN_BF16X3, 3),
                               ("bf16", crw_hip.CHAIN_BF16, 1)):
         if name not in args.modes.split(","):
@@ -377,6 +419,7 @@ def bench_chain(args):
             loss = step()
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
+        outputs[f"loss_{name}"] = loss
         if ref_loss is None:
             ref_loss = loss.item()
         flops = 2.0 * Np ** 3 * nprod * mult
@@ -385,6 +428,8 @@ def bench_chain(args):
                      "frac": flops / dt / 1e12 / peak, "bound": "mfma", "loss": loss.item(),
                      "loss_minus_f32": loss.item() - ref_loss, "products": nprod, "n_padded": Np,
                      "note": "whole affinity+softmax+chain+loss fwd+bwd wall time; flops = chain MFMA flops executed"}
+    if args.dump_outputs and outputs:
+        dump_outputs(args.dump_outputs, outputs)
     print(json.dumps({"metric": "chain fwd+bwd at kernel-only stress shape K", "workload": f"[B,T,N,C]=[1,{T},{N},{C}]",
                       "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "data": "synthetic", "modes": res}),
           flush=True)
@@ -430,16 +475,22 @@ def bench_shared(args):
         return loss
 
     dt_s, loss_s = timed(step_shared)
-    dt_i, _ = timed(step_items)
+    if args.dump_outputs:
+        params = list(net.parameters())
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor(loss_s), "params": torch.cat([p.detach().reshape(-1) for p in params]),
+                                         "grads": torch.cat([p.grad.reshape(-1) for p in params])})
     S = len(ds)
-    print(json.dumps({"metric": "overlapping items/sec (CRW fwd+bwd+Adam, shared column encoding)", "value": S / dt_s,
-                      "unit": "items/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt_s * 1e3,
-                      "higher_is_better": True, "data": "synthetic", "dtype": "f32 (bf16x3 conv trunk)",
-                      "config": {"workload": f"{H_RG}x{W_RG} radargram, all {S} overlapping items [T={T_SEQ},N=63,16x16] per step; "
-                                             f"{cols.shape[1]} patch-columns encoded once", "loss": loss_s},
-                      "itemwise": {"ms_per_8_items": dt_i * 1e3, "items_per_s": 8 / dt_i,
-                                   "what": "same model, CRW.forward on 8 overlapping items (each item re-encoded)"},
-                      "speedup_vs_itemwise": (S / dt_s) / (8 / dt_i)}), flush=True)
+    out = {"metric": "overlapping items/sec (CRW fwd+bwd+Adam, shared column encoding)", "value": S / dt_s,
+           "unit": "items/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt_s * 1e3,
+           "higher_is_better": True, "data": "synthetic", "dtype": "f32 (bf16x3 conv trunk)",
+           "config": {"workload": f"{H_RG}x{W_RG} radargram, all {S} overlapping items [T={T_SEQ},N=63,16x16] per step; "
+                                  f"{cols.shape[1]} patch-columns encoded once", "loss": loss_s}}
+    if args.full:
+        dt_i, _ = timed(step_items)
+        out["itemwise"] = {"ms_per_8_items": dt_i * 1e3, "items_per_s": 8 / dt_i,
+                           "what": "same model, CRW.forward on 8 overlapping items (each item re-encoded)"}
+        out["speedup_vs_itemwise"] = (S / dt_s) / (8 / dt_i)
+    print(json.dumps(out), flush=True)
 
 
 def bench_labelprop(args):
@@ -530,50 +581,54 @@ def bench_labelprop(args):
                             "note": "achieved = algorithmic fp32-equivalent flops (2 * P * 26 * 26 * cin * cout * 9, P = 12288 patches) / mean "
                                     "HIP-event time of the layer's launches inside the timed passes"})
         kernels.sort(key=lambda k: -k["launch_us"])
-    # label propagation alone (features resident), the part the HIP kernels own
-    with torch.no_grad():
-        feats = crw_hip_normalize(enc, seq, T, N)  # (the Resnet in train mode: the same batch -> the same batch statistics and features)
-    lp = LabelPropVOS_CRW(cfg)
-    seed = crw_utils.seed_labels(seg, N)
-    for _ in range(2):
-        lp.propagate_all(feats, seed, M)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        p2, _ = lp.propagate_all(feats, seed, M)
-    torch.cuda.synchronize()
-    dlp = (time.perf_counter() - t1) / args.steps
-    # CPU oracle on the same features (bounded: one pass)
-    emb = feats.cpu().numpy()
-    torch.set_num_threads(min(32, len(os.sched_getaffinity(0))))
-    tc = time.time()
-    ref = orc.labelprop(emb, seed.cpu().numpy(), M, cfg["CXT_SIZE"], cfg["RADIUS"], cfg["TEMP"], cfg["KNN"])
-    dcpu = time.time() - tc
-    match = float((p2.cpu().numpy() == ref).mean())
-    # free-running maps may differ downstream of fp32 near-ties; the teacher-forced fp64 audit says whether any differing
-    # label is NOT a near-tie (oracle.labelprop_tie_audit; must be 0)
-    _, Ldev = lp.propagate_all(feats, seed, M)
-    audit = orc.labelprop_tie_audit(emb, Ldev.cpu().numpy(), p2.cpu().numpy(), cfg["CXT_SIZE"], cfg["RADIUS"], cfg["TEMP"],
-                                    cfg["KNN"], eps=1e-5)
-    print(json.dumps({"metric": "label-map columns/sec (user-seed label propagation)", "value": W / dt, "unit": "radargram columns/s",
-                      "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True,
-                      "data": "synthetic", "dtype": "f32",
-                      "config": {"workload": f"{H}x{W} radargram, 32x32 patches overlap (24,0) -> [T,N]=[{T},{N}], {cfg}, "
-                                             + ("Resnet encoder (the reference's create_model(id = 1), train-mode BatchNorm as in scripts/test/test_mc1.py; whole "
-                                                "forward on the hand-written kernels, crw_rn_train_fwd)" if args.model == 1 else
-                                                "CNN encoder (whole conv trunk on the tiled HIP kernels, FC head on PyTorch-ROCm)")
-                                             + " + normalise + xent + top-k + gather",
-                                 "encoder_weights": (f"trained: {args.train_steps} Adam steps on the cycle loss from the seeded initialisation (label map must "
-                                                     "equal the oracle's outright)" if args.train_steps else
-                                                     "random initialisation (seed 11): near-uniform affinities, so the free-running label map may differ "
-                                                     "from the oracle's downstream of floating-point near-ties -- `label_mismatches_not_ties` (teacher-forced "
-                                                     "fp64 audit) must be 0; --train-steps 300 gives the exact-match case")},
-                      "labelprop_only": {"ms": dlp * 1e3, "columns_per_s": W / dlp,
-                                         "what": "crw_labelprop_topk + crw_labelprop_gather, features resident"},
-                      "cpu_baseline": {"value": W / dcpu, "unit": "radargram columns/s", "kind": "port", "cores": torch.get_num_threads(),
-                                       "sample": f"oracle labelprop (numpy) on the same features, one pass, {dcpu:.2f} s"},
-                      "label_agreement_with_oracle": match, "label_mismatches_not_ties": audit["not_ties"],
-                      "tie_audit": audit, **({"roofline": kernels[0], "roofline_kernels": kernels} if kernels else {})}), flush=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"label_map": pred, "xent": xent})
+    out = {"metric": "label-map columns/sec (user-seed label propagation)", "value": W / dt, "unit": "radargram columns/s",
+           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True,
+           "data": "synthetic", "dtype": "f32",
+           "config": {"workload": f"{H}x{W} radargram, 32x32 patches overlap (24,0) -> [T,N]=[{T},{N}], {cfg}, "
+                                  + ("Resnet encoder (the reference's create_model(id = 1), train-mode BatchNorm as in scripts/test/test_mc1.py; whole "
+                                     "forward on the hand-written kernels, crw_rn_train_fwd)" if args.model == 1 else
+                                     "CNN encoder (whole conv trunk on the tiled HIP kernels, FC head on PyTorch-ROCm)")
+                                  + " + normalise + xent + top-k + gather",
+                      "encoder_weights": (f"trained: {args.train_steps} Adam steps on the cycle loss from the seeded initialisation (label map must "
+                                          "equal the oracle's outright)" if args.train_steps else
+                                          "random initialisation (seed 11): near-uniform affinities, so the free-running label map may differ "
+                                          "from the oracle's downstream of floating-point near-ties -- `label_mismatches_not_ties` (teacher-forced "
+                                          "fp64 audit, --full) must be 0; --train-steps 300 gives the exact-match case")}}
+    if args.full:
+        # label propagation alone (features resident), the part the HIP kernels own
+        with torch.no_grad():
+            feats = crw_hip_normalize(enc, seq, T, N)  # (the Resnet in train mode: the same batch -> the same batch statistics and features)
+        lp = LabelPropVOS_CRW(cfg)
+        seed = crw_utils.seed_labels(seg, N)
+        for _ in range(2):
+            lp.propagate_all(feats, seed, M)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            p2, _ = lp.propagate_all(feats, seed, M)
+        torch.cuda.synchronize()
+        dlp = (time.perf_counter() - t1) / args.steps
+        # CPU oracle on the same features (bounded: one pass)
+        emb = feats.cpu().numpy()
+        torch.set_num_threads(min(32, len(os.sched_getaffinity(0))))
+        tc = time.time()
+        ref = orc.labelprop(emb, seed.cpu().numpy(), M, cfg["CXT_SIZE"], cfg["RADIUS"], cfg["TEMP"], cfg["KNN"])
+        dcpu = time.time() - tc
+        match = float((p2.cpu().numpy() == ref).mean())
+        # free-running maps may differ downstream of fp32 near-ties; the teacher-forced fp64 audit says whether any differing
+        # label is NOT a near-tie (oracle.labelprop_tie_audit; must be 0)
+        _, Ldev = lp.propagate_all(feats, seed, M)
+        audit = orc.labelprop_tie_audit(emb, Ldev.cpu().numpy(), p2.cpu().numpy(), cfg["CXT_SIZE"], cfg["RADIUS"], cfg["TEMP"],
+                                        cfg["KNN"], eps=1e-5)
+        out.update({"labelprop_only": {"ms": dlp * 1e3, "columns_per_s": W / dlp,
+                                       "what": "crw_labelprop_topk + crw_labelprop_gather, features resident"},
+                    "cpu_baseline": {"value": W / dcpu, "unit": "radargram columns/s", "kind": "port", "cores": torch.get_num_threads(),
+                                     "sample": f"oracle labelprop (numpy) on the same features, one pass, {dcpu:.2f} s"},
+                    "label_agreement_with_oracle": match, "label_mismatches_not_ties": audit["not_ties"],
+                    "tie_audit": audit, **({"roofline": kernels[0], "roofline_kernels": kernels} if kernels else {})})
+    print(json.dumps(out), flush=True)
 
 
 def crw_hip_normalize(enc, seq, T, N):
@@ -644,21 +699,21 @@ def main():
 
     def step():
         bucket.zero()
-        loss, _ = net(seq)
+        loss, A = net(seq)
         loss.backward()
         bucket.all_reduce_mean()
         opt.step()
-        return loss
+        return loss, A
 
     for _ in range(args.warmup):
-        loss = step()
+        loss, A = step()
     torch.cuda.synchronize()
     if args.repeats <= 0:
         # size the run: one more untimed pass of `steps` steps tells how long a repeat takes; every rank must run the same number
         # of repeats, so the slowest rank's estimate decides
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            loss = step()
+            loss, A = step()
         torch.cuda.synchronize()
         est = torch.tensor([time.perf_counter() - t0], device=device, dtype=torch.float64)
         if world > 1:
@@ -682,7 +737,7 @@ def main():
                 crw_hip.rn_timing(False)
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            loss = step()
+            loss, A = step()
         torch.cuda.synchronize()
         if world > 1:
             torch.distributed.barrier()
@@ -695,6 +750,8 @@ def main():
         rep_elapsed.append(el)
     elapsed = sorted(rep_elapsed)[len(rep_elapsed) // 2]  # the median repeat is the one reported
     final_loss = loss.item()
+    if rank == 0 and args.dump_outputs:  # the last timed step: its loss and logits, the gradient it reduced, the weights it left
+        dump_outputs(args.dump_outputs, {"loss": loss, "affinity": A, "grads": bucket.flat, "params": opt.flat})
     if rank == 0 and ev_stash is None:
         ev_stash, crw_hip.KERNEL_EVENTS = crw_hip.KERNEL_EVENTS, None
         if args.model == 1 and not args.no_events and getattr(enc, "hip_convs", None):
@@ -708,7 +765,7 @@ def main():
             "unit": "radargram columns/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "repeats": {"n": len(rep_elapsed), "what": "value / ms_per_step are the median of n timed regions of `steps` steps each "
-                                                       "(n sized to keep the GPU busy for about --gpu-seconds unless --repeats is given)",
+                                                       "(n = --repeats; with --repeats 0, sized to keep the GPU busy for about --gpu-seconds)",
                         "gpu_busy_s": sum(rep_elapsed),
                         "ms_per_step_min": min(rep_elapsed) / args.steps * 1e3, "ms_per_step_max": max(rep_elapsed) / args.steps * 1e3,
                         "ms_per_step_all": [round(e / args.steps * 1e3, 4) for e in rep_elapsed]},
@@ -851,7 +908,7 @@ def main():
                             "launch_us": bms * 1e3, "shape": "n=4096 batch=3",
                             "note": "MFMA flops executed" + (" (3 bf16 MFMAs per product: useful flops = 1/3)"
                                                              if split == 3 else "")}
-        if world == 1 and args.workload == "dense":
+        if world == 1 and args.workload == "dense" and args.full:
             # the same step with the opt-in hi/lo-pair chain arithmetic (CRW.chain = CRW_CHAIN_BF16X3: fp32-grade products at a third
             # of the bf16 rate instead of fp32 MFMA): at N = 497 the chain GEMMs are 11 % of the default step
             net.chain = crw_hip.CHAIN_BF16X3
@@ -860,7 +917,7 @@ def main():
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             for _ in range(args.steps):
-                l3 = step()
+                l3, _ = step()
             torch.cuda.synchronize()
             ms3 = (time.perf_counter() - t1) / args.steps * 1e3
             out["option_chain_bf16x3"] = {"ms_per_step": ms3, "value": cols_per_step / (ms3 * 1e-3), "loss_after_these_steps": l3.item(),
@@ -880,7 +937,7 @@ def main():
                 torch.cuda.synchronize()
                 t1 = time.perf_counter()
                 for _ in range(args.steps):
-                    lo = step()
+                    lo, _ = step()
                 torch.cuda.synchronize()
                 mso = (time.perf_counter() - t1) / args.steps * 1e3
                 out["options"][f"convs_{mode}"] = {"ms_per_step": mso, "value": cols_per_step / (mso * 1e-3), "unit": "radargram columns/s",

@@ -443,3 +443,30 @@ def test_resnet_hip_coverage_rule():
     net.model.layer2[0].bn1.eps = net.bn0.eps
     net.bn0.momentum = None                      # cumulative moving average: not implemented
     assert not ok(X(4, 1, 16, 16))
+
+
+def test_bench_plain_run_and_output_dump(tmp_path, monkeypatch):
+    """bench.py: a plain run times --steps steps once and runs none of the --full legs; --dump-outputs writes float32 (float64
+    kept), stays within 64 MB, and samples an oversized array the same way every time."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    a = bench.parse()
+    assert (a.steps, a.repeats, a.full) == (7, 1, False) and a.no_probe and a.no_cpu_baseline and a.no_events
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.repeats == 0 and not (a.no_probe or a.no_cpu_baseline or a.no_events)
+    big = torch.arange(9 << 20, dtype=torch.float64)  # 72 MB: over the budget on its own
+    arrays = {"loss": torch.tensor(0.5), "big": big, "labels": torch.arange(6)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big.npy", "labels.npy", "loss.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == (np.float64 if f == "big.npy" else np.float32) and np.array_equal(x, y)
+    s = np.load(tmp_path / "a" / "big.npy")  # a sample of arange: the values are the sampled indices
+    assert s.ndim == 1 and 0 < s.size < big.numel() and np.all(np.diff(s) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "labels.npy"), np.arange(6, dtype=np.float32))
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 0.5

@@ -1,4 +1,4 @@
-"""Print the in-step per-kernel times (HIP events of the timed steps) of bench.py JSON lines given as files."""
+"""Print the in-step per-kernel times (HIP events of the timed steps) of bench.py --full JSON lines given as files."""
 import json, sys
 cols = []
 for f in sys.argv[1:]:

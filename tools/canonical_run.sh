@@ -8,7 +8,7 @@ mkdir -p $O
 timeout -k 10 900 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee $O/status.txt
 tail -2 $O/pytest_gpu.log
 : > $O/lines.jsonl
-run() { echo "# bench.py $*" >> $O/lines.jsonl; timeout -k 10 400 python bench.py "$@" 2> $O/err.log | grep '^{' >> $O/lines.jsonl; echo "bench $* rc=$?" | tee -a $O/status.txt; }
+run() { echo "# bench.py $*" >> $O/lines.jsonl; timeout -k 10 400 python bench.py --full "$@" 2> $O/err.log | grep '^{' >> $O/lines.jsonl; echo "bench $* rc=$?" | tee -a $O/status.txt; }
 run
 run --convs bf16
 run --convs torch --no-probe --no-cpu-baseline

@@ -10,7 +10,7 @@ for rep in 1 2; do
   done
 done
 for lib in tools/ubench/libcrw_base.so radar-sounder-crw_amd/libcrw_hip.so tools/ubench/libcrw_base.so radar-sounder-crw_amd/libcrw_hip.so; do
-  CRW_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --no-cpu-baseline --no-probe 2>/dev/null | grep '^{' | python -c "
+  CRW_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-probe 2>/dev/null | grep '^{' | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('$lib', round(d['ms_per_step'],3), round(d['value']))
 for k in d['roofline_kernels']: print('   %-62s %8.1f us' % (k['kernel'][:62], k['launch_us']))" | tee -a $O/ab.log

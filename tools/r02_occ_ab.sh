@@ -9,7 +9,7 @@ for rep in 1 2; do
   done
 done
 for lib in radar-sounder-crw_amd/libcrw_hip.so tools/ubench/libcrw_exp.so radar-sounder-crw_amd/libcrw_hip.so tools/ubench/libcrw_exp.so; do
-  CRW_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --no-cpu-baseline --no-probe 2>/dev/null | grep '^{' | python -c "
+  CRW_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-probe 2>/dev/null | grep '^{' | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('$lib', round(d['ms_per_step'],3), round(d['value']))
 for k in d['roofline_kernels']:

@@ -13,5 +13,5 @@ for m in bf16 bf16x3 f32; do
   grep '^{' $O/chain_$m.log | tail -1 >> $O/lines.jsonl
 done
 cd /root/repo
-timeout -k 10 300 python bench.py --workload dense --steps 3 --warmup 1 --no-cpu-baseline --no-probe 2>/dev/null | grep '^{' >> $O/lines.jsonl; echo "dense rc=$?" | tee -a $O/status.txt
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-probe 2>/dev/null | grep '^{' >> $O/lines.jsonl; echo "default rc=$?" | tee -a $O/status.txt
+timeout -k 10 300 python bench.py --full --workload dense --steps 3 --warmup 1 --no-cpu-baseline --no-probe 2>/dev/null | grep '^{' >> $O/lines.jsonl; echo "dense rc=$?" | tee -a $O/status.txt
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-probe 2>/dev/null | grep '^{' >> $O/lines.jsonl; echo "default rc=$?" | tee -a $O/status.txt

@@ -10,7 +10,7 @@ for v in 0 1; do
   done
 done
 for v in 0 1 0 1; do
-  CRW_WGRAD=$v timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-probe 2>/dev/null | grep '^{' > $O/bench_v$v.json
+  CRW_WGRAD=$v timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-probe 2>/dev/null | grep '^{' > $O/bench_v$v.json
   python - <<PY
 import json
 d=json.load(open("$O/bench_v$v.json"))

@@ -13,9 +13,9 @@ for l in sys.stdin:
 "; }
 for rep in 1 2; do
   for nt in 512 1024; do
-    CRW_FRONT_NT=$nt timeout -k 10 300 python bench.py --no-probe --no-cpu-baseline 2>/dev/null | line "default NT=$nt"
+    CRW_FRONT_NT=$nt timeout -k 10 300 python bench.py --full --no-probe --no-cpu-baseline 2>/dev/null | line "default NT=$nt"
   done
 done
 for nt in 512 1024; do
-  CRW_FRONT_NT=$nt timeout -k 10 300 python bench.py --workload labelprop --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | line "labelprop NT=$nt"
+  CRW_FRONT_NT=$nt timeout -k 10 300 python bench.py --full --workload labelprop --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | line "labelprop NT=$nt"
 done

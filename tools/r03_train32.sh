@@ -2,7 +2,7 @@
 # round 3: training at BASELINE config 5's geometry (32x32 patches, tiled "map" kernels): bench line + per-kernel table
 set -o pipefail
 O=gpurun_out/r03t32; mkdir -p $O
-timeout -k 10 500 python bench.py --workload train32 --steps 5 --warmup 2 --repeats 3 --cpu-seconds 10 > $O/bench.log 2>&1; grep '^{' $O/bench.log > $O/line.json; python -c "
+timeout -k 10 500 python bench.py --full --workload train32 --steps 5 --warmup 2 --repeats 3 --cpu-seconds 10 > $O/bench.log 2>&1; grep '^{' $O/bench.log > $O/line.json; python -c "
 import json; d=json.load(open('$O/line.json')); print('train32 ms/step %.2f cols/s %.0f' % (d['ms_per_step'], d['value']), d.get('cpu_baseline', {}).get('value'))
 for k in d.get('roofline_kernels', [])[:20]: print('   %-70s x%d %8.1f us  alg %.3f exec %.3f' % (k['kernel'][:70], k['launches_per_step'], k['launch_us'], k['frac'], k['mfma_executed_frac']))
 "

@@ -11,7 +11,7 @@ if [ "$2" != "notest" ]; then
   tail -2 $O/pytest_gpu.log
 fi
 : > $O/lines.jsonl
-run() { echo "# bench.py $*" >> $O/lines.jsonl; timeout -k 10 400 python bench.py "$@" 2> $O/err.log | grep '^{' >> $O/lines.jsonl; echo "bench $* rc=$?" | tee -a $O/status.txt; }
+run() { echo "# bench.py $*" >> $O/lines.jsonl; timeout -k 10 400 python bench.py --full "$@" 2> $O/err.log | grep '^{' >> $O/lines.jsonl; echo "bench $* rc=$?" | tee -a $O/status.txt; }
 run
 run --model 1
 run --model 1 --convs torch --no-probe --no-cpu-baseline --repeats 3

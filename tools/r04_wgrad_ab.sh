@@ -12,6 +12,6 @@ for l in sys.stdin:
         print('$1', 'ms/step %.3f (min %.3f)' % (d['ms_per_step'], d['repeats']['ms_per_step_min']), ks)
 "; }
 for rep in 1 2 3; do
-  CRW_HIP_LIB=$PWD/tools/ubench/libcrw_base.so timeout -k 10 300 python bench.py --no-probe --no-cpu-baseline --repeats 7 2>/dev/null | line "base (1 ahead)" | tee -a $O/wgrad_ab.log
-  timeout -k 10 300 python bench.py --no-probe --no-cpu-baseline --repeats 7 2>/dev/null | line "this (2 ahead)" | tee -a $O/wgrad_ab.log
+  CRW_HIP_LIB=$PWD/tools/ubench/libcrw_base.so timeout -k 10 300 python bench.py --full --no-probe --no-cpu-baseline --repeats 7 2>/dev/null | line "base (1 ahead)" | tee -a $O/wgrad_ab.log
+  timeout -k 10 300 python bench.py --full --no-probe --no-cpu-baseline --repeats 7 2>/dev/null | line "this (2 ahead)" | tee -a $O/wgrad_ab.log
 done

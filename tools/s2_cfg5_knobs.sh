@@ -1,6 +1,6 @@
 # cfg5 (Resnet at 32x32 patches, inference): the gathered-product variants behind their A/B switches, one box
 O=gpurun_out/s2knobs; mkdir -p $O
-run() { name=$1; shift; env "$@" timeout -k 10 200 python bench.py --workload labelprop --model 1 --steps 10 --warmup 3 2> $O/$name.err | grep '^{' > $O/$name.json; echo "$name done"; }
+run() { name=$1; shift; env "$@" timeout -k 10 200 python bench.py --full --workload labelprop --model 1 --steps 10 --warmup 3 2> $O/$name.err | grep '^{' > $O/$name.json; echo "$name done"; }
 run default A=1
 run spec0 CRW_RN_SPEC=0
 run spec0_bk64 CRW_RN_SPEC=0 CRW_RN_BK=64
