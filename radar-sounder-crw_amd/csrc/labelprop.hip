@@ -132,11 +132,15 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // scoring -- matrix cores, loads, LDS scatter -- runs beside the other's selection -- vector compares), the first half's k best
 // carried into the second selection as extra candidates: top-k(A u B) = top-k(top-k(A) u B), and the carried candidates have the
 // lower indices, so "highest value, then lowest candidate index" picks the same list.  pf = context frames per chunk.
+// NCH = 0: the same with a RUNTIME number of chunks, ceil(nf / pf), for candidate lists too long for two halves (radius 30 / 60 at
+// 80 - 100 context frames: 3 888 / 11 781 candidates per query).  The argument holds chunk after chunk -- the k best carried into
+// each selection come from earlier chunks, so they have the lowest indices -- and the chunk size is that of NCH = 2 (pf * max_bi
+// <= 64 * TK_NV / 2 in registers, 64 KiB of scores at 1 024 candidates: two workgroups per CU).
 template <int CSTEPS, int NCH>  // C / 16: float4 per lane and row
-__global__ __launch_bounds__(TK_NT, 2 * NCH) void labelprop_topk_mfma_kernel(const float *__restrict__ ehat, int T, int N, int cxt, int radius, float temp,
-                                                                  int knn, int first_frame, int maxcand, int pf, float *__restrict__ W,
-                                                                  int32_t *__restrict__ I) {
-  constexpr int C = 16 * CSTEPS, NV = TK_NV / NCH;
+__global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_kernel(const float *__restrict__ ehat, int T, int N, int cxt, int radius,
+                                                                           float temp, int knn, int first_frame, int maxcand, int pf,
+                                                                           float *__restrict__ W, int32_t *__restrict__ I) {
+  constexpr int C = 16 * CSTEPS, NV = TK_NV / (NCH == 1 ? 1 : 2);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float *val = smem;  // [TK_Q][maxcand] (maxcand: candidates of ONE chunk)
   __shared__ float sel_v[TK_Q][MAX_KNN];
@@ -166,7 +170,8 @@ __global__ __launch_bounds__(TK_NT, 2 * NCH) void labelprop_topk_mfma_kernel(con
     bw2[h] = hi - lo + 1;
   }
 
-  for (int ch = 0; ch < NCH; ++ch) {
+  const int nch = NCH ? NCH : (nf + pf - 1) / pf;
+  for (int ch = 0; ch < nch; ++ch) {
     const int p0 = ch * pf, np = min(nf - p0, NCH == 1 ? nf : pf);  // this chunk's context frames [p0, p0 + np)
     if (np <= 0) break;                                            // (block-uniform)
     const int nitems = np * nkt;
@@ -278,7 +283,7 @@ __global__ __launch_bounds__(TK_NT, 2 * NCH) void labelprop_topk_mfma_kernel(con
         }
       }
     }
-    if (NCH > 1) __syncthreads();  // the next chunk's scores overwrite val; lane 0's sel stores are in LDS for the carried reads
+    if (NCH != 1) __syncthreads();  // the next chunk's scores overwrite val; lane 0's sel stores are in LDS for the carried reads
   }
   {
     __builtin_amdgcn_wave_barrier();
@@ -335,6 +340,20 @@ int launch_topk_mfma(const float *ehat, int T, int N, int cxt, int radius, float
   if (!one && CSTEPS <= 8 /* 256 channels: past 128 registers */ && (size_t)TK_Q * maxcand * 4 > 76 * 1024 && (long)pf * max_bi <= 64L * (TK_NV / 2))
     return launch_topk_mfma_n<CSTEPS, 2>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, s);
   return launch_topk_mfma_n<CSTEPS, 1>(ehat, T, N, cxt, radius, temp, knn, first_frame, (int)maxcand, max_nf, W, I, s);
+}
+
+// candidate lists past the two forms above (more than 64 * TK_NV candidates, or a tile's scores over 150 KiB): chunks of pf frames,
+// pf * max_bi <= 1 024 (the registers of NCH = 2), as many as the lists need, the chunks made even (ceil(max_nf / nch) frames each).
+// 256 channels are not offered: their operands alone fill the 128 registers of two workgroups per CU (the vector kernel takes them).
+constexpr int TK_LONG_CAND = 64 * (TK_NV / 2);
+template <int CSTEPS>
+int launch_topk_mfma_long(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int max_nf, int max_bi,
+                          float *W, int32_t *I, hipStream_t s) {
+  static_assert(CSTEPS <= 8, "256 channels: past 128 registers");
+  int pf = TK_LONG_CAND / max_bi;
+  const int nch = (max_nf + pf - 1) / pf;
+  pf = (max_nf + nch - 1) / nch;
+  return launch_topk_mfma_n<CSTEPS, 0>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, s);
 }
 
 __device__ inline float ld_l2(const float *p) {
@@ -779,12 +798,17 @@ int crw_labelprop_topk_grid(const float *ehat, int T, int N, int C, int cxt_size
   // CRW_LABELPROP_TOPK_VALU=1 keeps the vector kernel (A/B)
   static const bool valu = getenv("CRW_LABELPROP_TOPK_VALU") && getenv("CRW_LABELPROP_TOPK_VALU")[0] == '1';
   const long maxcand = max_nf * max_bi;
-  if (grid_w == 1 && !valu && N >= TK_Q && (C == 64 || C == 128 || C == 256) && maxcand <= 64L * TK_NV &&
-      (size_t)TK_Q * maxcand * 4 <= 150 * 1024 && (((uintptr_t)ehat) & 15) == 0) {
-    hipStream_t s = (hipStream_t)stream;
+  const bool column = grid_w == 1 && !valu && N >= TK_Q && (((uintptr_t)ehat) & 15) == 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (column && (C == 64 || C == 128 || C == 256) && maxcand <= 64L * TK_NV && (size_t)TK_Q * maxcand * 4 <= 150 * 1024) {
     if (C == 64) return launch_topk_mfma<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, s);
     if (C == 128) return launch_topk_mfma<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, s);
     return launch_topk_mfma<16>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, s);
+  }
+  // longer lists (radius 30 / 60 at 80 - 100 context frames): any number of chunks; a single frame's band must fit one chunk
+  if (column && (C == 64 || C == 128) && max_bi <= TK_LONG_CAND) {
+    if (C == 64) return launch_topk_mfma_long<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, s);
+    return launch_topk_mfma_long<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, s);
   }
   if (lds > 60 * 1024) return CRW_EINVAL;
   hipLaunchKernelGGL(labelprop_topk_kernel, dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T,

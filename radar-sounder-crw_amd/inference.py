@@ -21,6 +21,9 @@ includes three things one might not expect:
   * any error inside a correction is swallowed (bare ``except``, test_all.py:121-122).
 Label maps are upsampled to pixels with nearest-neighbour interpolation like the reference
 (``transforms.Resize(NEAREST)``).  Everything heavy runs in ``propagate`` (encoder + HIP kernels).
+
+``segment_radargrams`` is the other family of the reference's drivers: scripts/test/test_mc1.py, test_mc3.py and
+test_sharad.py (``main(args)``), three whole radargrams held in memory, one item each; their defaults are in ``DRIVERS``.
 """
 import torch
 import torch.nn.functional as TF
@@ -115,3 +118,127 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
         rev = torch.flip(rev, (-1,)).reshape(rows, -1)
         final = merge_reverse(forward, rev, dataset_id)
     return dict(pred=final, forward=forward, xent=xents, change_idx=changes)
+
+
+# the reference's three per-dataset drivers (scripts/test/test_mc1.py:19-30, test_mc3.py:19-33, test_sharad.py:19-32): argparse
+# defaults, the class count and encoder they hard-code, and the change points test_mc3 / test_sharad set by hand before correcting
+DRIVERS = {
+    'mc1': dict(patch_size=(32, 32), seq_length=100, overlap=(24, 0), cxt_size=80, radius=30, temp=0.1, knn=20, nclasses=4,
+                model=1, use_last=True, correction=False, change_idx=None, outputs=('mc1_res.pt',)),
+    'mc3': dict(patch_size=(32, 32), seq_length=100, overlap=(30, 0), cxt_size=100, radius=60, temp=0.01, knn=20, nclasses=5,
+                model=1, use_last=True, correction=True, change_idx=(38, 36, 52),
+                outputs=('mc3_res.pt', 'mc3_resy.pt', 'mc3_xenty.pt')),
+    'sharad': dict(patch_size=(16, 16), seq_length=100, overlap=(8, 0), cxt_size=100, radius=10, temp=0.1, knn=20, nclasses=5,
+                   model=1, use_last=True, correction=True, change_idx=(80, 67, 98), outputs=('s_res.pt', 's_xent.pt')),
+}
+
+
+def _items(rg, patch_size, overlap):
+    """[rows, cols] radargram -> [T, N, H, W]: every patch of the radargram, one item (test_mc1.py:68-72)."""
+    (H, W), (OH, OW) = patch_size, overlap
+    return rg.unfold(0, H, H - OH).unfold(1, W, W - OW).permute(1, 0, 2, 3)
+
+
+@torch.no_grad()
+def segment_radargrams(driver, radargrams, refs, encoder, refs_reversed=None, patch_size=None, seq_length=None, overlap=None,
+                       cxt_size=None, radius=None, temp=None, knn=None, use_last=None, correction=None, change_idx=None, lp=None):
+    """``main(args)`` of the reference's scripts/test/test_{mc1,mc3,sharad}.py (``driver``) without the plots.
+
+    radargrams, refs: three [rows, cols] radargrams and their reference segmentations, as the script holds them after loading
+    (``scripts/segment_drivers.py`` reads its files, casts and edits); refs_reversed: mc1's separate references of the reversed
+    radargrams.  Every other argument defaults to ``DRIVERS[driver]``; ``lp``: a label-propagation object (default
+    ``LabelPropVOS_CRW`` on the driver's CXT_SIZE / RADIUS / TEMP / KNN).
+    -> {output file name: object}, what the script passes to ``torch.save``, in the state it has at that call.
+
+    Operation for operation, which includes:
+      * every radargram is ONE item, ``unfold(0, H, H-OH).unfold(1, W, W-OW).permute(1,0,2,3)``; ``T``, ``N``, ``rg_len`` and
+        ``rg_h`` are those of radargram 0 and serve all three, and maps are upsampled (nearest) to ``(rg_h, rg_len)`` -- not to
+        the reference segmentation's row count;
+      * the forward pass seeds from ``ref[:rg_h, :W]`` (mc1 :98, mc3 :97, sharad :96); ``propagate`` still computes its change
+        point, which mc1 ignores and mc3 / sharad overwrite with hand-set ones (``change_idx``, mc3 :111-113, sharad :112-114);
+      * correction (mc3 only when ``correction`` is set, sharad always; mc1 never): the item is the TAIL ``rg[t][change_idx:]`` --
+        unlike test_all.py's ``get_smaller_item``, which takes the head --, ``px = (seq_length - change_idx) * (W - OW)`` with the
+        ``seq_length`` argument, not ``T``, the seed ``ref[:, rg_len-px : rg_len-px+W]`` over ALL rows, and the result resized to
+        ``(rg_h, px)`` into the last ``px`` columns; nothing is caught, an error ends the run (mc3 :116-132, sharad :118-129);
+      * reverse pass (mc1 / mc3 with ``use_last``; sharad declares the flag and never reads it): mc1 seeds from the reversed
+        reference ``refs_reversed[t][:rg_h, :W]`` (:110-122), mc3 from ``ref[:rg_h, -W:]`` (:136-148); ``use_last=True``, the map
+        flipped along its columns;
+      * merge, in place on the forward (mc3: corrected) maps as the scripts' list aliasing does: mc1 writes 2 where the reverse
+        map is 2, then 1 where it is 1 and the ALREADY UPDATED forward map is not 2 (:124-135); mc3 writes 2 where the reverse
+        map is 2 and the forward column holds no class 4, then 3 the same way (:150-160);
+      * outputs: mc1 ``mc1_res.pt`` (the merged maps); mc3 ``mc3_res.pt`` (the corrected maps as saved BEFORE the merge mutates
+        them), ``mc3_resy.pt`` (merged), ``mc3_xenty.pt`` (the forward passes' metric); sharad ``s_res.pt``, ``s_xent.pt``.
+        mc1 and mc3 without the reverse pass end in a NameError in the reference (the merged list is never made): refused here."""
+    from imported.labelprop import LabelPropVOS_CRW
+    if driver not in DRIVERS:
+        raise ValueError(f'unknown driver {driver!r} (one of {", ".join(DRIVERS)})')
+    d = DRIVERS[driver]
+    pick = lambda v, k: d[k] if v is None else v
+    patch_size, overlap = tuple(pick(patch_size, 'patch_size')), tuple(pick(overlap, 'overlap'))
+    seq_length, nclasses = pick(seq_length, 'seq_length'), d['nclasses']
+    use_last, correction = pick(use_last, 'use_last'), pick(correction, 'correction')
+    change_idx = pick(change_idx, 'change_idx')
+    if len(radargrams) != 3 or len(refs) != 3:
+        raise ValueError('the drivers segment exactly three radargrams')
+    if driver == 'mc1' and (refs_reversed is None or len(refs_reversed) != 3):
+        raise ValueError('mc1 seeds its reverse pass from three reversed references (refs_reversed)')
+    if driver in ('mc1', 'mc3') and not use_last:
+        raise ValueError(f'{driver}: the reference saves its maps only after the reverse pass (use_last)')
+    if driver != 'mc1' and (change_idx is None or len(change_idx) != 3):
+        raise ValueError(f'{driver}: three hand-set change points are needed (change_idx)')
+    if lp is None:
+        lp = LabelPropVOS_CRW(dict(CXT_SIZE=pick(cxt_size, 'cxt_size'), RADIUS=pick(radius, 'radius'), TEMP=pick(temp, 'temp'),
+                                   KNN=pick(knn, 'knn')))
+    OW = overlap[-1]
+    rg = [_items(r, patch_size, overlap) for r in radargrams]
+    T, N, H, W = rg[0].shape
+    rg_len = T * (W - OW) + OW
+    rg_h = N * (H - overlap[0]) + overlap[0]
+
+    maps, xents = [], []
+    for t in range(3):
+        pred, xent, _ = propagate(rg[t], refs[t][:rg_h, :W], encoder, lp, nclasses, False, use_last=False)
+        maps.append(_upsample(pred, rg_h, rg_len))
+        xents.append(xent)
+
+    if driver == 'sharad' or (driver == 'mc3' and correction):
+        for t, ci in enumerate(change_idx):
+            if ci is None:
+                continue
+            px = (seq_length - ci) * (patch_size[-1] - OW)
+            seg_ref = refs[t][:, rg_len - px:rg_len - px + W]
+            pred, _, _ = propagate(rg[t][ci:], seg_ref, encoder, lp, nclasses, False, use_last=False)
+            maps[t][:, rg_len - px:] = _upsample(pred, rg_h, px)
+
+    if driver == 'sharad':
+        return {'s_res.pt': maps, 's_xent.pt': xents}
+    saved = [m.clone() for m in maps] if driver == 'mc3' else None  # torch.save writes mc3_res.pt before the merge mutates the maps
+
+    rev = []
+    for t in range(3):
+        seg_ref = refs_reversed[t][:rg_h, :W] if driver == 'mc1' else refs[t][:rg_h, -W:]
+        pred, _, _ = propagate(rg[t], seg_ref, encoder, lp, nclasses, False, use_last=True)
+        rev.append(torch.flip(_upsample(pred, rg_h, rg_len), (-1,)))
+    merge = merge_mc1 if driver == 'mc1' else merge_mc3
+    for t in range(3):
+        merge(maps[t], rev[t])
+    if driver == 'mc1':
+        return {'mc1_res.pt': maps}
+    return {'mc3_res.pt': saved, 'mc3_resy.pt': maps, 'mc3_xenty.pt': xents}
+
+
+def merge_mc1(fwd, rev):
+    """test_mc1.py:129-133, in place on ``fwd``: class 2 of the reverse map wins; then class 1 wherever ``fwd`` -- already
+    updated by the first write -- is not 2."""
+    fwd[rev == 2] = 2
+    fwd[torch.logical_and(rev == 1, fwd != 2)] = 1
+    return fwd
+
+
+def merge_mc3(fwd, rev):
+    """test_mc3.py:155-158, in place on ``fwd``: classes 2, then 3, of the reverse map win in the columns of ``fwd`` that hold
+    no class 4."""
+    rows = fwd.shape[0]
+    for c in (2, 3):
+        fwd[torch.logical_and(rev == c, torch.all(fwd != 4, dim=0)[None].repeat(rows, 1))] = c
+    return fwd
