@@ -16,6 +16,8 @@
  *   crw_labelprop_gather .... weighted label sum + argmax, frame by frame     src/imported/labelprop.py:106-114, src/utils.py:152-160
  *   crw_labelprop_propagate . the same, chained prefix + parallel tail          (same lines; context bound of maskedatt.py:165-166)
  *   crw_xent_metric ......... "horizontality" metric                          src/utils.py:117-125
+ *   crw_confusion ........... remove_unc masks + pred.cpu() + sklearn
+ *                             classification_report / confusion_matrix counts scripts/test/test_all.py:161-187
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HBM) unless its name ends in _host;
@@ -42,7 +44,7 @@ extern "C" {
 /* Bumps when a signature changes or an entry point is added.  The ONE place the number is written: crw_abi_version() returns
  * it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
-#define CRW_ABI_VERSION 7
+#define CRW_ABI_VERSION 8
 
 #define CRW_OK 0
 #define CRW_EINVAL 1     /* bad shape / null pointer / unsupported size            */
@@ -143,6 +145,24 @@ int crw_pelt_rbf(const double *signal, int n, double pen, int min_size, int jump
 
 /* ehat [T,N,C] -> xent [N,T-1]  (channel-shifted within-frame affinity / 0.1, CE vs identity) */
 int crw_xent_metric(const float *ehat, int T, int N, int C, float *xent, crw_stream_t stream);
+
+/* evaluation ------------------------------------------------------------------------------ */
+/* Confusion matrix of a label map against its ground truth, with the reference's "remove uncertain class" masks as arguments
+ * (scripts/test/test_all.py:161-187) -- one pass over the maps in HBM instead of boolean-index copies, a device-to-host copy and
+ * two sklearn calls.  gt, pred, aux (may be NULL): P labels each, dense, of the dtype their code names (CRW_DT_F32: what
+ * `segment` returns, 4-byte aligned; CRW_DT_I8: what the drivers save); no other alignment is asked for (views into a wider map).
+ * counts [K][K]: counts[g][p] = pixels with ground truth g and prediction p that survive the mask.  A pixel is masked -- counted
+ * in dropped[0] -- when gt == ignore_gt, pred == ignore_pred or aux == ignore_aux (-1 = no such label; aux values are compared,
+ * never binned, so an ignore label may lie outside [0, K)).  A surviving pixel whose gt or pred is not an integer in [0, K) (NaN
+ * included) is counted in dropped[1] and in no bin; nothing is read out of bounds for any label value.
+ * 2 <= K <= 16.  P == 0 is valid and gives zeros.  counts and dropped are complete in stream order after the call and need no
+ * pre-clearing; integer sums: bit-reproducible.  ws: crw_confusion_ws_bytes(P, K) bytes (per-workgroup partial counts). */
+#define CRW_DT_F32 0
+#define CRW_DT_I8 1
+size_t crw_confusion_ws_bytes(size_t P, int K);
+int crw_confusion(const void *gt, int gt_dtype, const void *pred, int pred_dtype, const void *aux, int aux_dtype, size_t P, int K,
+                  int ignore_gt, int ignore_pred, int ignore_aux, int64_t *counts /* [K][K] */,
+                  int64_t *dropped /* [2]: masked, invalid */, void *ws, size_t ws_bytes, crw_stream_t stream);
 
 /* building blocks exported for tests and the roofline bench --------------------------------- */
 /* Weight gradient of the CNN encoder's linear head (nn.Linear(128, 128), src/encoder.py:40,55; autograd of

@@ -52,6 +52,8 @@ SIGNATURES = {
     "crw_pelt_rbf": (_c_int, [_p, _c_int, ctypes.c_double, _c_int, _c_int, ctypes.c_double, _p, _c_int]),
     "crw_labelprop_propagate": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
     "crw_xent_metric": (_c_int, [_p, _c_int, _c_int, _c_int, _p, _p]),
+    "crw_confusion_ws_bytes": (_c_sz, [_c_sz, _c_int]),
+    "crw_confusion": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _c_sz, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _c_sz, _p]),
     "crw_linear128_wgrad_ws_bytes": (_c_sz, [_c_int]),
     "crw_linear128_wgrad": (_c_int, [_p, _p, _p, _c_int, _p, _c_sz, _p]),
     "crw_adam_step": (_c_int, [_p, _p, _p, _p, ctypes.c_long, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
@@ -312,6 +314,80 @@ def xent_metric(ehat):
     out = torch.empty(N, T - 1, device=ehat.device, dtype=torch.float32)
     _check(lib().crw_xent_metric(_dev(ehat, "ehat"), T, N, C, _dev(out, "xent"), _stream()), "crw_xent_metric")
     return out
+
+
+# ------------------------------------------------------------------------------ evaluation
+DT_F32, DT_I8 = 0, 1
+
+
+class LabelError(CrwError, ValueError):
+    """Labels that are no integers in [0, K) survived the mask (dropped[1] of crw_confusion): the caller's data."""
+
+    def __init__(self, invalid, K):
+        ValueError.__init__(self, f"{invalid} unmasked label(s) are not integers in [0, {K}) (NaN included)")
+        self.what, self.status, self.hip_error, self.invalid = "crw_confusion", CRW_EINVAL, 0, invalid
+
+
+def _labels(t, name):
+    """Flat contiguous labels as one of the kernel's dtypes.  fp32 and int8 pass through; every other dtype becomes fp32, a value
+    that fp32 cannot hold exactly becoming NaN (counted as invalid) rather than a neighbouring label."""
+    t = t.reshape(-1)
+    if t.dtype == torch.bool:
+        t = t.to(torch.int8)
+    elif t.dtype not in (torch.float32, torch.int8):
+        f = t.to(torch.float32)
+        t = torch.where(f.to(t.dtype) == t, f, torch.full_like(f, float("nan")))
+    return t.contiguous()
+
+
+def confusion(gt, pred, K, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1):
+    """Confusion counts of ``pred`` against ``gt`` (any shape, same number of labels) -> (counts [K, K] int64, dropped [2] int64) on
+    the inputs' device: counts[g, p] = labels with ground truth g and prediction p; a label is masked (dropped[0]) where
+    gt == ignore_gt, pred == ignore_pred or aux == ignore_aux (-1: none), and a surviving label that is no integer in [0, K) is
+    counted in dropped[1] and in no bin.  Device tensors: one pass of crw_confusion, nothing synchronises; CPU tensors: the same
+    counts from torch.bincount."""
+    K = int(K)
+    if not 2 <= K <= 16:
+        raise ValueError(f"K must be in 2 ... 16 (got {K})")
+    if min(ignore_gt, ignore_pred, ignore_aux) < -1:
+        raise ValueError("an ignore label is a class id >= 0, or -1 for none")
+    if aux is None and ignore_aux != -1:
+        raise ValueError("ignore_aux needs aux")
+    P = gt.numel()
+    if pred.numel() != P or (aux is not None and aux.numel() != P):
+        raise ValueError(f"gt, pred{' and aux' if aux is not None else ''} must hold the same number of labels "
+                         f"(got {P}, {pred.numel()}{'' if aux is None else ', ' + str(aux.numel())})")
+    if pred.device != gt.device or (aux is not None and aux.device != gt.device):
+        raise ValueError("gt, pred and aux must live on one device")
+    if not gt.is_cuda:
+        return _confusion_cpu(gt, pred, K, aux, ignore_gt, ignore_pred, ignore_aux)
+    g, p = _labels(gt, "gt"), _labels(pred, "pred")
+    a = _labels(aux, "aux") if aux is not None else None
+    code = lambda t: DT_F32 if t.dtype == torch.float32 else DT_I8
+    out = torch.empty(K * K + 2, dtype=torch.int64, device=gt.device)
+    nbytes = lib().crw_confusion_ws_bytes(P, K)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=gt.device)
+    _check(lib().crw_confusion(_ptr(g), code(g), _ptr(p), code(p), _ptr(a) if a is not None else None,
+                               code(a) if a is not None else DT_I8, P, K, int(ignore_gt), int(ignore_pred), int(ignore_aux),
+                               _ptr(out), ctypes.c_void_p(out.data_ptr() + 8 * K * K), _ptr(ws), nbytes, _stream()), "crw_confusion")
+    return out[:K * K].view(K, K), out[K * K:]
+
+
+def _confusion_cpu(gt, pred, K, aux, ignore_gt, ignore_pred, ignore_aux):
+    g, p = gt.reshape(-1).to(torch.float64), pred.reshape(-1).to(torch.float64)
+    masked = torch.zeros(g.shape, dtype=torch.bool)
+    if ignore_gt >= 0:
+        masked |= g == ignore_gt
+    if ignore_pred >= 0:
+        masked |= p == ignore_pred
+    if ignore_aux >= 0:
+        masked |= aux.reshape(-1).to(torch.float64) == ignore_aux
+    valid = (g == g.floor()) & (g >= 0) & (g < K) & (p == p.floor()) & (p >= 0) & (p < K)  # NaN fails every comparison
+    keep = valid & ~masked
+    # masked and invalid labels go to two extra bins, like the kernel's: no boolean-indexed copy of the maps
+    idx = torch.where(keep, g * K + p, torch.where(masked, float(K * K), float(K * K + 1))).to(torch.int64)
+    out = torch.bincount(idx, minlength=K * K + 2)
+    return out[:K * K].view(K, K), out[K * K:]
 
 
 def gemm_f32(A, B, C=None, transA=False, transB=False, beta=False):

@@ -22,6 +22,9 @@ includes three things one might not expect:
 Label maps are upsampled to pixels with nearest-neighbour interpolation like the reference
 (``transforms.Resize(NEAREST)``).  Everything heavy runs in ``propagate`` (encoder + HIP kernels).
 
+``evaluate`` is the end of the same script (test_all.py:161-187): the ``--remove_unc`` masks and the report the reference prints,
+from one pass of the HIP kernel ``crw_confusion`` over the label map where ``segment`` left it (``metrics.Report``).
+
 ``segment_radargrams`` is the other family of the reference's drivers: scripts/test/test_mc1.py, test_mc3.py and
 test_sharad.py (``main(args)``), three whole radargrams held in memory, one item each; their defaults are in ``DRIVERS``.
 """
@@ -118,6 +121,68 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
         rev = torch.flip(rev, (-1,)).reshape(rows, -1)
         final = merge_reverse(forward, rev, dataset_id)
     return dict(pred=final, forward=forward, xent=xents, change_idx=changes)
+
+
+@torch.no_grad()
+def segment_one(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap, pos_embed=False, device='cuda'):
+    """``main(args)`` of the reference's scripts/test/test.py (:45-84) without the plots: the FIRST radargram only, forward pass
+    seeded from ``seg[:rg_h, :W]``, then always one correction -- at ``seq_length - 2`` when ``propagate`` finds no change point
+    (:70-71) -- on ``dataset.get_smaller_item(0, small)`` seeded from every row of ``seg``; nothing is caught, an error ends the
+    run.  The caller puts the encoder in eval mode (test.py:42).  -> dict(pred [rows, rg_len], change_idx)."""
+    T, (H, W), (oh, ow) = seq_length, patch_size, overlap
+    seq = dataset[0].to(device)
+    N = seq.shape[1]
+    rg_len = T * (W - ow) + ow
+    rg_h = N * (H - oh) + oh
+    seg = seg.to(device)
+    rows = seg.shape[0]
+    pred, _, change = propagate(seq, seg[:rg_h, :W], encoder, lp, nclasses, pos_embed, use_last=False)
+    final = _upsample(pred, rows, rg_len)
+    if change is None:
+        change = T - 2
+    small = T - change
+    px = small * (W - ow)
+    seq = dataset.get_smaller_item(0, small).to(device)
+    pred, _, _ = propagate(seq, seg[:, rg_len - px:rg_len - px + W], encoder, lp, nclasses, pos_embed, use_last=False)
+    final[:, rg_len - px:] = _upsample(pred, rows, px)
+    return dict(pred=final, change_idx=change)
+
+
+# dataset id -> number of classes, as utils.get_reference returns it (src/utils.py:57-70)
+NCLASSES = {0: 4, 1: 6, 2: 4, 3: 5}
+
+
+def evaluate(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None):
+    """The report of test_all.py:161-187 for a label map ``pred`` (``segment(...)['pred']``, or a saved int8 map) against the
+    reference segmentation ``seg`` cut to the same columns -> ``metrics.Report``.
+
+    ``remove_unc`` (the script's default): dataset 0 drops the pixels whose ``unc_seg`` -- the reference's dataset-2 map cut to the
+    same columns, required then -- is 4 (:162-167); dataset 1 drops the pixels whose ground truth or prediction is 5 (:168-172);
+    dataset 3 drops nothing (:173-175).  The rules are mask arguments of the one ``crw_hip.confusion`` call: no boolean-indexed
+    copy of the maps, no copy to the host but the K x K counts.  K = ``nclasses`` (default: the dataset's, labels 0 ... K-1); the
+    4s of dataset 0's uncertain map are compared, never binned.  A label outside 0 ... K-1 that survives the mask raises
+    ``crw_hip.LabelError`` (a ValueError)."""
+    from metrics import Report
+    if dataset_id not in (0, 1, 3):
+        raise ValueError(f'no report rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
+    K = NCLASSES[dataset_id] if nclasses is None else int(nclasses)
+    if pred.numel() != seg.numel():
+        raise ValueError(f'pred {tuple(pred.shape)} and seg {tuple(seg.shape)} must cover the same pixels')
+    seg = seg.to(pred.device)
+    mask = {}
+    if remove_unc and dataset_id == 0:
+        if unc_seg is None:
+            raise ValueError('dataset 0 with remove_unc needs unc_seg (the dataset-2 reference map, same columns)')
+        if unc_seg.numel() != seg.numel():
+            raise ValueError(f'unc_seg {tuple(unc_seg.shape)} and seg {tuple(seg.shape)} must cover the same pixels')
+        mask = dict(aux=unc_seg.to(pred.device), ignore_aux=4)
+    elif remove_unc and dataset_id == 1:
+        mask = dict(ignore_gt=5, ignore_pred=5)
+    counts, dropped = crw_hip.confusion(seg, pred, K, **mask)
+    dropped = [int(v) for v in dropped.cpu()]
+    if dropped[1]:
+        raise crw_hip.LabelError(dropped[1], K)
+    return Report(counts, dropped)
 
 
 # the reference's three per-dataset drivers (scripts/test/test_mc1.py:19-30, test_mc3.py:19-33, test_sharad.py:19-32): argparse

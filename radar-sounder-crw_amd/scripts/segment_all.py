@@ -1,0 +1,190 @@
+#!/usr/bin/env python3
+"""Dataset evaluation -- the reference's scripts/test/test_all.py (and, with ``--single``, scripts/test/test.py) with the same
+flags and defaults: segment every radargram of a dataset (``inference.segment``), save ``predicted_map.pt`` as int8
+(test_all.py:128), mask the uncertain class (``--remove_unc``, on by default) and print the classification report, the confusion
+matrix and the two elapsed times the reference prints (:183-188).  The report is one pass of the HIP kernel ``crw_confusion``
+over the label map on the GPU (``inference.evaluate``); scikit-learn is not used.
+
+    python radar-sounder-crw_amd/scripts/segment_all.py --dataset 3 --model_path sharad16_3.pt --output_folder out/
+    python radar-sounder-crw_amd/scripts/segment_all.py --synthetic 200 4800 --dataset 0 --use_last true --report_json r.json
+
+Additions: ``--data_path`` / ``--seg_path`` / ``--unc_seg_path`` / ``--model_path`` for the files the reference hard-codes
+(default: its paths, re-rooted by CRW_DATA_ROOT); ``--synthetic H W``: a seeded radargram with a layered reference map, no files,
+and -- without ``--model_path`` -- a random-init encoder; ``--report_json FILE``: the numbers (per-class scores, averages, IoU,
+matrix, dropped pixels, elapsed times); ``--iou``: also print the IoU table.
+Differences from the scripts:
+  * plots are not drawn;
+  * true / false flags read true / false (the scripts take any given string as true); ``--patch_size`` takes two numbers;
+    ``--temp`` is a float in both modes (test.py declares it int); ``--output_folder`` defaults to ``resources/output/``;
+  * the checkpoint may carry DataParallel's ``module.`` prefix or not;
+  * ``--dataset_full false``: the same items (every ``seq_length``-th) are segmented; the correction step, which the reference
+    then skips silently (its ``Subset`` has no ``get_smaller_item``; bare ``except``), is skipped with a note;
+  * ``--single`` follows test.py: dataset 3 / seq_length 80 / cxt 80 / radius 16 / temp 0.01 / knn 10 by default, the first
+    radargram only, encoder in eval mode (test.py:42), forward seed ``seg[:rg_h, :W]``, ``change_idx = seq_length - 2`` when none
+    is found, no ``try`` around the correction.  test.py saves and scores nothing; here the map is saved and scored like
+    test_all's (``--remove_unc`` applies), against the reference map's first ``rg_len`` columns.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import torch
+
+import inference
+from dataset import RGDataset, synthetic_radargram
+from segment_drivers import _flag, load_encoder
+from utils import create_dataset, create_model, get_reference
+
+# test_all.py:17-41 and test.py:12-31
+DEFAULTS = {
+    'all': dict(model=1, dataset=1, patch_size=(16, 16), seq_length=100, overlap=(8, 0), cxt_size=100, radius=10, temp=0.1, knn=20),
+    'single': dict(model=1, dataset=3, patch_size=(16, 16), seq_length=80, overlap=(8, 0), cxt_size=80, radius=16, temp=0.01, knn=10),
+}
+
+
+def get_args_parser():
+    p = argparse.ArgumentParser('CRW dataset evaluation (test_all.py; --single: test.py)', add_help=True)
+    p.add_argument('--single', action='store_true', help="scripts/test/test.py: first radargram, eval-mode encoder, one correction")
+    p.add_argument('--model', default=None, type=int, help='0=CNN,1=Resnet18')
+    p.add_argument('--dataset', default=None, type=int, help='0=MCORDS1,1=Miguel,3=SHARAD')
+    p.add_argument('--patch_size', default=None, nargs=2, type=int)
+    p.add_argument('--seq_length', default=None, type=int)
+    p.add_argument('--overlap', default=None, nargs='+', type=int)
+    p.add_argument('-c', '--cxt_size', default=None, type=int)
+    p.add_argument('-r', '--radius', default=None, type=int)
+    p.add_argument('-t', '--temp', default=None, type=float)
+    p.add_argument('-k', '--knn', default=None, type=int)
+    p.add_argument('--model_path', default=None, help='encoder state_dict (required unless --synthetic)')
+    p.add_argument('--output_folder', default='resources/output/')
+    p.add_argument('--pos_embed', default=False, type=_flag)
+    p.add_argument('--remove_unc', default=True, type=_flag, help='remove the uncertainty class from the report')
+    p.add_argument('--flip', default=False, type=_flag, help='test on the flipped radargram')
+    p.add_argument('--use_last', default=False, type=_flag, help='reverse pass seeded from the last sample, merged')
+    p.add_argument('--dataset_full', default=True, type=_flag)
+    p.add_argument('--correction', default=False, type=_flag, help='change-point detection and correction')
+    p.add_argument('--data_path', default=None, help='H x W radargram .pt file')
+    p.add_argument('--seg_path', default=None, help='reference segmentation .pt file')
+    p.add_argument('--unc_seg_path', default=None, help="dataset 0's map with the uncertain class 4 (the reference's dataset id 2)")
+    p.add_argument('--synthetic', default=None, nargs=2, type=int, metavar=('H', 'W'))
+    p.add_argument('--report_json', default=None, metavar='FILE')
+    p.add_argument('--iou', action='store_true', help='also print the per-class IoU table')
+    return p
+
+
+def with_defaults(args):
+    """Fill every flag left unset with the default of the script the mode stands for."""
+    for k, v in DEFAULTS['single' if args.single else 'all'].items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
+    args.patch_size, args.overlap = tuple(args.patch_size), tuple(args.overlap)
+    if len(args.overlap) != 2:
+        raise SystemExit('--overlap takes two numbers (vertical, horizontal)')
+    if args.dataset not in (0, 1, 3):
+        raise SystemExit(f'--dataset {args.dataset}: the reference defines 0, 1 and 3')
+    if args.model_path is None and args.synthetic is None:
+        raise SystemExit('--model_path is required (or --synthetic H W for a run without data)')
+    return args
+
+
+def synthetic_reference(H, W, nclasses, uncertain=False):
+    """A layered reference map for ``--synthetic``: ``nclasses`` bands whose interfaces undulate along-track; ``uncertain``: the
+    companion map of dataset 0 with a band of 4s around the middle interface."""
+    r = torch.arange(H).float()[:, None]
+    c = torch.arange(W).float()[None, :]
+    depth = r + 0.02 * H * torch.sin(2 * torch.pi * c / 900.0)
+    seg = torch.clamp(torch.floor(depth * nclasses / H), 0, nclasses - 1)
+    if uncertain:
+        seg[(depth - H / 2).abs() < 0.03 * H] = 4.0
+    return seg
+
+
+def load_data(args):
+    """-> (dataset, nclasses, seg, unc_seg | None), the reference's factories (test_all.py:57-60, 163-164)."""
+    dim, T = args.patch_size, args.seq_length
+    if args.synthetic is not None:
+        H, W = args.synthetic
+        ds = RGDataset.from_tensor(synthetic_radargram(H, W), T, dim, args.overlap, flip=args.flip)
+        N = ds[0].shape[1]
+        nclasses = inference.NCLASSES[args.dataset]
+        flip = (lambda m: torch.flip(m, (1,))) if args.flip else (lambda m: m)
+        seg = flip(synthetic_reference(H, W, nclasses)[:N * dim[0]])
+        unc = flip(synthetic_reference(H, W, nclasses, True)[:N * dim[0]]) if (args.dataset == 0 and args.remove_unc) else None
+        return ds, nclasses, seg, unc
+    ds = create_dataset(id=args.dataset, length=T, dim=dim, overlap=args.overlap, full=True, flip=args.flip, data_path=args.data_path)
+    N = ds[0].shape[1]
+    nclasses, seg = get_reference(id=args.dataset, h=N * dim[0], w=0, flip=args.flip, length=T, dim=dim, overlap=args.overlap,
+                                  seg_path=args.seg_path)
+    unc = None
+    if args.dataset == 0 and args.remove_unc:
+        _, unc = get_reference(id=2, h=N * dim[0], w=0, flip=args.flip, seg_path=args.unc_seg_path)
+    return ds, nclasses, seg, unc
+
+
+def main(args):
+    from imported.labelprop import LabelPropVOS_CRW
+    tim = time.time()
+    args = with_defaults(args)
+    print(args)
+    device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+    if args.model_path is not None:
+        encoder = load_encoder(args.model, args.model_path, device)
+    else:
+        encoder = create_model(args.model, args.pos_embed).to(device)
+    dataset, nclasses, seg, unc_seg = load_data(args)
+    lp = LabelPropVOS_CRW(dict(CXT_SIZE=args.cxt_size, RADIUS=args.radius, TEMP=args.temp, KNN=args.knn))
+    T, W, ow = args.seq_length, args.patch_size[1], args.overlap[1]
+    rg_len = T * (W - ow) + ow
+    if args.single:
+        encoder.train(False)
+        out = inference.segment_one(dataset, seg, encoder, lp, nclasses, T, args.patch_size, args.overlap, pos_embed=args.pos_embed,
+                                    device=device)
+        print('Correcting at', out['change_idx'])
+        final, forward = out['pred'], out['pred']
+    else:
+        tot_rg = seg.shape[-1] // rg_len
+        print('Num of radargrams:', tot_rg, 'Radargram length:', rg_len)
+        correction = args.correction
+        if correction and not args.dataset_full:
+            print('Correction skipped: it needs --dataset_full true (the reference skips it silently here)')
+            correction = False
+        out = inference.segment(dataset, seg, encoder, lp, nclasses, T, args.patch_size, args.overlap, pos_embed=args.pos_embed,
+                                correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device)
+        if correction:
+            print('Change point for each radargram:', out['change_idx'])
+        final, forward = out['pred'], out['forward']
+    cols = final.shape[1]
+    os.makedirs(args.output_folder, exist_ok=True)
+    torch.save(forward.to(torch.int8), os.path.join(args.output_folder, 'predicted_map.pt'))
+    if device.type == 'cuda':
+        torch.cuda.synchronize()
+    t_inference = time.time() - tim
+    print('Time elapsed (inference only):', t_inference)
+    print('Computing reports ...')
+    print('')
+    report = inference.evaluate(final, seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
+                                unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses)
+    print(report)
+    print(report.matrix_str())
+    if args.iou:
+        print('')
+        print(report.iou_str())
+    t_all = time.time() - tim
+    print('\nTime elapsed (inference + metrics):', t_all)
+    if args.report_json:
+        d = report.as_dict()
+        d.update(labels=report.labels, matrix=report.matrix.tolist(), dropped=dict(masked=report.dropped[0], invalid=report.dropped[1]),
+                 pixels=int(final.numel()), map_shape=list(final.shape), elapsed_inference_s=t_inference, elapsed_total_s=t_all,
+                 dataset=args.dataset, remove_unc=args.remove_unc, single=args.single)
+        with open(args.report_json, 'w') as f:
+            json.dump(d, f, indent=1)
+    return report
+
+
+if __name__ == '__main__':
+    torch.manual_seed(11)  # the scripts seed at import (test_all.py:14)
+    main(get_args_parser().parse_args())
