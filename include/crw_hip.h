@@ -15,6 +15,9 @@
  *                             softmax                                         src/imported/maskedatt.py:151-175
  *   crw_labelprop_gather .... weighted label sum + argmax, frame by frame     src/imported/labelprop.py:106-114, src/utils.py:152-160
  *   crw_labelprop_propagate . the same, chained prefix + parallel tail          (same lines; context bound of maskedatt.py:165-166)
+ *   crw_labelprop_topk_scores / crw_labelprop_sweep_weights / crw_labelprop_propagate_batch
+ *                             the same lists and labels for a whole grid of
+ *                             (radius, temp, knn) settings at once              scripts/launch/launch_test_batch.sh
  *   crw_xent_metric ......... "horizontality" metric                          src/utils.py:117-125
  *   crw_confusion ........... remove_unc masks + pred.cpu() + sklearn
  *                             classification_report / confusion_matrix counts scripts/test/test_all.py:161-187
@@ -41,7 +44,9 @@
 extern "C" {
 #endif
 
-/* Bumps when a signature changes or an entry point is added.  The ONE place the number is written: crw_abi_version() returns
+/* Bumps when a signature changes.  Entry points added at 8 without a bump (pure additions, no existing signature touched; the
+ * binding detects them by symbol, crw_hip.has_sweep()): crw_labelprop_topk_scores, crw_labelprop_sweep_weights,
+ * crw_labelprop_propagate_batch.  The ONE place the number is written: crw_abi_version() returns
  * it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
 #define CRW_ABI_VERSION 8
@@ -135,6 +140,31 @@ int crw_labelprop_gather(const float *seed, const float *W, const int32_t *I, in
  * the frame's own, never out of range.  Falls back to crw_labelprop_gather where the chained frames' labels exceed the LDS. */
 int crw_labelprop_propagate(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame,
                             int cxt_size, float *L, float *pred, crw_stream_t stream);
+
+/* Sweeps over (radius, temp, knn) -- the grid of the reference's scripts/launch/launch_test_batch.sh -- share everything that does
+ * not depend on the setting.  Each entry point is defined by equality with one above.
+ *
+ * crw_labelprop_topk_scores: crw_labelprop_topk_grid with kcap (1 ... 64) in place of knn, through the same kernels and the same
+ * route choice, with another last line of the epilogue: V [T-first_frame, kcap, N] is the selected logit fl(<key, query> / temp)
+ * in selection order instead of its softmax weight (empty slot: V = -inf, I = 0).  I equals crw_labelprop_topk_grid(..., knn =
+ * kcap)'s, and because selection is sequential (highest score, then lowest candidate index) its first k entries are the lists of
+ * knn = k.  Selection is per temperature, on the quotient: fp32 division maps distinct scores onto equal quotients, and the tie
+ * rule then orders them by index. */
+int crw_labelprop_topk_scores(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int kcap, int first_frame,
+                              int grid_w, float *V, int32_t *I, crw_stream_t stream);
+/* V [F, kcap, N] of the call above, knns: nk (1 ... 16) values on the HOST, each 1 ... kcap -> W [nk, F, kmax, N], kmax = max(knns):
+ * W[i][:, :knns[i], :] is bit-identical to the W of crw_labelprop_topk_grid(..., knn = knns[i]) (the epilogues' expression in their
+ * order: vmax = V[0]; the sum over j < knn, -inf -> 0; expf(v - vmax) / sum), slots >= knns[i] are 0. */
+int crw_labelprop_sweep_weights(const float *V, int F, int kcap, int N, const int *knns, int nk, float *W, crw_stream_t stream);
+/* crw_labelprop_propagate for G configurations at once: W [G, T-first_frame, knn, N]; configuration g's indices start at
+ * I + g * i_stride elements (0: one I shared by all); one seed [N] (or NULL: every L[g]'s frames < first_frame are filled);
+ * L [G, T*N, M], pred [G, N, T].  knn is the length of the lists as stored: a configuration with fewer neighbours pads with
+ * weights that are exactly 0 on valid indices (crw_labelprop_sweep_weights), which leaves every sum as it is.  Slice g of L and
+ * pred is bit-identical to crw_labelprop_propagate on that configuration's lists.  A workgroup per configuration walks the
+ * chained frames (frame 0 and a ring of recent frames in LDS, older labels from L), the frames beyond the context bound are a
+ * grid over (frame, configuration).  CRW_EINVAL: G > 65535, knn > 64, N * M > 7680 (a ring of four frames must fit the LDS). */
+int crw_labelprop_propagate_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M,
+                                  int knn, int first_frame, int cxt_size, float *L, float *pred, crw_stream_t stream);
 
 /* HOST function (no GPU work, host pointers): the change-point search of `propagate` (src/utils.py:125-132,
  * ruptures.Pelt(model="rbf").fit(signal).predict(pen)) -- PELT with the RBF kernel cost at ruptures' documented defaults

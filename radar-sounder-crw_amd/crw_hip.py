@@ -51,6 +51,9 @@ SIGNATURES = {
     "crw_labelprop_gather": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
     "crw_pelt_rbf": (_c_int, [_p, _c_int, ctypes.c_double, _c_int, _c_int, ctypes.c_double, _p, _c_int]),
     "crw_labelprop_propagate": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
+    "crw_labelprop_topk_scores": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_int, _c_int, _c_int, _p, _p, _p]),
+    "crw_labelprop_sweep_weights": (_c_int, [_p, _c_int, _c_int, _c_int, _p, _c_int, _p, _p]),
+    "crw_labelprop_propagate_batch": (_c_int, [_p, _p, _p, _c_sz] + [_c_int] * 7 + [_p, _p, _p]),
     "crw_xent_metric": (_c_int, [_p, _c_int, _c_int, _c_int, _p, _p]),
     "crw_confusion_ws_bytes": (_c_sz, [_c_sz, _c_int]),
     "crw_confusion": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _c_sz, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _c_sz, _p]),
@@ -122,26 +125,46 @@ SIGNATURES = {
     "crw_gemm_bf16": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _c_sz, _c_int, _p]),
 }
 
+# entry points added at ABI 8 without a bump: a library built before them still loads, `has_sweep()` tells
+SWEEP_ENTRY_POINTS = ("crw_labelprop_topk_scores", "crw_labelprop_sweep_weights", "crw_labelprop_propagate_batch")
+
 _lib = None
+_has_sweep = False
 
 
 def lib():
     """Load the HIP library (once).  Raises if it has not been built: `python -c 'import
     __graft_entry__ as g; g.build()'` or `make -C radar-sounder-crw_amd/csrc`."""
-    global _lib
+    global _lib, _has_sweep
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} not built -- the CRW hot path has no CPU/PyTorch fallback; "
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
+        missing = [n for n in SWEEP_ENTRY_POINTS if not hasattr(handle, n)]
         for name, (res, args) in SIGNATURES.items():
+            if name in missing:
+                continue
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
         if handle.crw_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} was built for ABI {handle.crw_abi_version()}, include/crw_hip.h says {ABI_VERSION}: "
                                "stale library -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
-        _lib = handle
+        _lib, _has_sweep = handle, not missing
     return _lib
+
+
+def has_sweep():
+    """True when the loaded library exports the sweep entry points (SWEEP_ENTRY_POINTS)."""
+    lib()
+    return _has_sweep
+
+
+def _sweep_lib():
+    if not has_sweep():
+        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks {', '.join(SWEEP_ENTRY_POINTS)} "
+                           "(added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
+    return lib()
 
 
 class CrwError(RuntimeError):
@@ -292,6 +315,71 @@ def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_
     _check(lib().crw_labelprop_gather(_dev(seed, "seed") if seed is not None else None, _dev(W, "W"),
                                       _dev(I, "I", torch.int32), T, N, M, knn, int(first_frame), _dev(L, "L"),
                                       _dev(pred, "pred"), _stream()), "crw_labelprop_gather")
+    return L, pred
+
+
+def labelprop_topk_scores(ehat, cxt_size, radius, temp, kcap, first_frame=1, grid_w=1, out=None):
+    """`labelprop_topk` with the selected logits V [T-first_frame, kcap, N] instead of their softmax weights (empty slot -inf), and
+    the same I: the lists of every knn <= kcap are their first knn entries (`labelprop_sweep_weights` makes the weights).
+    out: (V, I) tensors of those shapes to write into."""
+    T, N, C = ehat.shape
+    if out is not None:
+        V, I = out
+        if tuple(V.shape) != (T - first_frame, kcap, N) or tuple(I.shape) != tuple(V.shape):
+            raise RuntimeError(f"out must be two {(T - first_frame, kcap, N)} tensors (got {tuple(V.shape)}, {tuple(I.shape)})")
+    else:
+        V = torch.empty(T - first_frame, kcap, N, device=ehat.device, dtype=torch.float32)
+        I = torch.empty(T - first_frame, kcap, N, device=ehat.device, dtype=torch.int32)
+    _check(_sweep_lib().crw_labelprop_topk_scores(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(radius), float(temp), int(kcap),
+                                                  int(first_frame), int(grid_w), _dev(V, "V"), _dev(I, "I", torch.int32), _stream()),
+           "crw_labelprop_topk_scores")
+    return V, I
+
+
+def labelprop_sweep_weights(V, knns, out=None):
+    """V [F, kcap, N] of `labelprop_topk_scores`, knns: 1 ... 16 values in 1 ... kcap -> W [len(knns), F, max(knns), N]:
+    W[i][:, :knns[i]] is bitwise the W of `labelprop_topk(..., knn=knns[i])`, the slots behind are 0.  out: a [len(knns), F,
+    max(knns), N] view to write into."""
+    F, kcap, N = V.shape
+    knns = [int(k) for k in knns]
+    if not knns:
+        raise ValueError("knns is empty")
+    arr = (ctypes.c_int * len(knns))(*knns)
+    W = out if out is not None else torch.empty(len(knns), F, max(knns), N, device=V.device, dtype=torch.float32)
+    if tuple(W.shape) != (len(knns), F, max(knns), N):
+        raise RuntimeError(f"out must be {(len(knns), F, max(knns), N)} (got {tuple(W.shape)})")
+    _check(_sweep_lib().crw_labelprop_sweep_weights(_dev(V, "V"), F, kcap, N, arr, len(knns), _dev(W, "W"), _stream()),
+           "crw_labelprop_sweep_weights")
+    return W
+
+
+def labelprop_propagate_batch(seed, W, I, T, N, M, first_frame=1, cxt_size=None, L=None, pred=None):
+    """G configurations' `labelprop_gather(..., cxt_size=cxt_size)` in one call: W [G, T-first_frame, knn, N]; I the same shape, or
+    [T-first_frame, knn, N] shared by all -> (L [G, T*N, M], pred [G, N, T]), slice g bitwise what the per-configuration call
+    gives on W[g] (shorter lists padded with zero weights).  seed None: L's frames before first_frame are filled by the caller."""
+    if cxt_size is None:
+        raise ValueError("cxt_size (the context size the lists were made with) is required")
+    G, F, knn = W.shape[0], W.shape[1], W.shape[2]
+    if W.dim() != 4 or F != T - first_frame or W.shape[3] != N:
+        raise RuntimeError(f"W must be [G, {T - first_frame}, knn, {N}] (got {tuple(W.shape)})")
+    if tuple(I.shape) == tuple(W.shape):
+        stride = F * knn * N
+    elif tuple(I.shape) == tuple(W.shape[1:]):
+        stride = 0
+    else:
+        raise RuntimeError(f"I must be {tuple(W.shape)} or {tuple(W.shape[1:])} (got {tuple(I.shape)})")
+    if L is None:
+        if seed is None:
+            raise ValueError("without a seed, L (frames before first_frame filled) is required")
+        L = torch.empty(G, T * N, M, device=W.device, dtype=torch.float32)
+    if pred is None:
+        pred = torch.zeros(G, N, T, device=W.device, dtype=torch.float32)
+    if tuple(L.shape) != (G, T * N, M) or tuple(pred.shape) != (G, N, T):
+        raise RuntimeError(f"L must be {(G, T * N, M)} and pred {(G, N, T)} (got {tuple(L.shape)}, {tuple(pred.shape)})")
+    _check(_sweep_lib().crw_labelprop_propagate_batch(_dev(seed, "seed") if seed is not None else None, _dev(W, "W"),
+                                                      _dev(I, "I", torch.int32), stride, G, T, N, M, knn, int(first_frame),
+                                                      int(cxt_size), _dev(L, "L"), _dev(pred, "pred"), _stream()),
+           "crw_labelprop_propagate_batch")
     return L, pred
 
 

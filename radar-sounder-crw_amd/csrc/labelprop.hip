@@ -26,7 +26,7 @@ constexpr int MAX_KNN = 64;
 __global__ __launch_bounds__(256) void labelprop_topk_kernel(const float *__restrict__ ehat, int T, int N, int C,
                                                              int cxt, int radius, float temp, int knn,
                                                              int first_frame, int gw, float *__restrict__ W,
-                                                             int32_t *__restrict__ I) {
+                                                             int32_t *__restrict__ I, int raw) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int q = blockIdx.x, n = blockIdx.y + first_frame;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -109,9 +109,11 @@ __global__ __launch_bounds__(256) void labelprop_topk_kernel(const float *__rest
     float w = 0.f;
     int idx = 0;
     if (v != -INFINITY) {
-      w = expf(v - vmax) / ssum;
+      w = raw ? v : expf(v - vmax) / ssum;  // raw (crw_labelprop_topk_scores): the selected logit itself
       const int c = sel_i[tid], r = c % bw;
       idx = (c / bw) * N + (lo + r / bwj) * gw + lj + r % bwj;
+    } else if (raw) {
+      w = -INFINITY;
     }
     const long o = ((long)(n - first_frame) * knn + tid) * N + q;
     W[o] = w;
@@ -139,7 +141,7 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 template <int CSTEPS, int NCH>  // C / 16: float4 per lane and row
 __global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_kernel(const float *__restrict__ ehat, int T, int N, int cxt, int radius,
                                                                            float temp, int knn, int first_frame, int maxcand, int pf,
-                                                                           float *__restrict__ W, int32_t *__restrict__ I) {
+                                                                           float *__restrict__ W, int32_t *__restrict__ I, int raw) {
   constexpr int C = 16 * CSTEPS, NV = TK_NV / (NCH == 1 ? 1 : 2);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float *val = smem;  // [TK_Q][maxcand] (maxcand: candidates of ONE chunk)
@@ -299,9 +301,11 @@ __global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_k
         float w = 0.f;
         int idx = 0;
         if (x != -INFINITY) {
-          w = expf(x - vmax) / ssum;
+          w = raw ? x : expf(x - vmax) / ssum;  // raw (crw_labelprop_topk_scores): the selected logit itself
           const int c = sel_i[u][lane];
           idx = (c / bw2[h]) * N + lo2[h] + c % bw2[h];
+        } else if (raw) {
+          w = -INFINITY;
         }
         const long o = ((long)(n - first_frame) * knn + lane) * N + q0 + u;
         W[o] = w;
@@ -313,7 +317,7 @@ __global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_k
 
 template <int CSTEPS, int NCH>
 int launch_topk_mfma_n(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int chunkcand, int pf,
-                       float *W, int32_t *I, hipStream_t s) {
+                       float *W, int32_t *I, int raw, hipStream_t s) {
   const size_t lds = (size_t)TK_Q * chunkcand * 4;
   static bool attr = false;
   if (!attr) {
@@ -325,7 +329,7 @@ int launch_topk_mfma_n(const float *ehat, int T, int N, int cxt, int radius, flo
     attr = true;
   }
   hipLaunchKernelGGL((labelprop_topk_mfma_kernel<CSTEPS, NCH>), dim3((N + TK_Q - 1) / TK_Q, T - first_frame), dim3(TK_NT), lds, s, ehat, T, N,
-                     cxt, radius, temp, knn, first_frame, chunkcand, pf, W, I);
+                     cxt, radius, temp, knn, first_frame, chunkcand, pf, W, I, raw);
   return check_launch();
 }
 
@@ -333,13 +337,13 @@ int launch_topk_mfma_n(const float *ehat, int T, int N, int cxt, int radius, flo
 // in two halves, so that two workgroups share a CU (CRW_LABELPROP_TOPK_CHUNKS=1: always one piece, A/B)
 template <int CSTEPS>
 int launch_topk_mfma(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int max_nf, int max_bi, float *W,
-                     int32_t *I, hipStream_t s) {
+                     int32_t *I, int raw, hipStream_t s) {
   static const bool one = getenv("CRW_LABELPROP_TOPK_CHUNKS") && getenv("CRW_LABELPROP_TOPK_CHUNKS")[0] == '1';
   const long maxcand = (long)max_nf * max_bi;
   const int pf = (max_nf + 1) / 2;
   if (!one && CSTEPS <= 8 /* 256 channels: past 128 registers */ && (size_t)TK_Q * maxcand * 4 > 76 * 1024 && (long)pf * max_bi <= 64L * (TK_NV / 2))
-    return launch_topk_mfma_n<CSTEPS, 2>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, s);
-  return launch_topk_mfma_n<CSTEPS, 1>(ehat, T, N, cxt, radius, temp, knn, first_frame, (int)maxcand, max_nf, W, I, s);
+    return launch_topk_mfma_n<CSTEPS, 2>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, s);
+  return launch_topk_mfma_n<CSTEPS, 1>(ehat, T, N, cxt, radius, temp, knn, first_frame, (int)maxcand, max_nf, W, I, raw, s);
 }
 
 // candidate lists past the two forms above (more than 64 * TK_NV candidates, or a tile's scores over 150 KiB): chunks of pf frames,
@@ -348,12 +352,12 @@ int launch_topk_mfma(const float *ehat, int T, int N, int cxt, int radius, float
 constexpr int TK_LONG_CAND = 64 * (TK_NV / 2);
 template <int CSTEPS>
 int launch_topk_mfma_long(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int max_nf, int max_bi,
-                          float *W, int32_t *I, hipStream_t s) {
+                          float *W, int32_t *I, int raw, hipStream_t s) {
   static_assert(CSTEPS <= 8, "256 channels: past 128 registers");
   int pf = TK_LONG_CAND / max_bi;
   const int nch = (max_nf + pf - 1) / pf;
   pf = (max_nf + nch - 1) / nch;
-  return launch_topk_mfma_n<CSTEPS, 0>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, s);
+  return launch_topk_mfma_n<CSTEPS, 0>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, s);
 }
 
 __device__ inline float ld_l2(const float *p) {
@@ -618,6 +622,7 @@ __global__ __launch_bounds__(PX_NT) void labelprop_prefix_kernel(const float *__
     fetch_lists(first_frame, a, w);
     to_offsets(first_frame, a, w);
   }
+  lds_barrier();  // the read of slot first_frame & 1 above comes before loader 0's svc_store(first_frame + 2) into the same slot
 
   int turn = 0;  // (f - first_frame) % D
   for (int f = first_frame; f <= last_frame; ++f) {
@@ -682,6 +687,171 @@ __global__ __launch_bounds__(TAIL_NT) void labelprop_tail_kernel(const float *__
   const int tid = threadIdx.x, NM = N * M, n = t0 + blockIdx.x;
   const float *Wn = W + (long)(n - first_frame) * knn * N;
   const int32_t *In = I + (long)(n - first_frame) * knn * N;
+  const int row_lim = n * N - 1;
+  for (int it = tid; it < NM; it += TAIL_NT) {
+    const int q = it / M, c = it % M;
+    float p = 0.f;
+    for (int j0 = 0; j0 < knn; j0 += TAIL_CH) {
+      int idx[TAIL_CH];
+      float w[TAIL_CH], v[TAIL_CH];
+#pragma unroll
+      for (int u = 0; u < TAIL_CH; ++u) {
+        const int jj = min(j0 + u, knn - 1);
+        idx[u] = min(max(In[jj * N + q], 0), row_lim);
+        w[u] = Wn[jj * N + q];
+      }
+#pragma unroll
+      for (int u = 0; u < TAIL_CH; ++u) v[u] = L[(long)idx[u] * M + c];
+#pragma unroll
+      for (int u = 0; u < TAIL_CH; ++u)
+        if (j0 + u < knn) p += v[u] * w[u];
+    }
+    L[((long)n * N + q) * M + c] = p;
+    slot[it] = p;
+  }
+  __syncthreads();
+  for (int q = tid; q < N; q += TAIL_NT) {
+    const float *row = slot + q * M;
+    float bv = row[0];
+    int bi = 0;
+    for (int c = 1; c < M; ++c) {
+      const float x = row[c];
+      if (x > bv) { bv = x; bi = c; }
+    }
+    pred[(long)q * T + n] = (float)bi;
+  }
+}
+
+// ---- hyper-parameter sweeps (crw_labelprop_sweep_weights, crw_labelprop_propagate_batch) ----------------------------------------
+// The lists of knn = k are the first k entries of the lists of any larger knn (selection is sequential: highest score, then lowest
+// candidate index), so ONE selection at kcap = max(knns) (crw_labelprop_topk_scores: the logits instead of their softmax) serves
+// every knn of a (radius, temp) pair; what is per knn is the softmax over the first knn logits -- the epilogues' expression, in
+// their order: vmax = v[0]; ssum over j = 0 .. knn-1 (a prefix of the running sum); expf(v - vmax) / ssum.
+constexpr int SW_MAXK = 16;  // knn values per call
+struct SweepKnns {
+  int n, k[SW_MAXK];
+};
+__global__ __launch_bounds__(256) void labelprop_sweep_weights_kernel(const float *__restrict__ V, int F, int kcap, int N, int kmax,
+                                                                      SweepKnns ks, float *__restrict__ W) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;  // (frame, query)
+  if (e >= (long)F * N) return;
+  const int f = (int)(e / N), q = (int)(e - (long)f * N);
+  const float *v = V + (long)f * kcap * N + q;
+  const float vmax = v[0];
+  float S[SW_MAXK];
+#pragma unroll
+  for (int i = 0; i < SW_MAXK; ++i) S[i] = 1.f;
+  float ssum = 0.f;
+  for (int j = 0; j < kmax; ++j) {
+    const float x = v[(long)j * N];
+    ssum += (x == -INFINITY) ? 0.f : expf(x - vmax);
+#pragma unroll
+    for (int i = 0; i < SW_MAXK; ++i)
+      if (i < ks.n && ks.k[i] == j + 1) S[i] = ssum;
+  }
+  for (int j = 0; j < kmax; ++j) {
+    const float x = v[(long)j * N];
+    const float ex = expf(x - vmax);
+#pragma unroll
+    for (int i = 0; i < SW_MAXK; ++i)
+      if (i < ks.n) W[(((long)i * F + f) * kmax + j) * N + q] = (j < ks.k[i] && x != -INFINITY) ? ex / S[i] : 0.f;
+  }
+}
+
+// G configurations' chained frames first_frame .. last_frame, a workgroup per configuration (the chains run side by side on different
+// CUs, so a chain is kept simple: no roles, one barrier per frame).  Frame 0 and the most recent R frames' soft labels sit in LDS
+// (the ring of labelprop_gather_lds_kernel, same addressing; R covers every chained frame where they fit), older ones and the
+// caller's frames before first_frame come from L in global memory.  The lists are read from global memory PB_CH neighbours at a
+// time (they do not depend on the chain); the sum runs in neighbour order from 0.f like every other propagation kernel here, and
+// padding slots (weight exactly 0, a valid index) leave it as it is: p + v * 0.f == p for the finite labels.
+constexpr int PB_CH = 16;
+__global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float *__restrict__ seed, const float *__restrict__ W,
+                                                                     const int32_t *__restrict__ I, long i_stride, int T, int N, int M,
+                                                                     int knn, int first_frame, int last_frame, float *L,
+                                                                     float *__restrict__ pred, int R) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int tid = threadIdx.x, nt = (int)blockDim.x, NM = N * M, KN = knn * N, g = blockIdx.x;
+  W += (long)g * (T - first_frame) * KN;
+  I += (long)g * i_stride;
+  L += (long)g * T * NM;
+  pred += (long)g * N * T;
+  float *l0 = sm, *ring = l0 + NM;  // [NM], [R][NM]
+  for (int it = tid; it < NM; it += nt) {
+    float v;
+    if (seed) {
+      v = seed[it / M] == (float)(it % M) ? 1.f : 0.f;
+      st_l2(L + it, v);
+    } else {
+      v = ld_l2(L + it);
+    }
+    l0[it] = v;
+  }
+  if (seed)
+    for (int q = tid; q < N; q += nt) pred[(long)q * T] = seed[q];
+  __syncthreads();
+  const int RNM = R * NM;
+  for (int n = first_frame; n <= last_frame; ++n) {
+    const float *Wn = W + (long)(n - first_frame) * KN;
+    const int32_t *In = I + (long)(n - first_frame) * KN;
+    // frames [lo_f, n - 1] live in the ring; a frame f sits at flat offset (f % R) * NM
+    const int lo_f = max(first_frame, n - R + 1);
+    const int lo_idx = lo_f * N;               // first label-list row that is in the ring
+    const int epoch_base = (n / R - 1) * RNM;  // flat offset of the older of the (at most) two ring epochs in view
+    const int row_lim = n * N - 1;
+    float *slot = ring + (n % R) * NM;
+    for (int it = tid; it < NM; it += nt) {
+      const int q = it / M, c = it % M;
+      float p = 0.f;
+      for (int j0 = 0; j0 < knn; j0 += PB_CH) {
+        int idx[PB_CH];
+        float w[PB_CH], v[PB_CH];
+#pragma unroll
+        for (int u = 0; u < PB_CH; ++u) {
+          const int jj = min(j0 + u, knn - 1);
+          idx[u] = min(max(In[jj * N + q], 0), row_lim);  // in range whatever the lists hold (topk: < min(n, cxt + 1) * N)
+          w[u] = Wn[jj * N + q];
+        }
+#pragma unroll
+        for (int u = 0; u < PB_CH; ++u) {
+          // frame 0 sits in l0 = sm[0, NM), the ring behind it; a label older than the ring comes from global memory
+          int off = idx[u] * M + c - epoch_base;
+          if (off >= RNM) off -= RNM;
+          const bool first = idx[u] < N, old = !first && idx[u] < lo_idx;
+          const int a = first ? idx[u] * M + c : (old ? 0 : NM + off);
+          v[u] = sm[a];
+          if (old) v[u] = ld_l2(L + (long)idx[u] * M + c);
+        }
+#pragma unroll
+        for (int u = 0; u < PB_CH; ++u)
+          if (j0 + u < knn) p += v[u] * w[u];
+      }
+      st_l2(L + ((long)n * N + q) * M + c, p);
+      slot[it] = p;
+    }
+    __syncthreads();  // frame n's labels are in LDS; its slot is next written R frames (barriers) later
+    for (int q = tid; q < N; q += nt) {
+      const float *row = slot + q * M;
+      float bv = row[0];
+      int bi = 0;
+      for (int c = 1; c < M; ++c) {
+        const float x = row[c];
+        if (x > bv) { bv = x; bi = c; }
+      }
+      pred[(long)q * T + n] = (float)bi;
+    }
+  }
+}
+
+// labelprop_tail_kernel over (frame, configuration)
+__global__ __launch_bounds__(TAIL_NT) void labelprop_tail_batch_kernel(const float *__restrict__ W, const int32_t *__restrict__ I,
+                                                                       long i_stride, int T, int N, int M, int knn, int first_frame,
+                                                                       int t0, float *L, float *__restrict__ pred) {
+  extern __shared__ __attribute__((aligned(16))) float slot[];  // [N * M]
+  const int tid = threadIdx.x, NM = N * M, n = t0 + blockIdx.x, g = blockIdx.y;
+  const float *Wn = W + ((long)g * (T - first_frame) + (n - first_frame)) * knn * N;
+  const int32_t *In = I + (long)g * i_stride + (long)(n - first_frame) * knn * N;
+  L += (long)g * T * NM;
+  pred += (long)g * N * T;
   const int row_lim = n * N - 1;
   for (int it = tid; it < NM; it += TAIL_NT) {
     const int q = it / M, c = it % M;
@@ -782,10 +952,12 @@ __global__ __launch_bounds__(XENT_NT) void xent_metric_frame_kernel(const float 
 
 using namespace crw;
 
-extern "C" {
+namespace {
 
-int crw_labelprop_topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int knn, int first_frame,
-                            int grid_w, float *W, int32_t *I, crw_stream_t stream) {
+// one route choice for both output modes: raw = 0 softmax weights (crw_labelprop_topk_grid), 1 the selected logits
+// (crw_labelprop_topk_scores) -- the same kernels, the same selection, another last line of the epilogue
+int topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int knn, int first_frame, int grid_w, float *W,
+              int32_t *I, int raw, crw_stream_t stream) {
   crw::clear_stale_error();
   if (!ehat || !W || !I || T < 2 || N < 1 || C < 1 || cxt_size < 1 || radius < 1 || knn < 1 || knn > MAX_KNN ||
       !(temp > 0.f) || first_frame < 1 || first_frame >= T || grid_w < 1 || N % grid_w)
@@ -801,19 +973,33 @@ int crw_labelprop_topk_grid(const float *ehat, int T, int N, int C, int cxt_size
   const bool column = grid_w == 1 && !valu && N >= TK_Q && (((uintptr_t)ehat) & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
   if (column && (C == 64 || C == 128 || C == 256) && maxcand <= 64L * TK_NV && (size_t)TK_Q * maxcand * 4 <= 150 * 1024) {
-    if (C == 64) return launch_topk_mfma<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, s);
-    if (C == 128) return launch_topk_mfma<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, s);
-    return launch_topk_mfma<16>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, s);
+    if (C == 64) return launch_topk_mfma<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, s);
+    if (C == 128) return launch_topk_mfma<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, s);
+    return launch_topk_mfma<16>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, s);
   }
   // longer lists (radius 30 / 60 at 80 - 100 context frames): any number of chunks; a single frame's band must fit one chunk
   if (column && (C == 64 || C == 128) && max_bi <= TK_LONG_CAND) {
-    if (C == 64) return launch_topk_mfma_long<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, s);
-    return launch_topk_mfma_long<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, s);
+    if (C == 64) return launch_topk_mfma_long<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, s);
+    return launch_topk_mfma_long<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, s);
   }
   if (lds > 60 * 1024) return CRW_EINVAL;
   hipLaunchKernelGGL(labelprop_topk_kernel, dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T,
-                     N, C, cxt_size, radius, temp, knn, first_frame, grid_w, W, I);
+                     N, C, cxt_size, radius, temp, knn, first_frame, grid_w, W, I, raw);
   return check_launch();
+}
+
+}  // namespace
+
+extern "C" {
+
+int crw_labelprop_topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int knn, int first_frame,
+                            int grid_w, float *W, int32_t *I, crw_stream_t stream) {
+  return topk_grid(ehat, T, N, C, cxt_size, radius, temp, knn, first_frame, grid_w, W, I, 0, stream);
+}
+
+int crw_labelprop_topk_scores(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int kcap, int first_frame,
+                              int grid_w, float *V, int32_t *I, crw_stream_t stream) {
+  return topk_grid(ehat, T, N, C, cxt_size, radius, temp, kcap, first_frame, grid_w, V, I, 1, stream);
 }
 
 int crw_labelprop_topk(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int knn,
@@ -894,6 +1080,63 @@ int crw_labelprop_propagate(const float *seed, const float *W, const int32_t *I,
   }
   if (t0 < T) {
     hipLaunchKernelGGL(labelprop_tail_kernel, dim3(T - t0), dim3(TAIL_NT), (size_t)NM * 4, s, W, I, T, N, M, knn, first_frame, t0, L, pred);
+    return check_launch();
+  }
+  return CRW_OK;
+}
+
+int crw_labelprop_sweep_weights(const float *V, int F, int kcap, int N, const int *knns, int nk, float *W, crw_stream_t stream) {
+  crw::clear_stale_error();
+  if (!V || !W || !knns || F < 1 || N < 1 || kcap < 1 || kcap > MAX_KNN || nk < 1 || nk > SW_MAXK) return CRW_EINVAL;
+  SweepKnns ks;
+  ks.n = nk;
+  int kmax = 0;
+  for (int i = 0; i < SW_MAXK; ++i) {
+    ks.k[i] = i < nk ? knns[i] : 0;
+    if (i < nk && (knns[i] < 1 || knns[i] > kcap)) return CRW_EINVAL;
+    if (ks.k[i] > kmax) kmax = ks.k[i];
+  }
+  const long FN = (long)F * N;
+  if (FN > (1L << 30)) return CRW_EINVAL;
+  hipLaunchKernelGGL(labelprop_sweep_weights_kernel, dim3((unsigned)((FN + 255) / 256)), dim3(256), 0, (hipStream_t)stream, V, F, kcap, N,
+                     kmax, ks, W);
+  return check_launch();
+}
+
+int crw_labelprop_propagate_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M,
+                                  int knn, int first_frame, int cxt_size, float *L, float *pred, crw_stream_t stream) {
+  crw::clear_stale_error();
+  if (!W || !I || !L || !pred || G < 1 || G > 65535 || T < 2 || N < 1 || M < 1 || knn < 1 || knn > MAX_KNN || first_frame < 1 ||
+      first_frame >= T || cxt_size < 1)
+    return CRW_EINVAL;
+  const long NM = (long)N * M;
+  if ((long)T * N >= (1L << 30) / M || NM * 4 > 30 * 1024) return CRW_EINVAL;  // 32-bit label offsets; frame 0 + a ring of >= 4 frames in LDS
+  // the split of crw_labelprop_propagate: frames from t0 on read no label of this call
+  const int t0 = (T - first_frame == 1) ? first_frame : (first_frame > cxt_size + 1 ? first_frame : (cxt_size + 1 < T ? cxt_size + 1 : T));
+  const int last = t0 - 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (last >= first_frame || seed) {  // (no chained frame: the kernel writes frame 0 from the seed and returns)
+    long R = (150L * 1024) / (4 * NM) - 1;
+    if (R > last + 1) R = last + 1;
+    if (R < 2) R = 2;
+    static bool attr = false;
+    if (!attr) {
+      if (hipFuncSetAttribute((const void *)labelprop_chain_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
+          hipSuccess) {
+        g_last_hip_error = (int)hipGetLastError();
+        return CRW_EHIP;
+      }
+      attr = true;
+    }
+    const int nt = (int)(NM >= 1024 ? 1024 : (NM + 63) / 64 * 64);
+    hipLaunchKernelGGL(labelprop_chain_batch_kernel, dim3(G), dim3(nt), (size_t)(4 * NM * (R + 1)), s, seed, W, I, (long)i_stride, T, N, M,
+                       knn, first_frame, last, L, pred, (int)R);
+    const int rc = check_launch();
+    if (rc != CRW_OK) return rc;
+  }
+  if (t0 < T) {
+    hipLaunchKernelGGL(labelprop_tail_batch_kernel, dim3(T - t0, G), dim3(TAIL_NT), (size_t)NM * 4, s, W, I, (long)i_stride, T, N, M, knn,
+                       first_frame, t0, L, pred);
     return check_launch();
   }
   return CRW_OK;

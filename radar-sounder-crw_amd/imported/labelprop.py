@@ -7,7 +7,12 @@ Two entry points:
   * ``propagate_all(feats, seed, nclasses)`` -- whole radargram in two launches (what
     ``utils.propagate`` uses): affinities/top-k of every frame at once, then one sequential
     gather kernel.  Both produce identical label maps.
+
+``LabelPropSweep`` is ``propagate_all`` for a whole grid of (RADIUS, TEMP, KNN) settings on the same features -- the grid of the
+reference's scripts/launch/launch_test_batch.sh -- sharing what does not depend on the setting.
 """
+import os
+
 import torch
 
 import crw_hip
@@ -76,3 +81,62 @@ class LabelPropVOS_CRW(object):
         Wt, It = crw_hip.labelprop_topk(feats, self.cxt_size, self.radius, self.temperature, self.topk, first_frame=1, grid_w=grid_w)
         L, pred = crw_hip.labelprop_gather(seed.float().contiguous(), Wt, It, T, N, nclasses, first_frame=1, cxt_size=self.cxt_size)
         return pred, L
+
+
+class LabelPropSweep(object):
+    """Label propagation for every (RADIUS, TEMP, KNN) of a grid at one CXT_SIZE -- scripts/launch/launch_test_batch.sh runs
+    test_all.py once per point of such a grid.  ``configs``: the ``cfg`` dicts of ``LabelPropVOS_CRW`` in that script's loop order
+    (radius outermost, knn innermost); ``propagate_all`` returns the label map of every configuration, each exactly that of
+    ``LabelPropVOS_CRW(configs[g]).propagate_all``."""
+
+    def __init__(self, cxt_size, radii, temps, knns):
+        self.cxt_size = int(cxt_size)
+        self.radii, self.temps, self.knns = [int(r) for r in radii], [float(t) for t in temps], [int(k) for k in knns]
+        if not (self.radii and self.temps and self.knns):
+            raise ValueError("radii, temps and knns must each hold at least one value")
+        if min(self.knns) < 1 or len(self.knns) > 16:
+            raise ValueError("knns: 1 ... 16 values >= 1")
+        self.configs = [dict(CXT_SIZE=self.cxt_size, RADIUS=r, TEMP=t, KNN=k)
+                        for r in self.radii for t in self.temps for k in self.knns]
+
+    def __len__(self):
+        return len(self.configs)
+
+    def _check_grid(self, h, w):
+        if max(self.knns) > h * w:
+            raise RuntimeError(f"KNN={max(self.knns)} exceeds the number of nodes per frame ({h * w}); "
+                               "torch.topk in the reference raises for the first frame as well")
+
+    def propagate_all(self, feats, seed, nclasses, grid_w=1):
+        """feats [T,N,C] (normalised features), seed [N] float class ids of frame 0 -> pred [G,N,T] float class ids, G =
+        len(configs).
+
+        Per (radius, temp): ONE selection at kcap = max(knns) (`crw_hip.labelprop_topk_scores`; the lists of a smaller knn are
+        its first entries) and one `labelprop_sweep_weights` (the softmax of every knn, shorter lists padded with zero weights).
+        Then ONE `labelprop_propagate_batch` over all G configurations, a workgroup per configuration (it holds W and I
+        [G, T-1, kmax, N] and L [G, T*N, M] at once: 0.3 GB for the 60-point grid at [T, N] = [100, 190]).
+        CRW_SWEEP_PER_CONFIG=1 (read per call): a loop of `LabelPropVOS_CRW.propagate_all` over the configurations on the same
+        features instead -- the A/B arm of tools/sweep_timing.py, and the fallback."""
+        T, N, C = feats.shape
+        self._check_grid(N // grid_w, grid_w)
+        seed = seed.float().contiguous()
+        if os.environ.get("CRW_SWEEP_PER_CONFIG") == "1":
+            return torch.stack([LabelPropVOS_CRW(cfg).propagate_all(feats, seed, nclasses, grid_w=grid_w)[0] for cfg in self.configs])
+        nk, kmax, F = len(self.knns), max(self.knns), T - 1
+        P = len(self.radii) * len(self.temps)
+        W = torch.empty(P, nk, F, kmax, N, device=feats.device, dtype=torch.float32)
+        I = torch.empty(P, F, kmax, N, device=feats.device, dtype=torch.int32)
+        V = torch.empty(F, kmax, N, device=feats.device, dtype=torch.float32)
+        p = 0
+        for r in self.radii:
+            for t in self.temps:
+                crw_hip.labelprop_topk_scores(feats, self.cxt_size, r, t, kmax, first_frame=1, grid_w=grid_w, out=(V, I[p]))
+                crw_hip.labelprop_sweep_weights(V, self.knns, out=W[p])
+                p += 1
+        if P == 1:
+            Ig = I[0]  # one list of indices shared by every configuration
+        else:
+            Ig = I[:, None].expand(P, nk, F, kmax, N).reshape(P * nk, F, kmax, N)  # (a copy: the batch takes one stride)
+        _, pred = crw_hip.labelprop_propagate_batch(seed, W.view(P * nk, F, kmax, N), Ig, T, N, nclasses, first_frame=1,
+                                                    cxt_size=self.cxt_size)
+        return pred

@@ -25,6 +25,10 @@ Label maps are upsampled to pixels with nearest-neighbour interpolation like the
 ``evaluate`` is the end of the same script (test_all.py:161-187): the ``--remove_unc`` masks and the report the reference prints,
 from one pass of the HIP kernel ``crw_confusion`` over the label map where ``segment`` left it (``metrics.Report``).
 
+``segment_sweep`` / ``evaluate_sweep`` are ``segment`` / ``evaluate`` for a grid of (radius, temp, knn) settings -- what
+scripts/launch/launch_test_batch.sh does with one test_all.py run per setting -- with the encoder, the metric, the change points and
+the whole control flow run once (``utils.propagate_sweep``, ``imported.labelprop.LabelPropSweep``).
+
 ``segment_radargrams`` is the other family of the reference's drivers: scripts/test/test_mc1.py, test_mc3.py and
 test_sharad.py (``main(args)``), three whole radargrams held in memory, one item each; their defaults are in ``DRIVERS``.
 """
@@ -32,7 +36,7 @@ import torch
 import torch.nn.functional as TF
 
 import crw_hip
-from utils import propagate
+from utils import propagate, propagate_sweep
 
 
 def _upsample(pred, rows, cols):
@@ -123,6 +127,92 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     return dict(pred=final, forward=forward, xent=xents, change_idx=changes)
 
 
+def merge_reverse_batch(final_pred, pred_rev, dataset_id):
+    """`merge_reverse` on [G, rows, cols] maps, configuration by configuration."""
+    G = pred_rev.shape[0]
+    mask = pred_rev == 2
+    if dataset_id == 1:
+        mask = torch.logical_and(mask, final_pred != 3)
+        mask = torch.logical_and(mask, torch.all(pred_rev != 4, dim=1, keepdim=True))
+    elif dataset_id == 3:
+        mask = mask.clone()
+        mask.view(G, -1)[:, :mask[0].numel() // 2] = False
+    elif dataset_id != 0:
+        raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
+    out = final_pred.clone()
+    out[mask] = 2
+    return out
+
+
+def _upsample_batch(pred, rows, cols):
+    """[G, N, T] node labels -> [G, rows, cols] int8 pixel labels (nearest, the dtype the reference saves)."""
+    return TF.interpolate(pred[:, None].float(), size=(rows, cols), mode='nearest')[:, 0].to(torch.int8)
+
+
+@torch.no_grad()
+def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size, overlap, pos_embed=False,
+                  correction=False, use_last=False, dataset_id=0, device='cuda'):
+    """`segment` for every configuration of ``sweep`` (LabelPropSweep, G = len(sweep.configs)) with its control flow run ONCE:
+    which items are corrected, at which length (`get_smaller_item` and its permanent shortening of the dataset) and what the
+    reverse pass sees depend on the features alone, never on (radius, temp, knn).  Same exception policy in the correction.
+    -> dict(pred [G, rows, cols] int8 (after the optional reverse merge), forward [G, rows, cols] int8, xent list, change_idx
+            list, configs); pred[g] / forward[g] are `segment`'s maps for ``sweep.configs[g]`` (on a fresh dataset)."""
+    if dataset_id not in (0, 1, 3) and use_last:
+        raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
+    T, (H, W), (oh, ow) = seq_length, patch_size, overlap
+    N = dataset[0].shape[1]
+    rg_len = T * (W - ow) + ow
+    rg_h = N * (H - oh) + oh
+    idx = list(range(0, len(dataset), T))
+    n_rg = min(len(idx), seg.shape[-1] // rg_len)
+    idx = idx[:n_rg]
+    seg = seg[:, :n_rg * rg_len].to(device)
+    rows = seg.shape[0]
+
+    maps, xents, changes = [], [], []
+    for t, i in enumerate(idx):
+        seq = dataset[i].to(device)
+        seg_ref = seg[:rg_h, rg_len * t:rg_len * t + W]
+        pred, xent, change = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False)
+        maps.append(_upsample_batch(pred, rows, rg_len))
+        xents.append(xent)
+        changes.append(change)
+
+    if correction:
+        for t, change in enumerate(changes):
+            if change is None:
+                continue
+            small = T - change
+            px = small * (W - ow)
+            try:  # the policy of `segment`: data errors are skipped, failures of the HIP path are not
+                seq = dataset.get_smaller_item(idx[t], small).to(device)
+                seg_ref = seg[:, rg_len * t + rg_len - px:rg_len * t + rg_len - px + W]
+                pred, _, _ = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False)
+                maps[t][:, :, rg_len - px:] = _upsample_batch(pred, rows, px)
+            except crw_hip.CrwError as e:
+                if e.device_failure:
+                    raise
+            except torch.AcceleratorError:
+                raise
+            except Exception:
+                pass
+
+    forward = torch.cat(maps, dim=2)
+    final = forward
+    if use_last:
+        rev_maps = []
+        seg_rev = torch.flip(seg.unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
+        for t, i in enumerate(idx):
+            seq = dataset[i].to(device)
+            seg_ref = seg_rev[:, rg_len * t:rg_len * t + W]
+            pred, _, _ = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=True)
+            rev_maps.append(_upsample_batch(pred, rows, rg_len))
+        rev = torch.cat(rev_maps, dim=2).unfold(2, rg_len, rg_len)
+        rev = torch.flip(rev, (-1,)).reshape(rev.shape[0], rows, -1)
+        final = merge_reverse_batch(forward, rev, dataset_id)
+    return dict(pred=final, forward=forward, xent=xents, change_idx=changes, configs=list(sweep.configs))
+
+
 @torch.no_grad()
 def segment_one(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap, pos_embed=False, device='cuda'):
     """``main(args)`` of the reference's scripts/test/test.py (:45-84) without the plots: the FIRST radargram only, forward pass
@@ -183,6 +273,39 @@ def evaluate(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None
     if dropped[1]:
         raise crw_hip.LabelError(dropped[1], K)
     return Report(counts, dropped)
+
+
+def evaluate_sweep(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None):
+    """`evaluate` for the G maps of `segment_sweep` (pred [G, rows, cols], int8 on the device as it leaves them) -> G
+    ``metrics.Report``: G `crw_hip.confusion` calls queued back to back, ONE copy of all counts to the host at the end.  Same mask
+    rules; a label outside 0 ... K-1 that survives the mask in any map raises ``crw_hip.LabelError``."""
+    from metrics import Report
+    if dataset_id not in (0, 1, 3):
+        raise ValueError(f'no report rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
+    K = NCLASSES[dataset_id] if nclasses is None else int(nclasses)
+    if pred.dim() < 2 or pred[0].numel() != seg.numel():
+        raise ValueError(f'pred {tuple(pred.shape)} must be G maps covering the pixels of seg {tuple(seg.shape)}')
+    seg = seg.to(pred.device)
+    mask = {}
+    if remove_unc and dataset_id == 0:
+        if unc_seg is None:
+            raise ValueError('dataset 0 with remove_unc needs unc_seg (the dataset-2 reference map, same columns)')
+        if unc_seg.numel() != seg.numel():
+            raise ValueError(f'unc_seg {tuple(unc_seg.shape)} and seg {tuple(seg.shape)} must cover the same pixels')
+        mask = dict(aux=unc_seg.to(pred.device), ignore_aux=4)
+    elif remove_unc and dataset_id == 1:
+        mask = dict(ignore_gt=5, ignore_pred=5)
+    outs = [crw_hip.confusion(seg, p, K, **mask) for p in pred]
+    if not outs:
+        return []
+    host = torch.stack([torch.cat([c.reshape(-1), d]) for c, d in outs]).cpu()  # [G, K*K + 2]
+    reports = []
+    for row in host:
+        dropped = [int(v) for v in row[K * K:]]
+        if dropped[1]:
+            raise crw_hip.LabelError(dropped[1], K)
+        reports.append(Report(row[:K * K].view(K, K), dropped))
+    return reports
 
 
 # the reference's three per-dataset drivers (scripts/test/test_mc1.py:19-30, test_mc3.py:19-33, test_sharad.py:19-32): argparse

@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""Label-propagation parameter sweep -- what the reference's scripts/launch/launch_test_batch.sh does with one
+scripts/test/test_all.py run per point of the grid R = 45 50 55 60 65, T = 0.1 0.01 0.001, K = 15 20 25 30 -- in ONE pass over the
+dataset: the encoder, the metric, the change points and the control flow of the evaluation run once
+(``inference.segment_sweep``), the top-k lists once per (radius, temp), and the configurations' label propagations side by side
+(``imported.labelprop.LabelPropSweep``); then one report per configuration (``inference.evaluate_sweep``).
+
+    python radar-sounder-crw_amd/scripts/segment_sweep.py --dataset 3 --model_path sharad16_3.pt --use_last true
+    python radar-sounder-crw_amd/scripts/segment_sweep.py --synthetic 200 4800 --dataset 0 -r 5 10 -t 0.1 0.01 -k 5 10 --report_json s.json
+
+``segment_all.py``'s flags (not ``--single``), with ``-r`` / ``-t`` / ``-k`` taking lists (default: the grid above).  Prints one
+line per configuration (radius, temp, knn, accuracy, macro F1, weighted F1, mean IoU), then the best configuration by ``--select``
+(default macro F1; ties: the first in the grid's order) with its full report and matrix in the reference's text.  ``--reports``
+prints every full report; ``--report_json FILE`` writes all of them with the grid; ``--save_maps`` writes
+``predicted_map_r{r}_t{t}_k{k}.pt`` (int8, the forward map test_all.py saves) per configuration.
+CRW_SWEEP_PER_CONFIG=1: the label propagation as a loop over the configurations (same maps; the A/B arm)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import torch
+
+import inference
+import segment_all
+from segment_drivers import _flag, load_encoder
+from utils import create_model
+
+# scripts/launch/launch_test_batch.sh
+GRID = dict(radius=(45, 50, 55, 60, 65), temp=(0.1, 0.01, 0.001), knn=(15, 20, 25, 30))
+SELECT = {'macro_f1': lambda r: r.macro['f1'], 'weighted_f1': lambda r: r.weighted['f1'], 'accuracy': lambda r: r.accuracy,
+          'mean_iou': lambda r: r.mean_iou}
+
+
+def get_args_parser():
+    p = argparse.ArgumentParser('CRW label-propagation sweep (launch_test_batch.sh over test_all.py)', add_help=True)
+    p.add_argument('--model', default=None, type=int, help='0=CNN,1=Resnet18')
+    p.add_argument('--dataset', default=None, type=int, help='0=MCORDS1,1=Miguel,3=SHARAD')
+    p.add_argument('--patch_size', default=None, nargs=2, type=int)
+    p.add_argument('--seq_length', default=None, type=int)
+    p.add_argument('--overlap', default=None, nargs='+', type=int)
+    p.add_argument('-c', '--cxt_size', default=None, type=int)
+    p.add_argument('-r', '--radius', default=list(GRID['radius']), nargs='+', type=int)
+    p.add_argument('-t', '--temp', default=list(GRID['temp']), nargs='+', type=float)
+    p.add_argument('-k', '--knn', default=list(GRID['knn']), nargs='+', type=int)
+    p.add_argument('--model_path', default=None, help='encoder state_dict (required unless --synthetic)')
+    p.add_argument('--output_folder', default='resources/output/')
+    p.add_argument('--pos_embed', default=False, type=_flag)
+    p.add_argument('--remove_unc', default=True, type=_flag, help='remove the uncertainty class from the report')
+    p.add_argument('--flip', default=False, type=_flag, help='test on the flipped radargram')
+    p.add_argument('--use_last', default=False, type=_flag, help='reverse pass seeded from the last sample, merged')
+    p.add_argument('--dataset_full', default=True, type=_flag)
+    p.add_argument('--correction', default=False, type=_flag, help='change-point detection and correction')
+    p.add_argument('--data_path', default=None, help='H x W radargram .pt file')
+    p.add_argument('--seg_path', default=None, help='reference segmentation .pt file')
+    p.add_argument('--unc_seg_path', default=None, help="dataset 0's map with the uncertain class 4 (the reference's dataset id 2)")
+    p.add_argument('--synthetic', default=None, nargs=2, type=int, metavar=('H', 'W'))
+    p.add_argument('--select', default='macro_f1', choices=sorted(SELECT), help='the score the best configuration is picked by')
+    p.add_argument('--reports', action='store_true', help='print the full report of every configuration')
+    p.add_argument('--report_json', default=None, metavar='FILE')
+    p.add_argument('--save_maps', action='store_true', help='save every predicted_map_r{r}_t{t}_k{k}.pt (int8)')
+    return p
+
+
+def with_defaults(args):
+    """segment_all's defaults and checks for everything but the three swept flags."""
+    grid = args.radius, args.temp, args.knn
+    args.single = False
+    args.radius = args.temp = args.knn = 0  # (set: segment_all.with_defaults leaves them alone)
+    args = segment_all.with_defaults(args)
+    args.radius, args.temp, args.knn = grid
+    return args
+
+
+def report_dict(report):
+    d = report.as_dict()
+    d.update(labels=report.labels, matrix=report.matrix.tolist(), dropped=dict(masked=report.dropped[0], invalid=report.dropped[1]))
+    return d
+
+
+def main(args):
+    from imported.labelprop import LabelPropSweep
+    tim = time.time()
+    args = with_defaults(args)
+    print(args)
+    device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+    if args.model_path is not None:
+        encoder = load_encoder(args.model, args.model_path, device)
+    else:
+        encoder = create_model(args.model, args.pos_embed).to(device)
+    dataset, nclasses, seg, unc_seg = segment_all.load_data(args)
+    sweep = LabelPropSweep(args.cxt_size, args.radius, args.temp, args.knn)
+    T, W, ow = args.seq_length, args.patch_size[1], args.overlap[1]
+    rg_len = T * (W - ow) + ow
+    print('Num of radargrams:', seg.shape[-1] // rg_len, 'Radargram length:', rg_len, 'Configurations:', len(sweep.configs))
+    correction = args.correction
+    if correction and not args.dataset_full:
+        print('Correction skipped: it needs --dataset_full true (the reference skips it silently here)')
+        correction = False
+    out = inference.segment_sweep(dataset, seg, encoder, sweep, nclasses, T, args.patch_size, args.overlap, pos_embed=args.pos_embed,
+                                  correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device)
+    if correction:
+        print('Change point for each radargram:', out['change_idx'])
+    final, forward = out['pred'], out['forward']
+    cols = final.shape[-1]
+    if args.save_maps:
+        os.makedirs(args.output_folder, exist_ok=True)
+        for cfg, m in zip(sweep.configs, forward):
+            torch.save(m.clone(), os.path.join(args.output_folder, f"predicted_map_r{cfg['RADIUS']}_t{cfg['TEMP']}_k{cfg['KNN']}.pt"))
+    if device.type == 'cuda':
+        torch.cuda.synchronize()
+    t_inference = time.time() - tim
+    print('Time elapsed (inference only):', t_inference)
+    print('Computing reports ...')
+    print('')
+    reports = inference.evaluate_sweep(final, seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
+                                       unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses)
+    print('{:>6} {:>7} {:>4} {:>9} {:>9} {:>11} {:>9}'.format('radius', 'temp', 'knn', 'accuracy', 'macro f1', 'weighted f1', 'mean iou'))
+    for cfg, r in zip(sweep.configs, reports):
+        print('{:>6} {:>7g} {:>4} {:>9.4f} {:>9.4f} {:>11.4f} {:>9.4f}'.format(cfg['RADIUS'], cfg['TEMP'], cfg['KNN'], r.accuracy,
+                                                                               r.macro['f1'], r.weighted['f1'], r.mean_iou))
+        if args.reports:
+            print(r)
+            print(r.matrix_str())
+            print('')
+    scores = [float(SELECT[args.select](r)) for r in reports]
+    best = max(range(len(scores)), key=lambda g: (scores[g], -g))
+    cfg = sweep.configs[best]
+    print(f"\nBest by {args.select}: radius {cfg['RADIUS']} temp {cfg['TEMP']:g} knn {cfg['KNN']} ({scores[best]:.4f})\n")
+    print(reports[best])
+    print(reports[best].matrix_str())
+    t_all = time.time() - tim
+    print('\nTime elapsed (inference + metrics):', t_all)
+    if args.report_json:
+        d = dict(grid=dict(cxt_size=args.cxt_size, radius=list(args.radius), temp=list(args.temp), knn=list(args.knn)),
+                 select=args.select, best=dict(index=best, radius=cfg['RADIUS'], temp=cfg['TEMP'], knn=cfg['KNN'], score=scores[best]),
+                 configs=[dict(radius=c['RADIUS'], temp=c['TEMP'], knn=c['KNN'], score=s, report=report_dict(r))
+                          for c, s, r in zip(sweep.configs, scores, reports)],
+                 pixels=int(final[0].numel()), map_shape=list(final.shape[1:]), change_idx=out['change_idx'],
+                 elapsed_inference_s=t_inference, elapsed_total_s=t_all, dataset=args.dataset, remove_unc=args.remove_unc)
+        with open(args.report_json, 'w') as f:
+            json.dump(d, f, indent=1)
+    return reports, best
+
+
+if __name__ == '__main__':
+    torch.manual_seed(11)  # the scripts seed at import (test_all.py:14)
+    main(get_args_parser().parse_args())

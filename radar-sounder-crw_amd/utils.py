@@ -105,10 +105,9 @@ def change_point(xent, diffs=None):
         return None
 
 
-@torch.no_grad()
-def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last):
-    """seq [T,N,h,w]; seg_ref [rows, w] class ids of the first (or last) frame; model: encoder;
-    lp: LabelPropVOS_CRW  ->  (labels [N,T] float, xent [N,T-1] (CPU), change_idx | None)."""
+def _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last):
+    """The front of `propagate` / `propagate_sweep`: ONE encoder call on the whole item (the batch matters for the `Resnet`, whose
+    train-mode BatchNorm statistics are the batch's), normalised features [T,N,C] and the seed labels [N]."""
     T, N, H, W = seq.shape
     if use_last:
         seq = torch.flip(seq, (0,))
@@ -117,7 +116,15 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last):
         x = pos_embed(x)
     emb = model(x).reshape(T, N, -1).float().contiguous()
     feats = crw_hip.normalize(emb)
-    seed = seed_labels(seg_ref.to(feats.device), N)
+    return feats, seed_labels(seg_ref.to(feats.device), N)
+
+
+@torch.no_grad()
+def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last):
+    """seq [T,N,h,w]; seg_ref [rows, w] class ids of the first (or last) frame; model: encoder;
+    lp: LabelPropVOS_CRW  ->  (labels [N,T] float, xent [N,T-1] (CPU), change_idx | None)."""
+    T, N, H, W = seq.shape
+    feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
     if T == 1:  # a one-frame item (the correction step of test_all.py can ask for it): nothing to propagate, like the reference
         return seed[:, None].clone(), torch.zeros(N, 0), None
     xent = crw_hip.xent_metric(feats)
@@ -145,3 +152,20 @@ def ndiag_matrix(size, n=1):
     i = torch.arange(size)
     m = ((i[:, None] - i[None, :]).abs() <= max(n - 2, 0)).float()
     return m / m.sum(dim=1, keepdim=True)
+
+
+@torch.no_grad()
+def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last):
+    """`propagate` for every configuration of ``sweep`` (imported.labelprop.LabelPropSweep) at once: the encoder, the metric and
+    the change point do not depend on (radius, temp, knn) and run ONCE, on the batch `propagate` gives the encoder
+    ->  (labels [G,N,T] float, xent [N,T-1] (CPU), change_idx | None); labels[g] is `propagate`'s for ``sweep.configs[g]``."""
+    T, N, H, W = seq.shape
+    feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
+    G = len(sweep.configs)
+    if T == 1:
+        return seed[None, :, None].repeat(G, 1, 1), torch.zeros(N, 0), None
+    xent = crw_hip.xent_metric(feats)
+    diffs = column_diffs_async(xent) if T > 2 else None
+    pred = sweep.propagate_all(feats, seed, nclasses)
+    change_idx = change_point(xent, diffs)  # host work while the GPU propagates
+    return pred, xent.cpu(), change_idx
