@@ -21,6 +21,10 @@
  *   crw_xent_metric ......... "horizontality" metric                          src/utils.py:117-125
  *   crw_confusion ........... remove_unc masks + pred.cpu() + sklearn
  *                             classification_report / confusion_matrix counts scripts/test/test_all.py:161-187
+ *   crw_labelprop_confidence / crw_merge_confidence / crw_calibration
+ *                             the soft labels the scripts arg-max away          src/utils.py:160 (maskedatt.py CRW.forward:
+ *                             (per-node confidence, a merge ruled by it,        masks_pred_conf), scripts/test/test_all.py:146-159
+ *                             a reliability histogram): no reference twin
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HBM) unless its name ends in _host;
@@ -46,7 +50,8 @@ extern "C" {
 
 /* Bumps when a signature changes.  Entry points added at 8 without a bump (pure additions, no existing signature touched; the
  * binding detects them by symbol, crw_hip.has_sweep()): crw_labelprop_topk_scores, crw_labelprop_sweep_weights,
- * crw_labelprop_propagate_batch.  The ONE place the number is written: crw_abi_version() returns
+ * crw_labelprop_propagate_batch; then crw_labelprop_confidence, crw_merge_confidence, crw_calibration_ws_bytes, crw_calibration
+ * (crw_hip.has_confidence()).  The ONE place the number is written: crw_abi_version() returns
  * it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
 #define CRW_ABI_VERSION 8
@@ -193,6 +198,42 @@ size_t crw_confusion_ws_bytes(size_t P, int K);
 int crw_confusion(const void *gt, int gt_dtype, const void *pred, int pred_dtype, const void *aux, int aux_dtype, size_t P, int K,
                   int ignore_gt, int ignore_pred, int ignore_aux, int64_t *counts /* [K][K] */,
                   int64_t *dropped /* [2]: masked, invalid */, void *ws, size_t ws_bytes, crw_stream_t stream);
+
+/* confidence ------------------------------------------------------------------------------ */
+/* Confidence of every node from the soft labels of crw_labelprop_propagate / _gather: L [T*N, M] (a probability row per node,
+ * 4-byte aligned; 16-byte loads when it is 16-byte aligned and M % 4 == 0) -> conf [N, T], the layout of pred.  Columns >=
+ * first_frame are written (first_frame >= 1), and column 0 as well when first_frame == 1: frame 0's rows are then the one-hot
+ * seed, which gives 1 for every kind.  2 <= M <= 16.
+ *   CRW_CONF_MAXPROB  max_m p_m (bitwise the largest entry)
+ *   CRW_CONF_MARGIN   the largest entry minus the second largest, one fp32 subtraction; a duplicated maximum gives 0
+ *                     (both: a result above 1 reads 1 -- propagated rows sum to 1 within rounding only, and a confidence is a
+ *                     number in [0, 1], which crw_calibration insists on)
+ *   CRW_CONF_ENTROPY  1 + sum_m p_m ln p_m / ln M with 0 ln 0 = 0, fp32, terms added in index order, clamped to [0, 1] */
+#define CRW_CONF_MAXPROB 0
+#define CRW_CONF_MARGIN 1
+#define CRW_CONF_ENTROPY 2
+int crw_labelprop_confidence(const float *L, int T, int N, int M, int kind, int first_frame, float *conf, crw_stream_t stream);
+
+/* Per-pixel merge of two passes over the same P pixels by their confidence: the reverse pass wins where rev_conf > fwd_conf,
+ * strictly -- a tie keeps the forward label, and so does a NaN on either side.  out_lab / out_conf = the winner's label (copied,
+ * never decoded: any value) and confidence; took (uint8, may be NULL) = 1 where the reverse pass won.  lab_dtype: CRW_DT_F32 or
+ * CRW_DT_I8, one dtype for the three label maps; no alignment beyond the element's is asked for (views into a wider map take a
+ * scalar head / tail, or the scalar route throughout where the pointers share no 16-byte phase).  out_* may be fwd_*. */
+int crw_merge_confidence(const void *fwd_lab, const float *fwd_conf, const void *rev_lab, const float *rev_conf, int lab_dtype,
+                         size_t P, void *out_lab, float *out_conf, uint8_t *took, crw_stream_t stream);
+
+/* Reliability histogram of a confidence map: crw_confusion's pass (its operands, dtypes, mask and validity rules, in its order --
+ * dropped[0] and dropped[1] equal crw_confusion's on the same maps) with the surviving pixels binned by confidence instead of
+ * by class pair.  conf: P fp32 values; bin b = min(bins - 1, (int)floorf(conf * bins)), the product in fp32; 1 <= bins <= 64.
+ * counts [bins][2]: pixels, and pixels with gt == pred; conf_sum [bins] (double): the sum of the bin's confidences;
+ * dropped [3]: masked, invalid label, invalid confidence (NaN or outside [0, 1]; checked last, counted in no bin).
+ * P == 0 is valid and gives zeros; outputs are complete in stream order and need no pre-clearing.  The integers are
+ * bit-reproducible; conf_sum is bit-identical from run to run on the same P and pointer alignment (no atomics: lanes, waves and
+ * workgroups are added in a fixed order).  ws: crw_calibration_ws_bytes(P, K, bins) bytes, 8-byte aligned (0: bad K or bins). */
+size_t crw_calibration_ws_bytes(size_t P, int K, int bins);
+int crw_calibration(const void *gt, int gt_dtype, const void *pred, int pred_dtype, const float *conf, const void *aux, int aux_dtype,
+                    size_t P, int K, int bins, int ignore_gt, int ignore_pred, int ignore_aux, int64_t *counts /* [bins][2] */,
+                    double *conf_sum /* [bins] */, int64_t *dropped /* [3] */, void *ws, size_t ws_bytes, crw_stream_t stream);
 
 /* building blocks exported for tests and the roofline bench --------------------------------- */
 /* Weight gradient of the CNN encoder's linear head (nn.Linear(128, 128), src/encoder.py:40,55; autograd of

@@ -57,6 +57,11 @@ SIGNATURES = {
     "crw_xent_metric": (_c_int, [_p, _c_int, _c_int, _c_int, _p, _p]),
     "crw_confusion_ws_bytes": (_c_sz, [_c_sz, _c_int]),
     "crw_confusion": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _c_sz, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _c_sz, _p]),
+    "crw_labelprop_confidence": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
+    "crw_merge_confidence": (_c_int, [_p, _p, _p, _p, _c_int, _c_sz, _p, _p, _p, _p]),
+    "crw_calibration_ws_bytes": (_c_sz, [_c_sz, _c_int, _c_int]),
+    "crw_calibration": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _c_int, _c_sz, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p,
+                                 _c_sz, _p]),
     "crw_linear128_wgrad_ws_bytes": (_c_sz, [_c_int]),
     "crw_linear128_wgrad": (_c_int, [_p, _p, _p, _c_int, _p, _c_sz, _p]),
     "crw_adam_step": (_c_int, [_p, _p, _p, _p, ctypes.c_long, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
@@ -128,20 +133,24 @@ SIGNATURES = {
 # entry points added at ABI 8 without a bump: a library built before them still loads, `has_sweep()` tells
 SWEEP_ENTRY_POINTS = ("crw_labelprop_topk_scores", "crw_labelprop_sweep_weights", "crw_labelprop_propagate_batch")
 
+# likewise: the confidence entry points (`has_confidence()`)
+CONFIDENCE_ENTRY_POINTS = ("crw_labelprop_confidence", "crw_merge_confidence", "crw_calibration_ws_bytes", "crw_calibration")
+
 _lib = None
 _has_sweep = False
+_has_confidence = False
 
 
 def lib():
     """Load the HIP library (once).  Raises if it has not been built: `python -c 'import
     __graft_entry__ as g; g.build()'` or `make -C radar-sounder-crw_amd/csrc`."""
-    global _lib, _has_sweep
+    global _lib, _has_sweep, _has_confidence
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} not built -- the CRW hot path has no CPU/PyTorch fallback; "
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
-        missing = [n for n in SWEEP_ENTRY_POINTS if not hasattr(handle, n)]
+        missing = [n for n in SWEEP_ENTRY_POINTS + CONFIDENCE_ENTRY_POINTS if not hasattr(handle, n)]
         for name, (res, args) in SIGNATURES.items():
             if name in missing:
                 continue
@@ -150,7 +159,9 @@ def lib():
         if handle.crw_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} was built for ABI {handle.crw_abi_version()}, include/crw_hip.h says {ABI_VERSION}: "
                                "stale library -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
-        _lib, _has_sweep = handle, not missing
+        _lib = handle
+        _has_sweep = not set(missing) & set(SWEEP_ENTRY_POINTS)
+        _has_confidence = not set(missing) & set(CONFIDENCE_ENTRY_POINTS)
     return _lib
 
 
@@ -164,6 +175,19 @@ def _sweep_lib():
     if not has_sweep():
         raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks {', '.join(SWEEP_ENTRY_POINTS)} "
                            "(added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
+    return lib()
+
+
+def has_confidence():
+    """True when the loaded library exports the confidence entry points (CONFIDENCE_ENTRY_POINTS)."""
+    lib()
+    return _has_confidence
+
+
+def _confidence_lib():
+    if not has_confidence():
+        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
+                           f"{', '.join(CONFIDENCE_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
     return lib()
 
 
@@ -451,6 +475,8 @@ def confusion(gt, pred, K, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1
         return _confusion_cpu(gt, pred, K, aux, ignore_gt, ignore_pred, ignore_aux)
     g, p = _labels(gt, "gt"), _labels(pred, "pred")
     a = _labels(aux, "aux") if aux is not None else None
+    if P == 0:  # an empty tensor has no address: nothing to mask
+        a, ignore_aux = None, -1
     code = lambda t: DT_F32 if t.dtype == torch.float32 else DT_I8
     out = torch.empty(K * K + 2, dtype=torch.int64, device=gt.device)
     nbytes = lib().crw_confusion_ws_bytes(P, K)
@@ -476,6 +502,158 @@ def _confusion_cpu(gt, pred, K, aux, ignore_gt, ignore_pred, ignore_aux):
     idx = torch.where(keep, g * K + p, torch.where(masked, float(K * K), float(K * K + 1))).to(torch.int64)
     out = torch.bincount(idx, minlength=K * K + 2)
     return out[:K * K].view(K, K), out[K * K:]
+
+
+# ------------------------------------------------------------------------------ confidence
+CONF_KINDS = {"maxprob": 0, "margin": 1, "entropy": 2}
+
+
+def _conf_kind(kind):
+    if kind not in CONF_KINDS:
+        raise ValueError(f"confidence kind must be one of {', '.join(CONF_KINDS)} (got {kind!r})")
+    return CONF_KINDS[kind]
+
+
+def labelprop_confidence(L, T, N, M, kind="maxprob", first_frame=1):
+    """Soft labels L [T*N, M] (`labelprop_gather`'s, a probability row per node) -> conf [N, T] float32, the layout of pred:
+    'maxprob' the largest probability, 'margin' the largest minus the second largest (either reads 1 where rounding carried it above 1), 'entropy' 1 + sum p ln p / ln M (0 ln 0 = 0,
+    clamped to [0, 1]).  Columns >= first_frame are computed -- and column 0 when first_frame == 1 (the one-hot seed: 1) --, the
+    others are 0.  Device tensors: one launch of crw_labelprop_confidence, nothing synchronises; CPU tensors: the same formulas
+    in torch, fp32."""
+    code = _conf_kind(kind)
+    T, N, M, first_frame = int(T), int(N), int(M), int(first_frame)
+    if not 2 <= M <= 16:
+        raise ValueError(f"M must be in 2 ... 16 (got {M})")
+    if T < 1 or N < 1 or not 1 <= first_frame <= T:
+        raise ValueError(f"need T, N >= 1 and 1 <= first_frame <= T (got T={T}, N={N}, first_frame={first_frame})")
+    if L.numel() != T * N * M or L.dtype != torch.float32:
+        raise ValueError(f"L must be float32 [{T * N}, {M}] (got {L.dtype} {tuple(L.shape)})")
+    if not L.is_cuda:
+        return _labelprop_confidence_cpu(L, T, N, M, kind, first_frame)
+    L = L.contiguous()
+    conf = (torch.empty if first_frame == 1 else torch.zeros)(N, T, device=L.device, dtype=torch.float32)
+    _check(_confidence_lib().crw_labelprop_confidence(_ptr(L), T, N, M, code, first_frame, _ptr(conf), _stream()),
+           "crw_labelprop_confidence")
+    return conf
+
+
+def _labelprop_confidence_cpu(L, T, N, M, kind, first_frame):
+    p = L.reshape(T, N, M)
+    if kind == "maxprob":
+        c = p.max(-1).values.clamp(max=1.0)  # rows sum to 1 within rounding only: an entry an ulp above 1 reads 1, like the kernel's
+    elif kind == "margin":
+        top = torch.topk(p, 2, dim=-1).values
+        c = (top[..., 0] - top[..., 1]).clamp(max=1.0)
+    else:
+        plogp = torch.where(p > 0, p * torch.log(p), torch.zeros_like(p))
+        c = (1.0 + plogp.sum(-1) / torch.log(torch.tensor(float(M)))).clamp(0.0, 1.0)
+    c = c.t().contiguous()
+    if first_frame > 1:
+        c[:, :first_frame] = 0
+    return c
+
+
+def merge_confidence(fwd_lab, fwd_conf, rev_lab, rev_conf, out_lab=None, out_conf=None, want_took=False):
+    """Per-pixel merge of a forward and a reverse pass by confidence -> (labels, confidence, took | None): the reverse pass's
+    label and confidence where rev_conf > fwd_conf strictly, the forward pass's elsewhere -- on a tie, and where either confidence
+    is NaN.  Labels: float32 or int8, one dtype for both passes, copied as they are; took (``want_took``): uint8, 1 where the
+    reverse pass won.  out_lab / out_conf: contiguous tensors to write into; they may be fwd_lab / fwd_conf (in place).  Device
+    tensors: one launch of crw_merge_confidence, nothing synchronises; CPU tensors: torch.where."""
+    P = fwd_lab.numel()
+    if any(t.numel() != P for t in (fwd_conf, rev_lab, rev_conf)):
+        raise ValueError("the two label maps and the two confidence maps must cover the same pixels")
+    if fwd_lab.dtype != rev_lab.dtype or fwd_lab.dtype not in (torch.float32, torch.int8):
+        raise ValueError(f"labels must be float32 or int8, the same for both passes (got {fwd_lab.dtype}, {rev_lab.dtype})")
+    if fwd_conf.dtype != torch.float32 or rev_conf.dtype != torch.float32:
+        raise ValueError("confidences must be float32")
+    if any(t.device != fwd_lab.device for t in (fwd_conf, rev_lab, rev_conf)):
+        raise ValueError("labels and confidences must live on one device")
+    if out_lab is None:
+        out_lab = torch.empty(fwd_lab.shape, dtype=fwd_lab.dtype, device=fwd_lab.device)
+    if out_conf is None:
+        out_conf = torch.empty(fwd_lab.shape, dtype=torch.float32, device=fwd_lab.device)
+    if (out_lab.numel() != P or out_conf.numel() != P or out_lab.dtype != fwd_lab.dtype or out_conf.dtype != torch.float32
+            or not out_lab.is_contiguous() or not out_conf.is_contiguous() or out_lab.device != fwd_lab.device
+            or out_conf.device != fwd_lab.device):
+        raise ValueError("out_lab / out_conf must be contiguous, of the inputs' size, dtype and device")
+    took = torch.empty(fwd_lab.shape, dtype=torch.uint8, device=fwd_lab.device) if want_took else None
+    if not fwd_lab.is_cuda:
+        take = rev_conf.reshape(-1) > fwd_conf.reshape(-1)
+        lab = torch.where(take, rev_lab.reshape(-1), fwd_lab.reshape(-1))
+        conf = torch.where(take, rev_conf.reshape(-1), fwd_conf.reshape(-1))
+        out_lab.view(-1).copy_(lab)
+        out_conf.view(-1).copy_(conf)
+        if took is not None:
+            took.view(-1).copy_(take)
+        return out_lab, out_conf, took
+    fl, fc, rl, rc = (t.contiguous() for t in (fwd_lab, fwd_conf, rev_lab, rev_conf))
+    _check(_confidence_lib().crw_merge_confidence(_ptr(fl), _ptr(fc), _ptr(rl), _ptr(rc), DT_F32 if fl.dtype == torch.float32 else DT_I8,
+                                                  P, _ptr(out_lab), _ptr(out_conf), _ptr(took) if took is not None else None,
+                                                  _stream()), "crw_merge_confidence")
+    return out_lab, out_conf, took
+
+
+def calibration(gt, pred, conf, K, bins=10, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1):
+    """Reliability histogram of a confidence map -> (counts [bins, 2] int64, conf_sum [bins] float64, dropped [3] int64) on the
+    inputs' device.  `confusion`'s operands and its mask and validity rules (dropped[0] masked, dropped[1] invalid labels: the same
+    numbers `confusion` gives on the same maps), and the surviving pixels binned by confidence: bin = min(bins - 1,
+    floor(conf * bins)) in fp32; counts[b] = (pixels, pixels with gt == pred); conf_sum[b] = the sum of the bin's confidences; a
+    surviving pixel whose confidence is NaN or outside [0, 1] is counted in dropped[2] and in no bin.  Device tensors: one pass
+    of crw_calibration, nothing synchronises; CPU tensors: the same numbers from torch.bincount, conf_sum in float64."""
+    K, bins = int(K), int(bins)
+    if not 2 <= K <= 16:
+        raise ValueError(f"K must be in 2 ... 16 (got {K})")
+    if not 1 <= bins <= 64:
+        raise ValueError(f"bins must be in 1 ... 64 (got {bins})")
+    if min(ignore_gt, ignore_pred, ignore_aux) < -1:
+        raise ValueError("an ignore label is a class id >= 0, or -1 for none")
+    if aux is None and ignore_aux != -1:
+        raise ValueError("ignore_aux needs aux")
+    P = gt.numel()
+    if pred.numel() != P or conf.numel() != P or (aux is not None and aux.numel() != P):
+        raise ValueError(f"gt, pred, conf{' and aux' if aux is not None else ''} must hold the same number of pixels "
+                         f"(got {P}, {pred.numel()}, {conf.numel()}{'' if aux is None else ', ' + str(aux.numel())})")
+    if pred.device != gt.device or conf.device != gt.device or (aux is not None and aux.device != gt.device):
+        raise ValueError("gt, pred, conf and aux must live on one device")
+    if not conf.is_floating_point():
+        raise ValueError(f"conf must be a floating-point map (got {conf.dtype})")
+    c = conf.reshape(-1).to(torch.float32).contiguous()
+    if not gt.is_cuda:
+        return _calibration_cpu(gt, pred, c, K, bins, aux, ignore_gt, ignore_pred, ignore_aux)
+    g, p = _labels(gt, "gt"), _labels(pred, "pred")
+    a = _labels(aux, "aux") if aux is not None else None
+    if P == 0:  # an empty tensor has no address: nothing to mask
+        a, ignore_aux = None, -1
+    code = lambda t: DT_F32 if t.dtype == torch.float32 else DT_I8
+    out = torch.empty(3 * bins + 3, dtype=torch.int64, device=gt.device)  # counts [bins][2] | conf_sum [bins] (as bits) | dropped [3]
+    nbytes = _confidence_lib().crw_calibration_ws_bytes(P, K, bins)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=gt.device)
+    base = out.data_ptr()
+    _check(lib().crw_calibration(_ptr(g), code(g), _ptr(p), code(p), _ptr(c), _ptr(a) if a is not None else None,
+                                 code(a) if a is not None else DT_I8, P, K, bins, int(ignore_gt), int(ignore_pred), int(ignore_aux),
+                                 ctypes.c_void_p(base), ctypes.c_void_p(base + 16 * bins), ctypes.c_void_p(base + 24 * bins), _ptr(ws),
+                                 nbytes, _stream()), "crw_calibration")
+    return out[:2 * bins].view(bins, 2), out[2 * bins:3 * bins].view(torch.float64), out[3 * bins:]
+
+
+def _calibration_cpu(gt, pred, c, K, bins, aux, ignore_gt, ignore_pred, ignore_aux):
+    g, p = gt.reshape(-1).to(torch.float64), pred.reshape(-1).to(torch.float64)
+    masked = torch.zeros(g.shape, dtype=torch.bool)
+    if ignore_gt >= 0:
+        masked |= g == ignore_gt
+    if ignore_pred >= 0:
+        masked |= p == ignore_pred
+    if ignore_aux >= 0:
+        masked |= aux.reshape(-1).to(torch.float64) == ignore_aux
+    valid = (g == g.floor()) & (g >= 0) & (g < K) & (p == p.floor()) & (p >= 0) & (p < K)  # NaN fails every comparison
+    cvalid = (c >= 0) & (c <= 1)
+    binned = ~masked & valid & cvalid
+    b = torch.clamp(torch.floor(torch.where(binned, c, torch.zeros_like(c)) * bins), max=bins - 1).to(torch.int64)  # fp32 product
+    row = torch.where(masked, bins, torch.where(~valid, bins + 1, torch.where(~cvalid, bins + 2, b)))
+    n = torch.bincount(row, minlength=bins + 3)
+    ok = torch.bincount(row, weights=(binned & (g == p)).to(torch.float64), minlength=bins + 3).to(torch.int64)
+    s = torch.bincount(row, weights=torch.where(binned, c.to(torch.float64), torch.zeros(1, dtype=torch.float64)), minlength=bins + 3)
+    return torch.stack([n[:bins], ok[:bins]], 1), s[:bins], n[bins:]
 
 
 def gemm_f32(A, B, C=None, transA=False, transB=False, beta=False):

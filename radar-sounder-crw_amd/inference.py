@@ -47,6 +47,13 @@ def _upsample(pred, rows, cols):
 def merge_reverse(final_pred, pred_rev, dataset_id):
     """Class-specific merge of the reversed pass into the forward map (test_all.py:146-159):
     class 2 (bedrock) of the reversed pass wins, with per-dataset restrictions."""
+    out = final_pred.flatten().clone()
+    out[_reverse_rule_mask(final_pred, pred_rev, dataset_id)] = 2
+    return out.view_as(final_pred)
+
+
+def _reverse_rule_mask(final_pred, pred_rev, dataset_id):
+    """The pixels (flat, bool) at which `merge_reverse`'s class rule writes the reverse pass's label."""
     rows = pred_rev.shape[0]
     mask = pred_rev.flatten() == 2
     if dataset_id == 1:
@@ -58,18 +65,33 @@ def merge_reverse(final_pred, pred_rev, dataset_id):
         mask[:mask.numel() // 2] = False
     elif dataset_id != 0:
         raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
-    out = final_pred.flatten().clone()
-    out[mask] = 2
-    return out.view_as(final_pred)
+    return mask
 
 
 @torch.no_grad()
 def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap, pos_embed=False,
-            correction=False, use_last=False, dataset_id=0, device='cuda'):
+            correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule'):
     """dataset: RGDataset (full, overlapping items); seg: reference segmentation [rows, W_rg].
     -> dict(pred [rows, n_rg * rg_len] float labels after the optional reverse merge,
             forward: the forward (+ corrected) map the reference saves as int8 (test_all.py:128),
-            xent list, change_idx list)."""
+            xent list, change_idx list).
+
+    confidence: None, or a kind of `crw_hip.labelprop_confidence` ('maxprob', 'margin', 'entropy').  The dict then gains
+    ``conf`` and ``forward_conf``, float32 [rows, n_rg * rg_len]: the confidence of every pixel of ``pred`` / ``forward``, from the
+    soft labels of the pass that wrote the pixel's label -- upsampled, spliced by the correction and flipped exactly as the labels
+    are; 1 on every seed column.  ``pred`` and ``forward`` do not depend on it.
+    merge: how the reverse pass (``use_last``) enters ``pred``.  'rule': the reference's class rule (`merge_reverse`), defined for
+    dataset ids 0, 1 and 3; ``conf`` is the reverse pass's exactly where the rule wrote its label.  'confidence': per pixel, the
+    pass that is surer (`crw_hip.merge_confidence`: the reverse pass where its confidence is strictly larger) -- needs no class
+    semantics, so any ``dataset_id`` is accepted; needs ``confidence``."""
+    if merge not in ('rule', 'confidence'):
+        raise ValueError(f"merge must be 'rule' or 'confidence' (got {merge!r})")
+    if confidence is not None and confidence not in crw_hip.CONF_KINDS:
+        raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
+    if merge == 'confidence' and confidence is None:
+        raise ValueError("merge='confidence' needs a confidence kind (confidence='maxprob', 'margin' or 'entropy')")
+    want = confidence is not None
+    kw = dict(confidence=confidence) if want else {}  # `propagate` returns a fourth entry only when asked
     T, (H, W), (oh, ow) = seq_length, patch_size, overlap
     N = dataset[0].shape[1]
     rg_len = T * (W - ow) + ow
@@ -80,12 +102,14 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     seg = seg[:, :n_rg * rg_len].to(device)
     rows = seg.shape[0]
 
-    maps, xents, changes = [], [], []
+    maps, cmaps, xents, changes = [], [], [], []
     for t, i in enumerate(idx):
         seq = dataset[i].to(device)
         seg_ref = seg[:rg_h, rg_len * t:rg_len * t + W]
-        pred, xent, change = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=False)
+        pred, xent, change, *conf = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=False, **kw)
         maps.append(_upsample(pred, rows, rg_len))
+        if want:
+            cmaps.append(_upsample(conf[0], rows, rg_len))
         xents.append(xent)
         changes.append(change)
 
@@ -98,8 +122,11 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
             try:  # like the reference, a correction that fails on its DATA (shape / index errors) is skipped silently ...
                 seq = dataset.get_smaller_item(idx[t], small).to(device)  # first `small` columns; shortens the dataset
                 seg_ref = seg[:, rg_len * t + rg_len - px:rg_len * t + rg_len - px + W]
-                pred, _, _ = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=False)
+                pred, _, _, *conf = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=False, **kw)
+                tail = _upsample(conf[0], rows, px) if want else None
                 maps[t][:, rg_len - px:] = _upsample(pred, rows, px)
+                if want:  # the same window as the labels: spliced when they were, skipped when they were
+                    cmaps[t][:, rg_len - px:] = tail
             except crw_hip.CrwError as e:
                 # ... but a failure of the HIP path itself (CRW_EHIP: launch failure / GPU fault, CRW_EWORKSPACE) is not a data
                 # problem: the reference's bare `except` would hide a poisoned device context behind an uncorrected map.
@@ -112,19 +139,31 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
                 pass
 
     forward = torch.cat(maps, dim=1)
-    final = forward
+    forward_conf = torch.cat(cmaps, dim=1) if want else None
+    final, final_conf = forward, forward_conf
     if use_last:
-        rev_maps = []
+        rev_maps, rev_cmaps = [], []
         seg_rev = torch.flip(seg.unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
         for t, i in enumerate(idx):
             seq = dataset[i].to(device)
             seg_ref = seg_rev[:, rg_len * t:rg_len * t + W]
-            pred, _, _ = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=True)
+            pred, _, _, *conf = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=True, **kw)
             rev_maps.append(_upsample(pred, rows, rg_len))
-        rev = torch.cat(rev_maps, dim=1).unfold(1, rg_len, rg_len)
-        rev = torch.flip(rev, (-1,)).reshape(rows, -1)
-        final = merge_reverse(forward, rev, dataset_id)
-    return dict(pred=final, forward=forward, xent=xents, change_idx=changes)
+            if want:
+                rev_cmaps.append(_upsample(conf[0], rows, rg_len))
+        unflip = lambda m: torch.flip(torch.cat(m, dim=1).unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
+        rev = unflip(rev_maps)
+        if merge == 'confidence':
+            final, final_conf, _ = crw_hip.merge_confidence(forward, forward_conf, rev, unflip(rev_cmaps))
+        else:
+            final = merge_reverse(forward, rev, dataset_id)
+            if want:
+                ruled = _reverse_rule_mask(forward, rev, dataset_id).view_as(forward)
+                final_conf = torch.where(ruled, unflip(rev_cmaps), forward_conf)
+    out = dict(pred=final, forward=forward, xent=xents, change_idx=changes)
+    if want:
+        out.update(conf=final_conf, forward_conf=forward_conf)
+    return out
 
 
 def merge_reverse_batch(final_pred, pred_rev, dataset_id):
@@ -242,17 +281,8 @@ def segment_one(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, ove
 NCLASSES = {0: 4, 1: 6, 2: 4, 3: 5}
 
 
-def evaluate(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None):
-    """The report of test_all.py:161-187 for a label map ``pred`` (``segment(...)['pred']``, or a saved int8 map) against the
-    reference segmentation ``seg`` cut to the same columns -> ``metrics.Report``.
-
-    ``remove_unc`` (the script's default): dataset 0 drops the pixels whose ``unc_seg`` -- the reference's dataset-2 map cut to the
-    same columns, required then -- is 4 (:162-167); dataset 1 drops the pixels whose ground truth or prediction is 5 (:168-172);
-    dataset 3 drops nothing (:173-175).  The rules are mask arguments of the one ``crw_hip.confusion`` call: no boolean-indexed
-    copy of the maps, no copy to the host but the K x K counts.  K = ``nclasses`` (default: the dataset's, labels 0 ... K-1); the
-    4s of dataset 0's uncertain map are compared, never binned.  A label outside 0 ... K-1 that survives the mask raises
-    ``crw_hip.LabelError`` (a ValueError)."""
-    from metrics import Report
+def _report_rules(pred, seg, dataset_id, remove_unc, unc_seg, nclasses):
+    """`evaluate`'s argument checks and ``--remove_unc`` rules -> (K, seg on pred's device, mask arguments of the kernel call)."""
     if dataset_id not in (0, 1, 3):
         raise ValueError(f'no report rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
     K = NCLASSES[dataset_id] if nclasses is None else int(nclasses)
@@ -268,11 +298,45 @@ def evaluate(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None
         mask = dict(aux=unc_seg.to(pred.device), ignore_aux=4)
     elif remove_unc and dataset_id == 1:
         mask = dict(ignore_gt=5, ignore_pred=5)
+    return K, seg, mask
+
+
+def evaluate(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None):
+    """The report of test_all.py:161-187 for a label map ``pred`` (``segment(...)['pred']``, or a saved int8 map) against the
+    reference segmentation ``seg`` cut to the same columns -> ``metrics.Report``.
+
+    ``remove_unc`` (the script's default): dataset 0 drops the pixels whose ``unc_seg`` -- the reference's dataset-2 map cut to the
+    same columns, required then -- is 4 (:162-167); dataset 1 drops the pixels whose ground truth or prediction is 5 (:168-172);
+    dataset 3 drops nothing (:173-175).  The rules are mask arguments of the one ``crw_hip.confusion`` call: no boolean-indexed
+    copy of the maps, no copy to the host but the K x K counts.  K = ``nclasses`` (default: the dataset's, labels 0 ... K-1); the
+    4s of dataset 0's uncertain map are compared, never binned.  A label outside 0 ... K-1 that survives the mask raises
+    ``crw_hip.LabelError`` (a ValueError)."""
+    from metrics import Report
+    K, seg, mask = _report_rules(pred, seg, dataset_id, remove_unc, unc_seg, nclasses)
     counts, dropped = crw_hip.confusion(seg, pred, K, **mask)
     dropped = [int(v) for v in dropped.cpu()]
     if dropped[1]:
         raise crw_hip.LabelError(dropped[1], K)
     return Report(counts, dropped)
+
+
+def calibration(pred, conf, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None, bins=10):
+    """Does low confidence find the wrong pixels?  The reliability histogram of a confidence map ``conf`` (``segment(...,
+    confidence=kind)['conf']``) for the label map ``pred`` against ``seg`` -> ``metrics.Calibration`` (per-bin accuracy and mean
+    confidence, ECE / MCE, the risk-coverage curve).  `evaluate`'s arguments and mask rules, passed through as arguments of the one
+    ``crw_hip.calibration`` call: the pixels it bins are the pixels `evaluate` counts.  A surviving label outside 0 ... K-1 raises
+    ``crw_hip.LabelError``; a surviving confidence that is NaN or outside [0, 1] is counted in ``dropped[2]`` and binned nowhere."""
+    from metrics import Calibration
+    K, seg, mask = _report_rules(pred, seg, dataset_id, remove_unc, unc_seg, nclasses)
+    if conf.numel() != pred.numel():
+        raise ValueError(f'conf {tuple(conf.shape)} and pred {tuple(pred.shape)} must cover the same pixels')
+    counts, conf_sum, dropped = crw_hip.calibration(seg, pred, conf.to(pred.device), K, bins=bins, **mask)
+    host = torch.cat([counts.reshape(-1), conf_sum.view(torch.int64), dropped]).cpu()  # the one copy: 3 * bins + 3 numbers
+    nb = conf_sum.numel()
+    dropped = [int(v) for v in host[3 * nb:]]
+    if dropped[1]:
+        raise crw_hip.LabelError(dropped[1], K)
+    return Calibration(host[:2 * nb].view(nb, 2), host[2 * nb:3 * nb].view(torch.float64), dropped)
 
 
 def evaluate_sweep(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None):

@@ -11,6 +11,11 @@ and keeps its code.  sklearn's label semantics are kept, because the fixtures (t
 reported classes are those that occur in ``gt`` or in ``pred`` (after masking), ascending; a class absent from both has no row,
 no column and no share in the macro average; a 0 / 0 ratio is 0.0.  IoU is an addition and is printed by a method of its own
 (``iou_str``), so ``str(report)`` stays comparable with sklearn's text character for character.
+
+``Calibration`` is the companion for a confidence map (``inference.segment(..., confidence=kind)['conf']``): the reliability
+histogram of ``crw_hip.calibration`` -- per confidence bin, the pixels, the correct pixels and the summed confidence, under the same
+masks -- turned into the expected / maximum calibration error and the risk-coverage curve.  The reference has no twin: it marks
+"uncertain" pixels with a hand-drawn class (``--remove_unc``).
 """
 import numpy as np
 import torch
@@ -109,6 +114,95 @@ class Report:
         for n, v in zip(names, self.iou):
             text += "{:>{w}s}  {:>9.{d}f}\n".format(n, v, w=width, d=digits)
         return text + "\n{:>{w}s}  {:>9.{d}f}\n".format("mean", self.mean_iou, w=width, d=digits)
+
+
+class Calibration:
+    """Reliability of a confidence map, from the [bins, 2] counts (pixels, correct pixels), the [bins] confidence sums and the
+    dropped triple of ``crw_hip.calibration`` (tensors are copied to the host once: 3 * bins + 3 numbers).
+
+    Bin b holds the confidences in [b / bins, (b + 1) / bins) (the last one includes 1).  count / correct [bins] int64, accuracy /
+    mean_confidence [bins] float64 (NaN for an empty bin), total, overall accuracy, ece = sum_b count_b / total *
+    |accuracy_b - mean_confidence_b|, mce = the largest such gap (both over the non-empty bins; NaN when every bin is empty),
+    dropped (masked, invalid label, invalid confidence) or None."""
+
+    def __init__(self, counts, conf_sum, dropped=None):
+        host = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        counts = np.asarray(host(counts), dtype=np.int64)
+        if counts.ndim != 2 or counts.shape[1] != 2 or counts.shape[0] < 1:
+            raise ValueError(f"counts must be [bins, 2] (got shape {counts.shape})")
+        self.conf_sum = np.asarray(host(conf_sum), dtype=np.float64).reshape(-1)
+        if self.conf_sum.shape[0] != counts.shape[0]:
+            raise ValueError(f"conf_sum must hold one sum per bin (got {self.conf_sum.shape[0]} for {counts.shape[0]} bins)")
+        if (counts < 0).any() or (counts[:, 1] > counts[:, 0]).any():
+            raise ValueError("counts must be non-negative with correct <= pixels in every bin")
+        self.bins = counts.shape[0]
+        self.count, self.correct = counts[:, 0].copy(), counts[:, 1].copy()
+        self.dropped = None if dropped is None else tuple(int(v) for v in host(dropped))
+        self.total = int(self.count.sum())
+        self.edges = np.arange(self.bins + 1, dtype=np.float64) / self.bins
+        filled = self.count > 0
+        nan = np.full(self.bins, np.nan)
+        self.accuracy, self.mean_confidence = nan.copy(), nan.copy()
+        np.divide(self.correct, self.count, out=self.accuracy, where=filled)
+        np.divide(self.conf_sum, self.count, out=self.mean_confidence, where=filled)
+        gap = np.abs(self.accuracy - self.mean_confidence)[filled]
+        self.overall_accuracy = float(self.correct.sum() / self.total) if self.total else float("nan")
+        self.ece = float((gap * self.count[filled]).sum() / self.total) if self.total else float("nan")
+        self.mce = float(gap.max()) if self.total else float("nan")
+
+    def risk_coverage(self):
+        """Selective prediction at the thresholds b / bins, b = 0 ... bins - 1: keep the pixels whose confidence is at least the
+        threshold -> dict(threshold, coverage, accuracy) of [bins] arrays.  coverage = kept / total never grows with the
+        threshold (NaN throughout when no pixel was binned); accuracy of the kept pixels is NaN where none is kept."""
+        kept = np.cumsum(self.count[::-1])[::-1].astype(np.float64)
+        right = np.cumsum(self.correct[::-1])[::-1].astype(np.float64)
+        acc = np.full(self.bins, np.nan)
+        np.divide(right, kept, out=acc, where=kept > 0)
+        cov = kept / self.total if self.total else np.full(self.bins, np.nan)
+        return dict(threshold=self.edges[:-1].copy(), coverage=cov, accuracy=acc)
+
+    @property
+    def aurc(self):
+        """Area under the risk-coverage curve (risk = 1 - accuracy of the kept pixels): the trapezoid rule over coverage through
+        the thresholds that keep at least one pixel, continued from the smallest such coverage down to 0 at that point's risk.
+        Lower is better; NaN when no pixel was binned."""
+        rc = self.risk_coverage()
+        keep = rc["coverage"] > 0
+        if not self.total or not keep.any():
+            return float("nan")
+        cov, risk = rc["coverage"][keep][::-1], 1.0 - rc["accuracy"][keep][::-1]  # coverage ascending
+        return float(cov[0] * risk[0] + ((cov[1:] - cov[:-1]) * (risk[1:] + risk[:-1]) / 2).sum())
+
+    def coverage_at(self, accuracy):
+        """The largest coverage among the thresholds whose kept pixels reach ``accuracy`` (0.0 when none does)."""
+        rc = self.risk_coverage()
+        good = rc["accuracy"] >= accuracy  # NaN fails
+        return float(rc["coverage"][good].max()) if good.any() else 0.0
+
+    def to_dict(self):
+        rc = self.risk_coverage()
+        lst = lambda a: [float(v) for v in a]
+        d = dict(bins=self.bins, edges=lst(self.edges), count=[int(v) for v in self.count], correct=[int(v) for v in self.correct],
+                 accuracy=lst(self.accuracy), mean_confidence=lst(self.mean_confidence), total=self.total,
+                 overall_accuracy=self.overall_accuracy, ece=self.ece, mce=self.mce, aurc=self.aurc,
+                 risk_coverage=dict(threshold=lst(rc["threshold"]), coverage=lst(rc["coverage"]), accuracy=lst(rc["accuracy"])))
+        if self.dropped is not None:
+            d["dropped"] = dict(masked=self.dropped[0], invalid=self.dropped[1], invalid_confidence=self.dropped[2])
+        return d
+
+    def __str__(self, digits=4):
+        rc = self.risk_coverage()
+        num = lambda v: "{:>10}".format("-") if v != v else "{:>10.{d}f}".format(v, d=digits)
+        text = "{:>13} {:>12} {:>10} {:>10} {:>10} {:>10}\n\n".format("confidence", "pixels", "accuracy", "mean conf", "coverage",
+                                                                     "kept acc")
+        for b in range(self.bins):
+            name = "[{:.3f},{:.3f}{}".format(self.edges[b], self.edges[b + 1], "]" if b == self.bins - 1 else ")")
+            text += "{:>13} {:>12} {} {} {} {}\n".format(name, int(self.count[b]), num(self.accuracy[b]), num(self.mean_confidence[b]),
+                                                         num(rc["coverage"][b]), num(rc["accuracy"][b]))
+        text += "\n"
+        for name, v in (("ECE", self.ece), ("MCE", self.mce), ("AURC", self.aurc), ("accuracy", self.overall_accuracy)):
+            text += "{:>13} {:>12} {}\n".format(name, self.total if name == "accuracy" else "", num(v))
+        return text
 
 
 def _infer_K(gt, pred):

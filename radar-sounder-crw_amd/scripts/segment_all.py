@@ -11,7 +11,11 @@ over the label map on the GPU (``inference.evaluate``); scikit-learn is not used
 Additions: ``--data_path`` / ``--seg_path`` / ``--unc_seg_path`` / ``--model_path`` for the files the reference hard-codes
 (default: its paths, re-rooted by CRW_DATA_ROOT); ``--synthetic H W``: a seeded radargram with a layered reference map, no files,
 and -- without ``--model_path`` -- a random-init encoder; ``--report_json FILE``: the numbers (per-class scores, averages, IoU,
-matrix, dropped pixels, elapsed times); ``--iou``: also print the IoU table.
+matrix, dropped pixels, elapsed times); ``--iou``: also print the IoU table; ``--confidence {maxprob,margin,entropy}``: also the
+per-pixel confidence of the map (``inference.segment(..., confidence=...)``) and, after the confusion matrix, its calibration table
+(``inference.calibration``, ``--bins B`` confidence bins; ``--report_json`` gains a ``calibration`` key); ``--save_conf`` writes the
+confidence of the final map as ``confidence_map.pt`` (float32); ``--merge confidence``: the reverse pass of ``--use_last`` is merged
+per pixel by confidence instead of by the reference's class rule.  Without these flags the output is what it was.
 Differences from the scripts:
   * plots are not drawn;
   * true / false flags read true / false (the scripts take any given string as true); ``--patch_size`` takes two numbers;
@@ -73,6 +77,12 @@ def get_args_parser():
     p.add_argument('--synthetic', default=None, nargs=2, type=int, metavar=('H', 'W'))
     p.add_argument('--report_json', default=None, metavar='FILE')
     p.add_argument('--iou', action='store_true', help='also print the per-class IoU table')
+    p.add_argument('--confidence', default=None, choices=('maxprob', 'margin', 'entropy'),
+                   help='per-pixel confidence of the label map and its calibration table')
+    p.add_argument('--merge', default='rule', choices=('rule', 'confidence'),
+                   help="how --use_last merges the reverse pass: the reference's class rule, or per pixel the surer pass")
+    p.add_argument('--bins', default=10, type=int, metavar='B', help='confidence bins of the calibration table (1 ... 64)')
+    p.add_argument('--save_conf', action='store_true', help='write confidence_map.pt (needs --confidence)')
     return p
 
 
@@ -88,6 +98,17 @@ def with_defaults(args):
         raise SystemExit(f'--dataset {args.dataset}: the reference defines 0, 1 and 3')
     if args.model_path is None and args.synthetic is None:
         raise SystemExit('--model_path is required (or --synthetic H W for a run without data)')
+    return args
+
+
+def check_confidence_flags(args):
+    """The flags around ``--confidence`` (this script's alone; `with_defaults` also serves segment_sweep.py's parser)."""
+    if args.confidence is None and (args.merge == 'confidence' or args.save_conf):
+        raise SystemExit('--merge confidence and --save_conf need --confidence {maxprob,margin,entropy}')
+    if args.confidence is not None and args.single:
+        raise SystemExit('--confidence is not available with --single')
+    if not 1 <= args.bins <= 64:
+        raise SystemExit(f'--bins {args.bins}: 1 ... 64')
     return args
 
 
@@ -128,8 +149,10 @@ def load_data(args):
 def main(args):
     from imported.labelprop import LabelPropVOS_CRW
     tim = time.time()
-    args = with_defaults(args)
-    print(args)
+    args = check_confidence_flags(with_defaults(args))
+    # without --confidence the four flags that go with it do nothing, and the line reads as it did before they existed
+    hidden = () if args.confidence else ('confidence', 'merge', 'bins', 'save_conf')
+    print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
         encoder = load_encoder(args.model, args.model_path, device)
@@ -153,13 +176,16 @@ def main(args):
             print('Correction skipped: it needs --dataset_full true (the reference skips it silently here)')
             correction = False
         out = inference.segment(dataset, seg, encoder, lp, nclasses, T, args.patch_size, args.overlap, pos_embed=args.pos_embed,
-                                correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device)
+                                correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device,
+                                **(dict(confidence=args.confidence, merge=args.merge) if args.confidence else {}))
         if correction:
             print('Change point for each radargram:', out['change_idx'])
         final, forward = out['pred'], out['forward']
     cols = final.shape[1]
     os.makedirs(args.output_folder, exist_ok=True)
     torch.save(forward.to(torch.int8), os.path.join(args.output_folder, 'predicted_map.pt'))
+    if args.save_conf:
+        torch.save(out['conf'].cpu(), os.path.join(args.output_folder, 'confidence_map.pt'))
     if device.type == 'cuda':
         torch.cuda.synchronize()
     t_inference = time.time() - tim
@@ -170,6 +196,13 @@ def main(args):
                                 unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses)
     print(report)
     print(report.matrix_str())
+    cal = None
+    if args.confidence:
+        cal = inference.calibration(final, out['conf'], seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
+                                    unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses, bins=args.bins)
+        print('')
+        print(f'Calibration ({args.confidence}, merge: {args.merge}):')
+        print(cal)
     if args.iou:
         print('')
         print(report.iou_str())
@@ -180,6 +213,8 @@ def main(args):
         d.update(labels=report.labels, matrix=report.matrix.tolist(), dropped=dict(masked=report.dropped[0], invalid=report.dropped[1]),
                  pixels=int(final.numel()), map_shape=list(final.shape), elapsed_inference_s=t_inference, elapsed_total_s=t_all,
                  dataset=args.dataset, remove_unc=args.remove_unc, single=args.single)
+        if cal is not None:
+            d['calibration'] = dict(cal.to_dict(), kind=args.confidence, merge=args.merge)
         with open(args.report_json, 'w') as f:
             json.dump(d, f, indent=1)
     return report

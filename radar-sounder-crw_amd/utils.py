@@ -120,17 +120,24 @@ def _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last):
 
 
 @torch.no_grad()
-def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last):
+def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, confidence=None):
     """seq [T,N,h,w]; seg_ref [rows, w] class ids of the first (or last) frame; model: encoder;
-    lp: LabelPropVOS_CRW  ->  (labels [N,T] float, xent [N,T-1] (CPU), change_idx | None)."""
+    lp: LabelPropVOS_CRW  ->  (labels [N,T] float, xent [N,T-1] (CPU), change_idx | None).
+
+    confidence: None, or a kind of `crw_hip.labelprop_confidence` ('maxprob', 'margin', 'entropy') -- the tuple then gains a
+    fourth entry, conf [N,T] float on the labels' device: the confidence of every label, from the soft labels the propagation
+    wrote (the reference arg-maxes them away, src/utils.py:160); 1 in the seed column.  The labels do not depend on it."""
+    if confidence is not None and confidence not in crw_hip.CONF_KINDS:
+        raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
     T, N, H, W = seq.shape
     feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
     if T == 1:  # a one-frame item (the correction step of test_all.py can ask for it): nothing to propagate, like the reference
-        return seed[:, None].clone(), torch.zeros(N, 0), None
+        out = (seed[:, None].clone(), torch.zeros(N, 0), None)
+        return out if confidence is None else out + (torch.ones(N, 1, device=feats.device),)
     xent = crw_hip.xent_metric(feats)
     diffs = column_diffs_async(xent) if T > 2 else None  # on its way to the host before the label propagation is queued
     if hasattr(lp, 'propagate_all'):
-        pred, _ = lp.propagate_all(feats, seed, nclasses)
+        pred, L = lp.propagate_all(feats, seed, nclasses)
     else:  # foreign label-propagation object: reference's frame-by-frame protocol
         pred = torch.zeros(N, T, device=feats.device)
         pred[:, 0] = seed
@@ -142,8 +149,14 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last):
             fl.append(as_feat(n))
             ml.append(mask)
             pred[:, n] = mask.argmax(1).squeeze()
+        if confidence is not None:  # the masks `predict` returned, [1,M,N,1] each, as the rows of L
+            L = torch.cat(ml, 0)[..., 0].permute(0, 2, 1).reshape(T * N, nclasses).float().contiguous()
+    # queued right behind the propagation, before the host turns to the change point
+    conf = crw_hip.labelprop_confidence(L, T, N, nclasses, confidence) if confidence is not None else None
     # the change point is host work (PELT on T-2 samples): it runs while the GPU propagates the labels queued above
     change_idx = change_point(xent, diffs)
+    if confidence is not None:
+        return pred, xent.cpu(), change_idx, conf
     return pred, xent.cpu(), change_idx
 
 
