@@ -879,7 +879,8 @@ def test_labelprop_topk_on_matrix_cores_agrees_with_vector_kernel(hip, T, N, C, 
     """A radargram's column (N x 1 grid, N >= 16, C = 64 / 128 / 256) scores on the fp32 matrix cores
     (csrc/labelprop.hip labelprop_topk_mfma_kernel); a 1 x N grid is the same problem -- same candidates in the same order -- and runs
     the vector kernel.  Exact fp32 products in both, different summation order: the lists must agree except where two candidates
-    score within rounding of each other (then they carry the same weight to 1e-6), and the scores against fp64."""
+    score within rounding of each other (then they carry the same weight to 1e-6).  This compares the two kernels with each other
+    only; every list of either against fp64 logits: tests/test_labelprop_lists_gpu.py::test_topk_lists_against_fp64."""
     g = torch.Generator().manual_seed(T + N)
     feats = hip.normalize((torch.randn(1, N, C, generator=g) + 0.5 * torch.randn(T, N, C, generator=g)).float().cuda())
     Wm, Im = hip.labelprop_topk(feats, cxt, radius, 0.1, knn, first_frame=first, grid_w=1)
