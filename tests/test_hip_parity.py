@@ -671,21 +671,59 @@ def test_wgrad_patch_slice_lengths(hip, reps, split):
     torch.testing.assert_close(dw_s.cpu().double(), ref, rtol=1e-4, atol=1e-4 * ref.abs().max().item())
 
 
-@pytest.mark.parametrize("cin", [1, 2])
-@pytest.mark.parametrize("split", [3, 1])
-def test_encoder_front_kernels_match_torch(hip, cin, split):
-    """fused conv1-ReLU-pool-conv2-ReLU-pool forward and its backward against fp64 torch autograd."""
+def _pool_decisions_safe(pre, err):
+    """pre [P,C,H,W]: fp64 pre-activations in front of ReLU + maxpool 2x2/1, err: a bound on what the kernels' arithmetic can add
+    to each.  -> bool [P,C,H-1,W-1]: True where a window's gradient routing (arg-max and ReLU gate) is the same for every
+    perturbation within the bound: the maximum leads by more than the errors and is clear of zero, or all four values stay <= 0."""
+    win = lambda t: t.unfold(2, 2, 1).unfold(3, 2, 1).flatten(4)
+    v, e = win(pre), win(err).max(-1).values
+    top = v.topk(2, dim=-1).values
+    return ((top[..., 0] - top[..., 1] > 2 * e) & (top[..., 0] > e)) | (top[..., 0] < -e)
+
+
+def _well_posed_front_inputs(P, cin, h, w, w1, b1, w2, b2, g):
+    """Random patches x [P,cin,h,w] and output gradients dy [P,(h-6)*(w-6),32] on which a comparison of gradients with fp64 is
+    well posed.  Max-pooling and ReLU route a gradient by comparisons; where two candidates (or a maximum and zero) are closer
+    than the arithmetic's rounding error, fp64 and the kernels may rightly decide differently and a whole gradient term moves --
+    with 10^5..10^6 pooling windows in a test that is likely for a few of them.  The criterion looks at the fp64 reference
+    alone, with error bounds from the number formats: conv1 is fp32 FMA (at most 64 roundings of 2^-24 on the sum of absolute
+    products); conv2 runs on bf16 hi/lo pairs (8-bit significands: |lo| <= 2^-9 |hi|, the lo.lo product is dropped and each lo is
+    itself rounded: 3 * 2^-18 on the sum of absolute products) with fp32 accumulation (256 * 2^-24), plus conv1's error carried
+    through.  Patches with an unsafe pool1 / ReLU1 decision are redrawn; dy is set to zero at the pooled outputs whose
+    pool2 / ReLU2 decision is unsafe, so that whichever way it goes moves nothing."""
     import torch.nn.functional as TF
-    P = 7
+    w1, b1, w2, b2 = (t.detach() for t in (w1, b1, w2, b2))
+    keep = []
+    while sum(k.shape[0] for k in keep) < P:
+        x = torch.randn(P, cin, h, w, generator=g)
+        pre1 = TF.conv2d(x.double(), w1, b1, padding=1)
+        e1 = 64 * 2.0 ** -24 * (TF.conv2d(x.double().abs(), w1.abs(), b1.abs(), padding=1))
+        keep.append(x[_pool_decisions_safe(pre1, e1).flatten(1).all(1)])
+    x = torch.cat(keep)[:P]
+    xd = x.double()
+    e1 = 64 * 2.0 ** -24 * TF.conv2d(xd.abs(), w1.abs(), b1.abs(), padding=1)
+    a1 = TF.max_pool2d(TF.relu(TF.conv2d(xd, w1, b1, padding=1)), 2, 1)
+    pre2 = TF.conv2d(a1, w2, b2, padding=1)
+    e2 = (3 * 2.0 ** -18 + 256 * 2.0 ** -24) * TF.conv2d(a1, w2.abs(), b2.abs(), padding=1) + \
+        TF.conv2d(TF.max_pool2d(e1, 2, 1), w2.abs(), None, padding=1)
+    safe = _pool_decisions_safe(pre2, e2)  # [P,32,h-6,w-6]
+    dy = torch.randn(P, (h - 6) * (w - 6), 32, generator=g)
+    return x, dy * safe.permute(0, 2, 3, 1).reshape(dy.shape)
+
+
+def _front_16x16_vs_torch(hip, cin, split, P, well_posed=False):
+    import torch.nn.functional as TF
     g = torch.Generator().manual_seed(10 * cin + split)
-    x = torch.randn(P, cin, 16, 16, generator=g)
+    x = None if well_posed else torch.randn(P, cin, 16, 16, generator=g)
     w1 = (torch.randn(8, cin, 5, 5, generator=g) * 0.2).double().requires_grad_(True)
     b1 = (torch.randn(8, generator=g) * 0.1).double().requires_grad_(True)
     w2 = (torch.randn(32, 8, 5, 5, generator=g) * 0.07).double().requires_grad_(True)
     b2 = (torch.randn(32, generator=g) * 0.1).double().requires_grad_(True)
+    if well_posed:
+        x, dy = _well_posed_front_inputs(P, cin, 16, 16, w1, b1, w2, b2, g)
     a1 = TF.max_pool2d(TF.relu(TF.conv2d(x.double(), w1, b1, padding=1)), 2, 1)
     y = TF.max_pool2d(TF.relu(TF.conv2d(a1, w2, b2, padding=1)), 2, 1)  # [P,32,10,10]
-    dy = torch.randn(P, 100, 32, generator=g)
+    dy = dy if well_posed else torch.randn(P, 100, 32, generator=g)
     y.backward(dy.double().reshape(P, 10, 10, 32).permute(0, 3, 1, 2))
     c = lambda t: t.detach().float().cuda()
     w2f = hip.enc_front_pack(c(w2), split)
@@ -707,24 +745,37 @@ def test_encoder_front_kernels_match_torch(hip, cin, split):
         torch.testing.assert_close(got.cpu().double(), ref, **t)
 
 
-@pytest.mark.parametrize("cin,hw", [(1, (20, 27)), (2, (32, 32)), (1, (16, 16)), (1, (9, 12))])
+@pytest.mark.parametrize("cin", [1, 2])
 @pytest.mark.parametrize("split", [3, 1])
-def test_front_backward_on_tiles_matches_torch(hip, cin, hw, split):
-    """conv1-ReLU-pool-conv2-ReLU-pool backward on patches of any size (`crw_enc_front_bwd_map`: units of 10x10 output tiles,
-    partial tiles, a one-tile 16x16 case and a map smaller than a tile) against fp64 torch autograd."""
+def test_encoder_front_kernels_match_torch(hip, cin, split):
+    """fused conv1-ReLU-pool-conv2-ReLU-pool forward and its backward against fp64 torch autograd."""
+    _front_16x16_vs_torch(hip, cin, split, P=7)
+
+
+@pytest.mark.parametrize("split", [3, 1])
+def test_encoder_front_kernels_two_patches_per_workgroup(hip, split):
+    """The same at cin = 2 and P = 257 against the 256 slices of the backward kernels: two patches per workgroup, so the state
+    carried from one patch to the next (prefetch registers, the gradient planes' halo zeroed once, LDS aliases reused) is in
+    play; workgroup 128 holds one patch and workgroups 129-255 hold none and must write zero partial sums.  With 800 000
+    pooling windows the inputs are made well posed for the comparison with fp64 (`_well_posed_front_inputs`)."""
+    _front_16x16_vs_torch(hip, 2, split, P=257, well_posed=True)
+
+
+def _front_tiles_vs_torch(hip, cin, hw, split, P, well_posed=False):
     import torch.nn.functional as TF
-    P = 5
     h, w = hw
     g = torch.Generator().manual_seed(100 * cin + h + split)
-    x = torch.randn(P, cin, h, w, generator=g)
+    x = None if well_posed else torch.randn(P, cin, h, w, generator=g)
     w1 = (torch.randn(8, cin, 5, 5, generator=g) * 0.2).double().requires_grad_(True)
     b1 = (torch.randn(8, generator=g) * 0.1).double().requires_grad_(True)
     w2 = (torch.randn(32, 8, 5, 5, generator=g) * 0.07).double().requires_grad_(True)
     b2 = (torch.randn(32, generator=g) * 0.1).double().requires_grad_(True)
+    H, W = h - 6, w - 6
+    if well_posed:
+        x, dy = _well_posed_front_inputs(P, cin, h, w, w1, b1, w2, b2, g)
     a1 = TF.max_pool2d(TF.relu(TF.conv2d(x.double(), w1, b1, padding=1)), 2, 1)
     y = TF.max_pool2d(TF.relu(TF.conv2d(a1, w2, b2, padding=1)), 2, 1)  # [P,32,h-6,w-6]
-    H, W = h - 6, w - 6
-    dy = torch.randn(P, H * W, 32, generator=g)
+    dy = dy if well_posed else torch.randn(P, H * W, 32, generator=g)
     y.backward(dy.double().reshape(P, H, W, 32).permute(0, 3, 1, 2))
     c = lambda t: t.detach().float().cuda()
     w2f = hip.enc_front_pack(c(w2), split)
@@ -736,6 +787,23 @@ def test_front_backward_on_tiles_matches_torch(hip, cin, hw, split):
         t = dict(rtol=2e-3, atol=2e-3 * ref.abs().max().item()) if split == 3 else \
             dict(rtol=2e-1, atol=1.5e-1 * ref.abs().max().item())
         torch.testing.assert_close(got.cpu().double(), ref, **t)
+
+
+@pytest.mark.parametrize("cin,hw", [(1, (20, 27)), (2, (32, 32)), (1, (16, 16)), (1, (9, 12))])
+@pytest.mark.parametrize("split", [3, 1])
+def test_front_backward_on_tiles_matches_torch(hip, cin, hw, split):
+    """conv1-ReLU-pool-conv2-ReLU-pool backward on patches of any size (`crw_enc_front_bwd_map`: units of 10x10 output tiles,
+    partial tiles, a one-tile 16x16 case and a map smaller than a tile) against fp64 torch autograd."""
+    _front_tiles_vs_torch(hip, cin, hw, split, P=5)
+
+
+@pytest.mark.parametrize("cin,hw,P", [(1, (32, 32), 29), (2, (20, 27), 43)])
+@pytest.mark.parametrize("split", [3, 1])
+def test_front_backward_on_tiles_two_units_per_workgroup(hip, cin, hw, P, split):
+    """The same with more units than the 256 slices: 29 patches x 9 tiles = 261 units (131 workgroups of two units, the last
+    with one) and 43 patches x 6 tiles, some partial, = 258 units -- the tile kernel's unit loop runs twice, on LDS the
+    first unit left behind.  Inputs made well posed for the comparison with fp64 as in the 16x16 case."""
+    _front_tiles_vs_torch(hip, cin, hw, split, P=P, well_posed=True)
 
 
 LP_CASES = ["labelprop_trunc_T14N10", "labelprop_full_T40N48", "labelprop_last_T20N24", "labelprop_mc1_T100N12"]
