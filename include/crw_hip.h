@@ -25,6 +25,9 @@
  *                             the soft labels the scripts arg-max away          src/utils.py:160 (maskedatt.py CRW.forward:
  *                             (per-node confidence, a merge ruled by it,        masks_pred_conf), scripts/test/test_all.py:146-159
  *                             a reliability histogram): no reference twin
+ *   crw_labelmap_dense ...... bilinear upsampling of the soft labels + argmax,   src/imported/crw.py:124-127 (the upstream routine;
+ *                             the pixel map (and its confidence) in one pass     the radar scripts arg-max first and stretch the
+ *                                                                                node map with Resize(NEAREST): no twin there)
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HBM) unless its name ends in _host;
@@ -51,7 +54,7 @@ extern "C" {
 /* Bumps when a signature changes.  Entry points added at 8 without a bump (pure additions, no existing signature touched; the
  * binding detects them by symbol, crw_hip.has_sweep()): crw_labelprop_topk_scores, crw_labelprop_sweep_weights,
  * crw_labelprop_propagate_batch; then crw_labelprop_confidence, crw_merge_confidence, crw_calibration_ws_bytes, crw_calibration
- * (crw_hip.has_confidence()).  The ONE place the number is written: crw_abi_version() returns
+ * (crw_hip.has_confidence()); then crw_labelmap_dense (crw_hip.has_dense()).  The ONE place the number is written: crw_abi_version() returns
  * it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
 #define CRW_ABI_VERSION 8
@@ -234,6 +237,25 @@ size_t crw_calibration_ws_bytes(size_t P, int K, int bins);
 int crw_calibration(const void *gt, int gt_dtype, const void *pred, int pred_dtype, const float *conf, const void *aux, int aux_dtype,
                     size_t P, int K, int bins, int ignore_gt, int ignore_pred, int ignore_aux, int64_t *counts /* [bins][2] */,
                     double *conf_sum /* [bins] */, int64_t *dropped /* [3] */, void *ws, size_t ws_bytes, crw_stream_t stream);
+
+/* dense label maps ------------------------------------------------------------------------ */
+/* Pixel-resolution label map of one pass from its soft labels: L [T*N, M] (node (n, t) is row t*N + n; 4-byte aligned, wider
+ * loads where its address and M allow) is interpolated bilinearly to [rows, cols] -- rows along the nodes n, columns along the
+ * frames t -- and the interpolated row of every pixel is arg-maxed; the interpolated probabilities are never written.
+ * Geometry: the half-pixel convention of F.interpolate(mode='bilinear', align_corners=False), in integers.  For output row r:
+ * a = (2r + 1) N - rows, d = 2 rows (64-bit); a <= 0: i0 = i1 = 0, w = 0; else i0 = a / d; i0 >= N - 1: i0 = i1 = N - 1, w = 0;
+ * else i1 = i0 + 1, w = (float)(a - i0 d) / (float)d -- exact knots, and a weight that is the correctly rounded fp32 quotient of
+ * two integers fp32 holds exactly.  Columns likewise with T and cols.  1 <= rows, cols <= 2^22; T, N >= 1; 2 <= M <= 16.
+ * Arithmetic, per class, fp32 (contraction to FMA allowed): v = (1-wr) ((1-wc) p00 + wc p01) + wr ((1-wc) p10 + wc p11), p01 the
+ * next frame's node, p10 the next node.  Label: the class of the largest v, the lowest class on exact equality.  conf (conf_kind:
+ * a CRW_CONF_* kind; -1: none, conf NULL): crw_labelprop_confidence's formula on the interpolated row.  L is assumed finite.
+ * flip != 0: output column c holds what column cols - 1 - c would hold (the reverse pass's maps are mirrored).
+ * labels (label_dtype CRW_DT_F32 or CRW_DT_I8) and conf are [rows] x [cols] windows of maps with `ld` >= cols elements between
+ * rows (one pitch for both); no alignment beyond the element's is asked for: 16-byte stores (int8: packed 32-bit) where a lane's
+ * 4 pixels lie inside the window on such a boundary, single pixels at a row's head and tail; nothing outside the window is
+ * written.  One launch, plain vector stores, bit-reproducible. */
+int crw_labelmap_dense(const float *L, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
+                       int label_dtype, float *conf, size_t ld, crw_stream_t stream);
 
 /* building blocks exported for tests and the roofline bench --------------------------------- */
 /* Weight gradient of the CNN encoder's linear head (nn.Linear(128, 128), src/encoder.py:40,55; autograd of

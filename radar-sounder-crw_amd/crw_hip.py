@@ -62,6 +62,7 @@ SIGNATURES = {
     "crw_calibration_ws_bytes": (_c_sz, [_c_sz, _c_int, _c_int]),
     "crw_calibration": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _c_int, _c_sz, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p,
                                  _c_sz, _p]),
+    "crw_labelmap_dense": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _c_int, _p, _c_sz, _p]),
     "crw_linear128_wgrad_ws_bytes": (_c_sz, [_c_int]),
     "crw_linear128_wgrad": (_c_int, [_p, _p, _p, _c_int, _p, _c_sz, _p]),
     "crw_adam_step": (_c_int, [_p, _p, _p, _p, ctypes.c_long, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
@@ -136,21 +137,25 @@ SWEEP_ENTRY_POINTS = ("crw_labelprop_topk_scores", "crw_labelprop_sweep_weights"
 # likewise: the confidence entry points (`has_confidence()`)
 CONFIDENCE_ENTRY_POINTS = ("crw_labelprop_confidence", "crw_merge_confidence", "crw_calibration_ws_bytes", "crw_calibration")
 
+# likewise: the dense label map (`has_dense()`)
+DENSE_ENTRY_POINTS = ("crw_labelmap_dense",)
+
 _lib = None
 _has_sweep = False
 _has_confidence = False
+_has_dense = False
 
 
 def lib():
     """Load the HIP library (once).  Raises if it has not been built: `python -c 'import
     __graft_entry__ as g; g.build()'` or `make -C radar-sounder-crw_amd/csrc`."""
-    global _lib, _has_sweep, _has_confidence
+    global _lib, _has_sweep, _has_confidence, _has_dense
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} not built -- the CRW hot path has no CPU/PyTorch fallback; "
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
-        missing = [n for n in SWEEP_ENTRY_POINTS + CONFIDENCE_ENTRY_POINTS if not hasattr(handle, n)]
+        missing = [n for n in SWEEP_ENTRY_POINTS + CONFIDENCE_ENTRY_POINTS + DENSE_ENTRY_POINTS if not hasattr(handle, n)]
         for name, (res, args) in SIGNATURES.items():
             if name in missing:
                 continue
@@ -162,6 +167,7 @@ def lib():
         _lib = handle
         _has_sweep = not set(missing) & set(SWEEP_ENTRY_POINTS)
         _has_confidence = not set(missing) & set(CONFIDENCE_ENTRY_POINTS)
+        _has_dense = not set(missing) & set(DENSE_ENTRY_POINTS)
     return _lib
 
 
@@ -188,6 +194,19 @@ def _confidence_lib():
     if not has_confidence():
         raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
                            f"{', '.join(CONFIDENCE_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
+    return lib()
+
+
+def has_dense():
+    """True when the loaded library exports the dense label map's entry point (DENSE_ENTRY_POINTS)."""
+    lib()
+    return _has_dense
+
+
+def _dense_lib():
+    if not has_dense():
+        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
+                           f"{', '.join(DENSE_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
     return lib()
 
 
@@ -654,6 +673,96 @@ def _calibration_cpu(gt, pred, c, K, bins, aux, ignore_gt, ignore_pred, ignore_a
     ok = torch.bincount(row, weights=(binned & (g == p)).to(torch.float64), minlength=bins + 3).to(torch.int64)
     s = torch.bincount(row, weights=torch.where(binned, c.to(torch.float64), torch.zeros(1, dtype=torch.float64)), minlength=bins + 3)
     return torch.stack([n[:bins], ok[:bins]], 1), s[:bins], n[bins:]
+
+
+# ------------------------------------------------------------------------------ dense label maps
+DENSE_MAX_SIDE = 1 << 22
+
+
+def dense_knots(n_in, n_out, flip=False):
+    """Knots and weights of `labelmap_dense` along one axis of `n_out` pixels over `n_in` nodes, in integers (the half-pixel
+    convention of F.interpolate(mode='bilinear', align_corners=False)) -> (i0 int64 [n_out], i1 int64 [n_out], w float32 [n_out]).
+    a = (2x + 1) n_in - n_out over d = 2 n_out: exact knots, and the weight the correctly rounded fp32 quotient of two integers
+    fp32 holds exactly (n_out <= 2^22) -- no source coordinate in floating point."""
+    x = torch.arange(n_out, dtype=torch.int64)
+    if flip:
+        x = n_out - 1 - x
+    a, d = (2 * x + 1) * n_in - n_out, 2 * n_out
+    i0 = torch.div(a.clamp(min=0), d, rounding_mode="floor").clamp(max=n_in - 1)
+    inner = (a > 0) & (i0 < n_in - 1)
+    i1 = torch.where(inner, i0 + 1, i0)
+    w = torch.where(inner, (a - i0 * d).to(torch.float32) / float(d), torch.zeros(n_out))
+    return i0, i1, w
+
+
+def _window(t, name, rows, cols, dtype, device):
+    """A [rows, cols] output of `labelmap_dense`: contiguous, or a column window of a wider row-major map -> its pitch."""
+    if tuple(t.shape) != (rows, cols) or t.dtype != dtype or t.device != device:
+        raise ValueError(f"{name} must be {dtype} [{rows}, {cols}] on {device} (got {t.dtype} {tuple(t.shape)} on {t.device})")
+    if cols > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name} must be contiguous along its columns (stride {t.stride()}): a map, or a column window map[:, a:b]")
+    ld = t.stride(0) if rows > 1 else cols
+    if ld < cols:
+        raise ValueError(f"{name}: rows overlap (stride {t.stride()})")
+    return ld
+
+
+def labelmap_dense(L, T, N, M, rows, cols, *, confidence=None, flip=False, dtype=torch.float32, out=None, out_conf=None):
+    """Soft labels L [T*N, M] (a probability row per node, node (n, t) in row t*N + n) -> (labels [rows, cols], conf | None): the
+    rows interpolated bilinearly to pixels -- image rows along the nodes n, columns along the frames t, half-pixel convention, the
+    knots and weights of `dense_knots` -- and arg-maxed AFTER that (the lowest class on exact equality).  confidence: None, or a
+    kind of `labelprop_confidence` -- conf is then float32 [rows, cols], that formula on the interpolated row.  flip: the map
+    mirrored along its columns (the reverse pass's).  dtype: float32 (what `segment` returns) or int8 (what the drivers save).
+    out / out_conf: tensors to write into; they may be column windows of wider maps (``map[:, a:b]``, one pitch for both), anything
+    else that is not contiguous raises ValueError.  Device tensors: one launch of crw_labelmap_dense, nothing synchronises, the
+    interpolated probabilities are never written; CPU tensors: the same integer knots, fp32 weights, arithmetic and tie rule in
+    torch."""
+    code = -1 if confidence is None else _conf_kind(confidence)
+    T, N, M, rows, cols = int(T), int(N), int(M), int(rows), int(cols)
+    if not 2 <= M <= 16:
+        raise ValueError(f"M must be in 2 ... 16 (got {M})")
+    if T < 1 or N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
+        raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={T}, N={N}, rows={rows}, cols={cols})")
+    if L.numel() != T * N * M or L.dtype != torch.float32:
+        raise ValueError(f"L must be float32 [{T * N}, {M}] (got {L.dtype} {tuple(L.shape)})")
+    if dtype not in (torch.float32, torch.int8):
+        raise ValueError(f"dtype must be torch.float32 or torch.int8 (got {dtype})")
+    if out_conf is not None and confidence is None:
+        raise ValueError("out_conf needs a confidence kind")
+    if out is None:
+        out = torch.empty(rows, cols, dtype=dtype, device=L.device)
+    if out_conf is None and confidence is not None:
+        out_conf = torch.empty(rows, cols, dtype=torch.float32, device=L.device)
+    ld = _window(out, "out", rows, cols, dtype, L.device)
+    if out_conf is not None and _window(out_conf, "out_conf", rows, cols, torch.float32, L.device) != ld and rows > 1:
+        raise ValueError(f"out and out_conf must share one pitch (got {out.stride(0)} and {out_conf.stride(0)})")
+    L = L.contiguous()
+    if not L.is_cuda:
+        lab, conf = _labelmap_dense_cpu(L, T, N, M, rows, cols, confidence, flip)
+        out.copy_(lab.to(dtype))
+        if out_conf is not None:
+            out_conf.copy_(conf)
+        return out, out_conf
+    _check(_dense_lib().crw_labelmap_dense(_ptr(L), T, N, M, rows, cols, int(bool(flip)), code, _ptr(out),
+                                           DT_F32 if dtype == torch.float32 else DT_I8,
+                                           _ptr(out_conf) if out_conf is not None else None, ld, _stream()), "crw_labelmap_dense")
+    return out, out_conf
+
+
+def _labelmap_dense_cpu(L, T, N, M, rows, cols, confidence, flip):
+    i0, i1, wr = dense_knots(N, rows)
+    j0, j1, wc = dense_knots(T, cols, flip)
+    P = L.view(T, N, M)
+    wr, wc = wr[:, None, None], wc[None, :, None]
+    corner = lambda i, j: P[j[None, :], i[:, None]]  # [rows, cols, M]
+    top = (1 - wc) * corner(i0, j0) + wc * corner(i0, j1)
+    bot = (1 - wc) * corner(i1, j0) + wc * corner(i1, j1)
+    v = (1 - wr) * top + wr * bot
+    lab = v.argmax(-1)  # the first of equal maxima: the lowest class
+    conf = None
+    if confidence is not None:
+        conf = _labelprop_confidence_cpu(v.permute(1, 0, 2).reshape(rows * cols, M), cols, rows, M, confidence, 1)
+    return lab, conf
 
 
 def gemm_f32(A, B, C=None, transA=False, transB=False, beta=False):

@@ -13,6 +13,7 @@
 // __shfl_xor -- a fixed order -- and lane 0 adds the three numbers into the WAVE-PRIVATE histogram in LDS with plain loads and
 // stores.  The four waves' histograms are added in wave order, the workgroups' partials in index order.  Uniformly random bins
 // cost `bins` ballots per step (tools/confidence_timing.py times both).
+#include "confidence_of.h"
 #include "labelmap.h"
 
 namespace crw {
@@ -21,34 +22,6 @@ namespace {
 
 // ---- confidence of the soft labels ---------------------------------------------------------------------------------------------
 constexpr int LC_BLOCK = 256;
-
-template <int KIND>
-__device__ inline float confidence_of(const float (&p)[16], int M, float ln_m) {
-  if (KIND == CRW_CONF_ENTROPY) {
-    float s = 0.f;
-#pragma unroll
-    for (int m = 0; m < 16; ++m)
-      if (m < M) s += p[m] > 0.f ? p[m] * logf(p[m]) : 0.f;  // 0 ln 0 = 0
-    const float c = 1.f + s / ln_m;
-    return c != c ? c : fminf(fmaxf(c, 0.f), 1.f);
-  }
-  float m1 = p[0], m2 = -INFINITY;
-#pragma unroll
-  for (int m = 1; m < 16; ++m)
-    if (m < M) {
-      const float v = p[m];
-      if (v > m1 || v != v) {
-        m2 = m1;
-        m1 = v;
-      } else if (v > m2) {
-        m2 = v;
-      }
-    }
-  // a confidence is a number in [0, 1]: the rows of L sum to 1 within rounding only, so an entry (and a margin) can come out one or
-  // two ulps above 1 -- that reads 1, every value up to 1 passes through bit for bit (NaN too)
-  const float c = KIND == CRW_CONF_MAXPROB ? m1 : m1 - m2;
-  return c > 1.f ? 1.f : c;
-}
 
 // one node per thread, in L's order (rows of M floats: the threads of a wave read one contiguous stretch); conf is [N][T]
 template <int KIND>

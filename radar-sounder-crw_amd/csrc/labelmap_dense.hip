@@ -1,0 +1,224 @@
+// Pixel-resolution label map from the soft labels of crw_labelprop_propagate (L [T*N, M], one probability row per node): the
+// rows are interpolated bilinearly to [rows, cols] (half-pixel convention, the node is the centre of the cell it owns under the
+// nearest stretch) and arg-maxed AFTER that -- the upstream routine's order (imported/crw.py:124-127), which the radar scripts
+// replaced by arg-max + nearest.  The interpolated probabilities [M, rows, cols] are never written: a pixel's row lives in
+// registers, the outputs are the label (fp32 or int8) and, optionally, the confidence of the interpolated row.
+//
+// Shape.  The kernel is bound by its stores (1 or 4 [+ 4] bytes per pixel); its input is small -- 295 KB for T = 256, N = 48,
+// M = 6, well inside one XCD's 4 MiB L2 -- and a workgroup's tile of 16 rows x 256 columns touches a handful of nodes (4 x 10 at
+// 410 x 8192), which stay in the CU's L1: the node rows are read straight from memory, lanes of a wave mostly from the same
+// address, and a lane reads them once for consecutive pixels between the same knots.  What IS staged in LDS is the one expensive
+// thing per pixel, the 64-bit integer division behind every knot: a workgroup computes the knots and weights of its 16 rows and
+// 256 (+ 3) columns once, one division per thread, and every pixel looks its two up.
+//
+// A lane owns 4 consecutive pixels of a row that start on a 16-byte boundary of the fp32 outputs (a 4-byte boundary of an int8
+// map) and writes each output with one vector store; the groups that stick out of the window at a row's head and tail -- the map
+// may be a column window of a wider one, any pitch, any offset -- write their inside pixels one by one.  Plain stores only.
+#include "confidence_of.h"
+#include "labelmap.h"
+
+namespace crw {
+using namespace labelmap;
+namespace {
+
+constexpr int DN_BLOCK = 256;                  // 4 waves, one row each per step
+constexpr int DN_WAVES = DN_BLOCK / WAVE;
+constexpr int DN_LANE_PIX = 4;                 // pixels per lane
+constexpr int DN_COLS = WAVE * DN_LANE_PIX;    // columns per workgroup
+constexpr int DN_ROWS = 16;                    // rows per workgroup
+constexpr int DN_COL_KNOTS = DN_COLS + DN_LANE_PIX - 1;  // + the 3 columns a row's phase can shift the groups by
+
+struct DenseArgs {
+  const float *L;
+  void *lab;
+  float *conf;
+  size_t ld;
+  int T, N, M, rows, cols, flip;
+  int lab_phase;  // element index (mod 4) of lab's first pixel within a 16-byte (int8: 4-byte) unit
+  int conf_vec;   // conf shares that phase: 16-byte stores
+  float ln_m;
+};
+
+// Knot and weight of output index x on an axis of `n_out` pixels over `n_in` nodes, in integers: a = (2x + 1) n_in - n_out over
+// d = 2 n_out.  The knot is exact, the weight the correctly rounded quotient of two integers below 2^24.
+__device__ inline void knot(int x, int n_in, int n_out, int *i0, float *w) {
+  const long a = (2l * x + 1) * n_in - n_out, d = 2l * n_out;
+  *i0 = 0, *w = 0.f;
+  if (a <= 0) return;
+  const long q = a / d;
+  if (q >= n_in - 1) {
+    *i0 = n_in - 1;
+    return;
+  }
+  *i0 = (int)q;
+  *w = (float)(a - q * d) / (float)d;
+}
+
+template <int MCAP>
+__device__ inline void load_row(const float *__restrict__ row, int M, int vec, float (&p)[MCAP]) {
+  if (vec == 4) {
+#pragma unroll
+    for (int m = 0; m < MCAP; m += 4)
+      if (m < M) {
+        const float4 v = *reinterpret_cast<const float4 *>(row + m);
+        p[m] = v.x, p[m + 1] = v.y, p[m + 2] = v.z, p[m + 3] = v.w;
+      }
+  } else if (vec == 2) {
+#pragma unroll
+    for (int m = 0; m < MCAP; m += 2)
+      if (m < M) {
+        const float2 v = *reinterpret_cast<const float2 *>(row + m);
+        p[m] = v.x, p[m + 1] = v.y;
+      }
+  } else {
+#pragma unroll
+    for (int m = 0; m < MCAP; ++m)
+      if (m < M) p[m] = row[m];
+  }
+}
+
+// KIND: a CRW_CONF_* kind, or -1 for no confidence map; MCAP: 4, 8 or 16 >= M, the classes a lane keeps registers for
+template <typename LAB, int KIND, int MCAP>
+__global__ __launch_bounds__(DN_BLOCK) void labelmap_dense_kernel(DenseArgs a) {
+  __shared__ int col_j[DN_COL_KNOTS], row_i[DN_ROWS];
+  __shared__ float col_w[DN_COL_KNOTS], row_w[DN_ROWS];
+  const int row0 = blockIdx.x * DN_ROWS;
+  const long colb = (long)blockIdx.y * DN_COLS - (DN_LANE_PIX - 1);  // column of col_*[0]
+  for (int i = threadIdx.x; i < DN_COL_KNOTS + DN_ROWS; i += DN_BLOCK) {
+    int k = 0;
+    float w = 0.f;
+    if (i < DN_COL_KNOTS) {
+      const long c = colb + i;
+      if (c >= 0 && c < a.cols) knot(a.flip ? a.cols - 1 - (int)c : (int)c, a.T, a.cols, &k, &w);
+      col_j[i] = k, col_w[i] = w;  // outside the window: node 0, never stored
+    } else {
+      const int r = row0 + (i - DN_COL_KNOTS);
+      if (r < a.rows) knot(r, a.N, a.rows, &k, &w);
+      row_i[i - DN_COL_KNOTS] = k, row_w[i - DN_COL_KNOTS] = w;
+    }
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+  const int M = a.M, N = a.N;
+  const int vec = ((M & 3) == 0 && !((uintptr_t)a.L & 15)) ? 4 : ((M & 1) == 0 && !((uintptr_t)a.L & 7)) ? 2 : 1;
+  LAB *lab = static_cast<LAB *>(a.lab);
+
+  for (int rr = wave; rr < DN_ROWS; rr += DN_WAVES) {
+    const int r = row0 + rr;
+    if (r >= a.rows) break;
+    const int i0 = row_i[rr], i1 = i0 + 1 < N ? i0 + 1 : N - 1;
+    const float wr = row_w[rr];
+    const size_t rowoff = (size_t)r * a.ld;
+    const int phase = (int)((a.lab_phase + rowoff) & (DN_LANE_PIX - 1));
+    const int kx = DN_LANE_PIX * lane - phase + (DN_LANE_PIX - 1);  // this lane's first entry of col_*
+    const long c0 = colb + kx;                                      // its first column: -3 ... cols + 2
+    if (c0 >= a.cols) continue;
+
+    float p00[MCAP], p01[MCAP], p10[MCAP], p11[MCAP];
+    float lab4[DN_LANE_PIX], conf4[DN_LANE_PIX];
+    int pj0 = -1, pj1 = -1;
+#pragma unroll
+    for (int e = 0; e < DN_LANE_PIX; ++e) {
+      const int j0 = col_j[kx + e], j1 = j0 + 1 < a.T ? j0 + 1 : a.T - 1;
+      const float wc = col_w[kx + e];
+      if (j0 != pj0 || j1 != pj1) {  // consecutive pixels mostly sit between the same two frames
+        load_row(a.L + ((size_t)j0 * N + i0) * M, M, vec, p00);
+        load_row(a.L + ((size_t)j1 * N + i0) * M, M, vec, p01);
+        load_row(a.L + ((size_t)j0 * N + i1) * M, M, vec, p10);
+        load_row(a.L + ((size_t)j1 * N + i1) * M, M, vec, p11);
+        pj0 = j0, pj1 = j1;
+      }
+      float v[16], top1 = 0.f;
+      int best = 0;
+#pragma unroll
+      for (int m = 0; m < 16; ++m) {
+        v[m] = 0.f;
+        if (m < MCAP && m < M) {
+          const float top = (1.f - wc) * p00[m] + wc * p01[m];
+          const float bot = (1.f - wc) * p10[m] + wc * p11[m];
+          v[m] = (1.f - wr) * top + wr * bot;
+          if (m == 0 || v[m] > top1) top1 = v[m], best = m;  // strict: a tie keeps the lowest class
+        }
+      }
+      lab4[e] = (float)best;
+      conf4[e] = KIND >= 0 ? confidence_of<(KIND >= 0 ? KIND : 0)>(v, M, a.ln_m) : 0.f;
+    }
+
+    if (c0 >= 0 && c0 + DN_LANE_PIX <= a.cols) {  // a whole group: its first pixel sits on the vector boundary
+      if (sizeof(LAB) == 4) {
+        *reinterpret_cast<float4 *>(lab + rowoff + c0) = make_float4(lab4[0], lab4[1], lab4[2], lab4[3]);
+      } else {
+        const uint32_t pk = (uint32_t)lab4[0] | (uint32_t)lab4[1] << 8 | (uint32_t)lab4[2] << 16 | (uint32_t)lab4[3] << 24;
+        *reinterpret_cast<uint32_t *>(lab + rowoff + c0) = pk;
+      }
+      if (KIND >= 0) {
+        if (a.conf_vec) {
+          *reinterpret_cast<float4 *>(a.conf + rowoff + c0) = make_float4(conf4[0], conf4[1], conf4[2], conf4[3]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < DN_LANE_PIX; ++e) a.conf[rowoff + c0 + e] = conf4[e];
+        }
+      }
+    } else {  // head or tail of the row: the pixels inside the window, one by one
+#pragma unroll
+      for (int e = 0; e < DN_LANE_PIX; ++e) {
+        const long c = c0 + e;
+        if (c >= 0 && c < a.cols) {
+          lab[rowoff + c] = (LAB)lab4[e];
+          if (KIND >= 0) a.conf[rowoff + c] = conf4[e];
+        }
+      }
+    }
+  }
+}
+
+template <typename LAB, int KIND>
+void launch_dense_m(dim3 grid, hipStream_t s, const DenseArgs &a) {
+  if (a.M <= 4)
+    hipLaunchKernelGGL((labelmap_dense_kernel<LAB, KIND, 4>), grid, dim3(DN_BLOCK), 0, s, a);
+  else if (a.M <= 8)
+    hipLaunchKernelGGL((labelmap_dense_kernel<LAB, KIND, 8>), grid, dim3(DN_BLOCK), 0, s, a);
+  else
+    hipLaunchKernelGGL((labelmap_dense_kernel<LAB, KIND, 16>), grid, dim3(DN_BLOCK), 0, s, a);
+}
+
+template <typename LAB>
+void launch_dense(int kind, dim3 grid, hipStream_t s, const DenseArgs &a) {
+  if (kind < 0)
+    launch_dense_m<LAB, -1>(grid, s, a);
+  else if (kind == CRW_CONF_MAXPROB)
+    launch_dense_m<LAB, CRW_CONF_MAXPROB>(grid, s, a);
+  else if (kind == CRW_CONF_MARGIN)
+    launch_dense_m<LAB, CRW_CONF_MARGIN>(grid, s, a);
+  else
+    launch_dense_m<LAB, CRW_CONF_ENTROPY>(grid, s, a);
+}
+
+}  // namespace
+}  // namespace crw
+
+extern "C" int crw_labelmap_dense(const float *L, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
+                                  int label_dtype, float *conf, size_t ld, crw_stream_t stream) {
+  using namespace crw;
+  clear_stale_error();
+  constexpr int MAX_SIDE = 1 << 22;  // 2 * side < 2^24: the weights' numerators and denominators are exact in fp32
+  if (!L || !labels || T < 1 || N < 1 || M < 2 || M > 16 || rows < 1 || cols < 1 || rows > MAX_SIDE || cols > MAX_SIDE ||
+      !dtype_ok(label_dtype) || conf_kind < -1 || conf_kind > CRW_CONF_ENTROPY || (conf_kind == -1) != (conf == nullptr) ||
+      ld < (size_t)cols || ((uintptr_t)L & 3) || ((uintptr_t)conf & 3) || (label_dtype == CRW_DT_F32 && ((uintptr_t)labels & 3)))
+    return CRW_EINVAL;
+  DenseArgs a;
+  a.L = L, a.lab = labels, a.conf = conf, a.ld = ld;
+  a.T = T, a.N = N, a.M = M, a.rows = rows, a.cols = cols, a.flip = flip != 0;
+  a.lab_phase = (int)(((uintptr_t)labels / elem(label_dtype)) & (DN_LANE_PIX - 1));
+  a.conf_vec = conf && (int)(((uintptr_t)conf / 4) & (DN_LANE_PIX - 1)) == a.lab_phase;
+  a.ln_m = logf((float)M);
+  // a row's groups: ceil((cols + phase) / 4) <= (cols + 3 + 3) / 4
+  const unsigned groups = ((unsigned)cols + 2 * (DN_LANE_PIX - 1)) / DN_LANE_PIX;
+  const dim3 grid(((unsigned)rows + DN_ROWS - 1) / DN_ROWS, (groups + WAVE - 1) / WAVE);
+  if (label_dtype == CRW_DT_F32)
+    launch_dense<float>(conf_kind, grid, (hipStream_t)stream, a);
+  else
+    launch_dense<int8_t>(conf_kind, grid, (hipStream_t)stream, a);
+  return check_launch();
+}

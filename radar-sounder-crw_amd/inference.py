@@ -70,7 +70,7 @@ def _reverse_rule_mask(final_pred, pred_rev, dataset_id):
 
 @torch.no_grad()
 def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap, pos_embed=False,
-            correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule'):
+            correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest'):
     """dataset: RGDataset (full, overlapping items); seg: reference segmentation [rows, W_rg].
     -> dict(pred [rows, n_rg * rg_len] float labels after the optional reverse merge,
             forward: the forward (+ corrected) map the reference saves as int8 (test_all.py:128),
@@ -83,9 +83,16 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     merge: how the reverse pass (``use_last``) enters ``pred``.  'rule': the reference's class rule (`merge_reverse`), defined for
     dataset ids 0, 1 and 3; ``conf`` is the reverse pass's exactly where the rule wrote its label.  'confidence': per pixel, the
     pass that is surer (`crw_hip.merge_confidence`: the reverse pass where its confidence is strictly larger) -- needs no class
-    semantics, so any ``dataset_id`` is accepted; needs ``confidence``."""
+    semantics, so any ``dataset_id`` is accepted; needs ``confidence``.
+    upsample: how a pass's [N, T] nodes become pixels.  'nearest': the reference's -- arg-max per node, then Resize(NEAREST), every
+    class boundary on the node grid.  'bilinear': the upstream routine's order (imported/crw.py:124-127) -- the pass's soft labels
+    interpolated bilinearly to pixels and arg-maxed after that (`crw_hip.labelmap_dense`, one kernel per pass, straight into the
+    pass's column window of the map); ``conf`` / ``forward_conf`` are then the confidence of the INTERPOLATED distribution.  Same
+    passes, corrections, exception policy and merges."""
     if merge not in ('rule', 'confidence'):
         raise ValueError(f"merge must be 'rule' or 'confidence' (got {merge!r})")
+    if upsample not in ('nearest', 'bilinear'):
+        raise ValueError(f"upsample must be 'nearest' or 'bilinear' (got {upsample!r})")
     if confidence is not None and confidence not in crw_hip.CONF_KINDS:
         raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
     if merge == 'confidence' and confidence is None:
@@ -101,6 +108,9 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     idx = idx[:n_rg]
     seg = seg[:, :n_rg * rg_len].to(device)
     rows = seg.shape[0]
+    if upsample == 'bilinear':
+        return _segment_dense(dataset, seg, encoder, lp, nclasses, T, W, ow, N, rg_len, rg_h, idx, pos_embed, correction, use_last,
+                              dataset_id, device, confidence, merge)
 
     maps, cmaps, xents, changes = [], [], [], []
     for t, i in enumerate(idx):
@@ -160,6 +170,73 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
             if want:
                 ruled = _reverse_rule_mask(forward, rev, dataset_id).view_as(forward)
                 final_conf = torch.where(ruled, unflip(rev_cmaps), forward_conf)
+    out = dict(pred=final, forward=forward, xent=xents, change_idx=changes)
+    if want:
+        out.update(conf=final_conf, forward_conf=forward_conf)
+    return out
+
+
+def _segment_dense(dataset, seg, encoder, lp, nclasses, T, W, ow, N, rg_len, rg_h, idx, pos_embed, correction, use_last, dataset_id,
+                   device, confidence, merge):
+    """`segment(..., upsample='bilinear')` behind its argument checks: `segment`'s passes with every map written by
+    `crw_hip.labelmap_dense` from the pass's soft labels.  The maps are allocated ONCE at [rows, n_rg * rg_len] and every pass
+    writes its own column window: the forward pass its radargram's, a correction the last ``px`` columns of it -- only after its
+    `propagate` succeeded --, the reverse pass its radargram's, mirrored (``flip``).  No list of maps, no cat, no flip."""
+    want = confidence is not None
+    rows, n_rg = seg.shape[0], len(idx)
+    new = lambda: torch.empty(rows, n_rg * rg_len, device=device)
+
+    def dense(L, frames, out, out_conf, flip=False):
+        crw_hip.labelmap_dense(L, frames, N, nclasses, rows, out.shape[1], confidence=confidence, flip=flip, out=out,
+                               out_conf=out_conf)
+
+    forward, forward_conf = new(), (new() if want else None)
+    win = lambda m, a, b: m[:, a:b] if m is not None else None
+    xents, changes = [], []
+    for t, i in enumerate(idx):
+        seq = dataset[i].to(device)
+        seg_ref = seg[:rg_h, rg_len * t:rg_len * t + W]
+        _, xent, change, L = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=False, soft=True)
+        dense(L, seq.shape[0], win(forward, rg_len * t, rg_len * (t + 1)), win(forward_conf, rg_len * t, rg_len * (t + 1)))
+        xents.append(xent)
+        changes.append(change)
+
+    if correction:
+        for t, change in enumerate(changes):
+            if change is None:
+                continue
+            small = T - change
+            px = small * (W - ow)
+            try:  # `segment`'s policy: a correction that fails on its data is skipped, a failure of the HIP path is not
+                seq = dataset.get_smaller_item(idx[t], small).to(device)
+                seg_ref = seg[:, rg_len * t + rg_len - px:rg_len * t + rg_len - px + W]
+                _, _, _, L = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=False, soft=True)
+                a, b = rg_len * t + rg_len - px, rg_len * (t + 1)
+                dense(L, seq.shape[0], win(forward, a, b), win(forward_conf, a, b))
+            except crw_hip.CrwError as e:
+                if e.device_failure:
+                    raise
+            except torch.AcceleratorError:
+                raise
+            except Exception:
+                pass
+
+    final, final_conf = forward, forward_conf
+    if use_last:
+        rev, rev_conf = new(), (new() if want else None)
+        seg_rev = torch.flip(seg.unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
+        for t, i in enumerate(idx):
+            seq = dataset[i].to(device)
+            seg_ref = seg_rev[:, rg_len * t:rg_len * t + W]
+            _, _, _, L = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=True, soft=True)
+            dense(L, seq.shape[0], win(rev, rg_len * t, rg_len * (t + 1)), win(rev_conf, rg_len * t, rg_len * (t + 1)), flip=True)
+        if merge == 'confidence':
+            final, final_conf, _ = crw_hip.merge_confidence(forward, forward_conf, rev, rev_conf)
+        else:
+            final = merge_reverse(forward, rev, dataset_id)
+            if want:
+                ruled = _reverse_rule_mask(forward, rev, dataset_id).view_as(forward)
+                final_conf = torch.where(ruled, rev_conf, forward_conf)
     out = dict(pred=final, forward=forward, xent=xents, change_idx=changes)
     if want:
         out.update(conf=final_conf, forward_conf=forward_conf)

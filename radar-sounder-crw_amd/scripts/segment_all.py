@@ -15,7 +15,9 @@ matrix, dropped pixels, elapsed times); ``--iou``: also print the IoU table; ``-
 per-pixel confidence of the map (``inference.segment(..., confidence=...)``) and, after the confusion matrix, its calibration table
 (``inference.calibration``, ``--bins B`` confidence bins; ``--report_json`` gains a ``calibration`` key); ``--save_conf`` writes the
 confidence of the final map as ``confidence_map.pt`` (float32); ``--merge confidence``: the reverse pass of ``--use_last`` is merged
-per pixel by confidence instead of by the reference's class rule.  Without these flags the output is what it was.
+per pixel by confidence instead of by the reference's class rule; ``--upsample bilinear``: the maps come from the soft labels,
+interpolated bilinearly to pixels and arg-maxed after that (``inference.segment(..., upsample='bilinear')``; ``--report_json`` gains
+``"upsample": "bilinear"``) instead of the reference's arg-max + nearest stretch.  Without these flags the output is what it was.
 Differences from the scripts:
   * plots are not drawn;
   * true / false flags read true / false (the scripts take any given string as true); ``--patch_size`` takes two numbers;
@@ -83,6 +85,8 @@ def get_args_parser():
                    help="how --use_last merges the reverse pass: the reference's class rule, or per pixel the surer pass")
     p.add_argument('--bins', default=10, type=int, metavar='B', help='confidence bins of the calibration table (1 ... 64)')
     p.add_argument('--save_conf', action='store_true', help='write confidence_map.pt (needs --confidence)')
+    p.add_argument('--upsample', default='nearest', choices=('nearest', 'bilinear'),
+                   help="node labels to pixels: the reference's arg-max + nearest, or soft labels interpolated bilinearly, then arg-max")
     return p
 
 
@@ -109,6 +113,8 @@ def check_confidence_flags(args):
         raise SystemExit('--confidence is not available with --single')
     if not 1 <= args.bins <= 64:
         raise SystemExit(f'--bins {args.bins}: 1 ... 64')
+    if args.upsample != 'nearest' and args.single:
+        raise SystemExit('--upsample bilinear is not available with --single')
     return args
 
 
@@ -152,6 +158,8 @@ def main(args):
     args = check_confidence_flags(with_defaults(args))
     # without --confidence the four flags that go with it do nothing, and the line reads as it did before they existed
     hidden = () if args.confidence else ('confidence', 'merge', 'bins', 'save_conf')
+    if args.upsample == 'nearest':  # likewise
+        hidden += ('upsample',)
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -177,7 +185,8 @@ def main(args):
             correction = False
         out = inference.segment(dataset, seg, encoder, lp, nclasses, T, args.patch_size, args.overlap, pos_embed=args.pos_embed,
                                 correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device,
-                                **(dict(confidence=args.confidence, merge=args.merge) if args.confidence else {}))
+                                **(dict(confidence=args.confidence, merge=args.merge) if args.confidence else {}),
+                                **(dict(upsample=args.upsample) if args.upsample != 'nearest' else {}))
         if correction:
             print('Change point for each radargram:', out['change_idx'])
         final, forward = out['pred'], out['forward']
@@ -213,6 +222,8 @@ def main(args):
         d.update(labels=report.labels, matrix=report.matrix.tolist(), dropped=dict(masked=report.dropped[0], invalid=report.dropped[1]),
                  pixels=int(final.numel()), map_shape=list(final.shape), elapsed_inference_s=t_inference, elapsed_total_s=t_all,
                  dataset=args.dataset, remove_unc=args.remove_unc, single=args.single)
+        if args.upsample != 'nearest':
+            d['upsample'] = args.upsample
         if cal is not None:
             d['calibration'] = dict(cal.to_dict(), kind=args.confidence, merge=args.merge)
         with open(args.report_json, 'w') as f:

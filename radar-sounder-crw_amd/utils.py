@@ -120,20 +120,27 @@ def _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last):
 
 
 @torch.no_grad()
-def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, confidence=None):
+def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False):
     """seq [T,N,h,w]; seg_ref [rows, w] class ids of the first (or last) frame; model: encoder;
     lp: LabelPropVOS_CRW  ->  (labels [N,T] float, xent [N,T-1] (CPU), change_idx | None).
 
     confidence: None, or a kind of `crw_hip.labelprop_confidence` ('maxprob', 'margin', 'entropy') -- the tuple then gains a
     fourth entry, conf [N,T] float on the labels' device: the confidence of every label, from the soft labels the propagation
-    wrote (the reference arg-maxes them away, src/utils.py:160); 1 in the seed column.  The labels do not depend on it."""
+    wrote (the reference arg-maxes them away, src/utils.py:160); 1 in the seed column.  The labels do not depend on it.
+    soft: the tuple gains, as its LAST entry, the soft labels themselves: L [T*N, M] float32 on the labels' device, node (n, t) in
+    row t*N + n, frames in the pass's own order (reversed under ``use_last``, like the labels); frame 0 -- and a one-frame item --
+    is the one-hot of the seed.  What `crw_hip.labelmap_dense` turns into a pixel map."""
     if confidence is not None and confidence not in crw_hip.CONF_KINDS:
         raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
     T, N, H, W = seq.shape
     feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
     if T == 1:  # a one-frame item (the correction step of test_all.py can ask for it): nothing to propagate, like the reference
         out = (seed[:, None].clone(), torch.zeros(N, 0), None)
-        return out if confidence is None else out + (torch.ones(N, 1, device=feats.device),)
+        if confidence is not None:
+            out += (torch.ones(N, 1, device=feats.device),)
+        if soft:
+            out += ((seed[:, None] == torch.arange(nclasses, device=feats.device)[None, :]).float(),)
+        return out
     xent = crw_hip.xent_metric(feats)
     diffs = column_diffs_async(xent) if T > 2 else None  # on its way to the host before the label propagation is queued
     if hasattr(lp, 'propagate_all'):
@@ -149,15 +156,18 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, conf
             fl.append(as_feat(n))
             ml.append(mask)
             pred[:, n] = mask.argmax(1).squeeze()
-        if confidence is not None:  # the masks `predict` returned, [1,M,N,1] each, as the rows of L
+        if confidence is not None or soft:  # the masks `predict` returned, [1,M,N,1] each, as the rows of L
             L = torch.cat(ml, 0)[..., 0].permute(0, 2, 1).reshape(T * N, nclasses).float().contiguous()
     # queued right behind the propagation, before the host turns to the change point
     conf = crw_hip.labelprop_confidence(L, T, N, nclasses, confidence) if confidence is not None else None
     # the change point is host work (PELT on T-2 samples): it runs while the GPU propagates the labels queued above
     change_idx = change_point(xent, diffs)
+    out = (pred, xent.cpu(), change_idx)
     if confidence is not None:
-        return pred, xent.cpu(), change_idx, conf
-    return pred, xent.cpu(), change_idx
+        out += (conf,)
+    if soft:
+        out += (L,)
+    return out
 
 
 def ndiag_matrix(size, n=1):
