@@ -28,6 +28,8 @@
  *   crw_labelmap_dense ...... bilinear upsampling of the soft labels + argmax,   src/imported/crw.py:124-127 (the upstream routine;
  *                             the pixel map (and its confidence) in one pass     the radar scripts arg-max first and stretch the
  *                                                                                node map with Resize(NEAREST): no twin there)
+ *   crw_labelmap_dense_batch  the same map for every configuration of a sweep     (no twin: scripts/launch/launch_test_batch.sh
+ *                             in one launch                                       runs test_all.py per setting, nearest maps)
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HBM) unless its name ends in _host;
@@ -54,7 +56,8 @@ extern "C" {
 /* Bumps when a signature changes.  Entry points added at 8 without a bump (pure additions, no existing signature touched; the
  * binding detects them by symbol, crw_hip.has_sweep()): crw_labelprop_topk_scores, crw_labelprop_sweep_weights,
  * crw_labelprop_propagate_batch; then crw_labelprop_confidence, crw_merge_confidence, crw_calibration_ws_bytes, crw_calibration
- * (crw_hip.has_confidence()); then crw_labelmap_dense (crw_hip.has_dense()).  The ONE place the number is written: crw_abi_version() returns
+ * (crw_hip.has_confidence()); then crw_labelmap_dense (crw_hip.has_dense()); then crw_labelmap_dense_batch
+ * (crw_hip.has_dense_batch()).  The ONE place the number is written: crw_abi_version() returns
  * it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
 #define CRW_ABI_VERSION 8
@@ -246,8 +249,9 @@ int crw_calibration(const void *gt, int gt_dtype, const void *pred, int pred_dty
  * a = (2r + 1) N - rows, d = 2 rows (64-bit); a <= 0: i0 = i1 = 0, w = 0; else i0 = a / d; i0 >= N - 1: i0 = i1 = N - 1, w = 0;
  * else i1 = i0 + 1, w = (float)(a - i0 d) / (float)d -- exact knots, and a weight that is the correctly rounded fp32 quotient of
  * two integers fp32 holds exactly.  Columns likewise with T and cols.  1 <= rows, cols <= 2^22; T, N >= 1; 2 <= M <= 16.
- * Arithmetic, per class, fp32 (contraction to FMA allowed): v = (1-wr) ((1-wc) p00 + wc p01) + wr ((1-wc) p10 + wc p11), p01 the
- * next frame's node, p10 the next node.  Label: the class of the largest v, the lowest class on exact equality.  conf (conf_kind:
+ * Arithmetic, per class, fp32: v = (1-wr) ((1-wc) p00 + wc p01) + wr ((1-wc) p10 + wc p11), p01 the next frame's node, p10 the
+ * next node; each of the three sums as fma(w, b, round((1-w) a)) -- written out, not left to the compiler's contraction, so every
+ * pixel of this kernel and of crw_labelmap_dense_batch rounds alike.  Label: the class of the largest v, the lowest class on exact equality.  conf (conf_kind:
  * a CRW_CONF_* kind; -1: none, conf NULL): crw_labelprop_confidence's formula on the interpolated row.  L is assumed finite.
  * flip != 0: output column c holds what column cols - 1 - c would hold (the reverse pass's maps are mirrored).
  * labels (label_dtype CRW_DT_F32 or CRW_DT_I8) and conf are [rows] x [cols] windows of maps with `ld` >= cols elements between
@@ -256,6 +260,15 @@ int crw_calibration(const void *gt, int gt_dtype, const void *pred, int pred_dty
  * written.  One launch, plain vector stores, bit-reproducible. */
 int crw_labelmap_dense(const float *L, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
                        int label_dtype, float *conf, size_t ld, crw_stream_t stream);
+/* crw_labelmap_dense for the G configurations of a sweep's pass in ONE launch (no reference twin; correctness is equality with the
+ * one-map call).  L [G, T*N, M], as crw_labelprop_propagate_batch leaves it; configuration g's outputs are the [rows] x [cols]
+ * windows at labels + g * map_stride elements and conf + g * map_stride, pitch `ld` -- so maps[:, :, a:b] of a [G, rows, width]
+ * tensor is a valid target.  Slice g is bit-identical to crw_labelmap_dense(L + g*T*N*M, ...) written into the same window, labels
+ * and confidence (one device function holds the per-pixel arithmetic of both kernels); nothing outside the G windows is written.
+ * crw_labelmap_dense's limits, and 1 <= G <= 65535, map_stride >= (rows-1)*ld + cols.  One launch, plain vector stores, no atomics,
+ * bit-reproducible. */
+int crw_labelmap_dense_batch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
+                             int label_dtype, float *conf, size_t ld, size_t map_stride, crw_stream_t stream);
 
 /* building blocks exported for tests and the roofline bench --------------------------------- */
 /* Weight gradient of the CNN encoder's linear head (nn.Linear(128, 128), src/encoder.py:40,55; autograd of

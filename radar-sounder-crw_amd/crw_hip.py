@@ -63,6 +63,7 @@ SIGNATURES = {
     "crw_calibration": (_c_int, [_p, _c_int, _p, _c_int, _p, _p, _c_int, _c_sz, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p,
                                  _c_sz, _p]),
     "crw_labelmap_dense": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _c_int, _p, _c_sz, _p]),
+    "crw_labelmap_dense_batch": (_c_int, [_p] + [_c_int] * 8 + [_p, _c_int, _p, _c_sz, _c_sz, _p]),
     "crw_linear128_wgrad_ws_bytes": (_c_sz, [_c_int]),
     "crw_linear128_wgrad": (_c_int, [_p, _p, _p, _c_int, _p, _c_sz, _p]),
     "crw_adam_step": (_c_int, [_p, _p, _p, _p, ctypes.c_long, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
@@ -140,22 +141,27 @@ CONFIDENCE_ENTRY_POINTS = ("crw_labelprop_confidence", "crw_merge_confidence", "
 # likewise: the dense label map (`has_dense()`)
 DENSE_ENTRY_POINTS = ("crw_labelmap_dense",)
 
+# likewise: the dense label maps of a sweep's G configurations in one launch (`has_dense_batch()`)
+DENSE_BATCH_ENTRY_POINTS = ("crw_labelmap_dense_batch",)
+
 _lib = None
 _has_sweep = False
 _has_confidence = False
 _has_dense = False
+_has_dense_batch = False
 
 
 def lib():
     """Load the HIP library (once).  Raises if it has not been built: `python -c 'import
     __graft_entry__ as g; g.build()'` or `make -C radar-sounder-crw_amd/csrc`."""
-    global _lib, _has_sweep, _has_confidence, _has_dense
+    global _lib, _has_sweep, _has_confidence, _has_dense, _has_dense_batch
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} not built -- the CRW hot path has no CPU/PyTorch fallback; "
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
-        missing = [n for n in SWEEP_ENTRY_POINTS + CONFIDENCE_ENTRY_POINTS + DENSE_ENTRY_POINTS if not hasattr(handle, n)]
+        missing = [n for n in SWEEP_ENTRY_POINTS + CONFIDENCE_ENTRY_POINTS + DENSE_ENTRY_POINTS + DENSE_BATCH_ENTRY_POINTS
+                   if not hasattr(handle, n)]
         for name, (res, args) in SIGNATURES.items():
             if name in missing:
                 continue
@@ -168,6 +174,7 @@ def lib():
         _has_sweep = not set(missing) & set(SWEEP_ENTRY_POINTS)
         _has_confidence = not set(missing) & set(CONFIDENCE_ENTRY_POINTS)
         _has_dense = not set(missing) & set(DENSE_ENTRY_POINTS)
+        _has_dense_batch = not set(missing) & set(DENSE_BATCH_ENTRY_POINTS)
     return _lib
 
 
@@ -207,6 +214,19 @@ def _dense_lib():
     if not has_dense():
         raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
                            f"{', '.join(DENSE_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
+    return lib()
+
+
+def has_dense_batch():
+    """True when the loaded library exports the batched dense label map's entry point (DENSE_BATCH_ENTRY_POINTS)."""
+    lib()
+    return _has_dense_batch
+
+
+def _dense_batch_lib():
+    if not has_dense_batch():
+        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
+                           f"{', '.join(DENSE_BATCH_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
     return lib()
 
 
@@ -746,6 +766,71 @@ def labelmap_dense(L, T, N, M, rows, cols, *, confidence=None, flip=False, dtype
     _check(_dense_lib().crw_labelmap_dense(_ptr(L), T, N, M, rows, cols, int(bool(flip)), code, _ptr(out),
                                            DT_F32 if dtype == torch.float32 else DT_I8,
                                            _ptr(out_conf) if out_conf is not None else None, ld, _stream()), "crw_labelmap_dense")
+    return out, out_conf
+
+
+def _window_batch(t, name, G, rows, cols, dtype, device):
+    """A [G, rows, cols] output of `labelmap_dense_batch`: contiguous, or the column windows maps[:, :, a:b] of a wider
+    [G, rows, width] tensor -> (pitch between rows, elements between maps)."""
+    if tuple(t.shape) != (G, rows, cols) or t.dtype != dtype or t.device != device:
+        raise ValueError(f"{name} must be {dtype} [{G}, {rows}, {cols}] on {device} (got {t.dtype} {tuple(t.shape)} on {t.device})")
+    if cols > 1 and t.stride(2) != 1:
+        raise ValueError(f"{name} must be contiguous along its columns (stride {t.stride()}): maps, or column windows maps[:, :, a:b]")
+    ld = t.stride(1) if rows > 1 else cols
+    if ld < cols:
+        raise ValueError(f"{name}: rows overlap (stride {t.stride()})")
+    span = (rows - 1) * ld + cols
+    map_stride = t.stride(0) if G > 1 else span
+    if map_stride < span:
+        raise ValueError(f"{name}: maps overlap (stride {t.stride()})")
+    return ld, map_stride
+
+
+def labelmap_dense_batch(L, G, T, N, M, rows, cols, *, confidence=None, flip=False, dtype=torch.int8, out=None, out_conf=None):
+    """`labelmap_dense` for the G configurations of a sweep's pass at once: L [G, T*N, M] (`labelprop_propagate_batch`'s soft
+    labels) -> (labels [G, rows, cols], conf | None); slice g is `labelmap_dense(L[g], ...)` bit for bit, labels and confidence.
+    dtype: int8 (what `segment_sweep` keeps) or float32.  out / out_conf: [G, rows, cols] tensors to write into; they may be the
+    column windows ``maps[:, :, a:b]`` of wider [G, rows, width] tensors (one pitch and one map stride for both), anything else
+    that is not contiguous raises ValueError.  Device tensors: ONE launch of crw_labelmap_dense_batch, nothing synchronises; CPU
+    tensors: a loop of `labelmap_dense`'s CPU route over the configurations."""
+    code = -1 if confidence is None else _conf_kind(confidence)
+    G, T, N, M, rows, cols = int(G), int(T), int(N), int(M), int(rows), int(cols)
+    if not 1 <= G <= 65535:
+        raise ValueError(f"G must be in 1 ... 65535 (got {G})")
+    if not 2 <= M <= 16:
+        raise ValueError(f"M must be in 2 ... 16 (got {M})")
+    if T < 1 or N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
+        raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={T}, N={N}, rows={rows}, cols={cols})")
+    if L.numel() != G * T * N * M or L.dtype != torch.float32:
+        raise ValueError(f"L must be float32 [{G}, {T * N}, {M}] (got {L.dtype} {tuple(L.shape)})")
+    if dtype not in (torch.float32, torch.int8):
+        raise ValueError(f"dtype must be torch.float32 or torch.int8 (got {dtype})")
+    if out_conf is not None and confidence is None:
+        raise ValueError("out_conf needs a confidence kind")
+    if out is None:
+        out = torch.empty(G, rows, cols, dtype=dtype, device=L.device)
+    if out_conf is None and confidence is not None:
+        out_conf = torch.empty(G, rows, cols, dtype=torch.float32, device=L.device)
+    ld, map_stride = _window_batch(out, "out", G, rows, cols, dtype, L.device)
+    if out_conf is not None:
+        cld, cstride = _window_batch(out_conf, "out_conf", G, rows, cols, torch.float32, L.device)
+        if cld != ld and rows > 1:
+            raise ValueError(f"out and out_conf must share one pitch (got {out.stride(1)} and {out_conf.stride(1)})")
+        if cstride != map_stride and G > 1:
+            raise ValueError(f"out and out_conf must share one map stride (got {out.stride(0)} and {out_conf.stride(0)})")
+    L = L.contiguous()
+    if not L.is_cuda:
+        Lg = L.view(G, T * N, M)
+        for g in range(G):
+            lab, conf = _labelmap_dense_cpu(Lg[g], T, N, M, rows, cols, confidence, flip)
+            out[g].copy_(lab.to(dtype))
+            if out_conf is not None:
+                out_conf[g].copy_(conf)
+        return out, out_conf
+    _check(_dense_batch_lib().crw_labelmap_dense_batch(_ptr(L), G, T, N, M, rows, cols, int(bool(flip)), code, _ptr(out),
+                                                       DT_F32 if dtype == torch.float32 else DT_I8,
+                                                       _ptr(out_conf) if out_conf is not None else None, ld, map_stride, _stream()),
+           "crw_labelmap_dense_batch")
     return out, out_conf
 
 

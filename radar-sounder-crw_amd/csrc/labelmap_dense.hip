@@ -14,6 +14,10 @@
 // A lane owns 4 consecutive pixels of a row that start on a 16-byte boundary of the fp32 outputs (a 4-byte boundary of an int8
 // map) and writes each output with one vector store; the groups that stick out of the window at a row's head and tail -- the map
 // may be a column window of a wider one, any pitch, any offset -- write their inside pixels one by one.  Plain stores only.
+//
+// crw_labelmap_dense_batch is the same map for the G configurations of a parameter sweep in one launch (see its kernel below).
+#include <cstdlib>
+
 #include "confidence_of.h"
 #include "labelmap.h"
 
@@ -77,6 +81,33 @@ __device__ inline void load_row(const float *__restrict__ row, int M, int vec, f
   }
 }
 
+// One pixel: its row interpolated between the four node rows, the arg-max (strict: a tie keeps the lowest class) and the
+// confidence of the interpolated row.  The ONE text of this arithmetic: labelmap_dense_kernel and labelmap_dense_batch_kernel both
+// instantiate it.  One text is not yet one result: left to itself the compiler contracts a * b + c * d to FMAs site by site (and
+// turns (1 - w) * p into fma(-w, p, p)), differently in two kernels and even between the pixels of one lane.  So the roundings are
+// written out -- one product rounded, the other fused into the sum, at each of the three steps -- and contraction is off here.
+template <int KIND, int MCAP>
+__device__ __forceinline__ void dense_pixel(const float (&p00)[MCAP], const float (&p01)[MCAP], const float (&p10)[MCAP],
+                                            const float (&p11)[MCAP], float wc, float wr, int M, float ln_m, float *lab,
+                                            float *conf) {
+#pragma clang fp contract(off)
+  const float uc = 1.f - wc, ur = 1.f - wr;
+  float v[16], top1 = 0.f;
+  int best = 0;
+#pragma unroll
+  for (int m = 0; m < 16; ++m) {
+    v[m] = 0.f;
+    if (m < MCAP && m < M) {
+      const float top = __builtin_fmaf(wc, p01[m], uc * p00[m]);
+      const float bot = __builtin_fmaf(wc, p11[m], uc * p10[m]);
+      v[m] = __builtin_fmaf(wr, bot, ur * top);
+      if (m == 0 || v[m] > top1) top1 = v[m], best = m;  // strict: a tie keeps the lowest class
+    }
+  }
+  *lab = (float)best;
+  *conf = KIND >= 0 ? confidence_of<(KIND >= 0 ? KIND : 0)>(v, M, ln_m) : 0.f;
+}
+
 // KIND: a CRW_CONF_* kind, or -1 for no confidence map; MCAP: 4, 8 or 16 >= M, the classes a lane keeps registers for
 template <typename LAB, int KIND, int MCAP>
 __global__ __launch_bounds__(DN_BLOCK) void labelmap_dense_kernel(DenseArgs a) {
@@ -129,20 +160,7 @@ __global__ __launch_bounds__(DN_BLOCK) void labelmap_dense_kernel(DenseArgs a) {
         load_row(a.L + ((size_t)j1 * N + i1) * M, M, vec, p11);
         pj0 = j0, pj1 = j1;
       }
-      float v[16], top1 = 0.f;
-      int best = 0;
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        v[m] = 0.f;
-        if (m < MCAP && m < M) {
-          const float top = (1.f - wc) * p00[m] + wc * p01[m];
-          const float bot = (1.f - wc) * p10[m] + wc * p11[m];
-          v[m] = (1.f - wr) * top + wr * bot;
-          if (m == 0 || v[m] > top1) top1 = v[m], best = m;  // strict: a tie keeps the lowest class
-        }
-      }
-      lab4[e] = (float)best;
-      conf4[e] = KIND >= 0 ? confidence_of<(KIND >= 0 ? KIND : 0)>(v, M, a.ln_m) : 0.f;
+      dense_pixel<KIND, MCAP>(p00, p01, p10, p11, wc, wr, M, a.ln_m, &lab4[e], &conf4[e]);
     }
 
     if (c0 >= 0 && c0 + DN_LANE_PIX <= a.cols) {  // a whole group: its first pixel sits on the vector boundary
@@ -173,6 +191,109 @@ __global__ __launch_bounds__(DN_BLOCK) void labelmap_dense_kernel(DenseArgs a) {
   }
 }
 
+// The same map for the G configurations of a sweep's pass in ONE launch: L [G, T*N, M], configuration g's window `map_stride`
+// elements behind configuration g - 1's.  A workgroup stages the knots and weights of its 16 x 256 tile ONCE -- they depend on the
+// geometry alone -- and walks `chunk` configurations with them (blockIdx.z: the chunk); chunk = 1 is the plain "one configuration
+// per blockIdx.z" shape.  What changes with g: the four node rows (another slice of L), the output address, and with it the store
+// phase -- `map_stride` need not be a multiple of 4, so the lane-to-column assignment and a row's head and tail are per (g, row),
+// exactly those of crw_labelmap_dense on slice g's own base.  Pixels come from dense_pixel, the one-map kernel's.
+struct DenseBatchArgs {
+  DenseArgs d;        // L, lab, conf: configuration 0's; lab_phase: configuration 0's
+  size_t l_stride;    // floats between the configurations' soft labels (T * N * M)
+  size_t map_stride;  // elements between the configurations' windows
+  int G, chunk;
+};
+
+template <typename LAB, int KIND, int MCAP>
+__global__ __launch_bounds__(DN_BLOCK) void labelmap_dense_batch_kernel(DenseBatchArgs b) {
+  __shared__ int col_j[DN_COL_KNOTS], row_i[DN_ROWS];
+  __shared__ float col_w[DN_COL_KNOTS], row_w[DN_ROWS];
+  const DenseArgs &a = b.d;
+  const int row0 = blockIdx.x * DN_ROWS;
+  const long colb = (long)blockIdx.y * DN_COLS - (DN_LANE_PIX - 1);  // column of col_*[0]
+  for (int i = threadIdx.x; i < DN_COL_KNOTS + DN_ROWS; i += DN_BLOCK) {
+    int k = 0;
+    float w = 0.f;
+    if (i < DN_COL_KNOTS) {
+      const long c = colb + i;
+      if (c >= 0 && c < a.cols) knot(a.flip ? a.cols - 1 - (int)c : (int)c, a.T, a.cols, &k, &w);
+      col_j[i] = k, col_w[i] = w;  // outside the window: node 0, never stored
+    } else {
+      const int r = row0 + (i - DN_COL_KNOTS);
+      if (r < a.rows) knot(r, a.N, a.rows, &k, &w);
+      row_i[i - DN_COL_KNOTS] = k, row_w[i - DN_COL_KNOTS] = w;
+    }
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+  const int M = a.M, N = a.N;
+  const int g0 = blockIdx.z * b.chunk, g1 = g0 + b.chunk < b.G ? g0 + b.chunk : b.G;
+
+  for (int rr = wave; rr < DN_ROWS; rr += DN_WAVES) {
+    const int r = row0 + rr;
+    if (r >= a.rows) break;
+    const int i0 = row_i[rr], i1 = i0 + 1 < N ? i0 + 1 : N - 1;
+    const float wr = row_w[rr];
+    const size_t rowoff = (size_t)r * a.ld;
+
+    for (int g = g0; g < g1; ++g) {
+      const float *Lg = a.L + (size_t)g * b.l_stride;
+      const int vec = ((M & 3) == 0 && !((uintptr_t)Lg & 15)) ? 4 : ((M & 1) == 0 && !((uintptr_t)Lg & 7)) ? 2 : 1;
+      const size_t mapoff = (size_t)g * b.map_stride + rowoff;  // of this row in configuration g's window
+      LAB *lab = static_cast<LAB *>(a.lab) + mapoff;
+      float *conf = KIND >= 0 ? a.conf + mapoff : nullptr;
+      const int phase = (int)((a.lab_phase + mapoff) & (DN_LANE_PIX - 1));
+      const int kx = DN_LANE_PIX * lane - phase + (DN_LANE_PIX - 1);  // this lane's first entry of col_*
+      const long c0 = colb + kx;                                      // its first column: -3 ... cols + 2
+      if (c0 >= a.cols) continue;
+
+      float p00[MCAP], p01[MCAP], p10[MCAP], p11[MCAP];
+      float lab4[DN_LANE_PIX], conf4[DN_LANE_PIX];
+      int pj0 = -1, pj1 = -1;
+#pragma unroll
+      for (int e = 0; e < DN_LANE_PIX; ++e) {
+        const int j0 = col_j[kx + e], j1 = j0 + 1 < a.T ? j0 + 1 : a.T - 1;
+        const float wc = col_w[kx + e];
+        if (j0 != pj0 || j1 != pj1) {
+          load_row(Lg + ((size_t)j0 * N + i0) * M, M, vec, p00);
+          load_row(Lg + ((size_t)j1 * N + i0) * M, M, vec, p01);
+          load_row(Lg + ((size_t)j0 * N + i1) * M, M, vec, p10);
+          load_row(Lg + ((size_t)j1 * N + i1) * M, M, vec, p11);
+          pj0 = j0, pj1 = j1;
+        }
+        dense_pixel<KIND, MCAP>(p00, p01, p10, p11, wc, wr, M, a.ln_m, &lab4[e], &conf4[e]);
+      }
+
+      if (c0 >= 0 && c0 + DN_LANE_PIX <= a.cols) {  // a whole group: its first pixel sits on the vector boundary
+        if (sizeof(LAB) == 4) {
+          *reinterpret_cast<float4 *>(lab + c0) = make_float4(lab4[0], lab4[1], lab4[2], lab4[3]);
+        } else {
+          const uint32_t pk = (uint32_t)lab4[0] | (uint32_t)lab4[1] << 8 | (uint32_t)lab4[2] << 16 | (uint32_t)lab4[3] << 24;
+          *reinterpret_cast<uint32_t *>(lab + c0) = pk;
+        }
+        if (KIND >= 0) {
+          if (a.conf_vec) {  // conf shares the labels' phase in configuration 0, hence in every one
+            *reinterpret_cast<float4 *>(conf + c0) = make_float4(conf4[0], conf4[1], conf4[2], conf4[3]);
+          } else {
+#pragma unroll
+            for (int e = 0; e < DN_LANE_PIX; ++e) conf[c0 + e] = conf4[e];
+          }
+        }
+      } else {  // head or tail of the row: the pixels inside the window, one by one
+#pragma unroll
+        for (int e = 0; e < DN_LANE_PIX; ++e) {
+          const long c = c0 + e;
+          if (c >= 0 && c < a.cols) {
+            lab[c] = (LAB)lab4[e];
+            if (KIND >= 0) conf[c] = conf4[e];
+          }
+        }
+      }
+    }
+  }
+}
+
 template <typename LAB, int KIND>
 void launch_dense_m(dim3 grid, hipStream_t s, const DenseArgs &a) {
   if (a.M <= 4)
@@ -195,8 +316,73 @@ void launch_dense(int kind, dim3 grid, hipStream_t s, const DenseArgs &a) {
     launch_dense_m<LAB, CRW_CONF_ENTROPY>(grid, s, a);
 }
 
+template <typename LAB, int KIND>
+void launch_dense_batch_m(dim3 grid, hipStream_t s, const DenseBatchArgs &b) {
+  if (b.d.M <= 4)
+    hipLaunchKernelGGL((labelmap_dense_batch_kernel<LAB, KIND, 4>), grid, dim3(DN_BLOCK), 0, s, b);
+  else if (b.d.M <= 8)
+    hipLaunchKernelGGL((labelmap_dense_batch_kernel<LAB, KIND, 8>), grid, dim3(DN_BLOCK), 0, s, b);
+  else
+    hipLaunchKernelGGL((labelmap_dense_batch_kernel<LAB, KIND, 16>), grid, dim3(DN_BLOCK), 0, s, b);
+}
+
+template <typename LAB>
+void launch_dense_batch(int kind, dim3 grid, hipStream_t s, const DenseBatchArgs &b) {
+  if (kind < 0)
+    launch_dense_batch_m<LAB, -1>(grid, s, b);
+  else if (kind == CRW_CONF_MAXPROB)
+    launch_dense_batch_m<LAB, CRW_CONF_MAXPROB>(grid, s, b);
+  else if (kind == CRW_CONF_MARGIN)
+    launch_dense_batch_m<LAB, CRW_CONF_MARGIN>(grid, s, b);
+  else
+    launch_dense_batch_m<LAB, CRW_CONF_ENTROPY>(grid, s, b);
+}
+
+// configurations a workgroup walks with one set of knots: fastest or tied of 1 / 2 / 4 / 8 at G = 60, 410 x 3200, 5 - 17 % ahead of
+// one configuration per blockIdx.z (tools/sweep_dense_timing.py, profiles/sweep_dense_timing.log)
+constexpr int DN_BATCH_CHUNK = 4;
+
+// CRW_DENSE_BATCH_CHUNK (read per call): the other kernel shapes, for the A/B of tools/sweep_dense_timing.py; 1 = one
+// configuration per blockIdx.z.  The maps do not depend on it.
+int batch_chunk(int G) {
+  int chunk = DN_BATCH_CHUNK;
+  if (const char *e = getenv("CRW_DENSE_BATCH_CHUNK")) {
+    const int v = atoi(e);
+    if (v >= 1) chunk = v;
+  }
+  return chunk < G ? chunk : G;
+}
+
 }  // namespace
 }  // namespace crw
+
+extern "C" int crw_labelmap_dense_batch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, int conf_kind,
+                                        void *labels, int label_dtype, float *conf, size_t ld, size_t map_stride,
+                                        crw_stream_t stream) {
+  using namespace crw;
+  clear_stale_error();
+  constexpr int MAX_SIDE = 1 << 22;
+  if (!L || !labels || G < 1 || G > 65535 || T < 1 || N < 1 || M < 2 || M > 16 || rows < 1 || cols < 1 || rows > MAX_SIDE ||
+      cols > MAX_SIDE || !dtype_ok(label_dtype) || conf_kind < -1 || conf_kind > CRW_CONF_ENTROPY ||
+      (conf_kind == -1) != (conf == nullptr) || ld < (size_t)cols || map_stride < (size_t)(rows - 1) * ld + (size_t)cols ||
+      ((uintptr_t)L & 3) || ((uintptr_t)conf & 3) || (label_dtype == CRW_DT_F32 && ((uintptr_t)labels & 3)))
+    return CRW_EINVAL;  // (a slice's base is configuration 0's plus whole elements: 4-byte aligned when that is)
+  DenseBatchArgs b;
+  DenseArgs &a = b.d;
+  a.L = L, a.lab = labels, a.conf = conf, a.ld = ld;
+  a.T = T, a.N = N, a.M = M, a.rows = rows, a.cols = cols, a.flip = flip != 0;
+  a.lab_phase = (int)(((uintptr_t)labels / elem(label_dtype)) & (DN_LANE_PIX - 1));
+  a.conf_vec = conf && (int)(((uintptr_t)conf / 4) & (DN_LANE_PIX - 1)) == a.lab_phase;
+  a.ln_m = logf((float)M);
+  b.l_stride = (size_t)T * N * M, b.map_stride = map_stride, b.G = G, b.chunk = batch_chunk(G);
+  const unsigned groups = ((unsigned)cols + 2 * (DN_LANE_PIX - 1)) / DN_LANE_PIX;
+  const dim3 grid(((unsigned)rows + DN_ROWS - 1) / DN_ROWS, (groups + WAVE - 1) / WAVE, ((unsigned)G + b.chunk - 1) / b.chunk);
+  if (label_dtype == CRW_DT_F32)
+    launch_dense_batch<float>(conf_kind, grid, (hipStream_t)stream, b);
+  else
+    launch_dense_batch<int8_t>(conf_kind, grid, (hipStream_t)stream, b);
+  return check_launch();
+}
 
 extern "C" int crw_labelmap_dense(const float *L, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
                                   int label_dtype, float *conf, size_t ld, crw_stream_t stream) {

@@ -107,9 +107,10 @@ class LabelPropSweep(object):
             raise RuntimeError(f"KNN={max(self.knns)} exceeds the number of nodes per frame ({h * w}); "
                                "torch.topk in the reference raises for the first frame as well")
 
-    def propagate_all(self, feats, seed, nclasses, grid_w=1):
+    def propagate_all(self, feats, seed, nclasses, grid_w=1, soft=False):
         """feats [T,N,C] (normalised features), seed [N] float class ids of frame 0 -> pred [G,N,T] float class ids, G =
-        len(configs).
+        len(configs).  soft: -> (pred, L [G, T*N, M]), the soft labels of every configuration as well (the batch kernel writes them
+        anyway; the per-configuration arm stacks its G copies) -- what `crw_hip.labelmap_dense_batch` turns into pixel maps.
 
         Per (radius, temp): ONE selection at kcap = max(knns) (`crw_hip.labelprop_topk_scores`; the lists of a smaller knn are
         its first entries) and one `labelprop_sweep_weights` (the softmax of every knn, shorter lists padded with zero weights).
@@ -121,7 +122,10 @@ class LabelPropSweep(object):
         self._check_grid(N // grid_w, grid_w)
         seed = seed.float().contiguous()
         if os.environ.get("CRW_SWEEP_PER_CONFIG") == "1":
-            return torch.stack([LabelPropVOS_CRW(cfg).propagate_all(feats, seed, nclasses, grid_w=grid_w)[0] for cfg in self.configs])
+            if not soft:
+                return torch.stack([LabelPropVOS_CRW(cfg).propagate_all(feats, seed, nclasses, grid_w=grid_w)[0] for cfg in self.configs])
+            outs = [LabelPropVOS_CRW(cfg).propagate_all(feats, seed, nclasses, grid_w=grid_w) for cfg in self.configs]
+            return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
         nk, kmax, F = len(self.knns), max(self.knns), T - 1
         P = len(self.radii) * len(self.temps)
         W = torch.empty(P, nk, F, kmax, N, device=feats.device, dtype=torch.float32)
@@ -137,6 +141,6 @@ class LabelPropSweep(object):
             Ig = I[0]  # one list of indices shared by every configuration
         else:
             Ig = I[:, None].expand(P, nk, F, kmax, N).reshape(P * nk, F, kmax, N)  # (a copy: the batch takes one stride)
-        _, pred = crw_hip.labelprop_propagate_batch(seed, W.view(P * nk, F, kmax, N), Ig, T, N, nclasses, first_frame=1,
+        L, pred = crw_hip.labelprop_propagate_batch(seed, W.view(P * nk, F, kmax, N), Ig, T, N, nclasses, first_frame=1,
                                                     cxt_size=self.cxt_size)
-        return pred
+        return (pred, L) if soft else pred

@@ -243,8 +243,8 @@ def _segment_dense(dataset, seg, encoder, lp, nclasses, T, W, ow, N, rg_len, rg_
     return out
 
 
-def merge_reverse_batch(final_pred, pred_rev, dataset_id):
-    """`merge_reverse` on [G, rows, cols] maps, configuration by configuration."""
+def _reverse_rule_mask_batch(final_pred, pred_rev, dataset_id):
+    """`_reverse_rule_mask` on [G, rows, cols] maps -> bool [G, rows, cols]."""
     G = pred_rev.shape[0]
     mask = pred_rev == 2
     if dataset_id == 1:
@@ -255,6 +255,12 @@ def merge_reverse_batch(final_pred, pred_rev, dataset_id):
         mask.view(G, -1)[:, :mask[0].numel() // 2] = False
     elif dataset_id != 0:
         raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
+    return mask
+
+
+def merge_reverse_batch(final_pred, pred_rev, dataset_id):
+    """`merge_reverse` on [G, rows, cols] maps, configuration by configuration."""
+    mask = _reverse_rule_mask_batch(final_pred, pred_rev, dataset_id)
     out = final_pred.clone()
     out[mask] = 2
     return out
@@ -265,16 +271,39 @@ def _upsample_batch(pred, rows, cols):
     return TF.interpolate(pred[:, None].float(), size=(rows, cols), mode='nearest')[:, 0].to(torch.int8)
 
 
+def _upsample_conf_batch(conf, rows, cols):
+    """[G, N, T] node confidences -> [G, rows, cols] float32, `_upsample_batch`'s stretch."""
+    return TF.interpolate(conf[:, None].float(), size=(rows, cols), mode='nearest')[:, 0]
+
+
 @torch.no_grad()
 def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size, overlap, pos_embed=False,
-                  correction=False, use_last=False, dataset_id=0, device='cuda'):
+                  correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest'):
     """`segment` for every configuration of ``sweep`` (LabelPropSweep, G = len(sweep.configs)) with its control flow run ONCE:
     which items are corrected, at which length (`get_smaller_item` and its permanent shortening of the dataset) and what the
     reverse pass sees depend on the features alone, never on (radius, temp, knn).  Same exception policy in the correction.
     -> dict(pred [G, rows, cols] int8 (after the optional reverse merge), forward [G, rows, cols] int8, xent list, change_idx
-            list, configs); pred[g] / forward[g] are `segment`'s maps for ``sweep.configs[g]`` (on a fresh dataset)."""
-    if dataset_id not in (0, 1, 3) and use_last:
+            list, configs); pred[g] / forward[g] are `segment`'s maps for ``sweep.configs[g]`` (on a fresh dataset).
+
+    confidence / merge / upsample: `segment`'s arguments, checks and messages.  With a confidence kind the dict gains ``conf`` and
+    ``forward_conf`` [G, rows, cols] float32, slice g bit for bit `segment`'s for ``sweep.configs[g]`` under the same options.
+    merge='confidence': ONE `crw_hip.merge_confidence` over the G maps; it needs no class rule, so any ``dataset_id`` is accepted
+    (the class rule's dataset check applies to merge='rule' alone).  upsample='bilinear': the maps are allocated once at
+    [G, rows, n_rg * rg_len] and every pass writes its column window of all G maps with one `crw_hip.labelmap_dense_batch`.
+    It holds G-map tensors at once: with confidence, 5 bytes per pixel and configuration for the forward maps, as much again for
+    the reverse pass's and for the merge's result."""
+    if merge not in ('rule', 'confidence'):
+        raise ValueError(f"merge must be 'rule' or 'confidence' (got {merge!r})")
+    if upsample not in ('nearest', 'bilinear'):
+        raise ValueError(f"upsample must be 'nearest' or 'bilinear' (got {upsample!r})")
+    if confidence is not None and confidence not in crw_hip.CONF_KINDS:
+        raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
+    if merge == 'confidence' and confidence is None:
+        raise ValueError("merge='confidence' needs a confidence kind (confidence='maxprob', 'margin' or 'entropy')")
+    if merge == 'rule' and dataset_id not in (0, 1, 3) and use_last:
         raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
+    want = confidence is not None
+    kw = dict(confidence=confidence) if want else {}  # `propagate_sweep` returns a fourth entry only when asked
     T, (H, W), (oh, ow) = seq_length, patch_size, overlap
     N = dataset[0].shape[1]
     rg_len = T * (W - ow) + ow
@@ -284,13 +313,18 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     idx = idx[:n_rg]
     seg = seg[:, :n_rg * rg_len].to(device)
     rows = seg.shape[0]
+    if upsample == 'bilinear':
+        return _segment_sweep_dense(dataset, seg, encoder, sweep, nclasses, T, W, ow, N, rg_len, rg_h, idx, pos_embed, correction,
+                                    use_last, dataset_id, device, confidence, merge)
 
-    maps, xents, changes = [], [], []
+    maps, cmaps, xents, changes = [], [], [], []
     for t, i in enumerate(idx):
         seq = dataset[i].to(device)
         seg_ref = seg[:rg_h, rg_len * t:rg_len * t + W]
-        pred, xent, change = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False)
+        pred, xent, change, *conf = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False, **kw)
         maps.append(_upsample_batch(pred, rows, rg_len))
+        if want:
+            cmaps.append(_upsample_conf_batch(conf[0], rows, rg_len))
         xents.append(xent)
         changes.append(change)
 
@@ -303,8 +337,11 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
             try:  # the policy of `segment`: data errors are skipped, failures of the HIP path are not
                 seq = dataset.get_smaller_item(idx[t], small).to(device)
                 seg_ref = seg[:, rg_len * t + rg_len - px:rg_len * t + rg_len - px + W]
-                pred, _, _ = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False)
+                pred, _, _, *conf = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False, **kw)
+                tail = _upsample_conf_batch(conf[0], rows, px) if want else None
                 maps[t][:, :, rg_len - px:] = _upsample_batch(pred, rows, px)
+                if want:  # the same window as the labels: spliced when they were, skipped when they were
+                    cmaps[t][:, :, rg_len - px:] = tail
             except crw_hip.CrwError as e:
                 if e.device_failure:
                     raise
@@ -314,19 +351,99 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
                 pass
 
     forward = torch.cat(maps, dim=2)
-    final = forward
+    forward_conf = torch.cat(cmaps, dim=2) if want else None
+    final, final_conf = forward, forward_conf
     if use_last:
-        rev_maps = []
+        rev_maps, rev_cmaps = [], []
         seg_rev = torch.flip(seg.unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
         for t, i in enumerate(idx):
             seq = dataset[i].to(device)
             seg_ref = seg_rev[:, rg_len * t:rg_len * t + W]
-            pred, _, _ = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=True)
+            pred, _, _, *conf = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=True, **kw)
             rev_maps.append(_upsample_batch(pred, rows, rg_len))
+            if want:
+                rev_cmaps.append(_upsample_conf_batch(conf[0], rows, rg_len))
         rev = torch.cat(rev_maps, dim=2).unfold(2, rg_len, rg_len)
         rev = torch.flip(rev, (-1,)).reshape(rev.shape[0], rows, -1)
-        final = merge_reverse_batch(forward, rev, dataset_id)
-    return dict(pred=final, forward=forward, xent=xents, change_idx=changes, configs=list(sweep.configs))
+        if want:
+            rev_conf = torch.cat(rev_cmaps, dim=2).unfold(2, rg_len, rg_len)
+            rev_conf = torch.flip(rev_conf, (-1,)).reshape(rev_conf.shape[0], rows, -1)
+        if merge == 'confidence':
+            final, final_conf, _ = crw_hip.merge_confidence(forward, forward_conf, rev, rev_conf)
+        else:
+            final = merge_reverse_batch(forward, rev, dataset_id)
+            if want:
+                final_conf = torch.where(_reverse_rule_mask_batch(forward, rev, dataset_id), rev_conf, forward_conf)
+    out = dict(pred=final, forward=forward, xent=xents, change_idx=changes, configs=list(sweep.configs))
+    if want:
+        out.update(conf=final_conf, forward_conf=forward_conf)
+    return out
+
+
+def _segment_sweep_dense(dataset, seg, encoder, sweep, nclasses, T, W, ow, N, rg_len, rg_h, idx, pos_embed, correction, use_last,
+                         dataset_id, device, confidence, merge):
+    """`segment_sweep(..., upsample='bilinear')` behind its argument checks: `_segment_dense`'s passes with the G maps of a pass
+    written by ONE `crw_hip.labelmap_dense_batch` from the pass's soft labels L [G, T*N, M] into the pass's column window of maps
+    allocated once at [G, rows, n_rg * rg_len] (int8; float32 confidences) -- a correction's only after its `propagate_sweep`
+    succeeded, the reverse pass's mirrored.  Instead of G x passes launches of a few MB each."""
+    want = confidence is not None
+    G, rows, n_rg = len(sweep.configs), seg.shape[0], len(idx)
+    new = lambda dtype: torch.empty(G, rows, n_rg * rg_len, dtype=dtype, device=device)
+
+    def dense(L, frames, out, out_conf, flip=False):
+        crw_hip.labelmap_dense_batch(L, G, frames, N, nclasses, rows, out.shape[2], confidence=confidence, flip=flip,
+                                     dtype=torch.int8, out=out, out_conf=out_conf)
+
+    forward, forward_conf = new(torch.int8), (new(torch.float32) if want else None)
+    win = lambda m, a, b: m[:, :, a:b] if m is not None else None
+    xents, changes = [], []
+    for t, i in enumerate(idx):
+        seq = dataset[i].to(device)
+        seg_ref = seg[:rg_h, rg_len * t:rg_len * t + W]
+        _, xent, change, L = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False, soft=True)
+        dense(L, seq.shape[0], win(forward, rg_len * t, rg_len * (t + 1)), win(forward_conf, rg_len * t, rg_len * (t + 1)))
+        xents.append(xent)
+        changes.append(change)
+
+    if correction:
+        for t, change in enumerate(changes):
+            if change is None:
+                continue
+            small = T - change
+            px = small * (W - ow)
+            try:  # `segment`'s policy: a correction that fails on its data is skipped, a failure of the HIP path is not
+                seq = dataset.get_smaller_item(idx[t], small).to(device)
+                seg_ref = seg[:, rg_len * t + rg_len - px:rg_len * t + rg_len - px + W]
+                _, _, _, L = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False, soft=True)
+                a, b = rg_len * t + rg_len - px, rg_len * (t + 1)
+                dense(L, seq.shape[0], win(forward, a, b), win(forward_conf, a, b))
+            except crw_hip.CrwError as e:
+                if e.device_failure:
+                    raise
+            except torch.AcceleratorError:
+                raise
+            except Exception:
+                pass
+
+    final, final_conf = forward, forward_conf
+    if use_last:
+        rev, rev_conf = new(torch.int8), (new(torch.float32) if want else None)
+        seg_rev = torch.flip(seg.unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
+        for t, i in enumerate(idx):
+            seq = dataset[i].to(device)
+            seg_ref = seg_rev[:, rg_len * t:rg_len * t + W]
+            _, _, _, L = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=True, soft=True)
+            dense(L, seq.shape[0], win(rev, rg_len * t, rg_len * (t + 1)), win(rev_conf, rg_len * t, rg_len * (t + 1)), flip=True)
+        if merge == 'confidence':
+            final, final_conf, _ = crw_hip.merge_confidence(forward, forward_conf, rev, rev_conf)
+        else:
+            final = merge_reverse_batch(forward, rev, dataset_id)
+            if want:
+                final_conf = torch.where(_reverse_rule_mask_batch(forward, rev, dataset_id), rev_conf, forward_conf)
+    out = dict(pred=final, forward=forward, xent=xents, change_idx=changes, configs=list(sweep.configs))
+    if want:
+        out.update(conf=final_conf, forward_conf=forward_conf)
+    return out
 
 
 @torch.no_grad()
@@ -447,6 +564,32 @@ def evaluate_sweep(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasse
             raise crw_hip.LabelError(dropped[1], K)
         reports.append(Report(row[:K * K].view(K, K), dropped))
     return reports
+
+
+def calibration_sweep(pred, conf, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None, bins=10):
+    """`calibration` for the G maps of `segment_sweep(..., confidence=kind)` (pred [G, rows, cols], conf [G, rows, cols]) -> G
+    ``metrics.Calibration``: G `crw_hip.calibration` calls queued back to back, ONE copy of all histograms to the host at the end,
+    like `evaluate_sweep`.  Same mask rules; a label outside 0 ... K-1 that survives the mask in any map raises
+    ``crw_hip.LabelError``."""
+    from metrics import Calibration
+    if pred.dim() < 2 or pred[0].numel() != seg.numel():
+        raise ValueError(f'pred {tuple(pred.shape)} must be G maps covering the pixels of seg {tuple(seg.shape)}')
+    K, seg, mask = _report_rules(pred[0], seg, dataset_id, remove_unc, unc_seg, nclasses)
+    if conf.shape[0] != pred.shape[0] or conf.numel() != pred.numel():
+        raise ValueError(f'conf {tuple(conf.shape)} and pred {tuple(pred.shape)} must cover the same pixels')
+    conf = conf.to(pred.device)
+    outs = [crw_hip.calibration(seg, p, c, K, bins=bins, **mask) for p, c in zip(pred, conf)]
+    if not outs:
+        return []
+    host = torch.stack([torch.cat([n.reshape(-1), s.view(torch.int64), d]) for n, s, d in outs]).cpu()  # [G, 3 * bins + 3]
+    nb = outs[0][1].numel()
+    cals = []
+    for row in host:
+        dropped = [int(v) for v in row[3 * nb:]]
+        if dropped[1]:
+            raise crw_hip.LabelError(dropped[1], K)
+        cals.append(Calibration(row[:2 * nb].view(nb, 2), row[2 * nb:3 * nb].view(torch.float64), dropped))
+    return cals
 
 
 # the reference's three per-dataset drivers (scripts/test/test_mc1.py:19-30, test_mc3.py:19-33, test_sharad.py:19-32): argparse

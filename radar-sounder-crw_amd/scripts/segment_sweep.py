@@ -13,6 +13,12 @@ line per configuration (radius, temp, knn, accuracy, macro F1, weighted F1, mean
 (default macro F1; ties: the first in the grid's order) with its full report and matrix in the reference's text.  ``--reports``
 prints every full report; ``--report_json FILE`` writes all of them with the grid; ``--save_maps`` writes
 ``predicted_map_r{r}_t{t}_k{k}.pt`` (int8, the forward map test_all.py saves) per configuration.
+``--upsample bilinear`` / ``--confidence KIND`` / ``--merge confidence`` / ``--bins B``: ``segment_all.py``'s flags, for all
+configurations at once (``inference.segment_sweep``'s arguments; the G dense maps of a pass are one kernel launch).  With
+``--confidence`` every configuration's line gains its ECE and AURC (``inference.calibration_sweep``), the best configuration's
+calibration table follows its matrix, ``--report_json`` gains a ``calibration`` entry per configuration, and ``--select`` also
+takes ``ece`` and ``aurc`` -- lower is better: the smallest wins, ties go to the first in the grid's order, a NaN never wins
+unless every score is NaN.  Without these flags the script prints and writes what it did before them.
 CRW_SWEEP_PER_CONFIG=1: the label propagation as a loop over the configurations (same maps; the A/B arm)."""
 import argparse
 import json
@@ -34,6 +40,8 @@ from utils import create_model
 GRID = dict(radius=(45, 50, 55, 60, 65), temp=(0.1, 0.01, 0.001), knn=(15, 20, 25, 30))
 SELECT = {'macro_f1': lambda r: r.macro['f1'], 'weighted_f1': lambda r: r.weighted['f1'], 'accuracy': lambda r: r.accuracy,
           'mean_iou': lambda r: r.mean_iou}
+# scores of the calibration (``--confidence``): lower is better
+SELECT_CAL = {'ece': lambda c: c.ece, 'aurc': lambda c: c.aurc}
 
 
 def get_args_parser():
@@ -59,11 +67,40 @@ def get_args_parser():
     p.add_argument('--seg_path', default=None, help='reference segmentation .pt file')
     p.add_argument('--unc_seg_path', default=None, help="dataset 0's map with the uncertain class 4 (the reference's dataset id 2)")
     p.add_argument('--synthetic', default=None, nargs=2, type=int, metavar=('H', 'W'))
-    p.add_argument('--select', default='macro_f1', choices=sorted(SELECT), help='the score the best configuration is picked by')
+    p.add_argument('--select', default='macro_f1', choices=sorted(SELECT) + sorted(SELECT_CAL),
+                   help='the score the best configuration is picked by (ece, aurc: the lowest, need --confidence)')
     p.add_argument('--reports', action='store_true', help='print the full report of every configuration')
     p.add_argument('--report_json', default=None, metavar='FILE')
     p.add_argument('--save_maps', action='store_true', help='save every predicted_map_r{r}_t{t}_k{k}.pt (int8)')
+    p.add_argument('--confidence', default=None, choices=('maxprob', 'margin', 'entropy'),
+                   help='per-pixel confidence of every label map and its calibration (ECE / AURC columns)')
+    p.add_argument('--merge', default='rule', choices=('rule', 'confidence'),
+                   help="how --use_last merges the reverse pass: the reference's class rule, or per pixel the surer pass")
+    p.add_argument('--bins', default=10, type=int, metavar='B', help='confidence bins of the calibration (1 ... 64)')
+    p.add_argument('--upsample', default='nearest', choices=('nearest', 'bilinear'),
+                   help="node labels to pixels: the reference's arg-max + nearest, or soft labels interpolated bilinearly, then arg-max")
     return p
+
+
+def check_confidence_flags(args):
+    """The flags around ``--confidence``, as `segment_all.check_confidence_flags` reads them."""
+    if args.confidence is None and args.merge == 'confidence':
+        raise SystemExit('--merge confidence needs --confidence {maxprob,margin,entropy}')
+    if args.confidence is None and args.select in SELECT_CAL:
+        raise SystemExit(f'--select {args.select} needs --confidence {{maxprob,margin,entropy}}')
+    if not 1 <= args.bins <= 64:
+        raise SystemExit(f'--bins {args.bins}: 1 ... 64')
+    return args
+
+
+def pick_best(scores, lower_is_better=False):
+    """Index of the best score; ties: the first in the grid's order; a NaN never wins unless every score is NaN (then: 0)."""
+    real = [g for g, v in enumerate(scores) if v == v]
+    if not real:
+        return 0
+    if lower_is_better:
+        return min(real, key=lambda g: (scores[g], g))
+    return max(real, key=lambda g: (scores[g], -g))
 
 
 def with_defaults(args):
@@ -85,8 +122,12 @@ def report_dict(report):
 def main(args):
     from imported.labelprop import LabelPropSweep
     tim = time.time()
-    args = with_defaults(args)
-    print(args)
+    args = check_confidence_flags(with_defaults(args))
+    # without --confidence / --upsample the flags that go with them do nothing, and the line reads as it did before they existed
+    hidden = () if args.confidence else ('confidence', 'merge', 'bins')
+    if args.upsample == 'nearest':
+        hidden += ('upsample',)
+    print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
         encoder = load_encoder(args.model, args.model_path, device)
@@ -102,7 +143,9 @@ def main(args):
         print('Correction skipped: it needs --dataset_full true (the reference skips it silently here)')
         correction = False
     out = inference.segment_sweep(dataset, seg, encoder, sweep, nclasses, T, args.patch_size, args.overlap, pos_embed=args.pos_embed,
-                                  correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device)
+                                  correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device,
+                                  **(dict(confidence=args.confidence, merge=args.merge) if args.confidence else {}),
+                                  **(dict(upsample=args.upsample) if args.upsample != 'nearest' else {}))
     if correction:
         print('Change point for each radargram:', out['change_idx'])
     final, forward = out['pred'], out['forward']
@@ -119,20 +162,34 @@ def main(args):
     print('')
     reports = inference.evaluate_sweep(final, seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
                                        unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses)
-    print('{:>6} {:>7} {:>4} {:>9} {:>9} {:>11} {:>9}'.format('radius', 'temp', 'knn', 'accuracy', 'macro f1', 'weighted f1', 'mean iou'))
-    for cfg, r in zip(sweep.configs, reports):
+    cals = None
+    if args.confidence:
+        cals = inference.calibration_sweep(final, out['conf'], seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
+                                           unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses, bins=args.bins)
+    print('{:>6} {:>7} {:>4} {:>9} {:>9} {:>11} {:>9}'.format('radius', 'temp', 'knn', 'accuracy', 'macro f1', 'weighted f1', 'mean iou')
+          + (' {:>8} {:>8}'.format('ece', 'aurc') if cals else ''))
+    for g, (cfg, r) in enumerate(zip(sweep.configs, reports)):
         print('{:>6} {:>7g} {:>4} {:>9.4f} {:>9.4f} {:>11.4f} {:>9.4f}'.format(cfg['RADIUS'], cfg['TEMP'], cfg['KNN'], r.accuracy,
-                                                                               r.macro['f1'], r.weighted['f1'], r.mean_iou))
+                                                                               r.macro['f1'], r.weighted['f1'], r.mean_iou)
+              + (' {:>8.4f} {:>8.4f}'.format(cals[g].ece, cals[g].aurc) if cals else ''))
         if args.reports:
             print(r)
             print(r.matrix_str())
             print('')
-    scores = [float(SELECT[args.select](r)) for r in reports]
-    best = max(range(len(scores)), key=lambda g: (scores[g], -g))
+    if args.select in SELECT_CAL:
+        scores = [float(SELECT_CAL[args.select](c)) for c in cals]
+        best = pick_best(scores, lower_is_better=True)
+    else:
+        scores = [float(SELECT[args.select](r)) for r in reports]
+        best = max(range(len(scores)), key=lambda g: (scores[g], -g))
     cfg = sweep.configs[best]
     print(f"\nBest by {args.select}: radius {cfg['RADIUS']} temp {cfg['TEMP']:g} knn {cfg['KNN']} ({scores[best]:.4f})\n")
     print(reports[best])
     print(reports[best].matrix_str())
+    if cals:
+        print('')
+        print(f'Calibration ({args.confidence}, merge: {args.merge}):')
+        print(cals[best])
     t_all = time.time() - tim
     print('\nTime elapsed (inference + metrics):', t_all)
     if args.report_json:
@@ -142,6 +199,12 @@ def main(args):
                           for c, s, r in zip(sweep.configs, scores, reports)],
                  pixels=int(final[0].numel()), map_shape=list(final.shape[1:]), change_idx=out['change_idx'],
                  elapsed_inference_s=t_inference, elapsed_total_s=t_all, dataset=args.dataset, remove_unc=args.remove_unc)
+        if cals:
+            for c, cal in zip(d['configs'], cals):
+                c['calibration'] = cal.to_dict()
+            d.update(confidence=args.confidence, merge=args.merge)
+        if args.upsample != 'nearest':
+            d['upsample'] = args.upsample
         with open(args.report_json, 'w') as f:
             json.dump(d, f, indent=1)
     return reports, best

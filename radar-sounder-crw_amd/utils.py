@@ -178,17 +178,42 @@ def ndiag_matrix(size, n=1):
 
 
 @torch.no_grad()
-def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last):
+def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False):
     """`propagate` for every configuration of ``sweep`` (imported.labelprop.LabelPropSweep) at once: the encoder, the metric and
     the change point do not depend on (radius, temp, knn) and run ONCE, on the batch `propagate` gives the encoder
-    ->  (labels [G,N,T] float, xent [N,T-1] (CPU), change_idx | None); labels[g] is `propagate`'s for ``sweep.configs[g]``."""
+    ->  (labels [G,N,T] float, xent [N,T-1] (CPU), change_idx | None); labels[g] is `propagate`'s for ``sweep.configs[g]``.
+
+    confidence / soft: the tuple grows as `propagate`'s does -- conf [G,N,T] float, then, last, the soft labels L [G, T*N, M]
+    (frames in the pass's own order); conf[g] and L[g] are `propagate`'s for ``sweep.configs[g]``.  The confidence of all G
+    configurations is ONE `crw_hip.labelprop_confidence` call on the stack read as G*T frames of one pass: the formula is per row,
+    and every frame g*T is a one-hot seed, which reads 1."""
+    if confidence is not None and confidence not in crw_hip.CONF_KINDS:
+        raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
     T, N, H, W = seq.shape
     feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
     G = len(sweep.configs)
     if T == 1:
-        return seed[None, :, None].repeat(G, 1, 1), torch.zeros(N, 0), None
+        out = (seed[None, :, None].repeat(G, 1, 1), torch.zeros(N, 0), None)
+        if confidence is not None:
+            out += (torch.ones(G, N, 1, device=feats.device),)
+        if soft:
+            one_hot = (seed[:, None] == torch.arange(nclasses, device=feats.device)[None, :]).float()
+            out += (one_hot[None].repeat(G, 1, 1),)
+        return out
     xent = crw_hip.xent_metric(feats)
     diffs = column_diffs_async(xent) if T > 2 else None
-    pred = sweep.propagate_all(feats, seed, nclasses)
+    if confidence is None and not soft:
+        pred = sweep.propagate_all(feats, seed, nclasses)
+    else:
+        pred, L = sweep.propagate_all(feats, seed, nclasses, soft=True)
+    conf = None
+    if confidence is not None:  # queued right behind the propagation, before the host turns to the change point
+        conf = crw_hip.labelprop_confidence(L.reshape(G * T * N, nclasses), G * T, N, nclasses, confidence)  # [N, G*T]
+        conf = conf.view(N, G, T).permute(1, 0, 2)
     change_idx = change_point(xent, diffs)  # host work while the GPU propagates
-    return pred, xent.cpu(), change_idx
+    out = (pred, xent.cpu(), change_idx)
+    if confidence is not None:
+        out += (conf,)
+    if soft:
+        out += (L,)
+    return out
