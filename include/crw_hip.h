@@ -57,7 +57,7 @@ extern "C" {
  * binding detects them by symbol, crw_hip.has_sweep()): crw_labelprop_topk_scores, crw_labelprop_sweep_weights,
  * crw_labelprop_propagate_batch; then crw_labelprop_confidence, crw_merge_confidence, crw_calibration_ws_bytes, crw_calibration
  * (crw_hip.has_confidence()); then crw_labelmap_dense (crw_hip.has_dense()); then crw_labelmap_dense_batch
- * (crw_hip.has_dense_batch()).  The ONE place the number is written: crw_abi_version() returns
+ * (crw_hip.has_dense_batch()); then crw_horizons_ws_bytes, crw_horizons (crw_hip.has_horizons()).  The ONE place the number is written: crw_abi_version() returns
  * it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
 #define CRW_ABI_VERSION 8
@@ -204,6 +204,28 @@ size_t crw_confusion_ws_bytes(size_t P, int K);
 int crw_confusion(const void *gt, int gt_dtype, const void *pred, int pred_dtype, const void *aux, int aux_dtype, size_t P, int K,
                   int ignore_gt, int ignore_pred, int ignore_aux, int64_t *counts /* [K][K] */,
                   int64_t *dropped /* [2]: masked, invalid */, void *ws, size_t ws_bytes, crw_stream_t stream);
+
+/* Layer horizons and thickness of a label map against its ground truth: crw_confusion's operands, dtypes, mask and validity rules
+ * (dropped[0] and dropped[1] equal crw_confusion's on the same maps), read as [rows] x [cols] windows with `ld` >= cols elements
+ * between rows -- pixel (r, c) is element r * ld + c of every operand; nothing outside the windows is read, no alignment beyond
+ * the element's is asked for.  A masked or invalid pixel has no class in either map.  A run is a maximal set of consecutive rows
+ * of one column with one class in one map; it qualifies when it is at least min_run (>= 1) rows long.  Per map (0 gt, 1 pred),
+ * class k and column: top = the first row of the first qualifying run of k, bottom = the last row of the last one, count = the
+ * pixels in qualifying runs of k (the layer thickness); top = bottom = -1 and count = 0 when there is none.
+ * picks (may be NULL: then nothing of size cols is written) [2][3][K][cols] int32: map x (top, bottom, count).
+ * stats [K][18], over the columns: n_both (gt and pred have k), n_missing (gt only), n_spurious (pred only); then for top, bottom
+ * and count in turn, over the n_both columns with d = pred - gt: sum |d|, sum d^2, max |d|, columns with |d| <= tol, sum d.
+ * 2 <= K <= 16, tol >= 0, rows <= 32768 (d^2 < 2^30; every sum fits int64); rows == 0 or cols == 0 is valid and gives zero
+ * statistics.  row_slabs: a column's rows are scanned in that many slabs, one wave each, joined afterwards (a run that spans
+ * slab borders is judged once, at its whole length); 0 = the library chooses, 1 ... 8 forces the number (clamped to rows).
+ * Outputs are complete in stream order and need no pre-clearing; no global atomics (per-workgroup partials in ws, added -- the
+ * maxima: maximised -- by a second kernel in a fixed order): bit-reproducible.  ws: crw_horizons_ws_bytes(rows, cols, K) bytes,
+ * 8-byte aligned (0: bad arguments, or cols == 0). */
+size_t crw_horizons_ws_bytes(int rows, int cols, int K);
+int crw_horizons(const void *gt, int gt_dtype, const void *pred, int pred_dtype, const void *aux, int aux_dtype, int rows, int cols,
+                 size_t ld, int K, int ignore_gt, int ignore_pred, int ignore_aux, int min_run, int tol, int row_slabs,
+                 int32_t *picks /* [2][3][K][cols]; may be NULL */, int64_t *stats /* [K][18] */,
+                 int64_t *dropped /* [2]: masked, invalid */, void *ws, size_t ws_bytes, crw_stream_t stream);
 
 /* confidence ------------------------------------------------------------------------------ */
 /* Confidence of every node from the soft labels of crw_labelprop_propagate / _gather: L [T*N, M] (a probability row per node,

@@ -57,6 +57,8 @@ SIGNATURES = {
     "crw_xent_metric": (_c_int, [_p, _c_int, _c_int, _c_int, _p, _p]),
     "crw_confusion_ws_bytes": (_c_sz, [_c_sz, _c_int]),
     "crw_confusion": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _c_sz, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _c_sz, _p]),
+    "crw_horizons_ws_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
+    "crw_horizons": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_int, _c_sz] + [_c_int] * 7 + [_p, _p, _p, _p, _c_sz, _p]),
     "crw_labelprop_confidence": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p]),
     "crw_merge_confidence": (_c_int, [_p, _p, _p, _p, _c_int, _c_sz, _p, _p, _p, _p]),
     "crw_calibration_ws_bytes": (_c_sz, [_c_sz, _c_int, _c_int]),
@@ -144,7 +146,11 @@ DENSE_ENTRY_POINTS = ("crw_labelmap_dense",)
 # likewise: the dense label maps of a sweep's G configurations in one launch (`has_dense_batch()`)
 DENSE_BATCH_ENTRY_POINTS = ("crw_labelmap_dense_batch",)
 
+# likewise: layer horizons and thickness (`has_horizons()`)
+HORIZONS_ENTRY_POINTS = ("crw_horizons_ws_bytes", "crw_horizons")
+
 _lib = None
+_has_horizons = False
 _has_sweep = False
 _has_confidence = False
 _has_dense = False
@@ -154,14 +160,14 @@ _has_dense_batch = False
 def lib():
     """Load the HIP library (once).  Raises if it has not been built: `python -c 'import
     __graft_entry__ as g; g.build()'` or `make -C radar-sounder-crw_amd/csrc`."""
-    global _lib, _has_sweep, _has_confidence, _has_dense, _has_dense_batch
+    global _lib, _has_sweep, _has_confidence, _has_dense, _has_dense_batch, _has_horizons
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} not built -- the CRW hot path has no CPU/PyTorch fallback; "
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
         missing = [n for n in SWEEP_ENTRY_POINTS + CONFIDENCE_ENTRY_POINTS + DENSE_ENTRY_POINTS + DENSE_BATCH_ENTRY_POINTS
-                   if not hasattr(handle, n)]
+                   + HORIZONS_ENTRY_POINTS if not hasattr(handle, n)]
         for name, (res, args) in SIGNATURES.items():
             if name in missing:
                 continue
@@ -175,6 +181,7 @@ def lib():
         _has_confidence = not set(missing) & set(CONFIDENCE_ENTRY_POINTS)
         _has_dense = not set(missing) & set(DENSE_ENTRY_POINTS)
         _has_dense_batch = not set(missing) & set(DENSE_BATCH_ENTRY_POINTS)
+        _has_horizons = not set(missing) & set(HORIZONS_ENTRY_POINTS)
     return _lib
 
 
@@ -227,6 +234,19 @@ def _dense_batch_lib():
     if not has_dense_batch():
         raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
                            f"{', '.join(DENSE_BATCH_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
+    return lib()
+
+
+def has_horizons():
+    """True when the loaded library exports the horizon entry points (HORIZONS_ENTRY_POINTS)."""
+    lib()
+    return _has_horizons
+
+
+def _horizons_lib():
+    if not has_horizons():
+        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
+                           f"{', '.join(HORIZONS_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
     return lib()
 
 
@@ -541,6 +561,159 @@ def _confusion_cpu(gt, pred, K, aux, ignore_gt, ignore_pred, ignore_aux):
     idx = torch.where(keep, g * K + p, torch.where(masked, float(K * K), float(K * K + 1))).to(torch.int64)
     out = torch.bincount(idx, minlength=K * K + 2)
     return out[:K * K].view(K, K), out[K * K:]
+
+
+# ------------------------------------------------------------------------------ horizons
+HORIZON_STATS = 18           # per class: n_both, n_missing, n_spurious, then 5 numbers for each of top, bottom, count
+HORIZON_MAX_ROWS = 32768
+HORIZON_QUANTITIES = ("top", "bottom", "count")
+
+
+def _window2d(t):
+    """A 2-D label map (or a [rows, a:b] column window of one) as one of the kernel's dtypes; rows stay where they are when the
+    dtype is one of the kernel's and the window's rows are contiguous."""
+    if t.dtype == torch.bool:
+        t = t.to(torch.int8)
+    elif t.dtype not in (torch.float32, torch.int8):
+        f = t.to(torch.float32)
+        t = torch.where(f.to(t.dtype) == t, f, torch.full_like(f, float("nan")))
+    return t
+
+
+def _pitch(t):
+    """Elements between the rows of a 2-D window, or None when it has to be copied first."""
+    rows, cols = t.shape
+    if cols > 1 and t.stride(1) != 1:
+        return None
+    if rows <= 1:
+        return cols
+    return t.stride(0) if t.stride(0) >= cols else None
+
+
+def horizons(gt, pred, K, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1, min_run=1, tol=2, want_picks=False, row_slabs=0,
+             picks_out=None):
+    """Layer horizons and thickness of ``pred`` against ``gt`` ([rows, cols] maps, or ``[rows, a:b]`` column windows of wider ones)
+    -> (stats [K, 18] int64, dropped [2] int64[, picks [2, 3, K, cols] int32]) on the inputs' device.  Masks and validity are
+    `confusion`'s (``dropped`` equals its).  A run is a maximal stretch of one class down one column of one map and qualifies from
+    ``min_run`` rows on; per map (0 gt, 1 pred), class and column, picks = (top: first row of the first qualifying run, bottom: last
+    row of the last one, count: pixels in qualifying runs -- the thickness), -1 / -1 / 0 when there is none.  stats[k] = n_both,
+    n_missing (gt has k, pred does not), n_spurious, then for top, bottom and count over the n_both columns with d = pred - gt:
+    sum |d|, sum d^2, max |d|, columns with |d| <= tol, sum d.  Device tensors: one pass of crw_horizons, nothing synchronises;
+    windows that share one pitch are read where they lie (operands of differing pitch are made contiguous first).  ``row_slabs``:
+    0 lets the library cut the rows, 1 ... 8 forces the number of slabs.  ``picks_out``: a contiguous int32 [2, 3, K, cols] tensor
+    to write the picks into.  CPU tensors: the same integers from vectorised torch ops."""
+    K = int(K)
+    if not 2 <= K <= 16:
+        raise ValueError(f"K must be in 2 ... 16 (got {K})")
+    if min(ignore_gt, ignore_pred, ignore_aux) < -1:
+        raise ValueError("an ignore label is a class id >= 0, or -1 for none")
+    if aux is None and ignore_aux != -1:
+        raise ValueError("ignore_aux needs aux")
+    if gt.dim() != 2:
+        raise ValueError(f"gt must be a [rows, cols] map (got shape {tuple(gt.shape)})")
+    if pred.shape != gt.shape or (aux is not None and aux.shape != gt.shape):
+        raise ValueError(f"gt, pred{' and aux' if aux is not None else ''} must hold the same number of labels "
+                         f"(got {tuple(gt.shape)}, {tuple(pred.shape)}{'' if aux is None else ', ' + str(tuple(aux.shape))})")
+    if pred.device != gt.device or (aux is not None and aux.device != gt.device):
+        raise ValueError("gt, pred and aux must live on one device")
+    min_run, tol, row_slabs = int(min_run), int(tol), int(row_slabs)
+    if min_run < 1:
+        raise ValueError(f"min_run must be at least 1 (got {min_run})")
+    if tol < 0:
+        raise ValueError(f"tol must be at least 0 (got {tol})")
+    if not 0 <= row_slabs <= 8:
+        raise ValueError(f"row_slabs must be 0 (the library chooses) or 1 ... 8 (got {row_slabs})")
+    rows, cols = gt.shape
+    if rows > HORIZON_MAX_ROWS:
+        raise ValueError(f"rows must be at most {HORIZON_MAX_ROWS} (got {rows})")
+    if picks_out is not None:
+        want_picks = True
+        if (picks_out.dtype != torch.int32 or tuple(picks_out.shape) != (2, 3, K, cols) or not picks_out.is_contiguous()
+                or picks_out.device != gt.device):
+            raise ValueError(f"picks_out must be a contiguous int32 [2, 3, {K}, {cols}] tensor on the maps' device")
+    if not gt.is_cuda:
+        stats, dropped, picks = _horizons_cpu(gt, pred, K, aux, ignore_gt, ignore_pred, ignore_aux, min_run, tol)
+        if picks_out is not None:
+            picks = picks_out.copy_(picks)
+        return (stats, dropped, picks) if want_picks else (stats, dropped)
+    ops = [_window2d(t) for t in (gt, pred, aux) if t is not None]
+    pitches = [_pitch(t) for t in ops]
+    if rows * cols == 0:
+        ops, ld = ops[:2], cols  # an empty tensor has no address: nothing to mask
+        ignore_aux = -1
+    elif None in pitches or len(set(pitches)) > 1:
+        ops, ld = [t.contiguous() for t in ops], cols
+    else:
+        ld = pitches[0]
+    g, p = ops[0], ops[1]
+    a = ops[2] if len(ops) > 2 else None
+    code = lambda t: DT_F32 if t.dtype == torch.float32 else DT_I8
+    out = torch.empty(K * HORIZON_STATS + 2, dtype=torch.int64, device=gt.device)
+    picks = None
+    if want_picks:
+        picks = picks_out if picks_out is not None else torch.empty(2, 3, K, cols, dtype=torch.int32, device=gt.device)
+    L = _horizons_lib()
+    nbytes = L.crw_horizons_ws_bytes(rows, cols, K)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=gt.device)
+    _check(L.crw_horizons(_ptr(g), code(g), _ptr(p), code(p), _ptr(a) if a is not None else None, code(a) if a is not None else DT_I8,
+                          rows, cols, ld, K, int(ignore_gt), int(ignore_pred), int(ignore_aux), min_run, tol, row_slabs,
+                          _ptr(picks) if picks is not None and picks.numel() else None, _ptr(out),
+                          ctypes.c_void_p(out.data_ptr() + 8 * K * HORIZON_STATS), _ptr(ws), nbytes, _stream()), "crw_horizons")
+    stats, dropped = out[:K * HORIZON_STATS].view(K, HORIZON_STATS), out[K * HORIZON_STATS:]
+    return (stats, dropped, picks) if want_picks else (stats, dropped)
+
+
+def _horizons_cpu(gt, pred, K, aux, ignore_gt, ignore_pred, ignore_aux, min_run, tol):
+    rows, cols = gt.shape
+    g, p = gt.to(torch.float64), pred.to(torch.float64)
+    masked = torch.zeros(g.shape, dtype=torch.bool)
+    if ignore_gt >= 0:
+        masked |= g == ignore_gt
+    if ignore_pred >= 0:
+        masked |= p == ignore_pred
+    if ignore_aux >= 0:
+        masked |= aux.to(torch.float64) == ignore_aux
+    valid = (g == g.floor()) & (g >= 0) & (g < K) & (p == p.floor()) & (p >= 0) & (p < K)  # NaN fails every comparison
+    keep = valid & ~masked
+    dropped = torch.stack([masked.sum(), (~masked & ~valid).sum()]).to(torch.int64)
+    picks = torch.empty(2, 3, K, cols, dtype=torch.int32)
+    picks[:, :2], picks[:, 2] = -1, 0
+    if rows and cols:
+        r = torch.arange(rows)[:, None].expand(rows, cols)
+        for m, lab in enumerate((g, p)):
+            lab = torch.where(keep, lab, torch.full_like(lab, -1.0)).to(torch.int64)
+            change = torch.ones(rows, cols, dtype=torch.bool)
+            change[1:] = lab[1:] != lab[:-1]
+            start = torch.cummax(torch.where(change, r, torch.zeros_like(r)), 0).values  # first row of the pixel's run
+            last = torch.ones(rows, cols, dtype=torch.bool)
+            last[:-1] = change[1:]
+            end = torch.flip(torch.cummin(torch.flip(torch.where(last, r, torch.full_like(r, rows)), (0,)), 0).values, (0,))
+            good = (lab >= 0) & (end - start + 1 >= min_run)  # pixels of qualifying runs
+            hot = good[None] & (lab[None] == torch.arange(K)[:, None, None])  # [K, rows, cols]
+            n = hot.sum(1)
+            top = hot.to(torch.int8).argmax(1)
+            bottom = rows - 1 - torch.flip(hot, (1,)).to(torch.int8).argmax(1)
+            none = torch.full_like(n, -1)
+            picks[m, 0], picks[m, 1], picks[m, 2] = torch.where(n > 0, top, none), torch.where(n > 0, bottom, none), n
+    return _horizon_stats(picks, K, tol), dropped, picks
+
+
+def _horizon_stats(picks, K, tol):
+    """stats [K, 18] of picks [2, 3, K, cols] (CPU route)."""
+    pk = picks.to(torch.int64)
+    hg, hp = pk[0, 2] > 0, pk[1, 2] > 0
+    both = hg & hp
+    stats = torch.zeros(K, HORIZON_STATS, dtype=torch.int64)
+    stats[:, 0], stats[:, 1], stats[:, 2] = both.sum(1), (hg & ~hp).sum(1), (hp & ~hg).sum(1)
+    for q in range(3):
+        d = torch.where(both, pk[1, q] - pk[0, q], torch.zeros_like(pk[0, q]))
+        base = 3 + 5 * q
+        stats[:, base] = d.abs().sum(1)
+        stats[:, base + 1] = (d * d).sum(1)
+        stats[:, base + 2] = d.abs().max(1).values if d.shape[1] else 0
+        stats[:, base + 3] = (both & (d.abs() <= tol)).sum(1)
+        stats[:, base + 4] = d.sum(1)
+    return stats
 
 
 # ------------------------------------------------------------------------------ confidence

@@ -592,6 +592,58 @@ def calibration_sweep(pred, conf, seg, dataset_id, remove_unc=True, unc_seg=None
     return cals
 
 
+def _map2d(t, like):
+    """`t` as a [rows, cols] map of `like`'s shape (a flat or batched-by-one tensor is viewed, a window stays a window)."""
+    return t if t.dim() == 2 else t.reshape(like.shape[-2:])
+
+
+def horizons(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None, min_run=1, tol=2, want_picks=False,
+             row_spacing=1.0, unit='rows'):
+    """Where are the interfaces, and how thick are the layers?  Per class, the horizon and thickness errors of the label map
+    ``pred`` ([rows, cols]) against ``seg`` -> ``metrics.Horizons`` (with ``want_picks``: also the picks, int32 [2, 3, K, cols] on
+    pred's device: map (0 seg, 1 pred) x (top, bottom, count)).  `evaluate`'s arguments and mask rules, passed through as
+    arguments of the one ``crw_hip.horizons`` call: the pixels it sees are the pixels `evaluate` counts.  ``min_run``: the
+    shortest run of equal labels down a column that counts as a layer (1: any pixel); ``tol``: the rows within which a pick counts
+    as right.  A surviving label outside 0 ... K-1 raises ``crw_hip.LabelError``."""
+    from metrics import Horizons
+    K, seg, mask = _report_rules(pred, seg, dataset_id, remove_unc, unc_seg, nclasses)
+    if pred.dim() != 2:
+        raise ValueError(f'pred must be a [rows, cols] map (got shape {tuple(pred.shape)})')
+    mask = {k: (_map2d(v, pred) if torch.is_tensor(v) else v) for k, v in mask.items()}
+    out = crw_hip.horizons(_map2d(seg, pred), pred, K, min_run=min_run, tol=tol, want_picks=want_picks, **mask)
+    host = torch.cat([out[0].reshape(-1), out[1]]).cpu()  # the one copy: 18 K + 2 integers
+    dropped = [int(v) for v in host[18 * K:]]
+    if dropped[1]:
+        raise crw_hip.LabelError(dropped[1], K)
+    hz = Horizons(host[:18 * K].view(K, 18), dropped, pred.shape[0], pred.shape[1], min_run, tol, row_spacing=row_spacing, unit=unit)
+    return (hz, out[2]) if want_picks else hz
+
+
+def horizons_sweep(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None, min_run=1, tol=2, row_spacing=1.0,
+                   unit='rows'):
+    """`horizons` for the G maps of `segment_sweep` (pred [G, rows, cols]) -> G ``metrics.Horizons``: G `crw_hip.horizons` calls
+    queued back to back, ONE copy of all statistics to the host at the end, like `evaluate_sweep`.  Same mask rules; a label
+    outside 0 ... K-1 that survives the mask in any map raises ``crw_hip.LabelError``."""
+    from metrics import Horizons
+    if pred.dim() != 3 or pred[0].numel() != seg.numel():
+        raise ValueError(f'pred {tuple(pred.shape)} must be G [rows, cols] maps covering the pixels of seg {tuple(seg.shape)}')
+    K, seg, mask = _report_rules(pred[0], seg, dataset_id, remove_unc, unc_seg, nclasses)
+    mask = {k: (_map2d(v, pred) if torch.is_tensor(v) else v) for k, v in mask.items()}
+    seg = _map2d(seg, pred)
+    outs = [crw_hip.horizons(seg, p, K, min_run=min_run, tol=tol, **mask) for p in pred]
+    if not outs:
+        return []
+    host = torch.stack([torch.cat([s.reshape(-1), d]) for s, d in outs]).cpu()  # [G, 18 K + 2]
+    res = []
+    for row in host:
+        dropped = [int(v) for v in row[18 * K:]]
+        if dropped[1]:
+            raise crw_hip.LabelError(dropped[1], K)
+        res.append(Horizons(row[:18 * K].view(K, 18), dropped, pred.shape[1], pred.shape[2], min_run, tol, row_spacing=row_spacing,
+                            unit=unit))
+    return res
+
+
 # the reference's three per-dataset drivers (scripts/test/test_mc1.py:19-30, test_mc3.py:19-33, test_sharad.py:19-32): argparse
 # defaults, the class count and encoder they hard-code, and the change points test_mc3 / test_sharad set by hand before correcting
 DRIVERS = {

@@ -16,6 +16,10 @@ no column and no share in the macro average; a 0 / 0 ratio is 0.0.  IoU is an ad
 histogram of ``crw_hip.calibration`` -- per confidence bin, the pixels, the correct pixels and the summed confidence, under the same
 masks -- turned into the expected / maximum calibration error and the risk-coverage curve.  The reference has no twin: it marks
 "uncertain" pixels with a hand-drawn class (``--remove_unc``).
+
+``Horizons`` reports what a sounder segmentation is used for -- its interfaces: per class, in how many columns the layer was found,
+missed or invented, and how far its top, its bottom and its thickness lie from the ground truth's, from the [K, 18] integers of
+``crw_hip.horizons``.  No twin in the reference either.
 """
 import numpy as np
 import torch
@@ -202,6 +206,95 @@ class Calibration:
         text += "\n"
         for name, v in (("ECE", self.ece), ("MCE", self.mce), ("AURC", self.aurc), ("accuracy", self.overall_accuracy)):
             text += "{:>13} {:>12} {}\n".format(name, self.total if name == "accuracy" else "", num(v))
+        return text
+
+
+class Horizons:
+    """Horizon and thickness errors per class, from the [K, 18] statistics and the dropped pair of ``crw_hip.horizons`` (tensors
+    are copied to the host once: 18 K + 2 integers).
+
+    n_both / n_missing / n_spurious [K] int64: columns in which both maps, the ground truth only, the prediction only have a
+    qualifying run of the class.  presence_precision = n_both / (n_both + n_spurious), presence_recall = n_both / (n_both +
+    n_missing), NaN for 0 / 0.  For each quantity q in QUANTITIES ('top', 'bottom', 'thickness'; 'count' reads as 'thickness'),
+    over the n_both columns with d = pred - gt: errors[q] = dict(mae, rmse, bias, max: [K] float64 in ``unit`` = rows *
+    ``row_spacing``, NaN where n_both = 0; within: the fraction of those columns with |d| <= tol rows), with ``mae(k, q)`` for one
+    number.  The integers stay available: ``stats``, and sum_abs / sum_sq / max_abs / n_within / sum_d [q] in rows."""
+
+    QUANTITIES = ("top", "bottom", "thickness")
+
+    def __init__(self, stats, dropped, rows, cols, min_run, tol, row_spacing=1.0, unit="rows"):
+        host = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        stats = np.asarray(host(stats), dtype=np.int64)
+        if stats.ndim != 2 or stats.shape[1] != 18 or stats.shape[0] < 1:
+            raise ValueError(f"stats must be [K, 18] (got shape {stats.shape})")
+        if (stats[:, :3] < 0).any() or (stats[:, :3].sum(1) > cols).any():
+            raise ValueError("n_both + n_missing + n_spurious must lie in 0 ... cols for every class")
+        if not row_spacing > 0:
+            raise ValueError(f"row_spacing must be positive (got {row_spacing})")
+        self.stats, self.K = stats, stats.shape[0]
+        self.dropped = None if dropped is None else tuple(int(v) for v in host(dropped))
+        self.rows, self.cols, self.min_run, self.tol = int(rows), int(cols), int(min_run), int(tol)
+        self.row_spacing, self.unit = float(row_spacing), str(unit)
+        self.n_both, self.n_missing, self.n_spurious = stats[:, 0].copy(), stats[:, 1].copy(), stats[:, 2].copy()
+        nan_ratio = lambda num, den: np.divide(num, den, out=np.full(self.K, np.nan), where=np.asarray(den) != 0)
+        self.presence_precision = nan_ratio(self.n_both, self.n_both + self.n_spurious)
+        self.presence_recall = nan_ratio(self.n_both, self.n_both + self.n_missing)
+        self.sum_abs, self.sum_sq, self.max_abs, self.n_within, self.sum_d = {}, {}, {}, {}, {}
+        self.errors = {}
+        found = self.n_both > 0
+        for i, q in enumerate(self.QUANTITIES):
+            sa, sq, mx, nw, sd = (stats[:, 3 + 5 * i + j].copy() for j in range(5))
+            self.sum_abs[q], self.sum_sq[q], self.max_abs[q], self.n_within[q], self.sum_d[q] = sa, sq, mx, nw, sd
+            self.errors[q] = dict(mae=nan_ratio(sa, self.n_both) * self.row_spacing,
+                                  rmse=np.sqrt(nan_ratio(sq, self.n_both)) * self.row_spacing,
+                                  bias=nan_ratio(sd, self.n_both) * self.row_spacing,
+                                  max=np.where(found, mx * self.row_spacing, np.nan), within=nan_ratio(nw, self.n_both))
+
+    @classmethod
+    def _q(cls, q):
+        q = "thickness" if q == "count" else q
+        if q not in cls.QUANTITIES:
+            raise ValueError(f"quantity must be one of {cls.QUANTITIES} (got {q!r})")
+        return q
+
+    def mae(self, k, q="top"):
+        """Mean absolute error of class k's top, bottom or thickness, in ``unit``; NaN when no column has the class in both maps."""
+        return float(self.errors[self._q(q)]["mae"][k])
+
+    def mean_mae(self, q="top"):
+        """The unweighted mean of the classes' MAE over the classes with n_both > 0; NaN when there is none."""
+        v = self.errors[self._q(q)]["mae"][self.n_both > 0]
+        return float(v.mean()) if v.size else float("nan")
+
+    def to_dict(self):
+        lst = lambda a: [float(v) for v in a]
+        ints = lambda a: [int(v) for v in a]
+        d = dict(K=self.K, rows=self.rows, cols=self.cols, min_run=self.min_run, tol=self.tol, row_spacing=self.row_spacing,
+                 unit=self.unit, n_both=ints(self.n_both), n_missing=ints(self.n_missing), n_spurious=ints(self.n_spurious),
+                 presence_precision=lst(self.presence_precision), presence_recall=lst(self.presence_recall))
+        for q in self.QUANTITIES:
+            e = self.errors[q]
+            d[q] = dict(mae=lst(e["mae"]), rmse=lst(e["rmse"]), bias=lst(e["bias"]), max=lst(e["max"]),
+                        within_tol=lst(e["within"]), sum_abs_rows=ints(self.sum_abs[q]), sum_sq_rows=ints(self.sum_sq[q]),
+                        max_abs_rows=ints(self.max_abs[q]), n_within=ints(self.n_within[q]), sum_rows=ints(self.sum_d[q]),
+                        mean_mae=self.mean_mae(q))
+        if self.dropped is not None:
+            d["dropped"] = dict(masked=self.dropped[0], invalid=self.dropped[1])
+        return d
+
+    def __str__(self, digits=2):
+        num = lambda v, w=9: "{:>{w}}".format("-", w=w) if v != v else "{:>{w}.{d}f}".format(v, w=w, d=digits)
+        text = "Horizons (min_run {}, tol {} rows, distances in {}):\n".format(self.min_run, self.tol, self.unit)
+        text += "{:>5} {:>9} {:>8} {:>8} {:>8} {:>9} {:>9}  {:>9} {:>9} {:>9} {:>9} {:>9}\n\n".format(
+            "class", "quantity", "both", "missing", "spurious", "precision", "recall", "mae", "rmse", "bias", "max", "within")
+        for k in range(self.K):
+            for i, q in enumerate(self.QUANTITIES):
+                lead = "{:>5} {:>9} {:>8} {:>8} {:>8} {} {}".format(
+                    k, q, int(self.n_both[k]), int(self.n_missing[k]), int(self.n_spurious[k]), num(self.presence_precision[k]),
+                    num(self.presence_recall[k])) if i == 0 else "{:>5} {:>9} {:>8} {:>8} {:>8} {:>9} {:>9}".format("", q, "", "", "", "", "")
+                text += lead + "  " + " ".join(num(self.errors[q][x][k]) for x in ("mae", "rmse", "bias", "max", "within")) + "\n"
+        text += "\n{:>5} {:>9} {:>8} {:>8} {:>8} {:>9} {:>9}  {}\n".format("mean", "mae", "", "", "", "", "", " ".join(
+            "{}={}".format(q, num(self.mean_mae(q), 0).strip()) for q in self.QUANTITIES))
         return text
 
 

@@ -17,7 +17,12 @@ per-pixel confidence of the map (``inference.segment(..., confidence=...)``) and
 confidence of the final map as ``confidence_map.pt`` (float32); ``--merge confidence``: the reverse pass of ``--use_last`` is merged
 per pixel by confidence instead of by the reference's class rule; ``--upsample bilinear``: the maps come from the soft labels,
 interpolated bilinearly to pixels and arg-maxed after that (``inference.segment(..., upsample='bilinear')``; ``--report_json`` gains
-``"upsample": "bilinear"``) instead of the reference's arg-max + nearest stretch.  Without these flags the output is what it was.
+``"upsample": "bilinear"``) instead of the reference's arg-max + nearest stretch; ``--horizons``: after the confusion matrix (and the calibration table), the
+horizon table of ``inference.horizons`` -- per class, in how many columns the layer was found, missed or invented, and the error of
+its top, bottom and thickness -- with ``--min_run N`` (default 3: runs of fewer equal labels down a column are no layer), ``--tol
+ROWS`` (default 2), ``--row_spacing X`` / ``--row_unit NAME`` (the printed distances are rows * X, in NAME); ``--save_horizons``
+writes the picks as ``horizons.pt`` (int32 [2, 3, K, cols], CPU); ``--report_json`` gains a ``horizons`` key.  Without these flags
+the output is what it was.
 Differences from the scripts:
   * plots are not drawn;
   * true / false flags read true / false (the scripts take any given string as true); ``--patch_size`` takes two numbers;
@@ -87,7 +92,29 @@ def get_args_parser():
     p.add_argument('--save_conf', action='store_true', help='write confidence_map.pt (needs --confidence)')
     p.add_argument('--upsample', default='nearest', choices=('nearest', 'bilinear'),
                    help="node labels to pixels: the reference's arg-max + nearest, or soft labels interpolated bilinearly, then arg-max")
+    p.add_argument('--horizons', action='store_true', help='also print the horizon / thickness error table')
+    p.add_argument('--min_run', default=3, type=int, metavar='N', help='shortest run of equal labels down a column that is a layer')
+    p.add_argument('--tol', default=2, type=int, metavar='ROWS', help='a pick within this many rows counts as right')
+    p.add_argument('--row_spacing', default=1.0, type=float, metavar='X', help='distance between two rows, for the printed errors')
+    p.add_argument('--row_unit', default='rows', metavar='NAME', help='the unit --row_spacing is given in')
+    p.add_argument('--save_horizons', action='store_true', help='write horizons.pt, the picks (needs --horizons)')
     return p
+
+
+HORIZON_FLAGS = ('horizons', 'min_run', 'tol', 'row_spacing', 'row_unit', 'save_horizons')
+
+
+def check_horizon_flags(args):
+    """The flags around ``--horizons``."""
+    if args.save_horizons and not args.horizons:
+        raise SystemExit('--save_horizons needs --horizons')
+    if args.horizons and args.min_run < 1:
+        raise SystemExit(f'--min_run {args.min_run}: at least 1')
+    if args.horizons and args.tol < 0:
+        raise SystemExit(f'--tol {args.tol}: at least 0')
+    if args.horizons and not args.row_spacing > 0:
+        raise SystemExit(f'--row_spacing {args.row_spacing}: positive')
+    return args
 
 
 def with_defaults(args):
@@ -155,11 +182,13 @@ def load_data(args):
 def main(args):
     from imported.labelprop import LabelPropVOS_CRW
     tim = time.time()
-    args = check_confidence_flags(with_defaults(args))
+    args = check_horizon_flags(check_confidence_flags(with_defaults(args)))
     # without --confidence the four flags that go with it do nothing, and the line reads as it did before they existed
     hidden = () if args.confidence else ('confidence', 'merge', 'bins', 'save_conf')
     if args.upsample == 'nearest':  # likewise
         hidden += ('upsample',)
+    if not args.horizons:  # likewise
+        hidden += HORIZON_FLAGS
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -212,6 +241,16 @@ def main(args):
         print('')
         print(f'Calibration ({args.confidence}, merge: {args.merge}):')
         print(cal)
+    hz = None
+    if args.horizons:
+        hz, picks = inference.horizons(final, seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
+                                       unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses,
+                                       min_run=args.min_run, tol=args.tol, want_picks=True, row_spacing=args.row_spacing,
+                                       unit=args.row_unit)
+        print('')
+        print(hz)
+        if args.save_horizons:
+            torch.save(picks.cpu(), os.path.join(args.output_folder, 'horizons.pt'))
     if args.iou:
         print('')
         print(report.iou_str())
@@ -226,6 +265,8 @@ def main(args):
             d['upsample'] = args.upsample
         if cal is not None:
             d['calibration'] = dict(cal.to_dict(), kind=args.confidence, merge=args.merge)
+        if hz is not None:
+            d['horizons'] = hz.to_dict()
         with open(args.report_json, 'w') as f:
             json.dump(d, f, indent=1)
     return report

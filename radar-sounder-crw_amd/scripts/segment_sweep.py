@@ -18,7 +18,9 @@ configurations at once (``inference.segment_sweep``'s arguments; the G dense map
 ``--confidence`` every configuration's line gains its ECE and AURC (``inference.calibration_sweep``), the best configuration's
 calibration table follows its matrix, ``--report_json`` gains a ``calibration`` entry per configuration, and ``--select`` also
 takes ``ece`` and ``aurc`` -- lower is better: the smallest wins, ties go to the first in the grid's order, a NaN never wins
-unless every score is NaN.  Without these flags the script prints and writes what it did before them.
+unless every score is NaN.  ``--horizons`` (with ``--min_run N``, default 3, and ``--tol ROWS``, default 2): every configuration's
+line gains the mean top MAE of its horizons (``inference.horizons_sweep``; rows), ``--report_json`` a ``horizons`` entry per
+configuration, and ``--select`` also takes ``horizon_mae`` (offered only with ``--horizons``) -- the lowest wins, by the same rules.  Without these flags the script prints and writes what it did before them.
 CRW_SWEEP_PER_CONFIG=1: the label propagation as a loop over the configurations (same maps; the A/B arm)."""
 import argparse
 import json
@@ -42,9 +44,13 @@ SELECT = {'macro_f1': lambda r: r.macro['f1'], 'weighted_f1': lambda r: r.weight
           'mean_iou': lambda r: r.mean_iou}
 # scores of the calibration (``--confidence``): lower is better
 SELECT_CAL = {'ece': lambda c: c.ece, 'aurc': lambda c: c.aurc}
+# score of the horizons (``--horizons``): lower is better
+SELECT_HORIZON = {'horizon_mae': lambda h: h.mean_mae('top')}
 
 
-def get_args_parser():
+def get_args_parser(horizons=False):
+    """``horizons``: whether ``--horizons`` is on the command line -- only then is there a horizon score to select by, and only
+    then does ``--select`` offer ``horizon_mae``."""
     p = argparse.ArgumentParser('CRW label-propagation sweep (launch_test_batch.sh over test_all.py)', add_help=True)
     p.add_argument('--model', default=None, type=int, help='0=CNN,1=Resnet18')
     p.add_argument('--dataset', default=None, type=int, help='0=MCORDS1,1=Miguel,3=SHARAD')
@@ -67,8 +73,9 @@ def get_args_parser():
     p.add_argument('--seg_path', default=None, help='reference segmentation .pt file')
     p.add_argument('--unc_seg_path', default=None, help="dataset 0's map with the uncertain class 4 (the reference's dataset id 2)")
     p.add_argument('--synthetic', default=None, nargs=2, type=int, metavar=('H', 'W'))
-    p.add_argument('--select', default='macro_f1', choices=sorted(SELECT) + sorted(SELECT_CAL),
-                   help='the score the best configuration is picked by (ece, aurc: the lowest, need --confidence)')
+    p.add_argument('--select', default='macro_f1', choices=sorted(SELECT) + sorted(SELECT_CAL) + (sorted(SELECT_HORIZON) if horizons else []),
+                   help='the score the best configuration is picked by (ece, aurc: the lowest, need --confidence; horizon_mae: the '
+                        'lowest, needs --horizons)')
     p.add_argument('--reports', action='store_true', help='print the full report of every configuration')
     p.add_argument('--report_json', default=None, metavar='FILE')
     p.add_argument('--save_maps', action='store_true', help='save every predicted_map_r{r}_t{t}_k{k}.pt (int8)')
@@ -79,6 +86,9 @@ def get_args_parser():
     p.add_argument('--bins', default=10, type=int, metavar='B', help='confidence bins of the calibration (1 ... 64)')
     p.add_argument('--upsample', default='nearest', choices=('nearest', 'bilinear'),
                    help="node labels to pixels: the reference's arg-max + nearest, or soft labels interpolated bilinearly, then arg-max")
+    p.add_argument('--horizons', action='store_true', help="the mean top MAE of every configuration's horizons (a column)")
+    p.add_argument('--min_run', default=3, type=int, metavar='N', help='shortest run of equal labels down a column that is a layer')
+    p.add_argument('--tol', default=2, type=int, metavar='ROWS', help='a pick within this many rows counts as right')
     return p
 
 
@@ -90,6 +100,10 @@ def check_confidence_flags(args):
         raise SystemExit(f'--select {args.select} needs --confidence {{maxprob,margin,entropy}}')
     if not 1 <= args.bins <= 64:
         raise SystemExit(f'--bins {args.bins}: 1 ... 64')
+    if not args.horizons and args.select in SELECT_HORIZON:
+        raise SystemExit(f'--select {args.select} needs --horizons')
+    if args.horizons and (args.min_run < 1 or args.tol < 0):
+        raise SystemExit('--min_run is at least 1, --tol at least 0')
     return args
 
 
@@ -127,6 +141,8 @@ def main(args):
     hidden = () if args.confidence else ('confidence', 'merge', 'bins')
     if args.upsample == 'nearest':
         hidden += ('upsample',)
+    if not args.horizons:
+        hidden += ('horizons', 'min_run', 'tol')
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -166,17 +182,26 @@ def main(args):
     if args.confidence:
         cals = inference.calibration_sweep(final, out['conf'], seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
                                            unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses, bins=args.bins)
+    hzs = None
+    if args.horizons:
+        hzs = inference.horizons_sweep(final, seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
+                                       unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses,
+                                       min_run=args.min_run, tol=args.tol)
     print('{:>6} {:>7} {:>4} {:>9} {:>9} {:>11} {:>9}'.format('radius', 'temp', 'knn', 'accuracy', 'macro f1', 'weighted f1', 'mean iou')
-          + (' {:>8} {:>8}'.format('ece', 'aurc') if cals else ''))
+          + (' {:>8} {:>8}'.format('ece', 'aurc') if cals else '') + (' {:>11}'.format('horizon mae') if hzs else ''))
     for g, (cfg, r) in enumerate(zip(sweep.configs, reports)):
         print('{:>6} {:>7g} {:>4} {:>9.4f} {:>9.4f} {:>11.4f} {:>9.4f}'.format(cfg['RADIUS'], cfg['TEMP'], cfg['KNN'], r.accuracy,
                                                                                r.macro['f1'], r.weighted['f1'], r.mean_iou)
-              + (' {:>8.4f} {:>8.4f}'.format(cals[g].ece, cals[g].aurc) if cals else ''))
+              + (' {:>8.4f} {:>8.4f}'.format(cals[g].ece, cals[g].aurc) if cals else '')
+              + (' {:>11.4f}'.format(hzs[g].mean_mae('top')) if hzs else ''))
         if args.reports:
             print(r)
             print(r.matrix_str())
             print('')
-    if args.select in SELECT_CAL:
+    if args.select in SELECT_HORIZON:
+        scores = [float(SELECT_HORIZON[args.select](h)) for h in hzs]
+        best = pick_best(scores, lower_is_better=True)
+    elif args.select in SELECT_CAL:
         scores = [float(SELECT_CAL[args.select](c)) for c in cals]
         best = pick_best(scores, lower_is_better=True)
     else:
@@ -190,6 +215,9 @@ def main(args):
         print('')
         print(f'Calibration ({args.confidence}, merge: {args.merge}):')
         print(cals[best])
+    if hzs:
+        print('')
+        print(hzs[best])
     t_all = time.time() - tim
     print('\nTime elapsed (inference + metrics):', t_all)
     if args.report_json:
@@ -203,6 +231,9 @@ def main(args):
             for c, cal in zip(d['configs'], cals):
                 c['calibration'] = cal.to_dict()
             d.update(confidence=args.confidence, merge=args.merge)
+        if hzs:
+            for c, h in zip(d['configs'], hzs):
+                c['horizons'] = h.to_dict()
         if args.upsample != 'nearest':
             d['upsample'] = args.upsample
         with open(args.report_json, 'w') as f:
@@ -212,4 +243,4 @@ def main(args):
 
 if __name__ == '__main__':
     torch.manual_seed(11)  # the scripts seed at import (test_all.py:14)
-    main(get_args_parser().parse_args())
+    main(get_args_parser(horizons='--horizons' in sys.argv[1:]).parse_args())
