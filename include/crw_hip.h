@@ -15,6 +15,9 @@
  *                             softmax                                         src/imported/maskedatt.py:151-175
  *   crw_labelprop_gather .... weighted label sum + argmax, frame by frame     src/imported/labelprop.py:106-114, src/utils.py:152-160
  *   crw_labelprop_propagate . the same, chained prefix + parallel tail          (same lines; context bound of maskedatt.py:165-166)
+ *   crw_labelprop_propagate_sliding(_batch)
+ *                             the same sums with the indices applied to the      src/imported/crw.py (the vendored upstream routine
+ *                             frames they were scored on (opt-in rule)           gathers from the scored frames; labelprop.py does not)
  *   crw_labelprop_topk_scores / crw_labelprop_sweep_weights / crw_labelprop_propagate_batch
  *                             the same lists and labels for a whole grid of
  *                             (radius, temp, knn) settings at once              scripts/launch/launch_test_batch.sh
@@ -57,8 +60,9 @@ extern "C" {
  * binding detects them by symbol, crw_hip.has_sweep()): crw_labelprop_topk_scores, crw_labelprop_sweep_weights,
  * crw_labelprop_propagate_batch; then crw_labelprop_confidence, crw_merge_confidence, crw_calibration_ws_bytes, crw_calibration
  * (crw_hip.has_confidence()); then crw_labelmap_dense (crw_hip.has_dense()); then crw_labelmap_dense_batch
- * (crw_hip.has_dense_batch()); then crw_horizons_ws_bytes, crw_horizons (crw_hip.has_horizons()).  The ONE place the number is written: crw_abi_version() returns
- * it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
+ * (crw_hip.has_dense_batch()); then crw_horizons_ws_bytes, crw_horizons (crw_hip.has_horizons()); then
+ * crw_labelprop_propagate_sliding, crw_labelprop_propagate_sliding_batch (crw_hip.has_sliding()).  The ONE place the number is
+ * written: crw_abi_version() returns it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
 #define CRW_ABI_VERSION 8
 
@@ -176,6 +180,25 @@ int crw_labelprop_sweep_weights(const float *V, int F, int kcap, int N, const in
  * grid over (frame, configuration).  CRW_EINVAL: G > 65535, knn > 64, N * M > 7680 (a ring of four frames must fit the LDS). */
 int crw_labelprop_propagate_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M,
                                   int knn, int first_frame, int cxt_size, float *L, float *pred, crw_stream_t stream);
+
+/* The "sliding" context rule (opt-in; the reference's rule is the two entry points above).  W, I are the lists of
+ * crw_labelprop_topk(_grid) / _topk_scores at `cxt_size`, untouched; an index i of frame n addresses the list it was SCORED on,
+ * [frame 0, frames n - cxt_size .. n - 1], i.e. label row
+ *     row(i, n) = i                                  if i < N or n <= cxt_size + 1
+ *                 i + (n - cxt_size - 1) * N         otherwise
+ * and L[n] = sum_j W[j] * L[row(I[j], n)] in neighbour order from 0.f, pred the first maximum.  Defined as bit-identical L and pred
+ * to crw_labelprop_gather on lists whose indices were translated by row().  Every frame needs the one before it: one chain over all
+ * frames, no parallel tail.  Route: one workgroup with frame 0 and a ring of cxt_size + 1 frames in LDS when
+ * (cxt_size + 2) * N * M * 4 bytes + 16 KiB of list slots <= 150 KiB, knn <= 24, N * M <= 384 and knn * N <= 1024 (there an index
+ * outside [0, min(n, cxt_size + 1) * N) is clamped into it); otherwise crw_labelprop_gather's kernels with the translation done in
+ * the kernel (nothing is allocated, I is not copied).  CRW_LABELPROP_SLIDING_GENERAL=1 (read per call) takes the second route. */
+int crw_labelprop_propagate_sliding(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame,
+                                    int cxt_size, float *L, float *pred, crw_stream_t stream);
+/* G configurations at once, arguments and limits as crw_labelprop_propagate_batch: a workgroup per configuration walks ALL frames
+ * first_frame .. T-1 (no second launch).  Slice g of L and pred is bit-identical to crw_labelprop_propagate_sliding on that
+ * configuration's lists. */
+int crw_labelprop_propagate_sliding_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N,
+                                          int M, int knn, int first_frame, int cxt_size, float *L, float *pred, crw_stream_t stream);
 
 /* HOST function (no GPU work, host pointers): the change-point search of `propagate` (src/utils.py:125-132,
  * ruptures.Pelt(model="rbf").fit(signal).predict(pen)) -- PELT with the RBF kernel cost at ruptures' documented defaults

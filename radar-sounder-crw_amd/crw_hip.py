@@ -54,6 +54,8 @@ SIGNATURES = {
     "crw_labelprop_topk_scores": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_int, _c_int, _c_int, _p, _p, _p]),
     "crw_labelprop_sweep_weights": (_c_int, [_p, _c_int, _c_int, _c_int, _p, _c_int, _p, _p]),
     "crw_labelprop_propagate_batch": (_c_int, [_p, _p, _p, _c_sz] + [_c_int] * 7 + [_p, _p, _p]),
+    "crw_labelprop_propagate_sliding": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p]),
+    "crw_labelprop_propagate_sliding_batch": (_c_int, [_p, _p, _p, _c_sz] + [_c_int] * 7 + [_p, _p, _p]),
     "crw_xent_metric": (_c_int, [_p, _c_int, _c_int, _c_int, _p, _p]),
     "crw_confusion_ws_bytes": (_c_sz, [_c_sz, _c_int]),
     "crw_confusion": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _c_sz, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _c_sz, _p]),
@@ -149,8 +151,14 @@ DENSE_BATCH_ENTRY_POINTS = ("crw_labelmap_dense_batch",)
 # likewise: layer horizons and thickness (`has_horizons()`)
 HORIZONS_ENTRY_POINTS = ("crw_horizons_ws_bytes", "crw_horizons")
 
+# likewise: label propagation from the scored frames, the 'sliding' context rule (`has_sliding()`)
+SLIDING_ENTRY_POINTS = ("crw_labelprop_propagate_sliding", "crw_labelprop_propagate_sliding_batch")
+
+CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
+
 _lib = None
 _has_horizons = False
+_has_sliding = False
 _has_sweep = False
 _has_confidence = False
 _has_dense = False
@@ -160,14 +168,14 @@ _has_dense_batch = False
 def lib():
     """Load the HIP library (once).  Raises if it has not been built: `python -c 'import
     __graft_entry__ as g; g.build()'` or `make -C radar-sounder-crw_amd/csrc`."""
-    global _lib, _has_sweep, _has_confidence, _has_dense, _has_dense_batch, _has_horizons
+    global _lib, _has_sweep, _has_confidence, _has_dense, _has_dense_batch, _has_horizons, _has_sliding
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} not built -- the CRW hot path has no CPU/PyTorch fallback; "
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
         missing = [n for n in SWEEP_ENTRY_POINTS + CONFIDENCE_ENTRY_POINTS + DENSE_ENTRY_POINTS + DENSE_BATCH_ENTRY_POINTS
-                   + HORIZONS_ENTRY_POINTS if not hasattr(handle, n)]
+                   + HORIZONS_ENTRY_POINTS + SLIDING_ENTRY_POINTS if not hasattr(handle, n)]
         for name, (res, args) in SIGNATURES.items():
             if name in missing:
                 continue
@@ -182,6 +190,7 @@ def lib():
         _has_dense = not set(missing) & set(DENSE_ENTRY_POINTS)
         _has_dense_batch = not set(missing) & set(DENSE_BATCH_ENTRY_POINTS)
         _has_horizons = not set(missing) & set(HORIZONS_ENTRY_POINTS)
+        _has_sliding = not set(missing) & set(SLIDING_ENTRY_POINTS)
     return _lib
 
 
@@ -248,6 +257,25 @@ def _horizons_lib():
         raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
                            f"{', '.join(HORIZONS_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
     return lib()
+
+
+def has_sliding():
+    """True when the loaded library exports the sliding-context entry points (SLIDING_ENTRY_POINTS)."""
+    lib()
+    return _has_sliding
+
+
+def _sliding_lib():
+    if not has_sliding():
+        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
+                           f"{', '.join(SLIDING_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
+    return lib()
+
+
+def check_context(context):
+    if context not in CONTEXTS:
+        raise ValueError(f"context must be one of {CONTEXTS} (got {context!r})")
+    return context
 
 
 class CrwError(RuntimeError):
@@ -382,14 +410,35 @@ def labelprop_topk(ehat, cxt_size, radius, temp, knn, first_frame=1, grid_w=1):
     return W, I
 
 
-def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_size=None):
+def sliding_rows(I, N, cxt_size, first_frame=1):
+    """The 'sliding' rule's translation as torch ops: I [..., F, knn, N], the indices of `labelprop_topk(_scores)` for frames
+    first_frame .. first_frame + F - 1 at `cxt_size` -> the label rows they address when applied to the frames they were scored on:
+    i where i < N or n <= cxt_size + 1, else i + (n - cxt_size - 1) * N.  Same dtype and device, a new tensor."""
+    F = I.shape[-3]
+    n = torch.arange(first_frame, first_frame + F, device=I.device, dtype=I.dtype)
+    shift = ((n - (int(cxt_size) + 1)).clamp_(min=0) * int(N)).view(F, 1, 1)
+    return torch.where(I >= N, I + shift, I)
+
+
+def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_size=None, context="reference"):
     """cxt_size: the context size the lists were made with by `labelprop_topk` (same first_frame) -> crw_labelprop_propagate
-    (chained frames in one workgroup, the frames beyond the context bound all at once); None: any lists, one workgroup."""
+    (chained frames in one workgroup, the frames beyond the context bound all at once); None: any lists, one workgroup.
+    context='sliding' (needs cxt_size): the indices address the frames they were scored on -- crw_labelprop_propagate_sliding,
+    bitwise `labelprop_gather(seed, W, sliding_rows(I, N, cxt_size, first_frame), ...)` with cxt_size None."""
     knn = W.shape[1]
+    check_context(context)
+    if context == "sliding" and cxt_size is None:
+        raise ValueError("context='sliding' needs cxt_size (the context size the lists were made with)")
     if L is None:
         L = torch.empty(T * N, M, device=W.device, dtype=torch.float32)
     if pred is None:
         pred = torch.zeros(N, T, device=W.device, dtype=torch.float32)
+    if context == "sliding":
+        _check(_sliding_lib().crw_labelprop_propagate_sliding(_dev(seed, "seed") if seed is not None else None, _dev(W, "W"),
+                                                              _dev(I, "I", torch.int32), T, N, M, knn, int(first_frame), int(cxt_size),
+                                                              _dev(L, "L"), _dev(pred, "pred"), _stream()),
+               "crw_labelprop_propagate_sliding")
+        return L, pred
     if cxt_size is not None:
         _check(lib().crw_labelprop_propagate(_dev(seed, "seed") if seed is not None else None, _dev(W, "W"),
                                              _dev(I, "I", torch.int32), T, N, M, knn, int(first_frame), int(cxt_size),
@@ -436,12 +485,13 @@ def labelprop_sweep_weights(V, knns, out=None):
     return W
 
 
-def labelprop_propagate_batch(seed, W, I, T, N, M, first_frame=1, cxt_size=None, L=None, pred=None):
-    """G configurations' `labelprop_gather(..., cxt_size=cxt_size)` in one call: W [G, T-first_frame, knn, N]; I the same shape, or
+def labelprop_propagate_batch(seed, W, I, T, N, M, first_frame=1, cxt_size=None, L=None, pred=None, context="reference"):
+    """G configurations' `labelprop_gather(..., cxt_size=cxt_size, context=context)` in one call: W [G, T-first_frame, knn, N]; I the same shape, or
     [T-first_frame, knn, N] shared by all -> (L [G, T*N, M], pred [G, N, T]), slice g bitwise what the per-configuration call
     gives on W[g] (shorter lists padded with zero weights).  seed None: L's frames before first_frame are filled by the caller."""
     if cxt_size is None:
         raise ValueError("cxt_size (the context size the lists were made with) is required")
+    check_context(context)
     G, F, knn = W.shape[0], W.shape[1], W.shape[2]
     if W.dim() != 4 or F != T - first_frame or W.shape[3] != N:
         raise RuntimeError(f"W must be [G, {T - first_frame}, knn, {N}] (got {tuple(W.shape)})")
@@ -459,6 +509,12 @@ def labelprop_propagate_batch(seed, W, I, T, N, M, first_frame=1, cxt_size=None,
         pred = torch.zeros(G, N, T, device=W.device, dtype=torch.float32)
     if tuple(L.shape) != (G, T * N, M) or tuple(pred.shape) != (G, N, T):
         raise RuntimeError(f"L must be {(G, T * N, M)} and pred {(G, N, T)} (got {tuple(L.shape)}, {tuple(pred.shape)})")
+    if context == "sliding":
+        _check(_sliding_lib().crw_labelprop_propagate_sliding_batch(_dev(seed, "seed") if seed is not None else None, _dev(W, "W"),
+                                                                    _dev(I, "I", torch.int32), stride, G, T, N, M, knn,
+                                                                    int(first_frame), int(cxt_size), _dev(L, "L"), _dev(pred, "pred"),
+                                                                    _stream()), "crw_labelprop_propagate_sliding_batch")
+        return L, pred
     _check(_sweep_lib().crw_labelprop_propagate_batch(_dev(seed, "seed") if seed is not None else None, _dev(W, "W"),
                                                       _dev(I, "I", torch.int32), stride, G, T, N, M, knn, int(first_frame),
                                                       int(cxt_size), _dev(L, "L"), _dev(pred, "pred"), _stream()),

@@ -10,7 +10,8 @@
 //   (2) crw_labelprop_gather is the only sequential part: a single workgroup walks the frames and
 //       does the weighted label sums + argmax.
 // Index quirk kept on purpose: indices address the truncated key list
-// [frame 0, last cxt frames] but are applied to the untruncated label list.
+// [frame 0, last cxt frames] but are applied to the untruncated label list.  The opt-in 'sliding' rule
+// (crw_labelprop_propagate_sliding) applies them to the frames they were scored on instead; the lists are the same.
 #include "crw_common.h"
 #include <cstdlib>
 
@@ -369,11 +370,16 @@ __device__ inline void st_l2(float *p, float v) {
 
 // single workgroup; frame n reads soft labels written for earlier frames by other waves of this
 // same workgroup: stores/loads are agent-scope (L2) and separated by vmcnt(0) + barrier.
+// SLIDE (crw_labelprop_propagate_sliding): an index of frame n addresses the list it was scored on, [frame 0, frames n - cxt .. n - 1]
+// -- slide_row() below; false: the indices are label rows as they stand (cxt unused).
+__device__ inline int slide_row(int i, int n, int N, int cxt) { return (i >= N && n > cxt + 1) ? i + (n - cxt - 1) * N : i; }
+
+template <bool SLIDE>
 __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__restrict__ seed,
                                                                 const float *__restrict__ W,
                                                                 const int32_t *__restrict__ I, int T, int N, int M,
                                                                 int knn, int first_frame, float *L,
-                                                                float *__restrict__ pred) {
+                                                                float *__restrict__ pred, int cxt) {
   const int tid = threadIdx.x, nt = blockDim.x;
   if (seed) {
     for (int it = tid; it < N * M; it += nt) {
@@ -390,7 +396,10 @@ __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__r
     for (int it = tid; it < N * M; it += nt) {
       const int q = it / M, c = it % M;
       float p = 0.f;
-      for (int j = 0; j < knn; ++j) p += ld_l2(L + (long)In[j * N + q] * M + c) * Wn[j * N + q];
+      for (int j = 0; j < knn; ++j) {
+        const int r = SLIDE ? slide_row(In[j * N + q], n, N, cxt) : In[j * N + q];
+        p += ld_l2(L + (long)r * M + c) * Wn[j * N + q];
+      }
       st_l2(L + ((long)n * N + q) * M + c, p);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -416,11 +425,12 @@ __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__r
 // same order: bit-identical results.
 constexpr int GATHER_NT = 256, GATHER_PF = 8;  // threads; prefetch registers per thread (knn * N <= 2048)
 constexpr int GATHER_CH = 20;                  // neighbours whose LDS reads are in flight together (KNN = 20: one batch per output; 4: 0.64, 10: 0.61, 20: 0.58 ms per cfg5 pass)
+template <bool SLIDE>
 __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const float *__restrict__ seed,
                                                                          const float *__restrict__ W,
                                                                          const int32_t *__restrict__ I, int T, int N, int M,
                                                                          int knn, int first_frame, float *L,
-                                                                         float *__restrict__ pred, int R) {
+                                                                         float *__restrict__ pred, int R, int cxt) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, NM = N * M, KN = knn * N;
   float *l0 = sm, *ring = l0 + NM, *wbuf = ring + (long)R * NM;  // [NM], [R][NM], [2][KN]
@@ -473,7 +483,7 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
 #pragma unroll
         for (int u = 0; u < GATHER_CH; ++u) {
           const int jj = min(j0 + u, knn - 1);
-          idx[u] = in[jj * N + q];
+          idx[u] = SLIDE ? slide_row(in[jj * N + q], n, N, cxt) : in[jj * N + q];
           w[u] = wn[jj * N + q];
         }
 #pragma unroll
@@ -678,6 +688,182 @@ __global__ __launch_bounds__(PX_NT) void labelprop_prefix_kernel(const float *__
   }
 }
 
+// ---- propagation from the frames the lists were scored on (crw_labelprop_propagate_sliding) -------------------------------------
+// The other reading of the lists: index i of frame n addresses [frame 0, frames n - cxt .. n - 1] once n > cxt + 1 (slide_row), so
+// frame n needs frame n - 1 for every n -- ONE chain over all frames, no tail.  labelprop_prefix_kernel's roles and phases (compute
+// waves with one output per lane, list loaders in rotation, one arg-max wave, lds_barrier() per frame), but the labels in LDS are
+// frame 0 plus a RING of R = cxt + 1 frames: frame f >= 1 sits at NM + ((f - 1) % R) * NM.  Until the window slides that is the prefix
+// kernel's direct address i * M + c; afterwards it is that plus ((n - cxt - 1) % R) * NM, wrapped once -- one add and one compare per
+// neighbour, both kept per frame as running offsets (no division in the loop).  R = cxt + 1, not cxt: in phase n frame n is stored
+// while other lanes still read frame n - cxt, so the slot it takes must be that of frame n - cxt - 1.
+template <int KP>
+__global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__restrict__ seed, const float *__restrict__ W,
+                                                                  const int32_t *__restrict__ I, int T, int N, int M, int knn,
+                                                                  int first_frame, int cxt, int R, float *L, float *__restrict__ pred,
+                                                                  int ncw) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int tid = threadIdx.x, lane = tid & 63, NM = N * M, KN = knn * N, last_frame = T - 1;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // roles as in labelprop_prefix_kernel: compute waves [0, ncw), D list loaders, ONE arg-max wave (the last)
+  const int nwaves = (int)blockDim.x >> 6, D = nwaves - 1 - ncw;
+  const bool compute = wave < ncw, loader = !compute && wave < nwaves - 1, amax = wave == nwaves - 1;
+  const int lk = wave - ncw, at = tid - (nwaves - 1) * 64;
+  constexpr int KNP = 64 * PX_PF;
+  const int RNM = R * NM;
+  float *lab = sm;                                                                   // [NM] frame 0, [R][NM] the ring
+  int2 *pl = reinterpret_cast<int2 *>(lab + (((long)(R + 1) * NM + 1) & ~1L));  // [2][KNP] (index, weight bits), slot = frame & 1
+
+  // frame 0 (from the seed when given) and the frames before first_frame that a frame of this call can read: the last cxt of them
+  for (int it = tid; it < NM; it += (int)blockDim.x) {
+    float v;
+    if (seed) {
+      v = seed[it / M] == (float)(it % M) ? 1.f : 0.f;
+      L[it] = v;
+    } else {
+      v = L[it];
+    }
+    lab[it] = v;
+  }
+  {
+    const int fl = max(1, first_frame - cxt);
+    for (int it = tid; it < (first_frame - fl) * NM; it += (int)blockDim.x) {
+      const int f = fl + it / NM, r = it % NM;
+      lab[NM + ((f - 1) % R) * NM + r] = L[(long)f * NM + r];
+    }
+  }
+  if (seed)
+    for (int q = tid; q < N; q += (int)blockDim.x) pred[(long)q * T] = seed[q];
+
+  float pw[PX_PF];
+  int pi[PX_PF];
+  auto svc_load = [&](int f) {  // (clamped, unconditional: a frame past the last one re-reads the last one's lists, never used)
+    const long o = (long)(min(f, last_frame) - first_frame) * KN;
+#pragma unroll
+    for (int u = 0; u < PX_PF; ++u) {
+      const int e = min(lane + u * 64, KN - 1);
+      pw[u] = W[o + e];
+      pi[u] = I[o + e];
+    }
+  };
+  auto svc_store = [&](int f) {
+#pragma unroll
+    for (int u = 0; u < PX_PF; ++u) pl[(f & 1) * KNP + lane + u * 64] = int2{pi[u], __float_as_int(pw[u])};
+  };
+  if (loader) {
+    if (lk == 0) {
+      svc_load(first_frame);
+      svc_store(first_frame);
+    }
+    if (lk == (D > 1 ? 1 : 0)) {
+      svc_load(first_frame + 1);
+      svc_store(first_frame + 1);
+    }
+    svc_load(first_frame + 2 + lk);
+  }
+  lds_barrier();
+
+  const int it = min(tid, NM - 1), q = it / M, c = it % M;
+  int a[KP];
+  float w[KP];
+  auto fetch_lists = [&](int f, int (&ix)[KP], float (&ww)[KP]) {
+    const int2 *ln = pl + (f & 1) * KNP;
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+      const int2 e = ln[min(j, knn - 1) * N + q];
+      ix[j] = e.x;
+      ww[j] = __int_as_float(e.y);
+    }
+  };
+  // frame f's indices -> LDS offsets.  shift = ((f - cxt - 1) % R) * NM once the window slides, 0 before; the clamp keeps an index
+  // inside the list it addresses (topk: < min(f, cxt + 1) * N), i.e. on rows before the frame's own and inside the ring
+  auto to_offsets = [&](int f, int shift, int (&ix)[KP], float (&ww)[KP]) {
+    const int lim = min(f, cxt + 1) * N - 1;
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+      const int i = min(max(ix[j], 0), lim);
+      int o = i * M + c;
+      if (i >= N) {
+        o += shift;
+        if (o >= NM + RNM) o -= RNM;
+      }
+      ix[j] = o;
+      if (j >= knn) ww[j] = 0.f;  // padding slot: p + v * 0 = p
+    }
+  };
+  // running offsets (wave-uniform): shift of the frame whose offsets are made next, store slot of the frame computed next
+  int shift = first_frame > cxt + 1 ? ((first_frame - cxt - 1) % R) * NM : 0;
+  int wslot = NM + ((first_frame - 1) % R) * NM;
+  auto next_shift = [&](int f) {  // shift of frame f -> shift of frame f + 1
+    if (f + 1 > cxt + 1) {
+      shift += NM;
+      if (shift == RNM) shift = 0;
+    }
+  };
+  if (compute) {
+    fetch_lists(first_frame, a, w);
+    to_offsets(first_frame, shift, a, w);
+  }
+  next_shift(first_frame);
+  lds_barrier();  // the read of slot first_frame & 1 above comes before loader 0's svc_store(first_frame + 2) into the same slot
+
+  int turn = 0;       // (f - first_frame) % D
+  int pslot = wslot;  // slot of frame f - 1 (the arg-max wave's)
+  for (int f = first_frame; f <= last_frame; ++f) {
+    if (compute) {
+      float v[KP];
+#pragma unroll
+      for (int j = 0; j < KP; ++j) v[j] = lab[a[j]];
+      int na[KP];
+      float nw[KP];
+      fetch_lists(f + 1, na, nw);  // slot (f + 1) & 1: written before the previous barrier (past last_frame: unused)
+      float p = 0.f;
+#pragma unroll
+      for (int j = 0; j < KP; ++j) p += v[j] * w[j];
+      lab[wslot + it] = p;  // the slot of frame f - R: out of every window since frame f - 1
+      L[(long)f * NM + it] = p;
+      to_offsets(f + 1, shift, na, nw);
+#pragma unroll
+      for (int j = 0; j < KP; ++j) {
+        a[j] = na[j];
+        w[j] = nw[j];
+      }
+    } else if (loader) {
+      if (turn == lk) {
+        svc_store(f + 2);  // slot f & 1: last read (frame f's lists) before the previous barrier
+        svc_load(f + 2 + D);
+      }
+    } else if (f > first_frame) {  // arg-max of the previous frame (first maximum wins); its slot is next written R - 1 phases on
+      for (int qq = at; qq < N; qq += 64) {
+        const float *row = lab + pslot + qq * M;
+        float bv = row[0];
+        int bi = 0;
+        for (int cc = 1; cc < M; ++cc) {
+          const float x = row[cc];
+          if (x > bv) { bv = x; bi = cc; }
+        }
+        pred[(long)qq * T + f - 1] = (float)bi;
+      }
+    }
+    turn = turn + 1 == D ? 0 : turn + 1;
+    next_shift(f + 1);
+    pslot = wslot;
+    wslot = wslot + NM == NM + RNM ? NM : wslot + NM;
+    lds_barrier();
+  }
+  if (amax) {
+    for (int qq = at; qq < N; qq += 64) {
+      const float *row = lab + pslot + qq * M;
+      float bv = row[0];
+      int bi = 0;
+      for (int cc = 1; cc < M; ++cc) {
+        const float x = row[cc];
+        if (x > bv) { bv = x; bi = cc; }
+      }
+      pred[(long)qq * T + last_frame] = (float)bi;
+    }
+  }
+}
+
 // frames t0 .. T-1, none of which reads a label this launch writes: a workgroup per frame, neighbours' labels from L (global memory)
 constexpr int TAIL_NT = 256, TAIL_CH = 16;
 __global__ __launch_bounds__(TAIL_NT) void labelprop_tail_kernel(const float *__restrict__ W, const int32_t *__restrict__ I, int T, int N,
@@ -765,10 +951,11 @@ __global__ __launch_bounds__(256) void labelprop_sweep_weights_kernel(const floa
 // time (they do not depend on the chain); the sum runs in neighbour order from 0.f like every other propagation kernel here, and
 // padding slots (weight exactly 0, a valid index) leave it as it is: p + v * 0.f == p for the finite labels.
 constexpr int PB_CH = 16;
+template <bool SLIDE>  // slide_row() on every index before the clamp (crw_labelprop_propagate_sliding_batch)
 __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float *__restrict__ seed, const float *__restrict__ W,
                                                                      const int32_t *__restrict__ I, long i_stride, int T, int N, int M,
                                                                      int knn, int first_frame, int last_frame, float *L,
-                                                                     float *__restrict__ pred, int R) {
+                                                                     float *__restrict__ pred, int R, int cxt) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, nt = (int)blockDim.x, NM = N * M, KN = knn * N, g = blockIdx.x;
   W += (long)g * (T - first_frame) * KN;
@@ -808,7 +995,8 @@ __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float
 #pragma unroll
         for (int u = 0; u < PB_CH; ++u) {
           const int jj = min(j0 + u, knn - 1);
-          idx[u] = min(max(In[jj * N + q], 0), row_lim);  // in range whatever the lists hold (topk: < min(n, cxt + 1) * N)
+          const int raw_i = SLIDE ? slide_row(In[jj * N + q], n, N, cxt) : In[jj * N + q];
+          idx[u] = min(max(raw_i, 0), row_lim);  // in range whatever the lists hold (topk: < min(n, cxt + 1) * N)
           w[u] = Wn[jj * N + q];
         }
 #pragma unroll
@@ -988,6 +1176,83 @@ int topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, 
   return check_launch();
 }
 
+// the one-workgroup walk over any lists (crw_labelprop_gather; SLIDE: the general route of crw_labelprop_propagate_sliding, the
+// indices translated in the kernel)
+template <bool SLIDE>
+int launch_gather(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int cxt, float *L,
+                  float *pred, crw_stream_t stream) {
+  crw::clear_stale_error();
+  if (!W || !I || !L || !pred || T < 2 || N < 1 || M < 1 || knn < 1 || first_frame < 1 || first_frame >= T ||
+      (!seed && first_frame < 1))
+    return CRW_EINVAL;
+  // LDS-resident form when the lists of a frame fit the prefetch registers and at least a few frames fit the ring
+  const long NM = (long)N * M, KN = (long)knn * N;
+  const long budget = 150 * 1024 - 16 * KN;  // bytes left for frame 0 + the ring after the two (weight, index) list copies
+  long R = budget > 0 ? budget / (4 * NM) - 1 : 0;
+  if (R > T) R = T;
+  static const char *force_global = getenv("CRW_LABELPROP_GATHER_GLOBAL");  // diagnostics: the L2-round-trip kernel
+  if (KN <= (long)GATHER_NT * GATHER_PF && R >= 4 && (long)T * N < (1L << 30) / M && !force_global) {
+    const size_t lds = (size_t)(4 * (NM * (R + 1) + 4 * KN));
+    static bool attr = false;
+    if (!attr) {
+      if (hipFuncSetAttribute((const void *)labelprop_gather_lds_kernel<SLIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
+          hipSuccess) {
+        g_last_hip_error = (int)hipGetLastError();
+        return CRW_EHIP;
+      }
+      attr = true;
+    }
+    hipLaunchKernelGGL(labelprop_gather_lds_kernel<SLIDE>, dim3(1), dim3(GATHER_NT), lds, (hipStream_t)stream, seed, W, I, T, N, M,
+                       knn, first_frame, L, pred, (int)R, cxt);
+    return check_launch();
+  }
+  hipLaunchKernelGGL(labelprop_gather_kernel<SLIDE>, dim3(1), dim3(1024), 0, (hipStream_t)stream, seed, W, I, T, N, M, knn,
+                     first_frame, L, pred, cxt);
+  return check_launch();
+}
+
+// SLIDE: every frame is chained (last = T - 1, no tail launch), the indices translated in the kernel
+template <bool SLIDE>
+int launch_propagate_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M, int knn,
+                           int first_frame, int cxt_size, float *L, float *pred, crw_stream_t stream) {
+  crw::clear_stale_error();
+  if (!W || !I || !L || !pred || G < 1 || G > 65535 || T < 2 || N < 1 || M < 1 || knn < 1 || knn > MAX_KNN || first_frame < 1 ||
+      first_frame >= T || cxt_size < 1)
+    return CRW_EINVAL;
+  const long NM = (long)N * M;
+  if ((long)T * N >= (1L << 30) / M || NM * 4 > 30 * 1024) return CRW_EINVAL;  // 32-bit label offsets; frame 0 + a ring of >= 4 frames in LDS
+  // the split of crw_labelprop_propagate: frames from t0 on read no label of this call
+  const int t0 = SLIDE ? T
+                       : (T - first_frame == 1) ? first_frame : (first_frame > cxt_size + 1 ? first_frame : (cxt_size + 1 < T ? cxt_size + 1 : T));
+  const int last = t0 - 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (last >= first_frame || seed) {  // (no chained frame: the kernel writes frame 0 from the seed and returns)
+    long R = (150L * 1024) / (4 * NM) - 1;
+    if (R > last + 1) R = last + 1;
+    if (R < 2) R = 2;
+    static bool attr = false;
+    if (!attr) {
+      if (hipFuncSetAttribute((const void *)labelprop_chain_batch_kernel<SLIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
+          hipSuccess) {
+        g_last_hip_error = (int)hipGetLastError();
+        return CRW_EHIP;
+      }
+      attr = true;
+    }
+    const int nt = (int)(NM >= 1024 ? 1024 : (NM + 63) / 64 * 64);
+    hipLaunchKernelGGL(labelprop_chain_batch_kernel<SLIDE>, dim3(G), dim3(nt), (size_t)(4 * NM * (R + 1)), s, seed, W, I, (long)i_stride, T, N, M,
+                       knn, first_frame, last, L, pred, (int)R, cxt_size);
+    const int rc = check_launch();
+    if (rc != CRW_OK) return rc;
+  }
+  if (t0 < T) {
+    hipLaunchKernelGGL(labelprop_tail_batch_kernel, dim3(T - t0, G), dim3(TAIL_NT), (size_t)NM * 4, s, W, I, (long)i_stride, T, N, M, knn,
+                       first_frame, t0, L, pred);
+    return check_launch();
+  }
+  return CRW_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1009,34 +1274,7 @@ int crw_labelprop_topk(const float *ehat, int T, int N, int C, int cxt_size, int
 
 int crw_labelprop_gather(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn,
                          int first_frame, float *L, float *pred, crw_stream_t stream) {
-  crw::clear_stale_error();
-  if (!W || !I || !L || !pred || T < 2 || N < 1 || M < 1 || knn < 1 || first_frame < 1 || first_frame >= T ||
-      (!seed && first_frame < 1))
-    return CRW_EINVAL;
-  // LDS-resident form when the lists of a frame fit the prefetch registers and at least a few frames fit the ring
-  const long NM = (long)N * M, KN = (long)knn * N;
-  const long budget = 150 * 1024 - 16 * KN;  // bytes left for frame 0 + the ring after the two (weight, index) list copies
-  long R = budget > 0 ? budget / (4 * NM) - 1 : 0;
-  if (R > T) R = T;
-  static const char *force_global = getenv("CRW_LABELPROP_GATHER_GLOBAL");  // diagnostics: the L2-round-trip kernel
-  if (KN <= (long)GATHER_NT * GATHER_PF && R >= 4 && (long)T * N < (1L << 30) / M && !force_global) {
-    const size_t lds = (size_t)(4 * (NM * (R + 1) + 4 * KN));
-    static bool attr = false;
-    if (!attr) {
-      if (hipFuncSetAttribute((const void *)labelprop_gather_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
-          hipSuccess) {
-        g_last_hip_error = (int)hipGetLastError();
-        return CRW_EHIP;
-      }
-      attr = true;
-    }
-    hipLaunchKernelGGL(labelprop_gather_lds_kernel, dim3(1), dim3(GATHER_NT), lds, (hipStream_t)stream, seed, W, I, T, N, M,
-                       knn, first_frame, L, pred, (int)R);
-    return check_launch();
-  }
-  hipLaunchKernelGGL(labelprop_gather_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, seed, W, I, T, N, M, knn,
-                     first_frame, L, pred);
-  return check_launch();
+  return launch_gather<false>(seed, W, I, T, N, M, knn, first_frame, 0, L, pred, stream);
 }
 
 int crw_labelprop_propagate(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame,
@@ -1085,6 +1323,40 @@ int crw_labelprop_propagate(const float *seed, const float *W, const int32_t *I,
   return CRW_OK;
 }
 
+int crw_labelprop_propagate_sliding(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame,
+                                    int cxt_size, float *L, float *pred, crw_stream_t stream) {
+  crw::clear_stale_error();
+  if (!W || !I || !L || !pred || T < 2 || N < 1 || M < 1 || knn < 1 || first_frame < 1 || first_frame >= T || cxt_size < 1)
+    return CRW_EINVAL;
+  const long NM = (long)N * M, KN = (long)knn * N;
+  // the ring kernel: frame 0 + min(cxt + 1, T - 1) ring slots + the two list slots within the 150 KiB; at most 6 compute waves (one
+  // list loader and the arg-max wave beside them); a frame's lists in the loader's registers.
+  // CRW_LABELPROP_SLIDING_GENERAL=1 (read per call): the general kernels instead (A/B, tools/sliding_timing.py)
+  const char *gen = getenv("CRW_LABELPROP_SLIDING_GENERAL");
+  const long R = cxt_size + 1 < T - 1 ? cxt_size + 1 : T - 1;
+  const size_t lds = (size_t)((((R + 1) * NM + 1) & ~1L) * 4 + 16L * 64 * PX_PF);
+  const bool ring = !(gen && gen[0] == '1') && knn <= 24 /* 32 neighbours in registers spill */ && NM <= 384 && KN <= 64 * PX_PF &&
+                    lds <= 150 * 1024 && (long)T * N < (1L << 30) / M;
+  if (!ring) return launch_gather<true>(seed, W, I, T, N, M, knn, first_frame, cxt_size, L, pred, stream);
+  const int ncw = (int)((NM + 63) / 64), nld = PX_NT / 64 - 1 - ncw < 4 ? PX_NT / 64 - 1 - ncw : 4;
+  static bool attr[3] = {false, false, false};  // dynamic-LDS limit raised, per instantiation
+  auto launch = [&](auto kern, int which) -> int {
+    if (!attr[which]) {
+      if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
+        g_last_hip_error = (int)hipGetLastError();
+        return CRW_EHIP;
+      }
+      attr[which] = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(1), dim3((ncw + nld + 1) * 64), lds, (hipStream_t)stream, seed, W, I, T, N, M, knn, first_frame, cxt_size,
+                       (int)R, L, pred, ncw);
+    return check_launch();
+  };
+  if (knn <= 8) return launch(labelprop_slide_kernel<8>, 0);
+  if (knn <= 16) return launch(labelprop_slide_kernel<16>, 1);
+  return launch(labelprop_slide_kernel<24>, 2);
+}
+
 int crw_labelprop_sweep_weights(const float *V, int F, int kcap, int N, const int *knns, int nk, float *W, crw_stream_t stream) {
   crw::clear_stale_error();
   if (!V || !W || !knns || F < 1 || N < 1 || kcap < 1 || kcap > MAX_KNN || nk < 1 || nk > SW_MAXK) return CRW_EINVAL;
@@ -1105,41 +1377,12 @@ int crw_labelprop_sweep_weights(const float *V, int F, int kcap, int N, const in
 
 int crw_labelprop_propagate_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M,
                                   int knn, int first_frame, int cxt_size, float *L, float *pred, crw_stream_t stream) {
-  crw::clear_stale_error();
-  if (!W || !I || !L || !pred || G < 1 || G > 65535 || T < 2 || N < 1 || M < 1 || knn < 1 || knn > MAX_KNN || first_frame < 1 ||
-      first_frame >= T || cxt_size < 1)
-    return CRW_EINVAL;
-  const long NM = (long)N * M;
-  if ((long)T * N >= (1L << 30) / M || NM * 4 > 30 * 1024) return CRW_EINVAL;  // 32-bit label offsets; frame 0 + a ring of >= 4 frames in LDS
-  // the split of crw_labelprop_propagate: frames from t0 on read no label of this call
-  const int t0 = (T - first_frame == 1) ? first_frame : (first_frame > cxt_size + 1 ? first_frame : (cxt_size + 1 < T ? cxt_size + 1 : T));
-  const int last = t0 - 1;
-  hipStream_t s = (hipStream_t)stream;
-  if (last >= first_frame || seed) {  // (no chained frame: the kernel writes frame 0 from the seed and returns)
-    long R = (150L * 1024) / (4 * NM) - 1;
-    if (R > last + 1) R = last + 1;
-    if (R < 2) R = 2;
-    static bool attr = false;
-    if (!attr) {
-      if (hipFuncSetAttribute((const void *)labelprop_chain_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
-          hipSuccess) {
-        g_last_hip_error = (int)hipGetLastError();
-        return CRW_EHIP;
-      }
-      attr = true;
-    }
-    const int nt = (int)(NM >= 1024 ? 1024 : (NM + 63) / 64 * 64);
-    hipLaunchKernelGGL(labelprop_chain_batch_kernel, dim3(G), dim3(nt), (size_t)(4 * NM * (R + 1)), s, seed, W, I, (long)i_stride, T, N, M,
-                       knn, first_frame, last, L, pred, (int)R);
-    const int rc = check_launch();
-    if (rc != CRW_OK) return rc;
-  }
-  if (t0 < T) {
-    hipLaunchKernelGGL(labelprop_tail_batch_kernel, dim3(T - t0, G), dim3(TAIL_NT), (size_t)NM * 4, s, W, I, (long)i_stride, T, N, M, knn,
-                       first_frame, t0, L, pred);
-    return check_launch();
-  }
-  return CRW_OK;
+  return launch_propagate_batch<false>(seed, W, I, i_stride, G, T, N, M, knn, first_frame, cxt_size, L, pred, stream);
+}
+
+int crw_labelprop_propagate_sliding_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M,
+                                          int knn, int first_frame, int cxt_size, float *L, float *pred, crw_stream_t stream) {
+  return launch_propagate_batch<true>(seed, W, I, i_stride, G, T, N, M, knn, first_frame, cxt_size, L, pred, stream);
 }
 
 int crw_xent_metric(const float *ehat, int T, int N, int C, float *xent, crw_stream_t stream) {

@@ -8,6 +8,10 @@ Two entry points:
     ``utils.propagate`` uses): affinities/top-k of every frame at once, then one sequential
     gather kernel.  Both produce identical label maps.
 
+Optional ``cfg['CONTEXT']``: ``'reference'`` (the default: the reference's rule, its index quirk included) or ``'sliding'`` -- once a
+frame lies more than CXT_SIZE + 1 frames into the item, its neighbours' labels are taken from the frames the scores were taken on
+(frame 0 and the last CXT_SIZE frames), as upstream videowalk does (``crw_labelprop_propagate_sliding``).
+
 ``LabelPropSweep`` is ``propagate_all`` for a whole grid of (RADIUS, TEMP, KNN) settings on the same features -- the grid of the
 reference's scripts/launch/launch_test_batch.sh -- sharing what does not depend on the setting.
 """
@@ -26,6 +30,11 @@ class LabelPropVOS_CRW(object):
         self.radius = cfg['RADIUS']
         self.temperature = cfg['TEMP']
         self.topk = cfg['KNN']
+        # optional: which frames an index of a late frame (n > CXT_SIZE + 1) addresses -- 'reference': the untruncated label list,
+        # as the reference does (quirk Q7); 'sliding': the frames the scores were taken on (upstream videowalk's rule)
+        self.context = cfg.get('CONTEXT', 'reference')
+        if self.context not in crw_hip.CONTEXTS:
+            raise ValueError(f"cfg['CONTEXT'] must be one of {crw_hip.CONTEXTS} (got {self.context!r})")
         self.mask = None
         self.mask_hw = None
 
@@ -59,7 +68,9 @@ class LabelPropVOS_CRW(object):
         """feats: list of n [1,C,h,w] context features; masks: list of n [1,M,h,w] soft labels;
         curr_feat [1,C,h,w]  ->  soft labels of the current frame [1,M,h,w].  A radargram's frames are columns of patches
         (w = 1, what `utils.propagate` passes); any h x w grid is taken like the reference's (nodes in row-major order, the band
-        the Euclidean disc of `MaskedAttention`, src/imported/maskedatt.py:222-245)."""
+        the Euclidean disc of `MaskedAttention`, src/imported/maskedatt.py:222-245).
+        CONTEXT 'sliding': handed more than CXT_SIZE + 1 frames, the result is what the reference's `predict` returns on the
+        windowed lists `[feats[0]] + feats[-CXT_SIZE:]` (masks likewise)."""
         h, w = curr_feat.shape[-2:]
         self._check_grid(h, w)
         self._band(h, w, curr_feat.device)
@@ -69,7 +80,7 @@ class LabelPropVOS_CRW(object):
         L = torch.empty((n + 1) * N, M, device=E.device, dtype=torch.float32)
         L[:n * N] = torch.cat(list(masks), 0).flatten(2).permute(0, 2, 1).reshape(n * N, M)
         Wt, It = crw_hip.labelprop_topk(E, self.cxt_size, self.radius, self.temperature, self.topk, first_frame=n, grid_w=w)
-        crw_hip.labelprop_gather(None, Wt, It, n + 1, N, M, first_frame=n, L=L, cxt_size=self.cxt_size)
+        crw_hip.labelprop_gather(None, Wt, It, n + 1, N, M, first_frame=n, L=L, cxt_size=self.cxt_size, context=self.context)
         return L[n * N:].reshape(N, M).t().reshape(1, M, h, w)
 
     def propagate_all(self, feats, seed, nclasses, grid_w=1):
@@ -79,7 +90,8 @@ class LabelPropVOS_CRW(object):
         self._check_grid(N // grid_w, grid_w)
         self._band(N // grid_w, grid_w, feats.device)
         Wt, It = crw_hip.labelprop_topk(feats, self.cxt_size, self.radius, self.temperature, self.topk, first_frame=1, grid_w=grid_w)
-        L, pred = crw_hip.labelprop_gather(seed.float().contiguous(), Wt, It, T, N, nclasses, first_frame=1, cxt_size=self.cxt_size)
+        L, pred = crw_hip.labelprop_gather(seed.float().contiguous(), Wt, It, T, N, nclasses, first_frame=1, cxt_size=self.cxt_size,
+                                           context=self.context)
         return pred, L
 
 
@@ -89,8 +101,9 @@ class LabelPropSweep(object):
     (radius outermost, knn innermost); ``propagate_all`` returns the label map of every configuration, each exactly that of
     ``LabelPropVOS_CRW(configs[g]).propagate_all``."""
 
-    def __init__(self, cxt_size, radii, temps, knns):
+    def __init__(self, cxt_size, radii, temps, knns, context='reference'):
         self.cxt_size = int(cxt_size)
+        self.context = crw_hip.check_context(context)
         self.radii, self.temps, self.knns = [int(r) for r in radii], [float(t) for t in temps], [int(k) for k in knns]
         if not (self.radii and self.temps and self.knns):
             raise ValueError("radii, temps and knns must each hold at least one value")
@@ -98,6 +111,9 @@ class LabelPropSweep(object):
             raise ValueError("knns: 1 ... 16 values >= 1")
         self.configs = [dict(CXT_SIZE=self.cxt_size, RADIUS=r, TEMP=t, KNN=k)
                         for r in self.radii for t in self.temps for k in self.knns]
+        if self.context != 'reference':  # (the key is absent under the default rule: the dicts are what they were)
+            for cfg in self.configs:
+                cfg['CONTEXT'] = self.context
 
     def __len__(self):
         return len(self.configs)
@@ -142,5 +158,5 @@ class LabelPropSweep(object):
         else:
             Ig = I[:, None].expand(P, nk, F, kmax, N).reshape(P * nk, F, kmax, N)  # (a copy: the batch takes one stride)
         L, pred = crw_hip.labelprop_propagate_batch(seed, W.view(P * nk, F, kmax, N), Ig, T, N, nclasses, first_frame=1,
-                                                    cxt_size=self.cxt_size)
+                                                    cxt_size=self.cxt_size, context=self.context)
         return (pred, L) if soft else pred

@@ -665,13 +665,15 @@ def _items(rg, patch_size, overlap):
 
 @torch.no_grad()
 def segment_radargrams(driver, radargrams, refs, encoder, refs_reversed=None, patch_size=None, seq_length=None, overlap=None,
-                       cxt_size=None, radius=None, temp=None, knn=None, use_last=None, correction=None, change_idx=None, lp=None):
+                       cxt_size=None, radius=None, temp=None, knn=None, use_last=None, correction=None, change_idx=None, lp=None,
+                       context=None):
     """``main(args)`` of the reference's scripts/test/test_{mc1,mc3,sharad}.py (``driver``) without the plots.
 
     radargrams, refs: three [rows, cols] radargrams and their reference segmentations, as the script holds them after loading
     (``scripts/segment_drivers.py`` reads its files, casts and edits); refs_reversed: mc1's separate references of the reversed
     radargrams.  Every other argument defaults to ``DRIVERS[driver]``; ``lp``: a label-propagation object (default
-    ``LabelPropVOS_CRW`` on the driver's CXT_SIZE / RADIUS / TEMP / KNN).
+    ``LabelPropVOS_CRW`` on the driver's CXT_SIZE / RADIUS / TEMP / KNN); ``context``: that object's CONTEXT ('reference', the
+    default and what the scripts compute, or 'sliding': labels from the frames the scores were taken on).
     -> {output file name: object}, what the script passes to ``torch.save``, in the state it has at that call.
 
     Operation for operation, which includes:
@@ -712,7 +714,7 @@ def segment_radargrams(driver, radargrams, refs, encoder, refs_reversed=None, pa
         raise ValueError(f'{driver}: three hand-set change points are needed (change_idx)')
     if lp is None:
         lp = LabelPropVOS_CRW(dict(CXT_SIZE=pick(cxt_size, 'cxt_size'), RADIUS=pick(radius, 'radius'), TEMP=pick(temp, 'temp'),
-                                   KNN=pick(knn, 'knn')))
+                                   KNN=pick(knn, 'knn'), CONTEXT='reference' if context is None else context))
     OW = overlap[-1]
     rg = [_items(r, patch_size, overlap) for r in radargrams]
     T, N, H, W = rg[0].shape

@@ -70,6 +70,8 @@ def get_args_parser():
     p.add_argument('-r', '--radius', default=None, type=int)
     p.add_argument('-t', '--temp', default=None, type=float)
     p.add_argument('-k', '--knn', default=None, type=int)
+    p.add_argument('--context', default='reference', choices=('reference', 'sliding'),
+                   help="frames a late frame's neighbour indices address: the reference's rule, or the frames they were scored on")
     p.add_argument('--model_path', default=None, help='encoder state_dict (required unless --synthetic)')
     p.add_argument('--output_folder', default='resources/output/')
     p.add_argument('--pos_embed', default=False, type=_flag)
@@ -189,6 +191,8 @@ def main(args):
         hidden += ('upsample',)
     if not args.horizons:  # likewise
         hidden += HORIZON_FLAGS
+    if args.context == 'reference':  # likewise
+        hidden += ('context',)
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -196,7 +200,7 @@ def main(args):
     else:
         encoder = create_model(args.model, args.pos_embed).to(device)
     dataset, nclasses, seg, unc_seg = load_data(args)
-    lp = LabelPropVOS_CRW(dict(CXT_SIZE=args.cxt_size, RADIUS=args.radius, TEMP=args.temp, KNN=args.knn))
+    lp = LabelPropVOS_CRW(dict(CXT_SIZE=args.cxt_size, RADIUS=args.radius, TEMP=args.temp, KNN=args.knn, CONTEXT=args.context))
     T, W, ow = args.seq_length, args.patch_size[1], args.overlap[1]
     rg_len = T * (W - ow) + ow
     if args.single:
@@ -263,6 +267,8 @@ def main(args):
                  dataset=args.dataset, remove_unc=args.remove_unc, single=args.single)
         if args.upsample != 'nearest':
             d['upsample'] = args.upsample
+        if args.context != 'reference':
+            d['context'] = args.context
         if cal is not None:
             d['calibration'] = dict(cal.to_dict(), kind=args.confidence, merge=args.merge)
         if hz is not None:

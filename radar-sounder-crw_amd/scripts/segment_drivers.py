@@ -46,6 +46,8 @@ def get_args_parser():
     p.add_argument('-r', '--radius', default=None, type=int)
     p.add_argument('-t', '--temp', default=None, type=float)
     p.add_argument('-k', '--knn', default=None, type=int)
+    p.add_argument('--context', default='reference', choices=('reference', 'sliding'),
+                   help="frames a late frame's neighbour indices address: the reference's rule, or the frames they were scored on")
     p.add_argument('--use_last', default=None, type=_flag, help='reverse pass (mc1 / mc3; sharad never reads it)')
     p.add_argument('--correction', default=None, type=_flag, help='correction step (mc3; sharad always corrects, mc1 never)')
     p.add_argument('--change_idx', default=None, nargs=3, type=_change, help='hand-set change points of the three radargrams')
@@ -108,7 +110,7 @@ def main(args):
     out = segment_radargrams(args.driver, rg, sg, encoder, refs_reversed=sgr, patch_size=args.patch_size,
                              seq_length=args.seq_length, overlap=args.overlap, cxt_size=args.cxt_size, radius=args.radius,
                              temp=args.temp, knn=args.knn, use_last=args.use_last, correction=args.correction,
-                             change_idx=args.change_idx)
+                             change_idx=args.change_idx, context=args.context)
     os.makedirs(args.output_folder, exist_ok=True)
     for name, obj in out.items():
         torch.save(obj, os.path.join(args.output_folder, name))

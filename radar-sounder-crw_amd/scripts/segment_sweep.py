@@ -61,6 +61,8 @@ def get_args_parser(horizons=False):
     p.add_argument('-r', '--radius', default=list(GRID['radius']), nargs='+', type=int)
     p.add_argument('-t', '--temp', default=list(GRID['temp']), nargs='+', type=float)
     p.add_argument('-k', '--knn', default=list(GRID['knn']), nargs='+', type=int)
+    p.add_argument('--context', default='reference', choices=('reference', 'sliding'),
+                   help="frames a late frame's neighbour indices address: the reference's rule, or the frames they were scored on")
     p.add_argument('--model_path', default=None, help='encoder state_dict (required unless --synthetic)')
     p.add_argument('--output_folder', default='resources/output/')
     p.add_argument('--pos_embed', default=False, type=_flag)
@@ -143,6 +145,8 @@ def main(args):
         hidden += ('upsample',)
     if not args.horizons:
         hidden += ('horizons', 'min_run', 'tol')
+    if args.context == 'reference':  # likewise
+        hidden += ('context',)
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -150,7 +154,7 @@ def main(args):
     else:
         encoder = create_model(args.model, args.pos_embed).to(device)
     dataset, nclasses, seg, unc_seg = segment_all.load_data(args)
-    sweep = LabelPropSweep(args.cxt_size, args.radius, args.temp, args.knn)
+    sweep = LabelPropSweep(args.cxt_size, args.radius, args.temp, args.knn, context=args.context)
     T, W, ow = args.seq_length, args.patch_size[1], args.overlap[1]
     rg_len = T * (W - ow) + ow
     print('Num of radargrams:', seg.shape[-1] // rg_len, 'Radargram length:', rg_len, 'Configurations:', len(sweep.configs))
@@ -236,6 +240,8 @@ def main(args):
                 c['horizons'] = h.to_dict()
         if args.upsample != 'nearest':
             d['upsample'] = args.upsample
+        if args.context != 'reference':
+            d['context'] = args.context
         with open(args.report_json, 'w') as f:
             json.dump(d, f, indent=1)
     return reports, best
