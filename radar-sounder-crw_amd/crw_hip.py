@@ -944,16 +944,68 @@ def dense_knots(n_in, n_out, flip=False):
     return i0, i1, w
 
 
-def _window(t, name, rows, cols, dtype, device):
-    """A [rows, cols] output of `labelmap_dense`: contiguous, or a column window of a wider row-major map -> its pitch."""
-    if tuple(t.shape) != (rows, cols) or t.dtype != dtype or t.device != device:
-        raise ValueError(f"{name} must be {dtype} [{rows}, {cols}] on {device} (got {t.dtype} {tuple(t.shape)} on {t.device})")
-    if cols > 1 and t.stride(1) != 1:
-        raise ValueError(f"{name} must be contiguous along its columns (stride {t.stride()}): a map, or a column window map[:, a:b]")
-    ld = t.stride(0) if rows > 1 else cols
+def _window(t, name, lead, rows, cols, dtype, device):
+    """A [*lead, rows, cols] output of `labelmap_dense` (lead (): a map) or `labelmap_dense_batch` (lead (G,)): contiguous, or a
+    column window map[..., a:b] of a wider row-major tensor -> (pitch between rows, elements between maps)."""
+    shape = (*lead, rows, cols)
+    if tuple(t.shape) != shape or t.dtype != dtype or t.device != device:
+        raise ValueError(f"{name} must be {dtype} {list(shape)} on {device} (got {t.dtype} {tuple(t.shape)} on {t.device})")
+    if cols > 1 and t.stride(-1) != 1:
+        raise ValueError(f"{name} must be contiguous along its columns (stride {t.stride()}): a map, or a column window map[..., a:b]")
+    ld = t.stride(-2) if rows > 1 else cols
     if ld < cols:
         raise ValueError(f"{name}: rows overlap (stride {t.stride()})")
-    return ld
+    span = (rows - 1) * ld + cols
+    map_stride = t.stride(0) if lead and lead[0] > 1 else span
+    if map_stride < span:
+        raise ValueError(f"{name}: maps overlap (stride {t.stride()})")
+    return ld, map_stride
+
+
+def _labelmap_dense(L, G, T, N, M, rows, cols, confidence, flip, dtype, out, out_conf):
+    """`labelmap_dense` (G None: one map, no leading axis) and `labelmap_dense_batch` behind their signatures."""
+    code = -1 if confidence is None else _conf_kind(confidence)
+    T, N, M, rows, cols = int(T), int(N), int(M), int(rows), int(cols)
+    lead = () if G is None else (int(G),)
+    if lead and not 1 <= lead[0] <= 65535:
+        raise ValueError(f"G must be in 1 ... 65535 (got {lead[0]})")
+    if not 2 <= M <= 16:
+        raise ValueError(f"M must be in 2 ... 16 (got {M})")
+    if T < 1 or N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
+        raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={T}, N={N}, rows={rows}, cols={cols})")
+    if L.numel() != (lead[0] if lead else 1) * T * N * M or L.dtype != torch.float32:
+        raise ValueError(f"L must be float32 {[*lead, T * N, M]} (got {L.dtype} {tuple(L.shape)})")
+    if dtype not in (torch.float32, torch.int8):
+        raise ValueError(f"dtype must be torch.float32 or torch.int8 (got {dtype})")
+    if out_conf is not None and confidence is None:
+        raise ValueError("out_conf needs a confidence kind")
+    if out is None:
+        out = torch.empty(*lead, rows, cols, dtype=dtype, device=L.device)
+    if out_conf is None and confidence is not None:
+        out_conf = torch.empty(*lead, rows, cols, dtype=torch.float32, device=L.device)
+    ld, map_stride = _window(out, "out", lead, rows, cols, dtype, L.device)
+    if out_conf is not None:
+        cld, cstride = _window(out_conf, "out_conf", lead, rows, cols, torch.float32, L.device)
+        if cld != ld and rows > 1:
+            raise ValueError(f"out and out_conf must share one pitch (got {out.stride(-2)} and {out_conf.stride(-2)})")
+        if cstride != map_stride:  # (equal by construction for one map)
+            raise ValueError(f"out and out_conf must share one map stride (got {out.stride(0)} and {out_conf.stride(0)})")
+    L = L.contiguous()
+    if not L.is_cuda:
+        maps, confs = (out, out_conf) if lead else (out[None], None if out_conf is None else out_conf[None])
+        for g, Lg in enumerate(L.view(-1, T * N, M)):
+            lab, conf = _labelmap_dense_cpu(Lg, T, N, M, rows, cols, confidence, flip)
+            maps[g].copy_(lab.to(dtype))
+            if confs is not None:
+                confs[g].copy_(conf)
+        return out, out_conf
+    args = (T, N, M, rows, cols, int(bool(flip)), code, _ptr(out), DT_F32 if dtype == torch.float32 else DT_I8,
+            _ptr(out_conf) if out_conf is not None else None, ld)
+    if lead:
+        _check(_dense_batch_lib().crw_labelmap_dense_batch(_ptr(L), lead[0], *args, map_stride, _stream()), "crw_labelmap_dense_batch")
+    else:
+        _check(_dense_lib().crw_labelmap_dense(_ptr(L), *args, _stream()), "crw_labelmap_dense")
+    return out, out_conf
 
 
 def labelmap_dense(L, T, N, M, rows, cols, *, confidence=None, flip=False, dtype=torch.float32, out=None, out_conf=None):
@@ -966,53 +1018,7 @@ def labelmap_dense(L, T, N, M, rows, cols, *, confidence=None, flip=False, dtype
     else that is not contiguous raises ValueError.  Device tensors: one launch of crw_labelmap_dense, nothing synchronises, the
     interpolated probabilities are never written; CPU tensors: the same integer knots, fp32 weights, arithmetic and tie rule in
     torch."""
-    code = -1 if confidence is None else _conf_kind(confidence)
-    T, N, M, rows, cols = int(T), int(N), int(M), int(rows), int(cols)
-    if not 2 <= M <= 16:
-        raise ValueError(f"M must be in 2 ... 16 (got {M})")
-    if T < 1 or N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
-        raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={T}, N={N}, rows={rows}, cols={cols})")
-    if L.numel() != T * N * M or L.dtype != torch.float32:
-        raise ValueError(f"L must be float32 [{T * N}, {M}] (got {L.dtype} {tuple(L.shape)})")
-    if dtype not in (torch.float32, torch.int8):
-        raise ValueError(f"dtype must be torch.float32 or torch.int8 (got {dtype})")
-    if out_conf is not None and confidence is None:
-        raise ValueError("out_conf needs a confidence kind")
-    if out is None:
-        out = torch.empty(rows, cols, dtype=dtype, device=L.device)
-    if out_conf is None and confidence is not None:
-        out_conf = torch.empty(rows, cols, dtype=torch.float32, device=L.device)
-    ld = _window(out, "out", rows, cols, dtype, L.device)
-    if out_conf is not None and _window(out_conf, "out_conf", rows, cols, torch.float32, L.device) != ld and rows > 1:
-        raise ValueError(f"out and out_conf must share one pitch (got {out.stride(0)} and {out_conf.stride(0)})")
-    L = L.contiguous()
-    if not L.is_cuda:
-        lab, conf = _labelmap_dense_cpu(L, T, N, M, rows, cols, confidence, flip)
-        out.copy_(lab.to(dtype))
-        if out_conf is not None:
-            out_conf.copy_(conf)
-        return out, out_conf
-    _check(_dense_lib().crw_labelmap_dense(_ptr(L), T, N, M, rows, cols, int(bool(flip)), code, _ptr(out),
-                                           DT_F32 if dtype == torch.float32 else DT_I8,
-                                           _ptr(out_conf) if out_conf is not None else None, ld, _stream()), "crw_labelmap_dense")
-    return out, out_conf
-
-
-def _window_batch(t, name, G, rows, cols, dtype, device):
-    """A [G, rows, cols] output of `labelmap_dense_batch`: contiguous, or the column windows maps[:, :, a:b] of a wider
-    [G, rows, width] tensor -> (pitch between rows, elements between maps)."""
-    if tuple(t.shape) != (G, rows, cols) or t.dtype != dtype or t.device != device:
-        raise ValueError(f"{name} must be {dtype} [{G}, {rows}, {cols}] on {device} (got {t.dtype} {tuple(t.shape)} on {t.device})")
-    if cols > 1 and t.stride(2) != 1:
-        raise ValueError(f"{name} must be contiguous along its columns (stride {t.stride()}): maps, or column windows maps[:, :, a:b]")
-    ld = t.stride(1) if rows > 1 else cols
-    if ld < cols:
-        raise ValueError(f"{name}: rows overlap (stride {t.stride()})")
-    span = (rows - 1) * ld + cols
-    map_stride = t.stride(0) if G > 1 else span
-    if map_stride < span:
-        raise ValueError(f"{name}: maps overlap (stride {t.stride()})")
-    return ld, map_stride
+    return _labelmap_dense(L, None, T, N, M, rows, cols, confidence, flip, dtype, out, out_conf)
 
 
 def labelmap_dense_batch(L, G, T, N, M, rows, cols, *, confidence=None, flip=False, dtype=torch.int8, out=None, out_conf=None):
@@ -1022,45 +1028,7 @@ def labelmap_dense_batch(L, G, T, N, M, rows, cols, *, confidence=None, flip=Fal
     column windows ``maps[:, :, a:b]`` of wider [G, rows, width] tensors (one pitch and one map stride for both), anything else
     that is not contiguous raises ValueError.  Device tensors: ONE launch of crw_labelmap_dense_batch, nothing synchronises; CPU
     tensors: a loop of `labelmap_dense`'s CPU route over the configurations."""
-    code = -1 if confidence is None else _conf_kind(confidence)
-    G, T, N, M, rows, cols = int(G), int(T), int(N), int(M), int(rows), int(cols)
-    if not 1 <= G <= 65535:
-        raise ValueError(f"G must be in 1 ... 65535 (got {G})")
-    if not 2 <= M <= 16:
-        raise ValueError(f"M must be in 2 ... 16 (got {M})")
-    if T < 1 or N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
-        raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={T}, N={N}, rows={rows}, cols={cols})")
-    if L.numel() != G * T * N * M or L.dtype != torch.float32:
-        raise ValueError(f"L must be float32 [{G}, {T * N}, {M}] (got {L.dtype} {tuple(L.shape)})")
-    if dtype not in (torch.float32, torch.int8):
-        raise ValueError(f"dtype must be torch.float32 or torch.int8 (got {dtype})")
-    if out_conf is not None and confidence is None:
-        raise ValueError("out_conf needs a confidence kind")
-    if out is None:
-        out = torch.empty(G, rows, cols, dtype=dtype, device=L.device)
-    if out_conf is None and confidence is not None:
-        out_conf = torch.empty(G, rows, cols, dtype=torch.float32, device=L.device)
-    ld, map_stride = _window_batch(out, "out", G, rows, cols, dtype, L.device)
-    if out_conf is not None:
-        cld, cstride = _window_batch(out_conf, "out_conf", G, rows, cols, torch.float32, L.device)
-        if cld != ld and rows > 1:
-            raise ValueError(f"out and out_conf must share one pitch (got {out.stride(1)} and {out_conf.stride(1)})")
-        if cstride != map_stride and G > 1:
-            raise ValueError(f"out and out_conf must share one map stride (got {out.stride(0)} and {out_conf.stride(0)})")
-    L = L.contiguous()
-    if not L.is_cuda:
-        Lg = L.view(G, T * N, M)
-        for g in range(G):
-            lab, conf = _labelmap_dense_cpu(Lg[g], T, N, M, rows, cols, confidence, flip)
-            out[g].copy_(lab.to(dtype))
-            if out_conf is not None:
-                out_conf[g].copy_(conf)
-        return out, out_conf
-    _check(_dense_batch_lib().crw_labelmap_dense_batch(_ptr(L), G, T, N, M, rows, cols, int(bool(flip)), code, _ptr(out),
-                                                       DT_F32 if dtype == torch.float32 else DT_I8,
-                                                       _ptr(out_conf) if out_conf is not None else None, ld, map_stride, _stream()),
-           "crw_labelmap_dense_batch")
-    return out, out_conf
+    return _labelmap_dense(L, G, T, N, M, rows, cols, confidence, flip, dtype, out, out_conf)
 
 
 def _labelmap_dense_cpu(L, T, N, M, rows, cols, confidence, flip):

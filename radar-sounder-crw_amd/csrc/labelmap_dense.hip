@@ -15,7 +15,8 @@
 // map) and writes each output with one vector store; the groups that stick out of the window at a row's head and tail -- the map
 // may be a column window of a wider one, any pitch, any offset -- write their inside pixels one by one.  Plain stores only.
 //
-// crw_labelmap_dense_batch is the same map for the G configurations of a parameter sweep in one launch (see its kernel below).
+// crw_labelmap_dense_batch is the same map for the G configurations of a parameter sweep in one launch: the same kernel text
+// (stage_knots, dense_row) with a loop over the configurations around a row.
 #include <cstdlib>
 
 #include "confidence_of.h"
@@ -32,7 +33,7 @@ constexpr int DN_COLS = WAVE * DN_LANE_PIX;    // columns per workgroup
 constexpr int DN_ROWS = 16;                    // rows per workgroup
 constexpr int DN_COL_KNOTS = DN_COLS + DN_LANE_PIX - 1;  // + the 3 columns a row's phase can shift the groups by
 
-struct DenseArgs {
+struct DenseArgs {  // L, lab, conf, lab_phase: configuration 0's
   const float *L;
   void *lab;
   float *conf;
@@ -41,6 +42,15 @@ struct DenseArgs {
   int lab_phase;  // element index (mod 4) of lab's first pixel within a 16-byte (int8: 4-byte) unit
   int conf_vec;   // conf shares that phase: 16-byte stores
   float ln_m;
+  // the G configurations of crw_labelmap_dense_batch; crw_labelmap_dense is G = 1
+  size_t l_stride;    // floats between the configurations' soft labels (T * N * M)
+  size_t map_stride;  // elements between the configurations' windows
+  int G, chunk;       // configurations, and how many of them a workgroup walks
+};
+
+struct DenseKnots {  // a workgroup's tile: the knot and weight of each of its columns and rows
+  int col_j[DN_COL_KNOTS], row_i[DN_ROWS];
+  float col_w[DN_COL_KNOTS], row_w[DN_ROWS];
 };
 
 // Knot and weight of output index x on an axis of `n_out` pixels over `n_in` nodes, in integers: a = (2x + 1) n_in - n_out over
@@ -82,9 +92,9 @@ __device__ inline void load_row(const float *__restrict__ row, int M, int vec, f
 }
 
 // One pixel: its row interpolated between the four node rows, the arg-max (strict: a tie keeps the lowest class) and the
-// confidence of the interpolated row.  The ONE text of this arithmetic: labelmap_dense_kernel and labelmap_dense_batch_kernel both
-// instantiate it.  One text is not yet one result: left to itself the compiler contracts a * b + c * d to FMAs site by site (and
-// turns (1 - w) * p into fma(-w, p, p)), differently in two kernels and even between the pixels of one lane.  So the roundings are
+// confidence of the interpolated row.  The ONE text of this arithmetic, instantiated by every shape of the kernel.  One text is
+// not yet one result: left to itself the compiler contracts a * b + c * d to FMAs site by site (and turns (1 - w) * p into
+// fma(-w, p, p)), differently in two instantiations and even between the pixels of one lane.  So the roundings are
 // written out -- one product rounded, the other fused into the sum, at each of the three steps -- and contraction is off here.
 template <int KIND, int MCAP>
 __device__ __forceinline__ void dense_pixel(const float (&p00)[MCAP], const float (&p01)[MCAP], const float (&p10)[MCAP],
@@ -108,234 +118,127 @@ __device__ __forceinline__ void dense_pixel(const float (&p00)[MCAP], const floa
   *conf = KIND >= 0 ? confidence_of<(KIND >= 0 ? KIND : 0)>(v, M, ln_m) : 0.f;
 }
 
+// The knots and weights of the workgroup's 16 rows and 256 (+ 3) columns, one division per thread; they depend on the geometry
+// alone.  Ends in the barrier after which every thread may read them.
+__device__ inline void stage_knots(const DenseArgs &a, int row0, long colb, DenseKnots &k) {
+  for (int i = threadIdx.x; i < DN_COL_KNOTS + DN_ROWS; i += DN_BLOCK) {
+    int i0 = 0;
+    float w = 0.f;
+    if (i < DN_COL_KNOTS) {
+      const long c = colb + i;
+      if (c >= 0 && c < a.cols) knot(a.flip ? a.cols - 1 - (int)c : (int)c, a.T, a.cols, &i0, &w);
+      k.col_j[i] = i0, k.col_w[i] = w;  // outside the window: node 0, never stored
+    } else {
+      const int r = row0 + (i - DN_COL_KNOTS);
+      if (r < a.rows) knot(r, a.N, a.rows, &i0, &w);
+      k.row_i[i - DN_COL_KNOTS] = i0, k.row_w[i - DN_COL_KNOTS] = w;
+    }
+  }
+  __syncthreads();
+}
+
+// One row of one configuration: this lane's 4 pixels between the node rows i0 / i1 (weight wr) of the soft labels L, stored at
+// `off` elements behind lab / conf (the row's start in the configuration's window).  The store phase, and with it the
+// lane-to-column assignment and the row's head and tail, follows from `off`: neither the pitch nor the map stride need be a
+// multiple of 4.
 // KIND: a CRW_CONF_* kind, or -1 for no confidence map; MCAP: 4, 8 or 16 >= M, the classes a lane keeps registers for
 template <typename LAB, int KIND, int MCAP>
-__global__ __launch_bounds__(DN_BLOCK) void labelmap_dense_kernel(DenseArgs a) {
-  __shared__ int col_j[DN_COL_KNOTS], row_i[DN_ROWS];
-  __shared__ float col_w[DN_COL_KNOTS], row_w[DN_ROWS];
-  const int row0 = blockIdx.x * DN_ROWS;
-  const long colb = (long)blockIdx.y * DN_COLS - (DN_LANE_PIX - 1);  // column of col_*[0]
-  for (int i = threadIdx.x; i < DN_COL_KNOTS + DN_ROWS; i += DN_BLOCK) {
-    int k = 0;
-    float w = 0.f;
-    if (i < DN_COL_KNOTS) {
-      const long c = colb + i;
-      if (c >= 0 && c < a.cols) knot(a.flip ? a.cols - 1 - (int)c : (int)c, a.T, a.cols, &k, &w);
-      col_j[i] = k, col_w[i] = w;  // outside the window: node 0, never stored
-    } else {
-      const int r = row0 + (i - DN_COL_KNOTS);
-      if (r < a.rows) knot(r, a.N, a.rows, &k, &w);
-      row_i[i - DN_COL_KNOTS] = k, row_w[i - DN_COL_KNOTS] = w;
-    }
-  }
-  __syncthreads();
-
-  const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+__device__ __forceinline__ void dense_row(const DenseArgs &a, const DenseKnots &k, const float *__restrict__ L, size_t off,
+                                          long colb, int lane, int i0, int i1, float wr) {
   const int M = a.M, N = a.N;
-  const int vec = ((M & 3) == 0 && !((uintptr_t)a.L & 15)) ? 4 : ((M & 1) == 0 && !((uintptr_t)a.L & 7)) ? 2 : 1;
-  LAB *lab = static_cast<LAB *>(a.lab);
+  const int vec = ((M & 3) == 0 && !((uintptr_t)L & 15)) ? 4 : ((M & 1) == 0 && !((uintptr_t)L & 7)) ? 2 : 1;
+  LAB *lab = static_cast<LAB *>(a.lab) + off;
+  float *conf = KIND >= 0 ? a.conf + off : nullptr;
+  const int phase = (int)((a.lab_phase + off) & (DN_LANE_PIX - 1));
+  const int kx = DN_LANE_PIX * lane - phase + (DN_LANE_PIX - 1);  // this lane's first entry of col_*
+  const long c0 = colb + kx;                                      // its first column: -3 ... cols + 2
+  if (c0 >= a.cols) return;
 
-  for (int rr = wave; rr < DN_ROWS; rr += DN_WAVES) {
-    const int r = row0 + rr;
-    if (r >= a.rows) break;
-    const int i0 = row_i[rr], i1 = i0 + 1 < N ? i0 + 1 : N - 1;
-    const float wr = row_w[rr];
-    const size_t rowoff = (size_t)r * a.ld;
-    const int phase = (int)((a.lab_phase + rowoff) & (DN_LANE_PIX - 1));
-    const int kx = DN_LANE_PIX * lane - phase + (DN_LANE_PIX - 1);  // this lane's first entry of col_*
-    const long c0 = colb + kx;                                      // its first column: -3 ... cols + 2
-    if (c0 >= a.cols) continue;
+  float p00[MCAP], p01[MCAP], p10[MCAP], p11[MCAP];
+  float lab4[DN_LANE_PIX], conf4[DN_LANE_PIX];
+  int pj0 = -1, pj1 = -1;
+#pragma unroll
+  for (int e = 0; e < DN_LANE_PIX; ++e) {
+    const int j0 = k.col_j[kx + e], j1 = j0 + 1 < a.T ? j0 + 1 : a.T - 1;
+    const float wc = k.col_w[kx + e];
+    if (j0 != pj0 || j1 != pj1) {  // consecutive pixels mostly sit between the same two frames
+      load_row(L + ((size_t)j0 * N + i0) * M, M, vec, p00);
+      load_row(L + ((size_t)j1 * N + i0) * M, M, vec, p01);
+      load_row(L + ((size_t)j0 * N + i1) * M, M, vec, p10);
+      load_row(L + ((size_t)j1 * N + i1) * M, M, vec, p11);
+      pj0 = j0, pj1 = j1;
+    }
+    dense_pixel<KIND, MCAP>(p00, p01, p10, p11, wc, wr, M, a.ln_m, &lab4[e], &conf4[e]);
+  }
 
-    float p00[MCAP], p01[MCAP], p10[MCAP], p11[MCAP];
-    float lab4[DN_LANE_PIX], conf4[DN_LANE_PIX];
-    int pj0 = -1, pj1 = -1;
+  if (c0 >= 0 && c0 + DN_LANE_PIX <= a.cols) {  // a whole group: its first pixel sits on the vector boundary
+    if (sizeof(LAB) == 4) {
+      *reinterpret_cast<float4 *>(lab + c0) = make_float4(lab4[0], lab4[1], lab4[2], lab4[3]);
+    } else {
+      const uint32_t pk = (uint32_t)lab4[0] | (uint32_t)lab4[1] << 8 | (uint32_t)lab4[2] << 16 | (uint32_t)lab4[3] << 24;
+      *reinterpret_cast<uint32_t *>(lab + c0) = pk;
+    }
+    if (KIND >= 0) {
+      if (a.conf_vec) {  // conf shares the labels' phase in configuration 0, hence in every one
+        *reinterpret_cast<float4 *>(conf + c0) = make_float4(conf4[0], conf4[1], conf4[2], conf4[3]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < DN_LANE_PIX; ++e) conf[c0 + e] = conf4[e];
+      }
+    }
+  } else {  // head or tail of the row: the pixels inside the window, one by one
 #pragma unroll
     for (int e = 0; e < DN_LANE_PIX; ++e) {
-      const int j0 = col_j[kx + e], j1 = j0 + 1 < a.T ? j0 + 1 : a.T - 1;
-      const float wc = col_w[kx + e];
-      if (j0 != pj0 || j1 != pj1) {  // consecutive pixels mostly sit between the same two frames
-        load_row(a.L + ((size_t)j0 * N + i0) * M, M, vec, p00);
-        load_row(a.L + ((size_t)j1 * N + i0) * M, M, vec, p01);
-        load_row(a.L + ((size_t)j0 * N + i1) * M, M, vec, p10);
-        load_row(a.L + ((size_t)j1 * N + i1) * M, M, vec, p11);
-        pj0 = j0, pj1 = j1;
-      }
-      dense_pixel<KIND, MCAP>(p00, p01, p10, p11, wc, wr, M, a.ln_m, &lab4[e], &conf4[e]);
-    }
-
-    if (c0 >= 0 && c0 + DN_LANE_PIX <= a.cols) {  // a whole group: its first pixel sits on the vector boundary
-      if (sizeof(LAB) == 4) {
-        *reinterpret_cast<float4 *>(lab + rowoff + c0) = make_float4(lab4[0], lab4[1], lab4[2], lab4[3]);
-      } else {
-        const uint32_t pk = (uint32_t)lab4[0] | (uint32_t)lab4[1] << 8 | (uint32_t)lab4[2] << 16 | (uint32_t)lab4[3] << 24;
-        *reinterpret_cast<uint32_t *>(lab + rowoff + c0) = pk;
-      }
-      if (KIND >= 0) {
-        if (a.conf_vec) {
-          *reinterpret_cast<float4 *>(a.conf + rowoff + c0) = make_float4(conf4[0], conf4[1], conf4[2], conf4[3]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < DN_LANE_PIX; ++e) a.conf[rowoff + c0 + e] = conf4[e];
-        }
-      }
-    } else {  // head or tail of the row: the pixels inside the window, one by one
-#pragma unroll
-      for (int e = 0; e < DN_LANE_PIX; ++e) {
-        const long c = c0 + e;
-        if (c >= 0 && c < a.cols) {
-          lab[rowoff + c] = (LAB)lab4[e];
-          if (KIND >= 0) a.conf[rowoff + c] = conf4[e];
-        }
+      const long c = c0 + e;
+      if (c >= 0 && c < a.cols) {
+        lab[c] = (LAB)lab4[e];
+        if (KIND >= 0) conf[c] = conf4[e];
       }
     }
   }
 }
 
-// The same map for the G configurations of a sweep's pass in ONE launch: L [G, T*N, M], configuration g's window `map_stride`
-// elements behind configuration g - 1's.  A workgroup stages the knots and weights of its 16 x 256 tile ONCE -- they depend on the
-// geometry alone -- and walks `chunk` configurations with them (blockIdx.z: the chunk); chunk = 1 is the plain "one configuration
-// per blockIdx.z" shape.  What changes with g: the four node rows (another slice of L), the output address, and with it the store
-// phase -- `map_stride` need not be a multiple of 4, so the lane-to-column assignment and a row's head and tail are per (g, row),
-// exactly those of crw_labelmap_dense on slice g's own base.  Pixels come from dense_pixel, the one-map kernel's.
-struct DenseBatchArgs {
-  DenseArgs d;        // L, lab, conf: configuration 0's; lab_phase: configuration 0's
-  size_t l_stride;    // floats between the configurations' soft labels (T * N * M)
-  size_t map_stride;  // elements between the configurations' windows
-  int G, chunk;
-};
-
-template <typename LAB, int KIND, int MCAP>
-__global__ __launch_bounds__(DN_BLOCK) void labelmap_dense_batch_kernel(DenseBatchArgs b) {
-  __shared__ int col_j[DN_COL_KNOTS], row_i[DN_ROWS];
-  __shared__ float col_w[DN_COL_KNOTS], row_w[DN_ROWS];
-  const DenseArgs &a = b.d;
+// BATCH: the G configurations of a sweep's pass in ONE launch, L [G, T*N, M], configuration g's window `map_stride` elements behind
+// configuration g - 1's.  A workgroup stages the knots of its 16 x 256 tile ONCE and walks `chunk` configurations with them
+// (blockIdx.z: the chunk); chunk = 1 is the plain "one configuration per blockIdx.z" shape.  What changes with g: the four node
+// rows (another slice of L), the output address, and with it the store phase -- exactly those of the one-map kernel on slice g's
+// own base.  Without BATCH: one map, no loop.
+template <typename LAB, int KIND, int MCAP, bool BATCH>
+__global__ __launch_bounds__(DN_BLOCK) void labelmap_dense_kernel(DenseArgs a) {
+  __shared__ DenseKnots k;
   const int row0 = blockIdx.x * DN_ROWS;
   const long colb = (long)blockIdx.y * DN_COLS - (DN_LANE_PIX - 1);  // column of col_*[0]
-  for (int i = threadIdx.x; i < DN_COL_KNOTS + DN_ROWS; i += DN_BLOCK) {
-    int k = 0;
-    float w = 0.f;
-    if (i < DN_COL_KNOTS) {
-      const long c = colb + i;
-      if (c >= 0 && c < a.cols) knot(a.flip ? a.cols - 1 - (int)c : (int)c, a.T, a.cols, &k, &w);
-      col_j[i] = k, col_w[i] = w;  // outside the window: node 0, never stored
-    } else {
-      const int r = row0 + (i - DN_COL_KNOTS);
-      if (r < a.rows) knot(r, a.N, a.rows, &k, &w);
-      row_i[i - DN_COL_KNOTS] = k, row_w[i - DN_COL_KNOTS] = w;
-    }
-  }
-  __syncthreads();
+  stage_knots(a, row0, colb, k);
 
   const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
-  const int M = a.M, N = a.N;
-  const int g0 = blockIdx.z * b.chunk, g1 = g0 + b.chunk < b.G ? g0 + b.chunk : b.G;
-
+  const int g0 = blockIdx.z * a.chunk, g1 = g0 + a.chunk < a.G ? g0 + a.chunk : a.G;
   for (int rr = wave; rr < DN_ROWS; rr += DN_WAVES) {
     const int r = row0 + rr;
     if (r >= a.rows) break;
-    const int i0 = row_i[rr], i1 = i0 + 1 < N ? i0 + 1 : N - 1;
-    const float wr = row_w[rr];
+    const int i0 = k.row_i[rr], i1 = i0 + 1 < a.N ? i0 + 1 : a.N - 1;
+    const float wr = k.row_w[rr];
     const size_t rowoff = (size_t)r * a.ld;
-
-    for (int g = g0; g < g1; ++g) {
-      const float *Lg = a.L + (size_t)g * b.l_stride;
-      const int vec = ((M & 3) == 0 && !((uintptr_t)Lg & 15)) ? 4 : ((M & 1) == 0 && !((uintptr_t)Lg & 7)) ? 2 : 1;
-      const size_t mapoff = (size_t)g * b.map_stride + rowoff;  // of this row in configuration g's window
-      LAB *lab = static_cast<LAB *>(a.lab) + mapoff;
-      float *conf = KIND >= 0 ? a.conf + mapoff : nullptr;
-      const int phase = (int)((a.lab_phase + mapoff) & (DN_LANE_PIX - 1));
-      const int kx = DN_LANE_PIX * lane - phase + (DN_LANE_PIX - 1);  // this lane's first entry of col_*
-      const long c0 = colb + kx;                                      // its first column: -3 ... cols + 2
-      if (c0 >= a.cols) continue;
-
-      float p00[MCAP], p01[MCAP], p10[MCAP], p11[MCAP];
-      float lab4[DN_LANE_PIX], conf4[DN_LANE_PIX];
-      int pj0 = -1, pj1 = -1;
-#pragma unroll
-      for (int e = 0; e < DN_LANE_PIX; ++e) {
-        const int j0 = col_j[kx + e], j1 = j0 + 1 < a.T ? j0 + 1 : a.T - 1;
-        const float wc = col_w[kx + e];
-        if (j0 != pj0 || j1 != pj1) {
-          load_row(Lg + ((size_t)j0 * N + i0) * M, M, vec, p00);
-          load_row(Lg + ((size_t)j1 * N + i0) * M, M, vec, p01);
-          load_row(Lg + ((size_t)j0 * N + i1) * M, M, vec, p10);
-          load_row(Lg + ((size_t)j1 * N + i1) * M, M, vec, p11);
-          pj0 = j0, pj1 = j1;
-        }
-        dense_pixel<KIND, MCAP>(p00, p01, p10, p11, wc, wr, M, a.ln_m, &lab4[e], &conf4[e]);
-      }
-
-      if (c0 >= 0 && c0 + DN_LANE_PIX <= a.cols) {  // a whole group: its first pixel sits on the vector boundary
-        if (sizeof(LAB) == 4) {
-          *reinterpret_cast<float4 *>(lab + c0) = make_float4(lab4[0], lab4[1], lab4[2], lab4[3]);
-        } else {
-          const uint32_t pk = (uint32_t)lab4[0] | (uint32_t)lab4[1] << 8 | (uint32_t)lab4[2] << 16 | (uint32_t)lab4[3] << 24;
-          *reinterpret_cast<uint32_t *>(lab + c0) = pk;
-        }
-        if (KIND >= 0) {
-          if (a.conf_vec) {  // conf shares the labels' phase in configuration 0, hence in every one
-            *reinterpret_cast<float4 *>(conf + c0) = make_float4(conf4[0], conf4[1], conf4[2], conf4[3]);
-          } else {
-#pragma unroll
-            for (int e = 0; e < DN_LANE_PIX; ++e) conf[c0 + e] = conf4[e];
-          }
-        }
-      } else {  // head or tail of the row: the pixels inside the window, one by one
-#pragma unroll
-        for (int e = 0; e < DN_LANE_PIX; ++e) {
-          const long c = c0 + e;
-          if (c >= 0 && c < a.cols) {
-            lab[c] = (LAB)lab4[e];
-            if (KIND >= 0) conf[c] = conf4[e];
-          }
-        }
-      }
+    if (BATCH) {
+      for (int g = g0; g < g1; ++g)
+        dense_row<LAB, KIND, MCAP>(a, k, a.L + (size_t)g * a.l_stride, (size_t)g * a.map_stride + rowoff, colb, lane, i0, i1, wr);
+    } else {
+      dense_row<LAB, KIND, MCAP>(a, k, a.L, rowoff, colb, lane, i0, i1, wr);
     }
   }
 }
 
-template <typename LAB, int KIND>
-void launch_dense_m(dim3 grid, hipStream_t s, const DenseArgs &a) {
-  if (a.M <= 4)
-    hipLaunchKernelGGL((labelmap_dense_kernel<LAB, KIND, 4>), grid, dim3(DN_BLOCK), 0, s, a);
-  else if (a.M <= 8)
-    hipLaunchKernelGGL((labelmap_dense_kernel<LAB, KIND, 8>), grid, dim3(DN_BLOCK), 0, s, a);
-  else
-    hipLaunchKernelGGL((labelmap_dense_kernel<LAB, KIND, 16>), grid, dim3(DN_BLOCK), 0, s, a);
+template <typename LAB, int KIND, bool BATCH>
+auto dense_kernel_m(int M) {
+  return M <= 4 ? labelmap_dense_kernel<LAB, KIND, 4, BATCH>
+                : M <= 8 ? labelmap_dense_kernel<LAB, KIND, 8, BATCH> : labelmap_dense_kernel<LAB, KIND, 16, BATCH>;
 }
 
-template <typename LAB>
-void launch_dense(int kind, dim3 grid, hipStream_t s, const DenseArgs &a) {
-  if (kind < 0)
-    launch_dense_m<LAB, -1>(grid, s, a);
-  else if (kind == CRW_CONF_MAXPROB)
-    launch_dense_m<LAB, CRW_CONF_MAXPROB>(grid, s, a);
-  else if (kind == CRW_CONF_MARGIN)
-    launch_dense_m<LAB, CRW_CONF_MARGIN>(grid, s, a);
-  else
-    launch_dense_m<LAB, CRW_CONF_ENTROPY>(grid, s, a);
-}
-
-template <typename LAB, int KIND>
-void launch_dense_batch_m(dim3 grid, hipStream_t s, const DenseBatchArgs &b) {
-  if (b.d.M <= 4)
-    hipLaunchKernelGGL((labelmap_dense_batch_kernel<LAB, KIND, 4>), grid, dim3(DN_BLOCK), 0, s, b);
-  else if (b.d.M <= 8)
-    hipLaunchKernelGGL((labelmap_dense_batch_kernel<LAB, KIND, 8>), grid, dim3(DN_BLOCK), 0, s, b);
-  else
-    hipLaunchKernelGGL((labelmap_dense_batch_kernel<LAB, KIND, 16>), grid, dim3(DN_BLOCK), 0, s, b);
-}
-
-template <typename LAB>
-void launch_dense_batch(int kind, dim3 grid, hipStream_t s, const DenseBatchArgs &b) {
-  if (kind < 0)
-    launch_dense_batch_m<LAB, -1>(grid, s, b);
-  else if (kind == CRW_CONF_MAXPROB)
-    launch_dense_batch_m<LAB, CRW_CONF_MAXPROB>(grid, s, b);
-  else if (kind == CRW_CONF_MARGIN)
-    launch_dense_batch_m<LAB, CRW_CONF_MARGIN>(grid, s, b);
-  else
-    launch_dense_batch_m<LAB, CRW_CONF_ENTROPY>(grid, s, b);
+template <typename LAB, bool BATCH>
+auto dense_kernel(int kind, int M) {
+  return kind < 0 ? dense_kernel_m<LAB, -1, BATCH>(M)
+                  : kind == CRW_CONF_MAXPROB ? dense_kernel_m<LAB, CRW_CONF_MAXPROB, BATCH>(M)
+                  : kind == CRW_CONF_MARGIN ? dense_kernel_m<LAB, CRW_CONF_MARGIN, BATCH>(M)
+                                            : dense_kernel_m<LAB, CRW_CONF_ENTROPY, BATCH>(M);
 }
 
 // configurations a workgroup walks with one set of knots: fastest or tied of 1 / 2 / 4 / 8 at G = 60, 410 x 3200, 5 - 17 % ahead of
@@ -353,58 +256,45 @@ int batch_chunk(int G) {
   return chunk < G ? chunk : G;
 }
 
-}  // namespace
-}  // namespace crw
-
-extern "C" int crw_labelmap_dense_batch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, int conf_kind,
-                                        void *labels, int label_dtype, float *conf, size_t ld, size_t map_stride,
-                                        crw_stream_t stream) {
-  using namespace crw;
+// Both entry points behind their signatures: the argument checks, the kernel's arguments, the launch.  `chunk`: the
+// configurations a workgroup walks (the one-map entry point: G = 1, chunk = 1).
+template <bool BATCH>
+int dense_launch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
+                 int label_dtype, float *conf, size_t ld, size_t map_stride, int chunk, crw_stream_t stream) {
   clear_stale_error();
-  constexpr int MAX_SIDE = 1 << 22;
+  constexpr int MAX_SIDE = 1 << 22;  // 2 * side < 2^24: the weights' numerators and denominators are exact in fp32
   if (!L || !labels || G < 1 || G > 65535 || T < 1 || N < 1 || M < 2 || M > 16 || rows < 1 || cols < 1 || rows > MAX_SIDE ||
       cols > MAX_SIDE || !dtype_ok(label_dtype) || conf_kind < -1 || conf_kind > CRW_CONF_ENTROPY ||
       (conf_kind == -1) != (conf == nullptr) || ld < (size_t)cols || map_stride < (size_t)(rows - 1) * ld + (size_t)cols ||
       ((uintptr_t)L & 3) || ((uintptr_t)conf & 3) || (label_dtype == CRW_DT_F32 && ((uintptr_t)labels & 3)))
     return CRW_EINVAL;  // (a slice's base is configuration 0's plus whole elements: 4-byte aligned when that is)
-  DenseBatchArgs b;
-  DenseArgs &a = b.d;
-  a.L = L, a.lab = labels, a.conf = conf, a.ld = ld;
-  a.T = T, a.N = N, a.M = M, a.rows = rows, a.cols = cols, a.flip = flip != 0;
-  a.lab_phase = (int)(((uintptr_t)labels / elem(label_dtype)) & (DN_LANE_PIX - 1));
-  a.conf_vec = conf && (int)(((uintptr_t)conf / 4) & (DN_LANE_PIX - 1)) == a.lab_phase;
-  a.ln_m = logf((float)M);
-  b.l_stride = (size_t)T * N * M, b.map_stride = map_stride, b.G = G, b.chunk = batch_chunk(G);
-  const unsigned groups = ((unsigned)cols + 2 * (DN_LANE_PIX - 1)) / DN_LANE_PIX;
-  const dim3 grid(((unsigned)rows + DN_ROWS - 1) / DN_ROWS, (groups + WAVE - 1) / WAVE, ((unsigned)G + b.chunk - 1) / b.chunk);
-  if (label_dtype == CRW_DT_F32)
-    launch_dense_batch<float>(conf_kind, grid, (hipStream_t)stream, b);
-  else
-    launch_dense_batch<int8_t>(conf_kind, grid, (hipStream_t)stream, b);
-  return check_launch();
-}
-
-extern "C" int crw_labelmap_dense(const float *L, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
-                                  int label_dtype, float *conf, size_t ld, crw_stream_t stream) {
-  using namespace crw;
-  clear_stale_error();
-  constexpr int MAX_SIDE = 1 << 22;  // 2 * side < 2^24: the weights' numerators and denominators are exact in fp32
-  if (!L || !labels || T < 1 || N < 1 || M < 2 || M > 16 || rows < 1 || cols < 1 || rows > MAX_SIDE || cols > MAX_SIDE ||
-      !dtype_ok(label_dtype) || conf_kind < -1 || conf_kind > CRW_CONF_ENTROPY || (conf_kind == -1) != (conf == nullptr) ||
-      ld < (size_t)cols || ((uintptr_t)L & 3) || ((uintptr_t)conf & 3) || (label_dtype == CRW_DT_F32 && ((uintptr_t)labels & 3)))
-    return CRW_EINVAL;
   DenseArgs a;
   a.L = L, a.lab = labels, a.conf = conf, a.ld = ld;
   a.T = T, a.N = N, a.M = M, a.rows = rows, a.cols = cols, a.flip = flip != 0;
   a.lab_phase = (int)(((uintptr_t)labels / elem(label_dtype)) & (DN_LANE_PIX - 1));
   a.conf_vec = conf && (int)(((uintptr_t)conf / 4) & (DN_LANE_PIX - 1)) == a.lab_phase;
   a.ln_m = logf((float)M);
+  a.l_stride = (size_t)T * N * M, a.map_stride = map_stride, a.G = G, a.chunk = chunk;
   // a row's groups: ceil((cols + phase) / 4) <= (cols + 3 + 3) / 4
   const unsigned groups = ((unsigned)cols + 2 * (DN_LANE_PIX - 1)) / DN_LANE_PIX;
-  const dim3 grid(((unsigned)rows + DN_ROWS - 1) / DN_ROWS, (groups + WAVE - 1) / WAVE);
-  if (label_dtype == CRW_DT_F32)
-    launch_dense<float>(conf_kind, grid, (hipStream_t)stream, a);
-  else
-    launch_dense<int8_t>(conf_kind, grid, (hipStream_t)stream, a);
+  const dim3 grid(((unsigned)rows + DN_ROWS - 1) / DN_ROWS, (groups + WAVE - 1) / WAVE, ((unsigned)G + chunk - 1) / chunk);
+  const auto kernel = label_dtype == CRW_DT_F32 ? dense_kernel<float, BATCH>(conf_kind, M) : dense_kernel<int8_t, BATCH>(conf_kind, M);
+  hipLaunchKernelGGL(kernel, grid, dim3(DN_BLOCK), 0, (hipStream_t)stream, a);
   return check_launch();
+}
+
+}  // namespace
+}  // namespace crw
+
+extern "C" int crw_labelmap_dense_batch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, int conf_kind,
+                                        void *labels, int label_dtype, float *conf, size_t ld, size_t map_stride,
+                                        crw_stream_t stream) {
+  return crw::dense_launch<true>(L, G, T, N, M, rows, cols, flip, conf_kind, labels, label_dtype, conf, ld, map_stride,
+                                 crw::batch_chunk(G), stream);
+}
+
+extern "C" int crw_labelmap_dense(const float *L, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
+                                  int label_dtype, float *conf, size_t ld, crw_stream_t stream) {
+  // one map: nothing behind it to overlap, so any stride that covers it (checked: ld >= cols) serves
+  return crw::dense_launch<false>(L, 1, T, N, M, rows, cols, flip, conf_kind, labels, label_dtype, conf, ld, (size_t)rows * ld, 1, stream);
 }

@@ -40,32 +40,130 @@ from utils import propagate, propagate_sweep
 
 
 def _upsample(pred, rows, cols):
-    """[N, T] node labels -> [rows, cols] pixel labels (nearest)."""
-    return TF.interpolate(pred[None, None].float(), size=(rows, cols), mode='nearest')[0, 0]
+    """[..., N, T] node labels -> [..., rows, cols] pixel labels (nearest)."""
+    up = TF.interpolate(pred.reshape(-1, 1, *pred.shape[-2:]).float(), size=(rows, cols), mode='nearest')
+    return up.reshape(*pred.shape[:-2], rows, cols)
+
+
+def _reverse_rule_mask(final_pred, pred_rev, dataset_id):
+    """The pixels (bool, the maps' shape [..., rows, cols]) at which `merge_reverse`'s class rule writes the reverse pass's
+    label, map by map."""
+    mask = (pred_rev == 2).contiguous()
+    if dataset_id == 1:
+        mask = torch.logical_and(mask, final_pred != 3)
+        mask = torch.logical_and(mask, torch.all(pred_rev != 4, dim=-2, keepdim=True))
+    elif dataset_id == 3:
+        mask.flatten(-2)[..., :mask.shape[-2] * mask.shape[-1] // 2] = False  # the first half of each map's pixels
+    elif dataset_id != 0:
+        raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
+    return mask
 
 
 def merge_reverse(final_pred, pred_rev, dataset_id):
     """Class-specific merge of the reversed pass into the forward map (test_all.py:146-159):
     class 2 (bedrock) of the reversed pass wins, with per-dataset restrictions."""
-    out = final_pred.flatten().clone()
+    out = final_pred.clone()
     out[_reverse_rule_mask(final_pred, pred_rev, dataset_id)] = 2
-    return out.view_as(final_pred)
+    return out
 
 
-def _reverse_rule_mask(final_pred, pred_rev, dataset_id):
-    """The pixels (flat, bool) at which `merge_reverse`'s class rule writes the reverse pass's label."""
-    rows = pred_rev.shape[0]
-    mask = pred_rev.flatten() == 2
-    if dataset_id == 1:
-        mask = torch.logical_and(mask, final_pred.flatten() != 3)
-        under_ice = torch.all(pred_rev != 4, dim=0)[None].repeat(rows, 1).flatten()
-        mask = torch.logical_and(mask, under_ice)
-    elif dataset_id == 3:
-        mask = mask.clone()
-        mask[:mask.numel() // 2] = False
-    elif dataset_id != 0:
-        raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
-    return mask
+_reverse_rule_mask_batch = _reverse_rule_mask  # [G, rows, cols] maps, configuration by configuration
+merge_reverse_batch = merge_reverse
+
+
+def _check_options(confidence, merge, upsample):
+    """`segment`'s and `segment_sweep`'s checks of their three options."""
+    if merge not in ('rule', 'confidence'):
+        raise ValueError(f"merge must be 'rule' or 'confidence' (got {merge!r})")
+    if upsample not in ('nearest', 'bilinear'):
+        raise ValueError(f"upsample must be 'nearest' or 'bilinear' (got {upsample!r})")
+    if confidence is not None and confidence not in crw_hip.CONF_KINDS:
+        raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
+    if merge == 'confidence' and confidence is None:
+        raise ValueError("merge='confidence' needs a confidence kind (confidence='maxprob', 'margin' or 'entropy')")
+
+
+def _write_nearest(res, seq, out, out_conf, flip):
+    """The nearest writer of `_segment_passes`: a pass's arg-max labels res[0] (and node confidences res[3]), [..., N, T],
+    stretched into the windows -- both stretched before either is written; an int8 window casts."""
+    ups = [(out, _upsample(res[0], *out.shape[-2:]))]
+    if out_conf is not None:
+        ups.append((out_conf, _upsample(res[3], *out.shape[-2:])))
+    for window, up in ups:
+        window[...] = torch.flip(up, (-1,)) if flip else up
+
+
+def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run, write,
+                    lead=(), dtype=torch.float32, **extra):
+    """The passes of `segment` and `segment_sweep`, behind their argument checks -> their result dict (plus ``extra``).
+    run(seq, seg_ref, use_last): the variant's `propagate` call -> (pred, xent, change, ...).
+    write(res, seq, out, out_conf, flip): puts what `run` returned into a column window of the label map (and of the confidence
+    map, None unless ``want``), mirrored along the columns with ``flip``.
+    The maps are allocated ONCE at [*lead, rows, n_rg * rg_len] (labels ``dtype``, confidence float32) and every pass writes its
+    own column window: the forward pass its radargram's, a correction the last ``px`` columns of it -- only after everything of it
+    that can raise succeeded --, the reverse pass its radargram's, mirrored.  No list of maps, no cat, no flip of a map."""
+    T, (H, W), (oh, ow) = seq_length, patch_size, overlap
+    N = dataset[0].shape[1]
+    rg_len = T * (W - ow) + ow
+    rg_h = N * (H - oh) + oh
+    idx = list(range(0, len(dataset), T))
+    n_rg = min(len(idx), seg.shape[-1] // rg_len)
+    idx = idx[:n_rg]
+    seg = seg[:, :n_rg * rg_len].to(device)
+    rows = seg.shape[0]
+    new = lambda dt: torch.empty(*lead, rows, n_rg * rg_len, dtype=dt, device=device)
+    new_maps = lambda: (new(dtype), new(torch.float32) if want else None)
+    window = lambda maps, a, b: [m[..., a:b] if m is not None else None for m in maps]
+
+    forward, forward_conf = new_maps()
+    xents, changes = [], []
+    for t, i in enumerate(idx):
+        seq = dataset[i].to(device)
+        res = run(seq, seg[:rg_h, rg_len * t:rg_len * t + W], False)
+        write(res, seq, *window((forward, forward_conf), rg_len * t, rg_len * (t + 1)), False)
+        xents.append(res[1])
+        changes.append(res[2])
+
+    if correction:
+        for t, change in enumerate(changes):
+            if change is None:
+                continue
+            small = T - change
+            px = small * (W - ow)
+            try:  # like the reference, a correction that fails on its DATA (shape / index errors) is skipped silently ...
+                seq = dataset.get_smaller_item(idx[t], small).to(device)  # first `small` columns; shortens the dataset
+                a, b = rg_len * (t + 1) - px, rg_len * (t + 1)
+                res = run(seq, seg[:, a:a + W], False)
+                write(res, seq, *window((forward, forward_conf), a, b), False)  # labels and confidence: both or neither
+            except crw_hip.CrwError as e:
+                # ... but a failure of the HIP path itself (CRW_EHIP: launch failure / GPU fault, CRW_EWORKSPACE) is not a data
+                # problem: the reference's bare `except` would hide a poisoned device context behind an uncorrected map.
+                # CRW_EINVAL (a degenerate correction window: bad shape / unsupported size) IS the data and is skipped
+                if e.device_failure:
+                    raise
+            except torch.AcceleratorError:  # the device runtime's own errors (hipError* raised by PyTorch)
+                raise
+            except Exception:
+                pass
+
+    final, final_conf = forward, forward_conf
+    if use_last:
+        rev, rev_conf = new_maps()
+        seg_rev = torch.flip(seg.unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
+        for t, i in enumerate(idx):
+            seq = dataset[i].to(device)
+            res = run(seq, seg_rev[:, rg_len * t:rg_len * t + W], True)
+            write(res, seq, *window((rev, rev_conf), rg_len * t, rg_len * (t + 1)), True)
+        if merge == 'confidence':
+            final, final_conf, _ = crw_hip.merge_confidence(forward, forward_conf, rev, rev_conf)
+        else:
+            final = merge_reverse(forward, rev, dataset_id)
+            if want:
+                final_conf = torch.where(_reverse_rule_mask(forward, rev, dataset_id), rev_conf, forward_conf)
+    out = dict(pred=final, forward=forward, xent=xents, change_idx=changes, **extra)
+    if want:
+        out.update(conf=final_conf, forward_conf=forward_conf)
+    return out
 
 
 @torch.no_grad()
@@ -89,191 +187,20 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     interpolated bilinearly to pixels and arg-maxed after that (`crw_hip.labelmap_dense`, one kernel per pass, straight into the
     pass's column window of the map); ``conf`` / ``forward_conf`` are then the confidence of the INTERPOLATED distribution.  Same
     passes, corrections, exception policy and merges."""
-    if merge not in ('rule', 'confidence'):
-        raise ValueError(f"merge must be 'rule' or 'confidence' (got {merge!r})")
-    if upsample not in ('nearest', 'bilinear'):
-        raise ValueError(f"upsample must be 'nearest' or 'bilinear' (got {upsample!r})")
-    if confidence is not None and confidence not in crw_hip.CONF_KINDS:
-        raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
-    if merge == 'confidence' and confidence is None:
-        raise ValueError("merge='confidence' needs a confidence kind (confidence='maxprob', 'margin' or 'entropy')")
+    _check_options(confidence, merge, upsample)
     want = confidence is not None
-    kw = dict(confidence=confidence) if want else {}  # `propagate` returns a fourth entry only when asked
-    T, (H, W), (oh, ow) = seq_length, patch_size, overlap
-    N = dataset[0].shape[1]
-    rg_len = T * (W - ow) + ow
-    rg_h = N * (H - oh) + oh
-    idx = list(range(0, len(dataset), T))
-    n_rg = min(len(idx), seg.shape[-1] // rg_len)
-    idx = idx[:n_rg]
-    seg = seg[:, :n_rg * rg_len].to(device)
-    rows = seg.shape[0]
     if upsample == 'bilinear':
-        return _segment_dense(dataset, seg, encoder, lp, nclasses, T, W, ow, N, rg_len, rg_h, idx, pos_embed, correction, use_last,
-                              dataset_id, device, confidence, merge)
+        kw = dict(soft=True)
 
-    maps, cmaps, xents, changes = [], [], [], []
-    for t, i in enumerate(idx):
-        seq = dataset[i].to(device)
-        seg_ref = seg[:rg_h, rg_len * t:rg_len * t + W]
-        pred, xent, change, *conf = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=False, **kw)
-        maps.append(_upsample(pred, rows, rg_len))
-        if want:
-            cmaps.append(_upsample(conf[0], rows, rg_len))
-        xents.append(xent)
-        changes.append(change)
-
-    if correction:
-        for t, change in enumerate(changes):
-            if change is None:
-                continue
-            small = T - change
-            px = small * (W - ow)
-            try:  # like the reference, a correction that fails on its DATA (shape / index errors) is skipped silently ...
-                seq = dataset.get_smaller_item(idx[t], small).to(device)  # first `small` columns; shortens the dataset
-                seg_ref = seg[:, rg_len * t + rg_len - px:rg_len * t + rg_len - px + W]
-                pred, _, _, *conf = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=False, **kw)
-                tail = _upsample(conf[0], rows, px) if want else None
-                maps[t][:, rg_len - px:] = _upsample(pred, rows, px)
-                if want:  # the same window as the labels: spliced when they were, skipped when they were
-                    cmaps[t][:, rg_len - px:] = tail
-            except crw_hip.CrwError as e:
-                # ... but a failure of the HIP path itself (CRW_EHIP: launch failure / GPU fault, CRW_EWORKSPACE) is not a data
-                # problem: the reference's bare `except` would hide a poisoned device context behind an uncorrected map.
-                # CRW_EINVAL (a degenerate correction window: bad shape / unsupported size) IS the data and is skipped
-                if e.device_failure:
-                    raise
-            except torch.AcceleratorError:  # the device runtime's own errors (hipError* raised by PyTorch)
-                raise
-            except Exception:
-                pass
-
-    forward = torch.cat(maps, dim=1)
-    forward_conf = torch.cat(cmaps, dim=1) if want else None
-    final, final_conf = forward, forward_conf
-    if use_last:
-        rev_maps, rev_cmaps = [], []
-        seg_rev = torch.flip(seg.unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
-        for t, i in enumerate(idx):
-            seq = dataset[i].to(device)
-            seg_ref = seg_rev[:, rg_len * t:rg_len * t + W]
-            pred, _, _, *conf = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=True, **kw)
-            rev_maps.append(_upsample(pred, rows, rg_len))
-            if want:
-                rev_cmaps.append(_upsample(conf[0], rows, rg_len))
-        unflip = lambda m: torch.flip(torch.cat(m, dim=1).unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
-        rev = unflip(rev_maps)
-        if merge == 'confidence':
-            final, final_conf, _ = crw_hip.merge_confidence(forward, forward_conf, rev, unflip(rev_cmaps))
-        else:
-            final = merge_reverse(forward, rev, dataset_id)
-            if want:
-                ruled = _reverse_rule_mask(forward, rev, dataset_id).view_as(forward)
-                final_conf = torch.where(ruled, unflip(rev_cmaps), forward_conf)
-    out = dict(pred=final, forward=forward, xent=xents, change_idx=changes)
-    if want:
-        out.update(conf=final_conf, forward_conf=forward_conf)
-    return out
-
-
-def _segment_dense(dataset, seg, encoder, lp, nclasses, T, W, ow, N, rg_len, rg_h, idx, pos_embed, correction, use_last, dataset_id,
-                   device, confidence, merge):
-    """`segment(..., upsample='bilinear')` behind its argument checks: `segment`'s passes with every map written by
-    `crw_hip.labelmap_dense` from the pass's soft labels.  The maps are allocated ONCE at [rows, n_rg * rg_len] and every pass
-    writes its own column window: the forward pass its radargram's, a correction the last ``px`` columns of it -- only after its
-    `propagate` succeeded --, the reverse pass its radargram's, mirrored (``flip``).  No list of maps, no cat, no flip."""
-    want = confidence is not None
-    rows, n_rg = seg.shape[0], len(idx)
-    new = lambda: torch.empty(rows, n_rg * rg_len, device=device)
-
-    def dense(L, frames, out, out_conf, flip=False):
-        crw_hip.labelmap_dense(L, frames, N, nclasses, rows, out.shape[1], confidence=confidence, flip=flip, out=out,
-                               out_conf=out_conf)
-
-    forward, forward_conf = new(), (new() if want else None)
-    win = lambda m, a, b: m[:, a:b] if m is not None else None
-    xents, changes = [], []
-    for t, i in enumerate(idx):
-        seq = dataset[i].to(device)
-        seg_ref = seg[:rg_h, rg_len * t:rg_len * t + W]
-        _, xent, change, L = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=False, soft=True)
-        dense(L, seq.shape[0], win(forward, rg_len * t, rg_len * (t + 1)), win(forward_conf, rg_len * t, rg_len * (t + 1)))
-        xents.append(xent)
-        changes.append(change)
-
-    if correction:
-        for t, change in enumerate(changes):
-            if change is None:
-                continue
-            small = T - change
-            px = small * (W - ow)
-            try:  # `segment`'s policy: a correction that fails on its data is skipped, a failure of the HIP path is not
-                seq = dataset.get_smaller_item(idx[t], small).to(device)
-                seg_ref = seg[:, rg_len * t + rg_len - px:rg_len * t + rg_len - px + W]
-                _, _, _, L = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=False, soft=True)
-                a, b = rg_len * t + rg_len - px, rg_len * (t + 1)
-                dense(L, seq.shape[0], win(forward, a, b), win(forward_conf, a, b))
-            except crw_hip.CrwError as e:
-                if e.device_failure:
-                    raise
-            except torch.AcceleratorError:
-                raise
-            except Exception:
-                pass
-
-    final, final_conf = forward, forward_conf
-    if use_last:
-        rev, rev_conf = new(), (new() if want else None)
-        seg_rev = torch.flip(seg.unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
-        for t, i in enumerate(idx):
-            seq = dataset[i].to(device)
-            seg_ref = seg_rev[:, rg_len * t:rg_len * t + W]
-            _, _, _, L = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=True, soft=True)
-            dense(L, seq.shape[0], win(rev, rg_len * t, rg_len * (t + 1)), win(rev_conf, rg_len * t, rg_len * (t + 1)), flip=True)
-        if merge == 'confidence':
-            final, final_conf, _ = crw_hip.merge_confidence(forward, forward_conf, rev, rev_conf)
-        else:
-            final = merge_reverse(forward, rev, dataset_id)
-            if want:
-                ruled = _reverse_rule_mask(forward, rev, dataset_id).view_as(forward)
-                final_conf = torch.where(ruled, rev_conf, forward_conf)
-    out = dict(pred=final, forward=forward, xent=xents, change_idx=changes)
-    if want:
-        out.update(conf=final_conf, forward_conf=forward_conf)
-    return out
-
-
-def _reverse_rule_mask_batch(final_pred, pred_rev, dataset_id):
-    """`_reverse_rule_mask` on [G, rows, cols] maps -> bool [G, rows, cols]."""
-    G = pred_rev.shape[0]
-    mask = pred_rev == 2
-    if dataset_id == 1:
-        mask = torch.logical_and(mask, final_pred != 3)
-        mask = torch.logical_and(mask, torch.all(pred_rev != 4, dim=1, keepdim=True))
-    elif dataset_id == 3:
-        mask = mask.clone()
-        mask.view(G, -1)[:, :mask[0].numel() // 2] = False
-    elif dataset_id != 0:
-        raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
-    return mask
-
-
-def merge_reverse_batch(final_pred, pred_rev, dataset_id):
-    """`merge_reverse` on [G, rows, cols] maps, configuration by configuration."""
-    mask = _reverse_rule_mask_batch(final_pred, pred_rev, dataset_id)
-    out = final_pred.clone()
-    out[mask] = 2
-    return out
-
-
-def _upsample_batch(pred, rows, cols):
-    """[G, N, T] node labels -> [G, rows, cols] int8 pixel labels (nearest, the dtype the reference saves)."""
-    return TF.interpolate(pred[:, None].float(), size=(rows, cols), mode='nearest')[:, 0].to(torch.int8)
-
-
-def _upsample_conf_batch(conf, rows, cols):
-    """[G, N, T] node confidences -> [G, rows, cols] float32, `_upsample_batch`'s stretch."""
-    return TF.interpolate(conf[:, None].float(), size=(rows, cols), mode='nearest')[:, 0]
+        def write(res, seq, out, out_conf, flip):  # res[3]: the pass's soft labels L [T*N, M]
+            crw_hip.labelmap_dense(res[3], *seq.shape[:2], nclasses, *out.shape, confidence=confidence, flip=flip, out=out,
+                                   out_conf=out_conf)
+    else:
+        kw = dict(confidence=confidence) if want else {}  # `propagate` returns a fourth entry only when asked
+        write = _write_nearest
+    run = lambda seq, seg_ref, last: propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=last, **kw)
+    return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
+                           write)
 
 
 @torch.no_grad()
@@ -292,158 +219,23 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     [G, rows, n_rg * rg_len] and every pass writes its column window of all G maps with one `crw_hip.labelmap_dense_batch`.
     It holds G-map tensors at once: with confidence, 5 bytes per pixel and configuration for the forward maps, as much again for
     the reverse pass's and for the merge's result."""
-    if merge not in ('rule', 'confidence'):
-        raise ValueError(f"merge must be 'rule' or 'confidence' (got {merge!r})")
-    if upsample not in ('nearest', 'bilinear'):
-        raise ValueError(f"upsample must be 'nearest' or 'bilinear' (got {upsample!r})")
-    if confidence is not None and confidence not in crw_hip.CONF_KINDS:
-        raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
-    if merge == 'confidence' and confidence is None:
-        raise ValueError("merge='confidence' needs a confidence kind (confidence='maxprob', 'margin' or 'entropy')")
+    _check_options(confidence, merge, upsample)
     if merge == 'rule' and dataset_id not in (0, 1, 3) and use_last:
         raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
     want = confidence is not None
-    kw = dict(confidence=confidence) if want else {}  # `propagate_sweep` returns a fourth entry only when asked
-    T, (H, W), (oh, ow) = seq_length, patch_size, overlap
-    N = dataset[0].shape[1]
-    rg_len = T * (W - ow) + ow
-    rg_h = N * (H - oh) + oh
-    idx = list(range(0, len(dataset), T))
-    n_rg = min(len(idx), seg.shape[-1] // rg_len)
-    idx = idx[:n_rg]
-    seg = seg[:, :n_rg * rg_len].to(device)
-    rows = seg.shape[0]
+    G = len(sweep.configs)
     if upsample == 'bilinear':
-        return _segment_sweep_dense(dataset, seg, encoder, sweep, nclasses, T, W, ow, N, rg_len, rg_h, idx, pos_embed, correction,
-                                    use_last, dataset_id, device, confidence, merge)
+        kw = dict(soft=True)
 
-    maps, cmaps, xents, changes = [], [], [], []
-    for t, i in enumerate(idx):
-        seq = dataset[i].to(device)
-        seg_ref = seg[:rg_h, rg_len * t:rg_len * t + W]
-        pred, xent, change, *conf = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False, **kw)
-        maps.append(_upsample_batch(pred, rows, rg_len))
-        if want:
-            cmaps.append(_upsample_conf_batch(conf[0], rows, rg_len))
-        xents.append(xent)
-        changes.append(change)
-
-    if correction:
-        for t, change in enumerate(changes):
-            if change is None:
-                continue
-            small = T - change
-            px = small * (W - ow)
-            try:  # the policy of `segment`: data errors are skipped, failures of the HIP path are not
-                seq = dataset.get_smaller_item(idx[t], small).to(device)
-                seg_ref = seg[:, rg_len * t + rg_len - px:rg_len * t + rg_len - px + W]
-                pred, _, _, *conf = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False, **kw)
-                tail = _upsample_conf_batch(conf[0], rows, px) if want else None
-                maps[t][:, :, rg_len - px:] = _upsample_batch(pred, rows, px)
-                if want:  # the same window as the labels: spliced when they were, skipped when they were
-                    cmaps[t][:, :, rg_len - px:] = tail
-            except crw_hip.CrwError as e:
-                if e.device_failure:
-                    raise
-            except torch.AcceleratorError:
-                raise
-            except Exception:
-                pass
-
-    forward = torch.cat(maps, dim=2)
-    forward_conf = torch.cat(cmaps, dim=2) if want else None
-    final, final_conf = forward, forward_conf
-    if use_last:
-        rev_maps, rev_cmaps = [], []
-        seg_rev = torch.flip(seg.unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
-        for t, i in enumerate(idx):
-            seq = dataset[i].to(device)
-            seg_ref = seg_rev[:, rg_len * t:rg_len * t + W]
-            pred, _, _, *conf = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=True, **kw)
-            rev_maps.append(_upsample_batch(pred, rows, rg_len))
-            if want:
-                rev_cmaps.append(_upsample_conf_batch(conf[0], rows, rg_len))
-        rev = torch.cat(rev_maps, dim=2).unfold(2, rg_len, rg_len)
-        rev = torch.flip(rev, (-1,)).reshape(rev.shape[0], rows, -1)
-        if want:
-            rev_conf = torch.cat(rev_cmaps, dim=2).unfold(2, rg_len, rg_len)
-            rev_conf = torch.flip(rev_conf, (-1,)).reshape(rev_conf.shape[0], rows, -1)
-        if merge == 'confidence':
-            final, final_conf, _ = crw_hip.merge_confidence(forward, forward_conf, rev, rev_conf)
-        else:
-            final = merge_reverse_batch(forward, rev, dataset_id)
-            if want:
-                final_conf = torch.where(_reverse_rule_mask_batch(forward, rev, dataset_id), rev_conf, forward_conf)
-    out = dict(pred=final, forward=forward, xent=xents, change_idx=changes, configs=list(sweep.configs))
-    if want:
-        out.update(conf=final_conf, forward_conf=forward_conf)
-    return out
-
-
-def _segment_sweep_dense(dataset, seg, encoder, sweep, nclasses, T, W, ow, N, rg_len, rg_h, idx, pos_embed, correction, use_last,
-                         dataset_id, device, confidence, merge):
-    """`segment_sweep(..., upsample='bilinear')` behind its argument checks: `_segment_dense`'s passes with the G maps of a pass
-    written by ONE `crw_hip.labelmap_dense_batch` from the pass's soft labels L [G, T*N, M] into the pass's column window of maps
-    allocated once at [G, rows, n_rg * rg_len] (int8; float32 confidences) -- a correction's only after its `propagate_sweep`
-    succeeded, the reverse pass's mirrored.  Instead of G x passes launches of a few MB each."""
-    want = confidence is not None
-    G, rows, n_rg = len(sweep.configs), seg.shape[0], len(idx)
-    new = lambda dtype: torch.empty(G, rows, n_rg * rg_len, dtype=dtype, device=device)
-
-    def dense(L, frames, out, out_conf, flip=False):
-        crw_hip.labelmap_dense_batch(L, G, frames, N, nclasses, rows, out.shape[2], confidence=confidence, flip=flip,
-                                     dtype=torch.int8, out=out, out_conf=out_conf)
-
-    forward, forward_conf = new(torch.int8), (new(torch.float32) if want else None)
-    win = lambda m, a, b: m[:, :, a:b] if m is not None else None
-    xents, changes = [], []
-    for t, i in enumerate(idx):
-        seq = dataset[i].to(device)
-        seg_ref = seg[:rg_h, rg_len * t:rg_len * t + W]
-        _, xent, change, L = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False, soft=True)
-        dense(L, seq.shape[0], win(forward, rg_len * t, rg_len * (t + 1)), win(forward_conf, rg_len * t, rg_len * (t + 1)))
-        xents.append(xent)
-        changes.append(change)
-
-    if correction:
-        for t, change in enumerate(changes):
-            if change is None:
-                continue
-            small = T - change
-            px = small * (W - ow)
-            try:  # `segment`'s policy: a correction that fails on its data is skipped, a failure of the HIP path is not
-                seq = dataset.get_smaller_item(idx[t], small).to(device)
-                seg_ref = seg[:, rg_len * t + rg_len - px:rg_len * t + rg_len - px + W]
-                _, _, _, L = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=False, soft=True)
-                a, b = rg_len * t + rg_len - px, rg_len * (t + 1)
-                dense(L, seq.shape[0], win(forward, a, b), win(forward_conf, a, b))
-            except crw_hip.CrwError as e:
-                if e.device_failure:
-                    raise
-            except torch.AcceleratorError:
-                raise
-            except Exception:
-                pass
-
-    final, final_conf = forward, forward_conf
-    if use_last:
-        rev, rev_conf = new(torch.int8), (new(torch.float32) if want else None)
-        seg_rev = torch.flip(seg.unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
-        for t, i in enumerate(idx):
-            seq = dataset[i].to(device)
-            seg_ref = seg_rev[:, rg_len * t:rg_len * t + W]
-            _, _, _, L = propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=True, soft=True)
-            dense(L, seq.shape[0], win(rev, rg_len * t, rg_len * (t + 1)), win(rev_conf, rg_len * t, rg_len * (t + 1)), flip=True)
-        if merge == 'confidence':
-            final, final_conf, _ = crw_hip.merge_confidence(forward, forward_conf, rev, rev_conf)
-        else:
-            final = merge_reverse_batch(forward, rev, dataset_id)
-            if want:
-                final_conf = torch.where(_reverse_rule_mask_batch(forward, rev, dataset_id), rev_conf, forward_conf)
-    out = dict(pred=final, forward=forward, xent=xents, change_idx=changes, configs=list(sweep.configs))
-    if want:
-        out.update(conf=final_conf, forward_conf=forward_conf)
-    return out
+        def write(res, seq, out, out_conf, flip):  # res[3]: the pass's soft labels L [G, T*N, M]; ONE launch for the G maps
+            crw_hip.labelmap_dense_batch(res[3], G, *seq.shape[:2], nclasses, *out.shape[1:], confidence=confidence, flip=flip,
+                                         dtype=torch.int8, out=out, out_conf=out_conf)
+    else:
+        kw = dict(confidence=confidence) if want else {}  # `propagate_sweep` returns a fourth entry only when asked
+        write = _write_nearest
+    run = lambda seq, seg_ref, last: propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=last, **kw)
+    return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
+                           write, lead=(G,), dtype=torch.int8, configs=list(sweep.configs))
 
 
 @torch.no_grad()
@@ -495,6 +287,33 @@ def _report_rules(pred, seg, dataset_id, remove_unc, unc_seg, nclasses):
     return K, seg, mask
 
 
+def _dropped(tail, K):
+    """The drop counts that end a report's host row, as a list; a label outside 0 ... K-1 that survived the mask raises."""
+    dropped = [int(v) for v in tail]
+    if dropped[1]:
+        raise crw_hip.LabelError(dropped[1], K)
+    return dropped
+
+
+def _host_rows(outs):
+    """What G queued kernel calls returned (per call: integer tensors that end in the drop counts) -> [G, numbers per map] on the
+    host, in ONE copy; no call, no copy."""
+    return torch.stack([torch.cat([t.reshape(-1) for t in out]) for out in outs]).cpu() if outs else []
+
+
+def _calibration_of(row, nb, K):
+    """A host row of `crw_hip.calibration`'s outputs (counts [nb, 2], the bit pattern of conf_sum [nb], dropped [3])."""
+    from metrics import Calibration
+    return Calibration(row[:2 * nb].view(nb, 2), row[2 * nb:3 * nb].view(torch.float64), _dropped(row[3 * nb:], K))
+
+
+def _horizons_of(row, K, shape, min_run, tol, row_spacing, unit):
+    """A host row of `crw_hip.horizons`'s outputs (statistics [K, 18], dropped [2]) for a map of ``shape`` [rows, cols]."""
+    from metrics import Horizons
+    return Horizons(row[:18 * K].view(K, 18), _dropped(row[18 * K:], K), shape[0], shape[1], min_run, tol, row_spacing=row_spacing,
+                    unit=unit)
+
+
 def evaluate(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None):
     """The report of test_all.py:161-187 for a label map ``pred`` (``segment(...)['pred']``, or a saved int8 map) against the
     reference segmentation ``seg`` cut to the same columns -> ``metrics.Report``.
@@ -508,10 +327,7 @@ def evaluate(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None
     from metrics import Report
     K, seg, mask = _report_rules(pred, seg, dataset_id, remove_unc, unc_seg, nclasses)
     counts, dropped = crw_hip.confusion(seg, pred, K, **mask)
-    dropped = [int(v) for v in dropped.cpu()]
-    if dropped[1]:
-        raise crw_hip.LabelError(dropped[1], K)
-    return Report(counts, dropped)
+    return Report(counts, _dropped(dropped.cpu(), K))
 
 
 def calibration(pred, conf, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None, bins=10):
@@ -520,17 +336,12 @@ def calibration(pred, conf, seg, dataset_id, remove_unc=True, unc_seg=None, ncla
     confidence, ECE / MCE, the risk-coverage curve).  `evaluate`'s arguments and mask rules, passed through as arguments of the one
     ``crw_hip.calibration`` call: the pixels it bins are the pixels `evaluate` counts.  A surviving label outside 0 ... K-1 raises
     ``crw_hip.LabelError``; a surviving confidence that is NaN or outside [0, 1] is counted in ``dropped[2]`` and binned nowhere."""
-    from metrics import Calibration
     K, seg, mask = _report_rules(pred, seg, dataset_id, remove_unc, unc_seg, nclasses)
     if conf.numel() != pred.numel():
         raise ValueError(f'conf {tuple(conf.shape)} and pred {tuple(pred.shape)} must cover the same pixels')
     counts, conf_sum, dropped = crw_hip.calibration(seg, pred, conf.to(pred.device), K, bins=bins, **mask)
     host = torch.cat([counts.reshape(-1), conf_sum.view(torch.int64), dropped]).cpu()  # the one copy: 3 * bins + 3 numbers
-    nb = conf_sum.numel()
-    dropped = [int(v) for v in host[3 * nb:]]
-    if dropped[1]:
-        raise crw_hip.LabelError(dropped[1], K)
-    return Calibration(host[:2 * nb].view(nb, 2), host[2 * nb:3 * nb].view(torch.float64), dropped)
+    return _calibration_of(host, conf_sum.numel(), K)
 
 
 def evaluate_sweep(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None):
@@ -538,32 +349,11 @@ def evaluate_sweep(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasse
     ``metrics.Report``: G `crw_hip.confusion` calls queued back to back, ONE copy of all counts to the host at the end.  Same mask
     rules; a label outside 0 ... K-1 that survives the mask in any map raises ``crw_hip.LabelError``."""
     from metrics import Report
-    if dataset_id not in (0, 1, 3):
-        raise ValueError(f'no report rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
-    K = NCLASSES[dataset_id] if nclasses is None else int(nclasses)
     if pred.dim() < 2 or pred[0].numel() != seg.numel():
         raise ValueError(f'pred {tuple(pred.shape)} must be G maps covering the pixels of seg {tuple(seg.shape)}')
-    seg = seg.to(pred.device)
-    mask = {}
-    if remove_unc and dataset_id == 0:
-        if unc_seg is None:
-            raise ValueError('dataset 0 with remove_unc needs unc_seg (the dataset-2 reference map, same columns)')
-        if unc_seg.numel() != seg.numel():
-            raise ValueError(f'unc_seg {tuple(unc_seg.shape)} and seg {tuple(seg.shape)} must cover the same pixels')
-        mask = dict(aux=unc_seg.to(pred.device), ignore_aux=4)
-    elif remove_unc and dataset_id == 1:
-        mask = dict(ignore_gt=5, ignore_pred=5)
-    outs = [crw_hip.confusion(seg, p, K, **mask) for p in pred]
-    if not outs:
-        return []
-    host = torch.stack([torch.cat([c.reshape(-1), d]) for c, d in outs]).cpu()  # [G, K*K + 2]
-    reports = []
-    for row in host:
-        dropped = [int(v) for v in row[K * K:]]
-        if dropped[1]:
-            raise crw_hip.LabelError(dropped[1], K)
-        reports.append(Report(row[:K * K].view(K, K), dropped))
-    return reports
+    K, seg, mask = _report_rules(pred[0], seg, dataset_id, remove_unc, unc_seg, nclasses)
+    host = _host_rows([crw_hip.confusion(seg, p, K, **mask) for p in pred])  # [G, K*K + 2]
+    return [Report(row[:K * K].view(K, K), _dropped(row[K * K:], K)) for row in host]
 
 
 def calibration_sweep(pred, conf, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None, bins=10):
@@ -571,7 +361,6 @@ def calibration_sweep(pred, conf, seg, dataset_id, remove_unc=True, unc_seg=None
     ``metrics.Calibration``: G `crw_hip.calibration` calls queued back to back, ONE copy of all histograms to the host at the end,
     like `evaluate_sweep`.  Same mask rules; a label outside 0 ... K-1 that survives the mask in any map raises
     ``crw_hip.LabelError``."""
-    from metrics import Calibration
     if pred.dim() < 2 or pred[0].numel() != seg.numel():
         raise ValueError(f'pred {tuple(pred.shape)} must be G maps covering the pixels of seg {tuple(seg.shape)}')
     K, seg, mask = _report_rules(pred[0], seg, dataset_id, remove_unc, unc_seg, nclasses)
@@ -579,17 +368,8 @@ def calibration_sweep(pred, conf, seg, dataset_id, remove_unc=True, unc_seg=None
         raise ValueError(f'conf {tuple(conf.shape)} and pred {tuple(pred.shape)} must cover the same pixels')
     conf = conf.to(pred.device)
     outs = [crw_hip.calibration(seg, p, c, K, bins=bins, **mask) for p, c in zip(pred, conf)]
-    if not outs:
-        return []
-    host = torch.stack([torch.cat([n.reshape(-1), s.view(torch.int64), d]) for n, s, d in outs]).cpu()  # [G, 3 * bins + 3]
-    nb = outs[0][1].numel()
-    cals = []
-    for row in host:
-        dropped = [int(v) for v in row[3 * nb:]]
-        if dropped[1]:
-            raise crw_hip.LabelError(dropped[1], K)
-        cals.append(Calibration(row[:2 * nb].view(nb, 2), row[2 * nb:3 * nb].view(torch.float64), dropped))
-    return cals
+    host = _host_rows([(n, s.view(torch.int64), d) for n, s, d in outs])  # [G, 3 * bins + 3]
+    return [_calibration_of(row, outs[0][1].numel(), K) for row in host]
 
 
 def _map2d(t, like):
@@ -605,17 +385,13 @@ def horizons(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None
     arguments of the one ``crw_hip.horizons`` call: the pixels it sees are the pixels `evaluate` counts.  ``min_run``: the
     shortest run of equal labels down a column that counts as a layer (1: any pixel); ``tol``: the rows within which a pick counts
     as right.  A surviving label outside 0 ... K-1 raises ``crw_hip.LabelError``."""
-    from metrics import Horizons
     K, seg, mask = _report_rules(pred, seg, dataset_id, remove_unc, unc_seg, nclasses)
     if pred.dim() != 2:
         raise ValueError(f'pred must be a [rows, cols] map (got shape {tuple(pred.shape)})')
     mask = {k: (_map2d(v, pred) if torch.is_tensor(v) else v) for k, v in mask.items()}
     out = crw_hip.horizons(_map2d(seg, pred), pred, K, min_run=min_run, tol=tol, want_picks=want_picks, **mask)
     host = torch.cat([out[0].reshape(-1), out[1]]).cpu()  # the one copy: 18 K + 2 integers
-    dropped = [int(v) for v in host[18 * K:]]
-    if dropped[1]:
-        raise crw_hip.LabelError(dropped[1], K)
-    hz = Horizons(host[:18 * K].view(K, 18), dropped, pred.shape[0], pred.shape[1], min_run, tol, row_spacing=row_spacing, unit=unit)
+    hz = _horizons_of(host, K, pred.shape, min_run, tol, row_spacing, unit)
     return (hz, out[2]) if want_picks else hz
 
 
@@ -624,24 +400,13 @@ def horizons_sweep(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasse
     """`horizons` for the G maps of `segment_sweep` (pred [G, rows, cols]) -> G ``metrics.Horizons``: G `crw_hip.horizons` calls
     queued back to back, ONE copy of all statistics to the host at the end, like `evaluate_sweep`.  Same mask rules; a label
     outside 0 ... K-1 that survives the mask in any map raises ``crw_hip.LabelError``."""
-    from metrics import Horizons
     if pred.dim() != 3 or pred[0].numel() != seg.numel():
         raise ValueError(f'pred {tuple(pred.shape)} must be G [rows, cols] maps covering the pixels of seg {tuple(seg.shape)}')
     K, seg, mask = _report_rules(pred[0], seg, dataset_id, remove_unc, unc_seg, nclasses)
     mask = {k: (_map2d(v, pred) if torch.is_tensor(v) else v) for k, v in mask.items()}
     seg = _map2d(seg, pred)
-    outs = [crw_hip.horizons(seg, p, K, min_run=min_run, tol=tol, **mask) for p in pred]
-    if not outs:
-        return []
-    host = torch.stack([torch.cat([s.reshape(-1), d]) for s, d in outs]).cpu()  # [G, 18 K + 2]
-    res = []
-    for row in host:
-        dropped = [int(v) for v in row[18 * K:]]
-        if dropped[1]:
-            raise crw_hip.LabelError(dropped[1], K)
-        res.append(Horizons(row[:18 * K].view(K, 18), dropped, pred.shape[1], pred.shape[2], min_run, tol, row_spacing=row_spacing,
-                            unit=unit))
-    return res
+    host = _host_rows([crw_hip.horizons(seg, p, K, min_run=min_run, tol=tol, **mask) for p in pred])  # [G, 18 K + 2]
+    return [_horizons_of(row, K, pred.shape[1:], min_run, tol, row_spacing, unit) for row in host]
 
 
 # the reference's three per-dataset drivers (scripts/test/test_mc1.py:19-30, test_mc3.py:19-33, test_sharad.py:19-32): argparse
