@@ -33,6 +33,8 @@
  *                                                                                node map with Resize(NEAREST): no twin there)
  *   crw_labelmap_dense_batch  the same map for every configuration of a sweep     (no twin: scripts/launch/launch_test_batch.sh
  *                             in one launch                                       runs test_all.py per setting, nearest maps)
+ *   crw_labelmap_ordered[_batch]  the same interpolated probabilities decoded      (no twin: no script of the reference uses the
+ *                             under a layer order, a DP per pixel column          order of the layers down a trace)
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HBM) unless its name ends in _host;
@@ -61,7 +63,8 @@ extern "C" {
  * crw_labelprop_propagate_batch; then crw_labelprop_confidence, crw_merge_confidence, crw_calibration_ws_bytes, crw_calibration
  * (crw_hip.has_confidence()); then crw_labelmap_dense (crw_hip.has_dense()); then crw_labelmap_dense_batch
  * (crw_hip.has_dense_batch()); then crw_horizons_ws_bytes, crw_horizons (crw_hip.has_horizons()); then
- * crw_labelprop_propagate_sliding, crw_labelprop_propagate_sliding_batch (crw_hip.has_sliding()).  The ONE place the number is
+ * crw_labelprop_propagate_sliding, crw_labelprop_propagate_sliding_batch (crw_hip.has_sliding()); then
+ * crw_labelmap_ordered_workspace, crw_labelmap_ordered, crw_labelmap_ordered_batch (crw_hip.has_ordered()).  The ONE place the number is
  * written: crw_abi_version() returns it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
 #define CRW_ABI_VERSION 8
@@ -314,6 +317,33 @@ int crw_labelmap_dense(const float *L, int T, int N, int M, int rows, int cols, 
  * bit-reproducible. */
 int crw_labelmap_dense_batch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
                              int label_dtype, float *conf, size_t ld, size_t map_stride, crw_stream_t stream);
+
+/* Depth-ordered label maps: crw_labelmap_dense's interpolated probabilities v (the same device function, bit for bit), decoded
+ * per pixel column under a layer order instead of arg-maxed pixel by pixel.  order_host: S distinct classes of 0 ... M-1, top to
+ * bottom (a HOST array, read before the launch and passed to the kernel by value), 2 <= S <= M; a class outside it is never
+ * written.  With e[r][s] = v[r][c][order[s]], per column c, in fp32, one rounded add per row:
+ *   D[0][s] = e[0][s];   D[r][s] = e[r][s] + max_{s' <= s} D[r-1][s'],  predecessor: the LOWEST s' that attains the prefix maximum;
+ *   last state: the LOWEST s that attains max_s D[rows-1][s];  backtrack;  label[r] = order[state[r]].
+ * The labels of a column never step back in `order`; a column may start and end in any state, a layer may be absent.  The score is
+ * the SUM of the probabilities (the expected number of right pixels), not of their logarithms: seed frames are one-hot, L holds
+ * exact zeros.  Back-pointers: one bit per (row, state), "state s is a new prefix maximum" (strict >), a uint16 per pixel --
+ * pred(s) is the highest set bit <= s, because the prefix arg-max does not decrease with s.  They live in `ws`
+ * (crw_labelmap_ordered_workspace(G, rows, cols) bytes, 2-byte aligned; its layout is the kernel's; what it held before is never
+ * read): too few bytes -> CRW_EWORKSPACE.  conf (conf_kind as for crw_labelmap_dense) is the confidence of the interpolated row,
+ * bit for bit what crw_labelmap_dense writes: it does not depend on the decode.  labels / conf / ld / flip / label_dtype and every
+ * limit: crw_labelmap_dense's; in addition order_host and ws non-null, its entries distinct and in range, 2 <= S <= M -- all
+ * refused (CRW_EINVAL) before anything is launched.  One launch, one route for every size: a lane per column, a wave per 64
+ * columns, rows steps in series; plain vector stores, no atomics, bit-reproducible. */
+size_t crw_labelmap_ordered_workspace(int G, int rows, int cols);
+int crw_labelmap_ordered(const float *L, int T, int N, int M, int rows, int cols, int flip, const int *order_host, int S,
+                         int conf_kind, void *labels, int label_dtype, float *conf, size_t ld, void *ws, size_t ws_bytes,
+                         crw_stream_t stream);
+/* crw_labelmap_ordered for the G configurations of a sweep's pass in ONE launch (the configuration is a grid dimension): L, the
+ * windows, l_stride = T*N*M and map_stride as for crw_labelmap_dense_batch, one `order` for all.  Slice g is bit-identical to
+ * crw_labelmap_ordered(L + g*T*N*M, ...) written into the same window. */
+int crw_labelmap_ordered_batch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, const int *order_host,
+                               int S, int conf_kind, void *labels, int label_dtype, float *conf, size_t ld, size_t map_stride,
+                               void *ws, size_t ws_bytes, crw_stream_t stream);
 
 /* building blocks exported for tests and the roofline bench --------------------------------- */
 /* Weight gradient of the CNN encoder's linear head (nn.Linear(128, 128), src/encoder.py:40,55; autograd of

@@ -68,6 +68,9 @@ SIGNATURES = {
                                  _c_sz, _p]),
     "crw_labelmap_dense": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _c_int, _p, _c_sz, _p]),
     "crw_labelmap_dense_batch": (_c_int, [_p] + [_c_int] * 8 + [_p, _c_int, _p, _c_sz, _c_sz, _p]),
+    "crw_labelmap_ordered_workspace": (_c_sz, [_c_int, _c_int, _c_int]),
+    "crw_labelmap_ordered": (_c_int, [_p] + [_c_int] * 6 + [_p, _c_int, _c_int, _p, _c_int, _p, _c_sz, _p, _c_sz, _p]),
+    "crw_labelmap_ordered_batch": (_c_int, [_p] + [_c_int] * 7 + [_p, _c_int, _c_int, _p, _c_int, _p, _c_sz, _c_sz, _p, _c_sz, _p]),
     "crw_linear128_wgrad_ws_bytes": (_c_sz, [_c_int]),
     "crw_linear128_wgrad": (_c_int, [_p, _p, _p, _c_int, _p, _c_sz, _p]),
     "crw_adam_step": (_c_int, [_p, _p, _p, _p, ctypes.c_long, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
@@ -154,11 +157,15 @@ HORIZONS_ENTRY_POINTS = ("crw_horizons_ws_bytes", "crw_horizons")
 # likewise: label propagation from the scored frames, the 'sliding' context rule (`has_sliding()`)
 SLIDING_ENTRY_POINTS = ("crw_labelprop_propagate_sliding", "crw_labelprop_propagate_sliding_batch")
 
+# likewise: depth-ordered label maps (`has_ordered()`)
+ORDERED_ENTRY_POINTS = ("crw_labelmap_ordered_workspace", "crw_labelmap_ordered", "crw_labelmap_ordered_batch")
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 
 _lib = None
 _has_horizons = False
 _has_sliding = False
+_has_ordered = False
 _has_sweep = False
 _has_confidence = False
 _has_dense = False
@@ -168,14 +175,14 @@ _has_dense_batch = False
 def lib():
     """Load the HIP library (once).  Raises if it has not been built: `python -c 'import
     __graft_entry__ as g; g.build()'` or `make -C radar-sounder-crw_amd/csrc`."""
-    global _lib, _has_sweep, _has_confidence, _has_dense, _has_dense_batch, _has_horizons, _has_sliding
+    global _lib, _has_sweep, _has_confidence, _has_dense, _has_dense_batch, _has_horizons, _has_sliding, _has_ordered
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} not built -- the CRW hot path has no CPU/PyTorch fallback; "
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
         missing = [n for n in SWEEP_ENTRY_POINTS + CONFIDENCE_ENTRY_POINTS + DENSE_ENTRY_POINTS + DENSE_BATCH_ENTRY_POINTS
-                   + HORIZONS_ENTRY_POINTS + SLIDING_ENTRY_POINTS if not hasattr(handle, n)]
+                   + HORIZONS_ENTRY_POINTS + SLIDING_ENTRY_POINTS + ORDERED_ENTRY_POINTS if not hasattr(handle, n)]
         for name, (res, args) in SIGNATURES.items():
             if name in missing:
                 continue
@@ -191,6 +198,7 @@ def lib():
         _has_dense_batch = not set(missing) & set(DENSE_BATCH_ENTRY_POINTS)
         _has_horizons = not set(missing) & set(HORIZONS_ENTRY_POINTS)
         _has_sliding = not set(missing) & set(SLIDING_ENTRY_POINTS)
+        _has_ordered = not set(missing) & set(ORDERED_ENTRY_POINTS)
     return _lib
 
 
@@ -269,6 +277,19 @@ def _sliding_lib():
     if not has_sliding():
         raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
                            f"{', '.join(SLIDING_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
+    return lib()
+
+
+def has_ordered():
+    """True when the loaded library exports the depth-ordered label map's entry points (ORDERED_ENTRY_POINTS)."""
+    lib()
+    return _has_ordered
+
+
+def _ordered_lib():
+    if not has_ordered():
+        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
+                           f"{', '.join(ORDERED_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
     return lib()
 
 
@@ -1045,6 +1066,135 @@ def _labelmap_dense_cpu(L, T, N, M, rows, cols, confidence, flip):
     if confidence is not None:
         conf = _labelprop_confidence_cpu(v.permute(1, 0, 2).reshape(rows * cols, M), cols, rows, M, confidence, 1)
     return lab, conf
+
+
+# ------------------------------------------------------------------------------ depth-ordered label maps
+def check_order(order, M):
+    """`order` of `labelmap_ordered` -> a list of S distinct classes of 0 ... M-1, 2 <= S <= M (ValueError otherwise)."""
+    try:
+        out = [int(k) for k in order]
+    except TypeError:
+        raise ValueError(f"order must be a sequence of classes, top to bottom (got {order!r})") from None
+    if not 2 <= len(out) <= M:
+        raise ValueError(f"order must name 2 ... M = {M} classes (got {len(out)}: {out})")
+    if len(set(out)) != len(out) or min(out) < 0 or max(out) >= M:
+        raise ValueError(f"order must hold distinct classes of 0 ... {M - 1} (got {out})")
+    return out
+
+
+def labelmap_ordered_workspace(G, rows, cols):
+    """Bytes of back-pointer workspace `labelmap_ordered` (G = 1) / `labelmap_ordered_batch` need on the device."""
+    return _ordered_lib().crw_labelmap_ordered_workspace(int(G), int(rows), int(cols))
+
+
+def _labelmap_ordered(L, G, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace):
+    """`labelmap_ordered` (G None: one map, no leading axis) and `labelmap_ordered_batch` behind their signatures."""
+    code = -1 if confidence is None else _conf_kind(confidence)
+    T, N, M, rows, cols = int(T), int(N), int(M), int(rows), int(cols)
+    lead = () if G is None else (int(G),)
+    if lead and not 1 <= lead[0] <= 65535:
+        raise ValueError(f"G must be in 1 ... 65535 (got {lead[0]})")
+    if not 2 <= M <= 16:
+        raise ValueError(f"M must be in 2 ... 16 (got {M})")
+    order = check_order(order, M)
+    if T < 1 or N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
+        raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={T}, N={N}, rows={rows}, cols={cols})")
+    if L.numel() != (lead[0] if lead else 1) * T * N * M or L.dtype != torch.float32:
+        raise ValueError(f"L must be float32 {[*lead, T * N, M]} (got {L.dtype} {tuple(L.shape)})")
+    if dtype not in (torch.float32, torch.int8):
+        raise ValueError(f"dtype must be torch.float32 or torch.int8 (got {dtype})")
+    if out_conf is not None and confidence is None:
+        raise ValueError("out_conf needs a confidence kind")
+    if out is None:
+        out = torch.empty(*lead, rows, cols, dtype=dtype, device=L.device)
+    if out_conf is None and confidence is not None:
+        out_conf = torch.empty(*lead, rows, cols, dtype=torch.float32, device=L.device)
+    ld, map_stride = _window(out, "out", lead, rows, cols, dtype, L.device)
+    if out_conf is not None:
+        cld, cstride = _window(out_conf, "out_conf", lead, rows, cols, torch.float32, L.device)
+        if cld != ld and rows > 1:
+            raise ValueError(f"out and out_conf must share one pitch (got {out.stride(-2)} and {out_conf.stride(-2)})")
+        if cstride != map_stride:
+            raise ValueError(f"out and out_conf must share one map stride (got {out.stride(0)} and {out_conf.stride(0)})")
+    L = L.contiguous()
+    if not L.is_cuda:
+        maps, confs = (out, out_conf) if lead else (out[None], None if out_conf is None else out_conf[None])
+        for g, Lg in enumerate(L.view(-1, T * N, M)):
+            lab, conf = _labelmap_ordered_cpu(Lg, T, N, M, rows, cols, order, confidence, flip)
+            maps[g].copy_(lab.to(dtype))
+            if confs is not None:
+                confs[g].copy_(conf)
+        return out, out_conf
+    clib = _ordered_lib()
+    need = clib.crw_labelmap_ordered_workspace(lead[0] if lead else 1, rows, cols)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=L.device)
+    elif workspace.device != L.device or not workspace.is_contiguous():
+        raise ValueError(f"workspace must be a contiguous tensor on {L.device} (got {workspace.device})")
+    ws_bytes = workspace.numel() * workspace.element_size()
+    corder = (ctypes.c_int * len(order))(*order)
+    head = (T, N, M, rows, cols, int(bool(flip)), corder, len(order), code, _ptr(out), DT_F32 if dtype == torch.float32 else DT_I8,
+            _ptr(out_conf) if out_conf is not None else None, ld)
+    tail = (_ptr(workspace), ws_bytes, _stream())
+    if lead:
+        _check(clib.crw_labelmap_ordered_batch(_ptr(L), lead[0], *head, map_stride, *tail), "crw_labelmap_ordered_batch")
+    else:
+        _check(clib.crw_labelmap_ordered(_ptr(L), *head, *tail), "crw_labelmap_ordered")
+    return out, out_conf
+
+
+def labelmap_ordered(L, T, N, M, rows, cols, order, *, confidence=None, flip=False, dtype=torch.float32, out=None, out_conf=None,
+                     workspace=None):
+    """`labelmap_dense`'s interpolated probabilities decoded under a layer order -> (labels [rows, cols], conf | None).
+    order: S distinct classes of 0 ... M-1, top to bottom, 2 <= S <= M; a class outside it is never written.  Per pixel column, the
+    labelling whose position in `order` never steps back down the column and whose summed probability is the largest: in fp32,
+    D[0][s] = e[0][s], D[r][s] = e[r][s] + max_{s' <= s} D[r-1][s'] with e[r][s] the interpolated probability of class order[s],
+    the LOWEST s' on equal prefix maxima, the LOWEST s on equal final scores.  A column may start and end in any state; a layer may
+    be absent.  conf: `labelmap_dense`'s, bit for bit -- the confidence of the interpolated row, whatever the decode picked.
+    flip / dtype / out / out_conf: as for `labelmap_dense`.  workspace: a device tensor of at least
+    `labelmap_ordered_workspace(1, rows, cols)` bytes for the back-pointers (default: allocated per call; a short one raises
+    CrwError CRW_EWORKSPACE).  Device tensors: one launch of crw_labelmap_ordered, nothing synchronises; CPU tensors: the same
+    recurrence and tie rules in torch (a loop over rows, tensors over [S, cols]) on the CPU route's own interpolated values."""
+    return _labelmap_ordered(L, None, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace)
+
+
+def labelmap_ordered_batch(L, G, T, N, M, rows, cols, order, *, confidence=None, flip=False, dtype=torch.int8, out=None,
+                           out_conf=None, workspace=None):
+    """`labelmap_ordered` for the G configurations of a sweep's pass at once (one `order` for all): L [G, T*N, M] -> (labels
+    [G, rows, cols], conf | None); slice g is `labelmap_ordered(L[g], ...)` bit for bit.  out / out_conf / dtype: as for
+    `labelmap_dense_batch`; workspace: at least `labelmap_ordered_workspace(G, rows, cols)` bytes.  Device tensors: ONE launch of
+    crw_labelmap_ordered_batch; CPU tensors: a loop of `labelmap_ordered`'s CPU route."""
+    return _labelmap_ordered(L, G, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace)
+
+
+def _labelmap_ordered_cpu(L, T, N, M, rows, cols, order, confidence, flip):
+    i0, i1, wr = dense_knots(N, rows)
+    j0, j1, wc = dense_knots(T, cols, flip)
+    P = L.view(T, N, M)
+    wr, wc = wr[:, None, None], wc[None, :, None]
+    corner = lambda i, j: P[j[None, :], i[:, None]]  # [rows, cols, M]
+    top = (1 - wc) * corner(i0, j0) + wc * corner(i0, j1)
+    bot = (1 - wc) * corner(i1, j0) + wc * corner(i1, j1)
+    v = (1 - wr) * top + wr * bot  # `_labelmap_dense_cpu`'s values
+    conf = None
+    if confidence is not None:
+        conf = _labelprop_confidence_cpu(v.permute(1, 0, 2).reshape(rows * cols, M), cols, rows, M, confidence, 1)
+    S = len(order)
+    e = v[:, :, order].permute(0, 2, 1).contiguous()  # [rows, S, cols]
+    D = e[0].clone()
+    new = torch.ones(rows, S, cols, dtype=torch.bool)  # new[r, s]: state s is a new prefix maximum of D[r-1] (strict >)
+    for r in range(1, rows):
+        best = torch.cummax(D, 0).values
+        new[r, 1:] = D[1:] > best[:-1]
+        D = e[r] + best
+    idx = torch.arange(S)[:, None]
+    state = torch.where(D == D.max(0).values, idx, S).min(0).values  # the lowest state among equal maxima
+    states = torch.empty(rows, cols, dtype=torch.int64)
+    for r in range(rows - 1, 0, -1):
+        states[r] = state
+        state = torch.where(new[r] & (idx <= state[None]), idx, 0).max(0).values  # the highest new maximum <= state
+    states[0] = state
+    return torch.tensor(order)[states], conf
 
 
 def gemm_f32(A, B, C=None, transA=False, transB=False, beta=False):

@@ -17,6 +17,11 @@
 //
 // crw_labelmap_dense_batch is the same map for the G configurations of a parameter sweep in one launch: the same kernel text
 // (stage_knots, dense_row) with a loop over the configurations around a row.
+//
+// crw_labelmap_ordered[_batch] (the second half of this file) decode the same interpolated probabilities under a layer order: per
+// pixel column the labelling that is monotone in `order` and maximises the sum of the probabilities it picks -- a dynamic
+// programme down the column, a lane per column.  They live here because they read the pixels through knot, load_row and
+// dense_pixel of this file; their own text starts at "ordered label maps".
 #include <cstdlib>
 
 #include "confidence_of.h"
@@ -297,4 +302,261 @@ extern "C" int crw_labelmap_dense(const float *L, int T, int N, int M, int rows,
                                   int label_dtype, float *conf, size_t ld, crw_stream_t stream) {
   // one map: nothing behind it to overlap, so any stride that covers it (checked: ld >= cols) serves
   return crw::dense_launch<false>(L, 1, T, N, M, rows, cols, flip, conf_kind, labels, label_dtype, conf, ld, (size_t)rows * ld, 1, stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------ ordered label maps
+// The labelling of a pixel column that respects a layer order.  order[0 ... S-1]: distinct classes, top to bottom; e[r][s] =
+// v[r][c][order[s]], v the interpolated probability of dense_pixel.  In fp32, one rounded add per row:
+//   D[0][s] = e[0][s];  D[r][s] = e[r][s] + max_{s' <= s} D[r-1][s'],  predecessor: the LOWEST s' that attains the prefix maximum;
+//   last state: the LOWEST s that attains max_s D[rows-1][s];  backtrack;  label[r] = order[state[r]].
+// The prefix arg-max does not decrease with s, so ONE bit per (row, state) -- "state s is a new prefix maximum" (strict >, bit 0
+// always set) -- is the whole back-pointer: pred(s) = the highest set bit <= s.  A pixel's 16 bits are a uint16 word in the
+// caller's workspace, [G][rows][cols rounded up to 64]: a wave's row of words is one 128-byte segment.
+//
+// Shape.  One lane per pixel column, one wave (= one workgroup) per 64 columns and configuration, ONE route for every size.  The
+// lane's column knot never changes; the row knots are the wave's (64 at a time, one division per lane, handed round by readlane),
+// and the four node rows are loaded once per run of rows between the same two of them (rows / N rows), outside the loop over the
+// run: vector-memory operations return in order here, so a load inside it would make every row wait for the row before to
+// store.  The lane keeps the node rows twice: permuted by `order` (S entries, what the scan adds) and, with a confidence kind,
+// whole (what dense_pixel's confidence reads: conf does not depend on the decode and is dense_pixel's own, bit for bit).
+// Forward: D[S] in registers, a word and a conf store per row.
+// Backward: the words back, one label store per row -- a wave's row is one 64-byte (int8) or 256-byte (fp32) segment at any
+// pitch, offset and phase, so there is no head or tail.  A lane reads only words it wrote itself: whatever the workspace held
+// before is never read.  rows steps in series on cols / 64 waves: the kernel is bound by the latency of one step, not by memory
+// (96 µs at 410 x 8192, M = 4, int8, where crw_labelmap_dense takes 10.6: profiles/ordered_timing.log).  The tests hold the map to
+// feasibility and to an fp64 score within 2 (rows B + (rows^2 + 2 rows) 2^-25) of the optimum, B = 12 * 2^-24 the bound on an
+// interpolated probability (DESIGN.md section 3b derives it).  Not measured: anything on a real radargram.
+namespace crw {
+namespace {
+
+constexpr int OD_CHUNK = WAVE;  // row knots the wave holds at a time, a lane each
+// back-pointer words the backward scan has in flight: its step is one dependent load otherwise (a label store of an int8 map may
+// alias anything, so the compiler keeps load and store in order).  8 against 1: tools/ordered_timing.py, profiles/ordered_timing.log
+constexpr int OD_BACK = 8;
+
+struct OrderedArgs {
+  DenseArgs d;          // lab_phase, conf_vec, chunk: unused
+  uint64_t order;       // order[s] in bits 4s ... 4s + 3
+  int S;
+  uint16_t *ws;         // [G][rows][ws_ld]
+  size_t ws_ld;         // cols rounded up to a multiple of 64
+  int back;             // 1: the backward scan loads a word per step; otherwise OD_BACK words at a time
+};
+
+__device__ __forceinline__ int order_at(uint64_t order, int s) { return (int)(order >> (4 * s)) & 15; }
+
+// The S entries of a node row that `order` names, in its order.
+template <int SCAP>
+__device__ __forceinline__ void load_ordered(const float *__restrict__ row, uint64_t order, int S, float (&p)[SCAP]) {
+#pragma unroll
+  for (int s = 0; s < SCAP; ++s)
+    if (s < S) p[s] = row[order_at(order, s)];
+}
+
+// dense_pixel's interpolated values for the first S entries of the four rows -- ITS three lines, the roundings written out the
+// same way, contraction off: on rows permuted by load_ordered, e[s] is bit for bit the v[order[s]] dense_pixel computes (fmaf and
+// a rounded product leave the compiler no choice; dense_pixel itself hands out no v, and its text stays as the dense kernels
+// were verified with).  In two halves, because a lane's column never changes: the first two lines once per pair of node rows
+// (ordered_sides), the third once per pixel (ordered_values).
+template <int SCAP>
+__device__ __forceinline__ void ordered_sides(const float (&p00)[SCAP], const float (&p01)[SCAP], const float (&p10)[SCAP],
+                                              const float (&p11)[SCAP], float wc, int S, float (&top)[SCAP], float (&bot)[SCAP]) {
+#pragma clang fp contract(off)
+  const float uc = 1.f - wc;
+#pragma unroll
+  for (int s = 0; s < SCAP; ++s) {
+    top[s] = bot[s] = 0.f;
+    if (s < S) {
+      top[s] = __builtin_fmaf(wc, p01[s], uc * p00[s]);
+      bot[s] = __builtin_fmaf(wc, p11[s], uc * p10[s]);
+    }
+  }
+}
+
+template <int SCAP>
+__device__ __forceinline__ void ordered_values(const float (&top)[SCAP], const float (&bot)[SCAP], float wr, int S, float (&e)[SCAP]) {
+#pragma clang fp contract(off)
+  const float ur = 1.f - wr;
+#pragma unroll
+  for (int s = 0; s < SCAP; ++s) e[s] = s < S ? __builtin_fmaf(wr, bot[s], ur * top[s]) : -INFINITY;  // beyond S: never a maximum
+}
+
+// lane `l` (uniform) of a value every lane holds, dead lanes included
+__device__ __forceinline__ int lane_int(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ float lane_float(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+// KIND: a CRW_CONF_* kind, or -1 for no confidence map; MCAP: 4, 8 or 16 >= M >= S
+template <typename LAB, int KIND, int MCAP>
+__global__ __launch_bounds__(WAVE) void labelmap_ordered_kernel(OrderedArgs a) {
+  const DenseArgs &d = a.d;
+  const int M = d.M, N = d.N, S = a.S, rows = d.rows;
+  const int lane = threadIdx.x, g = blockIdx.y;
+  const long c = (long)blockIdx.x * WAVE + lane;
+  const bool live = c < d.cols;  // a dead lane holds row knots and touches no memory
+  const float *__restrict__ L = d.L + (size_t)g * d.l_stride;
+  const int vec = ((M & 3) == 0 && !((uintptr_t)L & 15)) ? 4 : ((M & 1) == 0 && !((uintptr_t)L & 7)) ? 2 : 1;
+  LAB *lab = static_cast<LAB *>(d.lab) + (size_t)g * d.map_stride + (live ? c : 0);
+  float *conf = KIND >= 0 ? d.conf + (size_t)g * d.map_stride + (live ? c : 0) : nullptr;
+  uint16_t *ws = a.ws + (size_t)g * rows * a.ws_ld + (live ? c : 0);
+
+  int j0 = 0;
+  float wc = 0.f;
+  if (live) knot(d.flip ? d.cols - 1 - (int)c : (int)c, d.T, d.cols, &j0, &wc);
+  const int j1 = j0 + 1 < d.T ? j0 + 1 : d.T - 1;
+
+  // D[-1] = 0: row 0 is a step like every other, D[0][s] = e[0][s] + 0 exactly (its back-pointer word is written and never read)
+  float D[MCAP];
+#pragma unroll
+  for (int s = 0; s < MCAP; ++s) D[s] = 0.f;
+  for (int r0 = 0; r0 < rows; r0 += OD_CHUNK) {
+    int ki = 0;  // row r0 + lane's knot and weight: one division per lane and 64 rows, handed round by readlane
+    float kw = 0.f;
+    if (r0 + lane < rows) knot(r0 + lane, N, rows, &ki, &kw);
+    const int rn = rows - r0 < OD_CHUNK ? rows - r0 : OD_CHUNK;
+    if (!live) continue;
+    for (int rr = 0; rr < rn;) {  // a run of rows between the same two node rows (rows / N of them)
+      const int i0 = lane_int(ki, rr), i1 = i0 + 1 < N ? i0 + 1 : N - 1;
+      const float *n00 = L + ((size_t)j0 * N + i0) * M, *n01 = L + ((size_t)j1 * N + i0) * M;
+      const float *n10 = L + ((size_t)j0 * N + i1) * M, *n11 = L + ((size_t)j1 * N + i1) * M;
+      float q00[MCAP], q01[MCAP], q10[MCAP], q11[MCAP];  // the node rows permuted by order: the scan's
+      float p00[MCAP], p01[MCAP], p10[MCAP], p11[MCAP];  // the whole node rows: the confidence's
+      load_ordered(n00, a.order, S, q00), load_ordered(n01, a.order, S, q01);
+      load_ordered(n10, a.order, S, q10), load_ordered(n11, a.order, S, q11);
+      if (KIND >= 0) {
+        load_row(n00, M, vec, p00), load_row(n01, M, vec, p01);
+        load_row(n10, M, vec, p10), load_row(n11, M, vec, p11);
+      }
+      float top[MCAP], bot[MCAP], e[MCAP];
+      ordered_sides(q00, q01, q10, q11, wc, S, top, bot);
+      do {  // no load in here: the stores of one row need not land before the next row starts
+        const int r = r0 + rr;
+        const float wr = lane_float(kw, rr);
+        ordered_values(top, bot, wr, S, e);
+        if (KIND >= 0) {
+          float argmax_label, cf;
+          dense_pixel<KIND, MCAP>(p00, p01, p10, p11, wc, wr, M, d.ln_m, &argmax_label, &cf);
+          conf[(size_t)r * d.ld] = cf;
+        }
+        // adds, compares and selects only: nothing here can contract, nothing branches.  A state beyond S has e = -inf, so its
+        // D is -inf from row 0 on: never a prefix maximum, never the last state
+        float best = D[0];
+        unsigned word = 1u;
+        D[0] = e[0] + best;
+#pragma unroll
+        for (int s = 1; s < MCAP; ++s) {
+          const bool up = D[s] > best;  // strict: the lowest state that attains the prefix maximum
+          best = up ? D[s] : best;
+          word |= up ? 1u << s : 0u;
+          D[s] = e[s] + best;
+        }
+        ws[(size_t)r * a.ws_ld] = (uint16_t)word;
+        ++rr;
+      } while (rr < rn && lane_int(ki, rr) == i0);
+    }
+  }
+  if (!live) return;
+
+  int state = 0;
+  float top = D[0];
+#pragma unroll
+  for (int s = 1; s < MCAP; ++s)
+    if (D[s] > top) top = D[s], state = s;  // strict: the lowest state that attains the maximum (beyond S: -inf)
+  int r = rows - 1;
+  if (a.back != 1)
+    for (; r >= OD_BACK; r -= OD_BACK) {  // rows r ... r - 7, all >= 1: their words first, then the chain through them
+      unsigned words[OD_BACK];
+#pragma unroll
+      for (int k = 0; k < OD_BACK; ++k) words[k] = ws[(size_t)(r - k) * a.ws_ld];
+#pragma unroll
+      for (int k = 0; k < OD_BACK; ++k) {
+        lab[(size_t)(r - k) * d.ld] = (LAB)order_at(a.order, state);
+        state = 31 - __builtin_clz(words[k] & ((2u << state) - 1u));
+      }
+    }
+  for (; r >= 1; --r) {
+    lab[(size_t)r * d.ld] = (LAB)order_at(a.order, state);
+    const unsigned word = ws[(size_t)r * a.ws_ld] & ((2u << state) - 1u);  // bit 0 is set: never empty
+    state = 31 - __builtin_clz(word);
+  }
+  lab[0] = (LAB)order_at(a.order, state);
+}
+
+template <typename LAB, int KIND>
+auto ordered_kernel_m(int M) {
+  return M <= 4 ? labelmap_ordered_kernel<LAB, KIND, 4> : M <= 8 ? labelmap_ordered_kernel<LAB, KIND, 8> : labelmap_ordered_kernel<LAB, KIND, 16>;
+}
+
+template <typename LAB>
+auto ordered_kernel(int kind, int M) {
+  return kind < 0 ? ordered_kernel_m<LAB, -1>(M)
+                  : kind == CRW_CONF_MAXPROB ? ordered_kernel_m<LAB, CRW_CONF_MAXPROB>(M)
+                  : kind == CRW_CONF_MARGIN ? ordered_kernel_m<LAB, CRW_CONF_MARGIN>(M)
+                                            : ordered_kernel_m<LAB, CRW_CONF_ENTROPY>(M);
+}
+
+// CRW_ORDERED_BACK (read per call): 1 = the backward scan with one word in flight, the other arm of tools/ordered_timing.py's
+// A/B.  The maps do not depend on it.
+int ordered_back() {
+  const char *e = getenv("CRW_ORDERED_BACK");
+  return e && atoi(e) == 1 ? 1 : OD_BACK;
+}
+
+size_t ordered_ws_ld(int cols) { return ((size_t)cols + WAVE - 1) / WAVE * WAVE; }
+
+size_t ordered_ws_bytes(int G, int rows, int cols) {
+  if (G < 1 || rows < 1 || cols < 1) return 0;
+  return (size_t)G * rows * ordered_ws_ld(cols) * sizeof(uint16_t);
+}
+
+// Both entry points behind their signatures.  The argument checks are dense_launch's (repeated, its text is left alone), then
+// the order's and the workspace's; nothing is launched unless all pass.
+int ordered_launch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, const int *order, int S, int conf_kind,
+                   void *labels, int label_dtype, float *conf, size_t ld, size_t map_stride, void *ws, size_t ws_bytes,
+                   crw_stream_t stream) {
+  clear_stale_error();
+  constexpr int MAX_SIDE = 1 << 22;
+  if (!L || !labels || G < 1 || G > 65535 || T < 1 || N < 1 || M < 2 || M > 16 || rows < 1 || cols < 1 || rows > MAX_SIDE ||
+      cols > MAX_SIDE || !dtype_ok(label_dtype) || conf_kind < -1 || conf_kind > CRW_CONF_ENTROPY ||
+      (conf_kind == -1) != (conf == nullptr) || ld < (size_t)cols || map_stride < (size_t)(rows - 1) * ld + (size_t)cols ||
+      ((uintptr_t)L & 3) || ((uintptr_t)conf & 3) || (label_dtype == CRW_DT_F32 && ((uintptr_t)labels & 3)))
+    return CRW_EINVAL;
+  if (!order || S < 2 || S > M || !ws || ((uintptr_t)ws & 1)) return CRW_EINVAL;
+  uint64_t packed = 0;
+  unsigned seen = 0;
+  for (int s = 0; s < S; ++s) {
+    if (order[s] < 0 || order[s] >= M || (seen >> order[s] & 1)) return CRW_EINVAL;
+    seen |= 1u << order[s];
+    packed |= (uint64_t)order[s] << (4 * s);
+  }
+  if (ws_bytes < ordered_ws_bytes(G, rows, cols)) return CRW_EWORKSPACE;
+  OrderedArgs a;
+  a.d.L = L, a.d.lab = labels, a.d.conf = conf, a.d.ld = ld;
+  a.d.T = T, a.d.N = N, a.d.M = M, a.d.rows = rows, a.d.cols = cols, a.d.flip = flip != 0;
+  a.d.lab_phase = 0, a.d.conf_vec = 0;
+  a.d.ln_m = logf((float)M);
+  a.d.l_stride = (size_t)T * N * M, a.d.map_stride = map_stride, a.d.G = G, a.d.chunk = 1;
+  a.order = packed, a.S = S, a.ws = static_cast<uint16_t *>(ws), a.ws_ld = ordered_ws_ld(cols), a.back = ordered_back();
+  const dim3 grid((unsigned)(a.ws_ld / WAVE), (unsigned)G);
+  const auto kernel = label_dtype == CRW_DT_F32 ? ordered_kernel<float>(conf_kind, M) : ordered_kernel<int8_t>(conf_kind, M);
+  hipLaunchKernelGGL(kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, a);
+  return check_launch();
+}
+
+}  // namespace
+}  // namespace crw
+
+extern "C" size_t crw_labelmap_ordered_workspace(int G, int rows, int cols) { return crw::ordered_ws_bytes(G, rows, cols); }
+
+extern "C" int crw_labelmap_ordered_batch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, const int *order,
+                                          int S, int conf_kind, void *labels, int label_dtype, float *conf, size_t ld,
+                                          size_t map_stride, void *ws, size_t ws_bytes, crw_stream_t stream) {
+  return crw::ordered_launch(L, G, T, N, M, rows, cols, flip, order, S, conf_kind, labels, label_dtype, conf, ld, map_stride, ws,
+                             ws_bytes, stream);
+}
+
+extern "C" int crw_labelmap_ordered(const float *L, int T, int N, int M, int rows, int cols, int flip, const int *order, int S,
+                                    int conf_kind, void *labels, int label_dtype, float *conf, size_t ld, void *ws, size_t ws_bytes,
+                                    crw_stream_t stream) {
+  return crw::ordered_launch(L, 1, T, N, M, rows, cols, flip, order, S, conf_kind, labels, label_dtype, conf, ld, (size_t)rows * ld,
+                             ws, ws_bytes, stream);
 }

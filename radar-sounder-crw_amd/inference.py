@@ -71,8 +71,8 @@ _reverse_rule_mask_batch = _reverse_rule_mask  # [G, rows, cols] maps, configura
 merge_reverse_batch = merge_reverse
 
 
-def _check_options(confidence, merge, upsample):
-    """`segment`'s and `segment_sweep`'s checks of their three options."""
+def _check_options(confidence, merge, upsample, decode='argmax', order=None, nclasses=None):
+    """`segment`'s and `segment_sweep`'s checks of their options -> `order` as a list (None unless decode='ordered')."""
     if merge not in ('rule', 'confidence'):
         raise ValueError(f"merge must be 'rule' or 'confidence' (got {merge!r})")
     if upsample not in ('nearest', 'bilinear'):
@@ -81,6 +81,17 @@ def _check_options(confidence, merge, upsample):
         raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
     if merge == 'confidence' and confidence is None:
         raise ValueError("merge='confidence' needs a confidence kind (confidence='maxprob', 'margin' or 'entropy')")
+    if decode not in ('argmax', 'ordered'):
+        raise ValueError(f"decode must be 'argmax' or 'ordered' (got {decode!r})")
+    if decode == 'argmax':
+        if order is not None:
+            raise ValueError("order needs decode='ordered'")
+        return None
+    if upsample != 'bilinear':
+        raise ValueError("decode='ordered' needs upsample='bilinear' (it decodes the interpolated soft labels)")
+    if order is None:
+        raise ValueError("decode='ordered' needs an order (the classes from top to bottom, e.g. order=(0, 1, 2, 3))")
+    return crw_hip.check_order(order, int(nclasses))
 
 
 def _write_nearest(res, seq, out, out_conf, flip):
@@ -168,7 +179,8 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
 
 @torch.no_grad()
 def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap, pos_embed=False,
-            correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest'):
+            correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
+            decode='argmax', order=None):
     """dataset: RGDataset (full, overlapping items); seg: reference segmentation [rows, W_rg].
     -> dict(pred [rows, n_rg * rg_len] float labels after the optional reverse merge,
             forward: the forward (+ corrected) map the reference saves as int8 (test_all.py:128),
@@ -186,26 +198,39 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     class boundary on the node grid.  'bilinear': the upstream routine's order (imported/crw.py:124-127) -- the pass's soft labels
     interpolated bilinearly to pixels and arg-maxed after that (`crw_hip.labelmap_dense`, one kernel per pass, straight into the
     pass's column window of the map); ``conf`` / ``forward_conf`` are then the confidence of the INTERPOLATED distribution.  Same
-    passes, corrections, exception policy and merges."""
-    _check_options(confidence, merge, upsample)
+    passes, corrections, exception policy and merges.
+    decode: how a pixel's class is read from the interpolated probabilities.  'argmax': per pixel.  'ordered' (needs
+    upsample='bilinear' and ``order``, the classes from top to bottom; no per-dataset default, the class semantics are the
+    caller's): per pixel column, the labelling that never steps back in ``order`` and collects the largest summed probability
+    (`crw_hip.labelmap_ordered` where 'argmax' calls `labelmap_dense`; same passes, corrections, exception policy and merges;
+    ``conf`` / ``forward_conf`` unchanged, they do not depend on the decode).  The dict then gains ``decode`` and ``order``.
+    The guarantee: every pass's window is monotone in ``order`` down every column, so ``forward`` is, and ``pred`` without a
+    reverse pass; after merge='rule' / 'confidence' the merged ``pred`` takes pixels of two monotone maps and need not be."""
+    order = _check_options(confidence, merge, upsample, decode, order, nclasses)
     want = confidence is not None
+    extra = dict(decode=decode, order=order) if order else {}
     if upsample == 'bilinear':
         kw = dict(soft=True)
 
         def write(res, seq, out, out_conf, flip):  # res[3]: the pass's soft labels L [T*N, M]
-            crw_hip.labelmap_dense(res[3], *seq.shape[:2], nclasses, *out.shape, confidence=confidence, flip=flip, out=out,
-                                   out_conf=out_conf)
+            if order:
+                crw_hip.labelmap_ordered(res[3], *seq.shape[:2], nclasses, *out.shape, order, confidence=confidence, flip=flip,
+                                         out=out, out_conf=out_conf)
+            else:
+                crw_hip.labelmap_dense(res[3], *seq.shape[:2], nclasses, *out.shape, confidence=confidence, flip=flip, out=out,
+                                       out_conf=out_conf)
     else:
         kw = dict(confidence=confidence) if want else {}  # `propagate` returns a fourth entry only when asked
         write = _write_nearest
     run = lambda seq, seg_ref, last: propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=last, **kw)
     return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
-                           write)
+                           write, **extra)
 
 
 @torch.no_grad()
 def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size, overlap, pos_embed=False,
-                  correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest'):
+                  correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
+                  decode='argmax', order=None):
     """`segment` for every configuration of ``sweep`` (LabelPropSweep, G = len(sweep.configs)) with its control flow run ONCE:
     which items are corrected, at which length (`get_smaller_item` and its permanent shortening of the dataset) and what the
     reverse pass sees depend on the features alone, never on (radius, temp, knn).  Same exception policy in the correction.
@@ -218,8 +243,10 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     (the class rule's dataset check applies to merge='rule' alone).  upsample='bilinear': the maps are allocated once at
     [G, rows, n_rg * rg_len] and every pass writes its column window of all G maps with one `crw_hip.labelmap_dense_batch`.
     It holds G-map tensors at once: with confidence, 5 bytes per pixel and configuration for the forward maps, as much again for
-    the reverse pass's and for the merge's result."""
-    _check_options(confidence, merge, upsample)
+    the reverse pass's and for the merge's result.  decode / order: `segment`'s, one ``order`` for the G configurations, every
+    pass ONE `crw_hip.labelmap_ordered_batch`; slice g stays `segment`'s for ``sweep.configs[g]`` under the same options."""
+    order = _check_options(confidence, merge, upsample, decode, order, nclasses)
+    extra = dict(decode=decode, order=order) if order else {}
     if merge == 'rule' and dataset_id not in (0, 1, 3) and use_last:
         raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
     want = confidence is not None
@@ -228,14 +255,18 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
         kw = dict(soft=True)
 
         def write(res, seq, out, out_conf, flip):  # res[3]: the pass's soft labels L [G, T*N, M]; ONE launch for the G maps
-            crw_hip.labelmap_dense_batch(res[3], G, *seq.shape[:2], nclasses, *out.shape[1:], confidence=confidence, flip=flip,
-                                         dtype=torch.int8, out=out, out_conf=out_conf)
+            if order:
+                crw_hip.labelmap_ordered_batch(res[3], G, *seq.shape[:2], nclasses, *out.shape[1:], order, confidence=confidence,
+                                               flip=flip, dtype=torch.int8, out=out, out_conf=out_conf)
+            else:
+                crw_hip.labelmap_dense_batch(res[3], G, *seq.shape[:2], nclasses, *out.shape[1:], confidence=confidence, flip=flip,
+                                             dtype=torch.int8, out=out, out_conf=out_conf)
     else:
         kw = dict(confidence=confidence) if want else {}  # `propagate_sweep` returns a fourth entry only when asked
         write = _write_nearest
     run = lambda seq, seg_ref, last: propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=last, **kw)
     return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
-                           write, lead=(G,), dtype=torch.int8, configs=list(sweep.configs))
+                           write, lead=(G,), dtype=torch.int8, configs=list(sweep.configs), **extra)
 
 
 @torch.no_grad()

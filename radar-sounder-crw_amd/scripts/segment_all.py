@@ -17,7 +17,10 @@ per-pixel confidence of the map (``inference.segment(..., confidence=...)``) and
 confidence of the final map as ``confidence_map.pt`` (float32); ``--merge confidence``: the reverse pass of ``--use_last`` is merged
 per pixel by confidence instead of by the reference's class rule; ``--upsample bilinear``: the maps come from the soft labels,
 interpolated bilinearly to pixels and arg-maxed after that (``inference.segment(..., upsample='bilinear')``; ``--report_json`` gains
-``"upsample": "bilinear"``) instead of the reference's arg-max + nearest stretch; ``--horizons``: after the confusion matrix (and the calibration table), the
+``"upsample": "bilinear"``) instead of the reference's arg-max + nearest stretch; ``--decode ordered --order K [K ...]`` (with
+``--upsample bilinear``): every pixel column is decoded as a whole -- the labelling that never steps back in the order given, top
+to bottom, and collects the most probability (``inference.segment(..., decode='ordered', order=...)``; no per-dataset default;
+``--report_json`` gains ``"decode"`` and ``"order"``); ``--horizons``: after the confusion matrix (and the calibration table), the
 horizon table of ``inference.horizons`` -- per class, in how many columns the layer was found, missed or invented, and the error of
 its top, bottom and thickness -- with ``--min_run N`` (default 3: runs of fewer equal labels down a column are no layer), ``--tol
 ROWS`` (default 2), ``--row_spacing X`` / ``--row_unit NAME`` (the printed distances are rows * X, in NAME); ``--save_horizons``
@@ -94,6 +97,10 @@ def get_args_parser():
     p.add_argument('--save_conf', action='store_true', help='write confidence_map.pt (needs --confidence)')
     p.add_argument('--upsample', default='nearest', choices=('nearest', 'bilinear'),
                    help="node labels to pixels: the reference's arg-max + nearest, or soft labels interpolated bilinearly, then arg-max")
+    p.add_argument('--decode', default='argmax', choices=('argmax', 'ordered'),
+                   help="interpolated soft labels to classes (--upsample bilinear): arg-max per pixel, or per column the best "
+                        "labelling that never steps back in --order")
+    p.add_argument('--order', default=None, nargs='+', type=int, metavar='K', help='the classes from top to bottom, for --decode ordered')
     p.add_argument('--horizons', action='store_true', help='also print the horizon / thickness error table')
     p.add_argument('--min_run', default=3, type=int, metavar='N', help='shortest run of equal labels down a column that is a layer')
     p.add_argument('--tol', default=2, type=int, metavar='ROWS', help='a pick within this many rows counts as right')
@@ -144,6 +151,15 @@ def check_confidence_flags(args):
         raise SystemExit(f'--bins {args.bins}: 1 ... 64')
     if args.upsample != 'nearest' and args.single:
         raise SystemExit('--upsample bilinear is not available with --single')
+    return check_decode_flags(args)
+
+
+def check_decode_flags(args):
+    """The flags around ``--decode`` (also segment_sweep.py's)."""
+    if args.decode == 'ordered' and (args.upsample != 'bilinear' or not args.order):
+        raise SystemExit('--decode ordered needs --upsample bilinear and --order K [K ...] (the classes from top to bottom)')
+    if args.decode != 'ordered' and args.order:
+        raise SystemExit('--order needs --decode ordered')
     return args
 
 
@@ -193,6 +209,8 @@ def main(args):
         hidden += HORIZON_FLAGS
     if args.context == 'reference':  # likewise
         hidden += ('context',)
+    if args.decode == 'argmax':  # likewise
+        hidden += ('decode', 'order')
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -219,7 +237,8 @@ def main(args):
         out = inference.segment(dataset, seg, encoder, lp, nclasses, T, args.patch_size, args.overlap, pos_embed=args.pos_embed,
                                 correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device,
                                 **(dict(confidence=args.confidence, merge=args.merge) if args.confidence else {}),
-                                **(dict(upsample=args.upsample) if args.upsample != 'nearest' else {}))
+                                **(dict(upsample=args.upsample) if args.upsample != 'nearest' else {}),
+                                **(dict(decode=args.decode, order=args.order) if args.decode != 'argmax' else {}))
         if correction:
             print('Change point for each radargram:', out['change_idx'])
         final, forward = out['pred'], out['forward']
@@ -269,6 +288,8 @@ def main(args):
             d['upsample'] = args.upsample
         if args.context != 'reference':
             d['context'] = args.context
+        if args.decode != 'argmax':
+            d.update(decode=args.decode, order=list(out['order']))
         if cal is not None:
             d['calibration'] = dict(cal.to_dict(), kind=args.confidence, merge=args.merge)
         if hz is not None:

@@ -14,7 +14,8 @@ line per configuration (radius, temp, knn, accuracy, macro F1, weighted F1, mean
 prints every full report; ``--report_json FILE`` writes all of them with the grid; ``--save_maps`` writes
 ``predicted_map_r{r}_t{t}_k{k}.pt`` (int8, the forward map test_all.py saves) per configuration.
 ``--upsample bilinear`` / ``--confidence KIND`` / ``--merge confidence`` / ``--bins B``: ``segment_all.py``'s flags, for all
-configurations at once (``inference.segment_sweep``'s arguments; the G dense maps of a pass are one kernel launch).  With
+configurations at once (``inference.segment_sweep``'s arguments; the G dense maps of a pass are one kernel launch); likewise
+``--decode ordered --order K [K ...]`` (one order for all configurations; ``--report_json`` gains ``"decode"`` and ``"order"``).  With
 ``--confidence`` every configuration's line gains its ECE and AURC (``inference.calibration_sweep``), the best configuration's
 calibration table follows its matrix, ``--report_json`` gains a ``calibration`` entry per configuration, and ``--select`` also
 takes ``ece`` and ``aurc`` -- lower is better: the smallest wins, ties go to the first in the grid's order, a NaN never wins
@@ -88,6 +89,10 @@ def get_args_parser(horizons=False):
     p.add_argument('--bins', default=10, type=int, metavar='B', help='confidence bins of the calibration (1 ... 64)')
     p.add_argument('--upsample', default='nearest', choices=('nearest', 'bilinear'),
                    help="node labels to pixels: the reference's arg-max + nearest, or soft labels interpolated bilinearly, then arg-max")
+    p.add_argument('--decode', default='argmax', choices=('argmax', 'ordered'),
+                   help="interpolated soft labels to classes (--upsample bilinear): arg-max per pixel, or per column the best "
+                        "labelling that never steps back in --order")
+    p.add_argument('--order', default=None, nargs='+', type=int, metavar='K', help='the classes from top to bottom, for --decode ordered')
     p.add_argument('--horizons', action='store_true', help="the mean top MAE of every configuration's horizons (a column)")
     p.add_argument('--min_run', default=3, type=int, metavar='N', help='shortest run of equal labels down a column that is a layer')
     p.add_argument('--tol', default=2, type=int, metavar='ROWS', help='a pick within this many rows counts as right')
@@ -106,7 +111,7 @@ def check_confidence_flags(args):
         raise SystemExit(f'--select {args.select} needs --horizons')
     if args.horizons and (args.min_run < 1 or args.tol < 0):
         raise SystemExit('--min_run is at least 1, --tol at least 0')
-    return args
+    return segment_all.check_decode_flags(args)
 
 
 def pick_best(scores, lower_is_better=False):
@@ -147,6 +152,8 @@ def main(args):
         hidden += ('horizons', 'min_run', 'tol')
     if args.context == 'reference':  # likewise
         hidden += ('context',)
+    if args.decode == 'argmax':  # likewise
+        hidden += ('decode', 'order')
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -165,7 +172,8 @@ def main(args):
     out = inference.segment_sweep(dataset, seg, encoder, sweep, nclasses, T, args.patch_size, args.overlap, pos_embed=args.pos_embed,
                                   correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device,
                                   **(dict(confidence=args.confidence, merge=args.merge) if args.confidence else {}),
-                                  **(dict(upsample=args.upsample) if args.upsample != 'nearest' else {}))
+                                  **(dict(upsample=args.upsample) if args.upsample != 'nearest' else {}),
+                                  **(dict(decode=args.decode, order=args.order) if args.decode != 'argmax' else {}))
     if correction:
         print('Change point for each radargram:', out['change_idx'])
     final, forward = out['pred'], out['forward']
@@ -242,6 +250,8 @@ def main(args):
             d['upsample'] = args.upsample
         if args.context != 'reference':
             d['context'] = args.context
+        if args.decode != 'argmax':
+            d.update(decode=args.decode, order=list(out['order']))
         with open(args.report_json, 'w') as f:
             json.dump(d, f, indent=1)
     return reports, best
