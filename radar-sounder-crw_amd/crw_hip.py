@@ -162,27 +162,26 @@ ORDERED_ENTRY_POINTS = ("crw_labelmap_ordered_workspace", "crw_labelmap_ordered"
 
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 
+# group -> its entry points.  `has_<group>()` tells whether the loaded library exports them, `_<group>_lib()` is lib() or the
+# error that names the stale library
+OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_ENTRY_POINTS, "dense": DENSE_ENTRY_POINTS,
+                         "dense_batch": DENSE_BATCH_ENTRY_POINTS, "horizons": HORIZONS_ENTRY_POINTS,
+                         "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS}
+
 _lib = None
-_has_horizons = False
-_has_sliding = False
-_has_ordered = False
-_has_sweep = False
-_has_confidence = False
-_has_dense = False
-_has_dense_batch = False
+_present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
 
 
 def lib():
     """Load the HIP library (once).  Raises if it has not been built: `python -c 'import
     __graft_entry__ as g; g.build()'` or `make -C radar-sounder-crw_amd/csrc`."""
-    global _lib, _has_sweep, _has_confidence, _has_dense, _has_dense_batch, _has_horizons, _has_sliding, _has_ordered
+    global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} not built -- the CRW hot path has no CPU/PyTorch fallback; "
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
-        missing = [n for n in SWEEP_ENTRY_POINTS + CONFIDENCE_ENTRY_POINTS + DENSE_ENTRY_POINTS + DENSE_BATCH_ENTRY_POINTS
-                   + HORIZONS_ENTRY_POINTS + SLIDING_ENTRY_POINTS + ORDERED_ENTRY_POINTS if not hasattr(handle, n)]
+        missing = {n for names in OPTIONAL_ENTRY_POINTS.values() for n in names if not hasattr(handle, n)}
         for name, (res, args) in SIGNATURES.items():
             if name in missing:
                 continue
@@ -192,105 +191,37 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} was built for ABI {handle.crw_abi_version()}, include/crw_hip.h says {ABI_VERSION}: "
                                "stale library -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
         _lib = handle
-        _has_sweep = not set(missing) & set(SWEEP_ENTRY_POINTS)
-        _has_confidence = not set(missing) & set(CONFIDENCE_ENTRY_POINTS)
-        _has_dense = not set(missing) & set(DENSE_ENTRY_POINTS)
-        _has_dense_batch = not set(missing) & set(DENSE_BATCH_ENTRY_POINTS)
-        _has_horizons = not set(missing) & set(HORIZONS_ENTRY_POINTS)
-        _has_sliding = not set(missing) & set(SLIDING_ENTRY_POINTS)
-        _has_ordered = not set(missing) & set(ORDERED_ENTRY_POINTS)
+        _present.update((group, not missing & set(names)) for group, names in OPTIONAL_ENTRY_POINTS.items())
     return _lib
 
 
-def has_sweep():
-    """True when the loaded library exports the sweep entry points (SWEEP_ENTRY_POINTS)."""
-    lib()
-    return _has_sweep
+def _optional(group, what):
+    """(has_<group>, _<group>_lib) of one group of OPTIONAL_ENTRY_POINTS; `what` words the group in has_<group>'s docstring."""
+    names = OPTIONAL_ENTRY_POINTS[group]
+
+    def has():
+        lib()
+        return _present[group]
+
+    def checked_lib():
+        handle = lib()
+        if not _present[group]:
+            raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks {', '.join(names)} "
+                               "(added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
+        return handle
+
+    has.__name__, checked_lib.__name__ = f"has_{group}", f"_{group}_lib"
+    has.__doc__ = f"True when the loaded library exports {what} ({group.upper()}_ENTRY_POINTS)."
+    return has, checked_lib
 
 
-def _sweep_lib():
-    if not has_sweep():
-        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks {', '.join(SWEEP_ENTRY_POINTS)} "
-                           "(added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
-    return lib()
-
-
-def has_confidence():
-    """True when the loaded library exports the confidence entry points (CONFIDENCE_ENTRY_POINTS)."""
-    lib()
-    return _has_confidence
-
-
-def _confidence_lib():
-    if not has_confidence():
-        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
-                           f"{', '.join(CONFIDENCE_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
-    return lib()
-
-
-def has_dense():
-    """True when the loaded library exports the dense label map's entry point (DENSE_ENTRY_POINTS)."""
-    lib()
-    return _has_dense
-
-
-def _dense_lib():
-    if not has_dense():
-        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
-                           f"{', '.join(DENSE_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
-    return lib()
-
-
-def has_dense_batch():
-    """True when the loaded library exports the batched dense label map's entry point (DENSE_BATCH_ENTRY_POINTS)."""
-    lib()
-    return _has_dense_batch
-
-
-def _dense_batch_lib():
-    if not has_dense_batch():
-        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
-                           f"{', '.join(DENSE_BATCH_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
-    return lib()
-
-
-def has_horizons():
-    """True when the loaded library exports the horizon entry points (HORIZONS_ENTRY_POINTS)."""
-    lib()
-    return _has_horizons
-
-
-def _horizons_lib():
-    if not has_horizons():
-        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
-                           f"{', '.join(HORIZONS_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
-    return lib()
-
-
-def has_sliding():
-    """True when the loaded library exports the sliding-context entry points (SLIDING_ENTRY_POINTS)."""
-    lib()
-    return _has_sliding
-
-
-def _sliding_lib():
-    if not has_sliding():
-        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
-                           f"{', '.join(SLIDING_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
-    return lib()
-
-
-def has_ordered():
-    """True when the loaded library exports the depth-ordered label map's entry points (ORDERED_ENTRY_POINTS)."""
-    lib()
-    return _has_ordered
-
-
-def _ordered_lib():
-    if not has_ordered():
-        raise RuntimeError(f"{LIB_PATH} is a stale libcrw_hip.so: it reports ABI {ABI_VERSION} but lacks "
-                           f"{', '.join(ORDERED_ENTRY_POINTS)} (added at that ABI) -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
-    return lib()
+has_sweep, _sweep_lib = _optional("sweep", "the sweep entry points")
+has_confidence, _confidence_lib = _optional("confidence", "the confidence entry points")
+has_dense, _dense_lib = _optional("dense", "the dense label map's entry point")
+has_dense_batch, _dense_batch_lib = _optional("dense_batch", "the batched dense label map's entry point")
+has_horizons, _horizons_lib = _optional("horizons", "the horizon entry points")
+has_sliding, _sliding_lib = _optional("sliding", "the sliding-context entry points")
+has_ordered, _ordered_lib = _optional("ordered", "the depth-ordered label map's entry points")
 
 
 def check_context(context):
@@ -576,16 +507,63 @@ class LabelError(CrwError, ValueError):
         self.what, self.status, self.hip_error, self.invalid = "crw_confusion", CRW_EINVAL, 0, invalid
 
 
-def _labels(t, name):
-    """Flat contiguous labels as one of the kernel's dtypes.  fp32 and int8 pass through; every other dtype becomes fp32, a value
+def _dt(t):
+    """The C ABI's dtype code of an operand in one of the kernels' dtypes (an absent one: DT_I8, never read)."""
+    return DT_F32 if t is not None and t.dtype == torch.float32 else DT_I8
+
+
+def _kernel_dtype(t):
+    """Labels as one of the kernels' dtypes, the shape kept.  fp32 and int8 pass through; every other dtype becomes fp32, a value
     that fp32 cannot hold exactly becoming NaN (counted as invalid) rather than a neighbouring label."""
-    t = t.reshape(-1)
     if t.dtype == torch.bool:
         t = t.to(torch.int8)
     elif t.dtype not in (torch.float32, torch.int8):
         f = t.to(torch.float32)
         t = torch.where(f.to(t.dtype) == t, f, torch.full_like(f, float("nan")))
-    return t.contiguous()
+    return t
+
+
+def _labels(t, name):
+    """Flat contiguous labels as one of the kernels' dtypes (`_kernel_dtype`)."""
+    return _kernel_dtype(t.reshape(-1)).contiguous()
+
+
+def _report_args(K, aux, ignore_gt, ignore_pred, ignore_aux, bins=1):
+    """The argument checks `confusion`, `horizons` and `calibration` (`bins`: its alone) share -> K as an int."""
+    K = int(K)
+    if not 2 <= K <= 16:
+        raise ValueError(f"K must be in 2 ... 16 (got {K})")
+    if not 1 <= bins <= 64:
+        raise ValueError(f"bins must be in 1 ... 64 (got {bins})")
+    if min(ignore_gt, ignore_pred, ignore_aux) < -1:
+        raise ValueError("an ignore label is a class id >= 0, or -1 for none")
+    if aux is None and ignore_aux != -1:
+        raise ValueError("ignore_aux needs aux")
+    return K
+
+
+def _report_operands(names, ops, aux, size, noun):
+    """The operands `names` (`ops`, gt first) and aux (None: absent) of a report are of one `size(t)` and live on one device."""
+    ops = [*ops, aux] if aux is not None else ops
+    if any(size(t) != size(ops[0]) for t in ops):
+        raise ValueError(f"{names}{' and aux' if aux is not None else ''} must hold the same number of {noun} "
+                         f"(got {', '.join(str(size(t)) for t in ops)})")
+    if any(t.device != ops[0].device for t in ops):
+        raise ValueError(f"{names} and aux must live on one device")
+
+
+def _mask_valid(g, p, aux, K, ignore_gt, ignore_pred, ignore_aux):
+    """The mask and validity rule of the report kernels (csrc/labelmap.h) on float64 labels g, p of one shape (aux: as given)
+    -> (masked, valid), two bool tensors of that shape."""
+    masked = torch.zeros(g.shape, dtype=torch.bool)
+    if ignore_gt >= 0:
+        masked |= g == ignore_gt
+    if ignore_pred >= 0:
+        masked |= p == ignore_pred
+    if ignore_aux >= 0:
+        masked |= aux.reshape(g.shape).to(torch.float64) == ignore_aux
+    valid = (g == g.floor()) & (g >= 0) & (g < K) & (p == p.floor()) & (p >= 0) & (p < K)  # NaN fails every comparison
+    return masked, valid
 
 
 def confusion(gt, pred, K, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1):
@@ -594,45 +572,26 @@ def confusion(gt, pred, K, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1
     gt == ignore_gt, pred == ignore_pred or aux == ignore_aux (-1: none), and a surviving label that is no integer in [0, K) is
     counted in dropped[1] and in no bin.  Device tensors: one pass of crw_confusion, nothing synchronises; CPU tensors: the same
     counts from torch.bincount."""
-    K = int(K)
-    if not 2 <= K <= 16:
-        raise ValueError(f"K must be in 2 ... 16 (got {K})")
-    if min(ignore_gt, ignore_pred, ignore_aux) < -1:
-        raise ValueError("an ignore label is a class id >= 0, or -1 for none")
-    if aux is None and ignore_aux != -1:
-        raise ValueError("ignore_aux needs aux")
+    K = _report_args(K, aux, ignore_gt, ignore_pred, ignore_aux)
+    _report_operands("gt, pred", (gt, pred), aux, torch.Tensor.numel, "labels")
     P = gt.numel()
-    if pred.numel() != P or (aux is not None and aux.numel() != P):
-        raise ValueError(f"gt, pred{' and aux' if aux is not None else ''} must hold the same number of labels "
-                         f"(got {P}, {pred.numel()}{'' if aux is None else ', ' + str(aux.numel())})")
-    if pred.device != gt.device or (aux is not None and aux.device != gt.device):
-        raise ValueError("gt, pred and aux must live on one device")
     if not gt.is_cuda:
         return _confusion_cpu(gt, pred, K, aux, ignore_gt, ignore_pred, ignore_aux)
     g, p = _labels(gt, "gt"), _labels(pred, "pred")
     a = _labels(aux, "aux") if aux is not None else None
     if P == 0:  # an empty tensor has no address: nothing to mask
         a, ignore_aux = None, -1
-    code = lambda t: DT_F32 if t.dtype == torch.float32 else DT_I8
     out = torch.empty(K * K + 2, dtype=torch.int64, device=gt.device)
     nbytes = lib().crw_confusion_ws_bytes(P, K)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=gt.device)
-    _check(lib().crw_confusion(_ptr(g), code(g), _ptr(p), code(p), _ptr(a) if a is not None else None,
-                               code(a) if a is not None else DT_I8, P, K, int(ignore_gt), int(ignore_pred), int(ignore_aux),
-                               _ptr(out), ctypes.c_void_p(out.data_ptr() + 8 * K * K), _ptr(ws), nbytes, _stream()), "crw_confusion")
+    _check(lib().crw_confusion(_ptr(g), _dt(g), _ptr(p), _dt(p), _ptr(a), _dt(a), P, K, int(ignore_gt), int(ignore_pred),
+                               int(ignore_aux), _ptr(out), ctypes.c_void_p(out.data_ptr() + 8 * K * K), _ptr(ws), nbytes, _stream()), "crw_confusion")
     return out[:K * K].view(K, K), out[K * K:]
 
 
 def _confusion_cpu(gt, pred, K, aux, ignore_gt, ignore_pred, ignore_aux):
     g, p = gt.reshape(-1).to(torch.float64), pred.reshape(-1).to(torch.float64)
-    masked = torch.zeros(g.shape, dtype=torch.bool)
-    if ignore_gt >= 0:
-        masked |= g == ignore_gt
-    if ignore_pred >= 0:
-        masked |= p == ignore_pred
-    if ignore_aux >= 0:
-        masked |= aux.reshape(-1).to(torch.float64) == ignore_aux
-    valid = (g == g.floor()) & (g >= 0) & (g < K) & (p == p.floor()) & (p >= 0) & (p < K)  # NaN fails every comparison
+    masked, valid = _mask_valid(g, p, aux, K, ignore_gt, ignore_pred, ignore_aux)
     keep = valid & ~masked
     # masked and invalid labels go to two extra bins, like the kernel's: no boolean-indexed copy of the maps
     idx = torch.where(keep, g * K + p, torch.where(masked, float(K * K), float(K * K + 1))).to(torch.int64)
@@ -644,17 +603,6 @@ def _confusion_cpu(gt, pred, K, aux, ignore_gt, ignore_pred, ignore_aux):
 HORIZON_STATS = 18           # per class: n_both, n_missing, n_spurious, then 5 numbers for each of top, bottom, count
 HORIZON_MAX_ROWS = 32768
 HORIZON_QUANTITIES = ("top", "bottom", "count")
-
-
-def _window2d(t):
-    """A 2-D label map (or a [rows, a:b] column window of one) as one of the kernel's dtypes; rows stay where they are when the
-    dtype is one of the kernel's and the window's rows are contiguous."""
-    if t.dtype == torch.bool:
-        t = t.to(torch.int8)
-    elif t.dtype not in (torch.float32, torch.int8):
-        f = t.to(torch.float32)
-        t = torch.where(f.to(t.dtype) == t, f, torch.full_like(f, float("nan")))
-    return t
 
 
 def _pitch(t):
@@ -679,20 +627,10 @@ def horizons(gt, pred, K, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1,
     windows that share one pitch are read where they lie (operands of differing pitch are made contiguous first).  ``row_slabs``:
     0 lets the library cut the rows, 1 ... 8 forces the number of slabs.  ``picks_out``: a contiguous int32 [2, 3, K, cols] tensor
     to write the picks into.  CPU tensors: the same integers from vectorised torch ops."""
-    K = int(K)
-    if not 2 <= K <= 16:
-        raise ValueError(f"K must be in 2 ... 16 (got {K})")
-    if min(ignore_gt, ignore_pred, ignore_aux) < -1:
-        raise ValueError("an ignore label is a class id >= 0, or -1 for none")
-    if aux is None and ignore_aux != -1:
-        raise ValueError("ignore_aux needs aux")
+    K = _report_args(K, aux, ignore_gt, ignore_pred, ignore_aux)
     if gt.dim() != 2:
         raise ValueError(f"gt must be a [rows, cols] map (got shape {tuple(gt.shape)})")
-    if pred.shape != gt.shape or (aux is not None and aux.shape != gt.shape):
-        raise ValueError(f"gt, pred{' and aux' if aux is not None else ''} must hold the same number of labels "
-                         f"(got {tuple(gt.shape)}, {tuple(pred.shape)}{'' if aux is None else ', ' + str(tuple(aux.shape))})")
-    if pred.device != gt.device or (aux is not None and aux.device != gt.device):
-        raise ValueError("gt, pred and aux must live on one device")
+    _report_operands("gt, pred", (gt, pred), aux, lambda t: tuple(t.shape), "labels")
     min_run, tol, row_slabs = int(min_run), int(tol), int(row_slabs)
     if min_run < 1:
         raise ValueError(f"min_run must be at least 1 (got {min_run})")
@@ -713,7 +651,8 @@ def horizons(gt, pred, K, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1,
         if picks_out is not None:
             picks = picks_out.copy_(picks)
         return (stats, dropped, picks) if want_picks else (stats, dropped)
-    ops = [_window2d(t) for t in (gt, pred, aux) if t is not None]
+    # rows stay where they are when the dtype is one of the kernel's and the window's rows are contiguous
+    ops = [_kernel_dtype(t) for t in (gt, pred, aux) if t is not None]
     pitches = [_pitch(t) for t in ops]
     if rows * cols == 0:
         ops, ld = ops[:2], cols  # an empty tensor has no address: nothing to mask
@@ -724,7 +663,6 @@ def horizons(gt, pred, K, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1,
         ld = pitches[0]
     g, p = ops[0], ops[1]
     a = ops[2] if len(ops) > 2 else None
-    code = lambda t: DT_F32 if t.dtype == torch.float32 else DT_I8
     out = torch.empty(K * HORIZON_STATS + 2, dtype=torch.int64, device=gt.device)
     picks = None
     if want_picks:
@@ -732,7 +670,7 @@ def horizons(gt, pred, K, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1,
     L = _horizons_lib()
     nbytes = L.crw_horizons_ws_bytes(rows, cols, K)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=gt.device)
-    _check(L.crw_horizons(_ptr(g), code(g), _ptr(p), code(p), _ptr(a) if a is not None else None, code(a) if a is not None else DT_I8,
+    _check(L.crw_horizons(_ptr(g), _dt(g), _ptr(p), _dt(p), _ptr(a), _dt(a),
                           rows, cols, ld, K, int(ignore_gt), int(ignore_pred), int(ignore_aux), min_run, tol, row_slabs,
                           _ptr(picks) if picks is not None and picks.numel() else None, _ptr(out),
                           ctypes.c_void_p(out.data_ptr() + 8 * K * HORIZON_STATS), _ptr(ws), nbytes, _stream()), "crw_horizons")
@@ -743,14 +681,7 @@ def horizons(gt, pred, K, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1,
 def _horizons_cpu(gt, pred, K, aux, ignore_gt, ignore_pred, ignore_aux, min_run, tol):
     rows, cols = gt.shape
     g, p = gt.to(torch.float64), pred.to(torch.float64)
-    masked = torch.zeros(g.shape, dtype=torch.bool)
-    if ignore_gt >= 0:
-        masked |= g == ignore_gt
-    if ignore_pred >= 0:
-        masked |= p == ignore_pred
-    if ignore_aux >= 0:
-        masked |= aux.to(torch.float64) == ignore_aux
-    valid = (g == g.floor()) & (g >= 0) & (g < K) & (p == p.floor()) & (p >= 0) & (p < K)  # NaN fails every comparison
+    masked, valid = _mask_valid(g, p, aux, K, ignore_gt, ignore_pred, ignore_aux)
     keep = valid & ~masked
     dropped = torch.stack([masked.sum(), (~masked & ~valid).sum()]).to(torch.int64)
     picks = torch.empty(2, 3, K, cols, dtype=torch.int32)
@@ -876,7 +807,7 @@ def merge_confidence(fwd_lab, fwd_conf, rev_lab, rev_conf, out_lab=None, out_con
             took.view(-1).copy_(take)
         return out_lab, out_conf, took
     fl, fc, rl, rc = (t.contiguous() for t in (fwd_lab, fwd_conf, rev_lab, rev_conf))
-    _check(_confidence_lib().crw_merge_confidence(_ptr(fl), _ptr(fc), _ptr(rl), _ptr(rc), DT_F32 if fl.dtype == torch.float32 else DT_I8,
+    _check(_confidence_lib().crw_merge_confidence(_ptr(fl), _ptr(fc), _ptr(rl), _ptr(rc), _dt(fl),
                                                   P, _ptr(out_lab), _ptr(out_conf), _ptr(took) if took is not None else None,
                                                   _stream()), "crw_merge_confidence")
     return out_lab, out_conf, took
@@ -890,20 +821,9 @@ def calibration(gt, pred, conf, K, bins=10, aux=None, ignore_gt=-1, ignore_pred=
     surviving pixel whose confidence is NaN or outside [0, 1] is counted in dropped[2] and in no bin.  Device tensors: one pass
     of crw_calibration, nothing synchronises; CPU tensors: the same numbers from torch.bincount, conf_sum in float64."""
     K, bins = int(K), int(bins)
-    if not 2 <= K <= 16:
-        raise ValueError(f"K must be in 2 ... 16 (got {K})")
-    if not 1 <= bins <= 64:
-        raise ValueError(f"bins must be in 1 ... 64 (got {bins})")
-    if min(ignore_gt, ignore_pred, ignore_aux) < -1:
-        raise ValueError("an ignore label is a class id >= 0, or -1 for none")
-    if aux is None and ignore_aux != -1:
-        raise ValueError("ignore_aux needs aux")
+    K = _report_args(K, aux, ignore_gt, ignore_pred, ignore_aux, bins)
+    _report_operands("gt, pred, conf", (gt, pred, conf), aux, torch.Tensor.numel, "pixels")
     P = gt.numel()
-    if pred.numel() != P or conf.numel() != P or (aux is not None and aux.numel() != P):
-        raise ValueError(f"gt, pred, conf{' and aux' if aux is not None else ''} must hold the same number of pixels "
-                         f"(got {P}, {pred.numel()}, {conf.numel()}{'' if aux is None else ', ' + str(aux.numel())})")
-    if pred.device != gt.device or conf.device != gt.device or (aux is not None and aux.device != gt.device):
-        raise ValueError("gt, pred, conf and aux must live on one device")
     if not conf.is_floating_point():
         raise ValueError(f"conf must be a floating-point map (got {conf.dtype})")
     c = conf.reshape(-1).to(torch.float32).contiguous()
@@ -913,28 +833,19 @@ def calibration(gt, pred, conf, K, bins=10, aux=None, ignore_gt=-1, ignore_pred=
     a = _labels(aux, "aux") if aux is not None else None
     if P == 0:  # an empty tensor has no address: nothing to mask
         a, ignore_aux = None, -1
-    code = lambda t: DT_F32 if t.dtype == torch.float32 else DT_I8
     out = torch.empty(3 * bins + 3, dtype=torch.int64, device=gt.device)  # counts [bins][2] | conf_sum [bins] (as bits) | dropped [3]
     nbytes = _confidence_lib().crw_calibration_ws_bytes(P, K, bins)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=gt.device)
     base = out.data_ptr()
-    _check(lib().crw_calibration(_ptr(g), code(g), _ptr(p), code(p), _ptr(c), _ptr(a) if a is not None else None,
-                                 code(a) if a is not None else DT_I8, P, K, bins, int(ignore_gt), int(ignore_pred), int(ignore_aux),
-                                 ctypes.c_void_p(base), ctypes.c_void_p(base + 16 * bins), ctypes.c_void_p(base + 24 * bins), _ptr(ws),
-                                 nbytes, _stream()), "crw_calibration")
+    _check(lib().crw_calibration(_ptr(g), _dt(g), _ptr(p), _dt(p), _ptr(c), _ptr(a), _dt(a), P, K, bins, int(ignore_gt),
+                                 int(ignore_pred), int(ignore_aux), ctypes.c_void_p(base), ctypes.c_void_p(base + 16 * bins),
+                                 ctypes.c_void_p(base + 24 * bins), _ptr(ws), nbytes, _stream()), "crw_calibration")
     return out[:2 * bins].view(bins, 2), out[2 * bins:3 * bins].view(torch.float64), out[3 * bins:]
 
 
 def _calibration_cpu(gt, pred, c, K, bins, aux, ignore_gt, ignore_pred, ignore_aux):
     g, p = gt.reshape(-1).to(torch.float64), pred.reshape(-1).to(torch.float64)
-    masked = torch.zeros(g.shape, dtype=torch.bool)
-    if ignore_gt >= 0:
-        masked |= g == ignore_gt
-    if ignore_pred >= 0:
-        masked |= p == ignore_pred
-    if ignore_aux >= 0:
-        masked |= aux.reshape(-1).to(torch.float64) == ignore_aux
-    valid = (g == g.floor()) & (g >= 0) & (g < K) & (p == p.floor()) & (p >= 0) & (p < K)  # NaN fails every comparison
+    masked, valid = _mask_valid(g, p, aux, K, ignore_gt, ignore_pred, ignore_aux)
     cvalid = (c >= 0) & (c <= 1)
     binned = ~masked & valid & cvalid
     b = torch.clamp(torch.floor(torch.where(binned, c, torch.zeros_like(c)) * bins), max=bins - 1).to(torch.int64)  # fp32 product
@@ -983,8 +894,12 @@ def _window(t, name, lead, rows, cols, dtype, device):
     return ld, map_stride
 
 
-def _labelmap_dense(L, G, T, N, M, rows, cols, confidence, flip, dtype, out, out_conf):
-    """`labelmap_dense` (G None: one map, no leading axis) and `labelmap_dense_batch` behind their signatures."""
+_ARGMAX = object()  # `_labelmap`'s order for the arg-max maps (None is a caller's order like any other: `check_order` refuses it)
+
+
+def _labelmap(L, G, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace=None):
+    """The four label-map functions behind their signatures.  G None: one map, no leading axis, otherwise the `_batch` form;
+    order _ARGMAX: `labelmap_dense`, otherwise `labelmap_ordered`'s decode under it (`workspace`: its alone)."""
     code = -1 if confidence is None else _conf_kind(confidence)
     T, N, M, rows, cols = int(T), int(N), int(M), int(rows), int(cols)
     lead = () if G is None else (int(G),)
@@ -992,6 +907,8 @@ def _labelmap_dense(L, G, T, N, M, rows, cols, confidence, flip, dtype, out, out
         raise ValueError(f"G must be in 1 ... 65535 (got {lead[0]})")
     if not 2 <= M <= 16:
         raise ValueError(f"M must be in 2 ... 16 (got {M})")
+    if order is not _ARGMAX:
+        order = check_order(order, M)
     if T < 1 or N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
         raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={T}, N={N}, rows={rows}, cols={cols})")
     if L.numel() != (lead[0] if lead else 1) * T * N * M or L.dtype != torch.float32:
@@ -1015,17 +932,35 @@ def _labelmap_dense(L, G, T, N, M, rows, cols, confidence, flip, dtype, out, out
     if not L.is_cuda:
         maps, confs = (out, out_conf) if lead else (out[None], None if out_conf is None else out_conf[None])
         for g, Lg in enumerate(L.view(-1, T * N, M)):
-            lab, conf = _labelmap_dense_cpu(Lg, T, N, M, rows, cols, confidence, flip)
+            if order is _ARGMAX:
+                lab, conf = _labelmap_dense_cpu(Lg, T, N, M, rows, cols, confidence, flip)
+            else:
+                lab, conf = _labelmap_ordered_cpu(Lg, T, N, M, rows, cols, order, confidence, flip)
             maps[g].copy_(lab.to(dtype))
             if confs is not None:
                 confs[g].copy_(conf)
         return out, out_conf
-    args = (T, N, M, rows, cols, int(bool(flip)), code, _ptr(out), DT_F32 if dtype == torch.float32 else DT_I8,
-            _ptr(out_conf) if out_conf is not None else None, ld)
+    # the C signatures: L, [G,] geometry, [order, S,] windows, [map_stride,] [workspace, its bytes,] stream
+    geometry = (T, N, M, rows, cols, int(bool(flip)))
+    windows = (code, _ptr(out), _dt(out), _ptr(out_conf), ld)
+    if order is _ARGMAX:
+        if lead:
+            _check(_dense_batch_lib().crw_labelmap_dense_batch(_ptr(L), *lead, *geometry, *windows, map_stride, _stream()),
+                   "crw_labelmap_dense_batch")
+        else:
+            _check(_dense_lib().crw_labelmap_dense(_ptr(L), *geometry, *windows, _stream()), "crw_labelmap_dense")
+        return out, out_conf
+    clib = _ordered_lib()
+    if workspace is None:
+        workspace = torch.empty(clib.crw_labelmap_ordered_workspace(*lead or (1,), rows, cols), dtype=torch.uint8, device=L.device)
+    elif workspace.device != L.device or not workspace.is_contiguous():
+        raise ValueError(f"workspace must be a contiguous tensor on {L.device} (got {workspace.device})")
+    decode = ((ctypes.c_int * len(order))(*order), len(order))
+    tail = (_ptr(workspace), workspace.numel() * workspace.element_size(), _stream())
     if lead:
-        _check(_dense_batch_lib().crw_labelmap_dense_batch(_ptr(L), lead[0], *args, map_stride, _stream()), "crw_labelmap_dense_batch")
+        _check(clib.crw_labelmap_ordered_batch(_ptr(L), *lead, *geometry, *decode, *windows, map_stride, *tail), "crw_labelmap_ordered_batch")
     else:
-        _check(_dense_lib().crw_labelmap_dense(_ptr(L), *args, _stream()), "crw_labelmap_dense")
+        _check(clib.crw_labelmap_ordered(_ptr(L), *geometry, *decode, *windows, *tail), "crw_labelmap_ordered")
     return out, out_conf
 
 
@@ -1039,7 +974,7 @@ def labelmap_dense(L, T, N, M, rows, cols, *, confidence=None, flip=False, dtype
     else that is not contiguous raises ValueError.  Device tensors: one launch of crw_labelmap_dense, nothing synchronises, the
     interpolated probabilities are never written; CPU tensors: the same integer knots, fp32 weights, arithmetic and tie rule in
     torch."""
-    return _labelmap_dense(L, None, T, N, M, rows, cols, confidence, flip, dtype, out, out_conf)
+    return _labelmap(L, None, T, N, M, rows, cols, _ARGMAX, confidence, flip, dtype, out, out_conf)
 
 
 def labelmap_dense_batch(L, G, T, N, M, rows, cols, *, confidence=None, flip=False, dtype=torch.int8, out=None, out_conf=None):
@@ -1049,10 +984,11 @@ def labelmap_dense_batch(L, G, T, N, M, rows, cols, *, confidence=None, flip=Fal
     column windows ``maps[:, :, a:b]`` of wider [G, rows, width] tensors (one pitch and one map stride for both), anything else
     that is not contiguous raises ValueError.  Device tensors: ONE launch of crw_labelmap_dense_batch, nothing synchronises; CPU
     tensors: a loop of `labelmap_dense`'s CPU route over the configurations."""
-    return _labelmap_dense(L, G, T, N, M, rows, cols, confidence, flip, dtype, out, out_conf)
+    return _labelmap(L, G, T, N, M, rows, cols, _ARGMAX, confidence, flip, dtype, out, out_conf)
 
 
-def _labelmap_dense_cpu(L, T, N, M, rows, cols, confidence, flip):
+def _interpolated(L, T, N, M, rows, cols, flip):
+    """The interpolated probabilities v [rows, cols, M] of the CPU route: `dense_knots`' knots and weights, fp32."""
     i0, i1, wr = dense_knots(N, rows)
     j0, j1, wc = dense_knots(T, cols, flip)
     P = L.view(T, N, M)
@@ -1060,12 +996,20 @@ def _labelmap_dense_cpu(L, T, N, M, rows, cols, confidence, flip):
     corner = lambda i, j: P[j[None, :], i[:, None]]  # [rows, cols, M]
     top = (1 - wc) * corner(i0, j0) + wc * corner(i0, j1)
     bot = (1 - wc) * corner(i1, j0) + wc * corner(i1, j1)
-    v = (1 - wr) * top + wr * bot
-    lab = v.argmax(-1)  # the first of equal maxima: the lowest class
-    conf = None
-    if confidence is not None:
-        conf = _labelprop_confidence_cpu(v.permute(1, 0, 2).reshape(rows * cols, M), cols, rows, M, confidence, 1)
-    return lab, conf
+    return (1 - wr) * top + wr * bot
+
+
+def _interpolated_confidence(v, confidence):
+    """conf [rows, cols] of v [rows, cols, M] (`labelprop_confidence`'s formulas), or None without a kind."""
+    if confidence is None:
+        return None
+    rows, cols, M = v.shape
+    return _labelprop_confidence_cpu(v.permute(1, 0, 2).reshape(rows * cols, M), cols, rows, M, confidence, 1)
+
+
+def _labelmap_dense_cpu(L, T, N, M, rows, cols, confidence, flip):
+    v = _interpolated(L, T, N, M, rows, cols, flip)
+    return v.argmax(-1), _interpolated_confidence(v, confidence)  # the first of equal maxima: the lowest class
 
 
 # ------------------------------------------------------------------------------ depth-ordered label maps
@@ -1087,62 +1031,6 @@ def labelmap_ordered_workspace(G, rows, cols):
     return _ordered_lib().crw_labelmap_ordered_workspace(int(G), int(rows), int(cols))
 
 
-def _labelmap_ordered(L, G, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace):
-    """`labelmap_ordered` (G None: one map, no leading axis) and `labelmap_ordered_batch` behind their signatures."""
-    code = -1 if confidence is None else _conf_kind(confidence)
-    T, N, M, rows, cols = int(T), int(N), int(M), int(rows), int(cols)
-    lead = () if G is None else (int(G),)
-    if lead and not 1 <= lead[0] <= 65535:
-        raise ValueError(f"G must be in 1 ... 65535 (got {lead[0]})")
-    if not 2 <= M <= 16:
-        raise ValueError(f"M must be in 2 ... 16 (got {M})")
-    order = check_order(order, M)
-    if T < 1 or N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
-        raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={T}, N={N}, rows={rows}, cols={cols})")
-    if L.numel() != (lead[0] if lead else 1) * T * N * M or L.dtype != torch.float32:
-        raise ValueError(f"L must be float32 {[*lead, T * N, M]} (got {L.dtype} {tuple(L.shape)})")
-    if dtype not in (torch.float32, torch.int8):
-        raise ValueError(f"dtype must be torch.float32 or torch.int8 (got {dtype})")
-    if out_conf is not None and confidence is None:
-        raise ValueError("out_conf needs a confidence kind")
-    if out is None:
-        out = torch.empty(*lead, rows, cols, dtype=dtype, device=L.device)
-    if out_conf is None and confidence is not None:
-        out_conf = torch.empty(*lead, rows, cols, dtype=torch.float32, device=L.device)
-    ld, map_stride = _window(out, "out", lead, rows, cols, dtype, L.device)
-    if out_conf is not None:
-        cld, cstride = _window(out_conf, "out_conf", lead, rows, cols, torch.float32, L.device)
-        if cld != ld and rows > 1:
-            raise ValueError(f"out and out_conf must share one pitch (got {out.stride(-2)} and {out_conf.stride(-2)})")
-        if cstride != map_stride:
-            raise ValueError(f"out and out_conf must share one map stride (got {out.stride(0)} and {out_conf.stride(0)})")
-    L = L.contiguous()
-    if not L.is_cuda:
-        maps, confs = (out, out_conf) if lead else (out[None], None if out_conf is None else out_conf[None])
-        for g, Lg in enumerate(L.view(-1, T * N, M)):
-            lab, conf = _labelmap_ordered_cpu(Lg, T, N, M, rows, cols, order, confidence, flip)
-            maps[g].copy_(lab.to(dtype))
-            if confs is not None:
-                confs[g].copy_(conf)
-        return out, out_conf
-    clib = _ordered_lib()
-    need = clib.crw_labelmap_ordered_workspace(lead[0] if lead else 1, rows, cols)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=L.device)
-    elif workspace.device != L.device or not workspace.is_contiguous():
-        raise ValueError(f"workspace must be a contiguous tensor on {L.device} (got {workspace.device})")
-    ws_bytes = workspace.numel() * workspace.element_size()
-    corder = (ctypes.c_int * len(order))(*order)
-    head = (T, N, M, rows, cols, int(bool(flip)), corder, len(order), code, _ptr(out), DT_F32 if dtype == torch.float32 else DT_I8,
-            _ptr(out_conf) if out_conf is not None else None, ld)
-    tail = (_ptr(workspace), ws_bytes, _stream())
-    if lead:
-        _check(clib.crw_labelmap_ordered_batch(_ptr(L), lead[0], *head, map_stride, *tail), "crw_labelmap_ordered_batch")
-    else:
-        _check(clib.crw_labelmap_ordered(_ptr(L), *head, *tail), "crw_labelmap_ordered")
-    return out, out_conf
-
-
 def labelmap_ordered(L, T, N, M, rows, cols, order, *, confidence=None, flip=False, dtype=torch.float32, out=None, out_conf=None,
                      workspace=None):
     """`labelmap_dense`'s interpolated probabilities decoded under a layer order -> (labels [rows, cols], conf | None).
@@ -1155,7 +1043,7 @@ def labelmap_ordered(L, T, N, M, rows, cols, order, *, confidence=None, flip=Fal
     `labelmap_ordered_workspace(1, rows, cols)` bytes for the back-pointers (default: allocated per call; a short one raises
     CrwError CRW_EWORKSPACE).  Device tensors: one launch of crw_labelmap_ordered, nothing synchronises; CPU tensors: the same
     recurrence and tie rules in torch (a loop over rows, tensors over [S, cols]) on the CPU route's own interpolated values."""
-    return _labelmap_ordered(L, None, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace)
+    return _labelmap(L, None, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace)
 
 
 def labelmap_ordered_batch(L, G, T, N, M, rows, cols, order, *, confidence=None, flip=False, dtype=torch.int8, out=None,
@@ -1164,21 +1052,11 @@ def labelmap_ordered_batch(L, G, T, N, M, rows, cols, order, *, confidence=None,
     [G, rows, cols], conf | None); slice g is `labelmap_ordered(L[g], ...)` bit for bit.  out / out_conf / dtype: as for
     `labelmap_dense_batch`; workspace: at least `labelmap_ordered_workspace(G, rows, cols)` bytes.  Device tensors: ONE launch of
     crw_labelmap_ordered_batch; CPU tensors: a loop of `labelmap_ordered`'s CPU route."""
-    return _labelmap_ordered(L, G, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace)
+    return _labelmap(L, G, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace)
 
 
 def _labelmap_ordered_cpu(L, T, N, M, rows, cols, order, confidence, flip):
-    i0, i1, wr = dense_knots(N, rows)
-    j0, j1, wc = dense_knots(T, cols, flip)
-    P = L.view(T, N, M)
-    wr, wc = wr[:, None, None], wc[None, :, None]
-    corner = lambda i, j: P[j[None, :], i[:, None]]  # [rows, cols, M]
-    top = (1 - wc) * corner(i0, j0) + wc * corner(i0, j1)
-    bot = (1 - wc) * corner(i1, j0) + wc * corner(i1, j1)
-    v = (1 - wr) * top + wr * bot  # `_labelmap_dense_cpu`'s values
-    conf = None
-    if confidence is not None:
-        conf = _labelprop_confidence_cpu(v.permute(1, 0, 2).reshape(rows * cols, M), cols, rows, M, confidence, 1)
+    v = _interpolated(L, T, N, M, rows, cols, flip)  # `_labelmap_dense_cpu`'s values
     S = len(order)
     e = v[:, :, order].permute(0, 2, 1).contiguous()  # [rows, S, cols]
     D = e[0].clone()
@@ -1194,7 +1072,7 @@ def _labelmap_ordered_cpu(L, T, N, M, rows, cols, order, confidence, flip):
         states[r] = state
         state = torch.where(new[r] & (idx <= state[None]), idx, 0).max(0).values  # the highest new maximum <= state
     states[0] = state
-    return torch.tensor(order)[states], conf
+    return torch.tensor(order)[states], _interpolated_confidence(v, confidence)
 
 
 def gemm_f32(A, B, C=None, transA=False, transB=False, beta=False):

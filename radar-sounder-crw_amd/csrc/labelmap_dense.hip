@@ -23,6 +23,7 @@
 // programme down the column, a lane per column.  They live here because they read the pixels through knot, load_row and
 // dense_pixel of this file; their own text starts at "ordered label maps".
 #include <cstdlib>
+#include <type_traits>
 
 #include "confidence_of.h"
 #include "labelmap.h"
@@ -96,16 +97,22 @@ __device__ inline void load_row(const float *__restrict__ row, int M, int vec, f
   }
 }
 
-// One pixel: its row interpolated between the four node rows, the arg-max (strict: a tie keeps the lowest class) and the
-// confidence of the interpolated row.  The ONE text of this arithmetic, instantiated by every shape of the kernel.  One text is
-// not yet one result: left to itself the compiler contracts a * b + c * d to FMAs site by site (and turns (1 - w) * p into
-// fma(-w, p, p)), differently in two instantiations and even between the pixels of one lane.  So the roundings are
-// written out -- one product rounded, the other fused into the sum, at each of the three steps -- and contraction is off here.
+// One step of the interpolation, u = 1 - w: u * a + w * b.  The ONE text of this arithmetic: dense_pixel takes its three steps
+// through it, and so do ordered_sides / ordered_values.  One text is not yet one result: left to itself the compiler contracts
+// a * b + c * d to FMAs site by site (and turns (1 - w) * p into fma(-w, p, p)), differently in two instantiations and even
+// between the pixels of one lane.  So the roundings are written out -- one product rounded, the other fused into the sum -- and
+// contraction is off here.
+__device__ __forceinline__ float dense_lerp(float w, float u, float a, float b) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(w, b, u * a);
+}
+
+// One pixel: its row interpolated between the four node rows (three dense_lerp steps per class), the arg-max (strict: a tie
+// keeps the lowest class) and the confidence of the interpolated row.  Instantiated by every shape of the kernel.
 template <int KIND, int MCAP>
 __device__ __forceinline__ void dense_pixel(const float (&p00)[MCAP], const float (&p01)[MCAP], const float (&p10)[MCAP],
                                             const float (&p11)[MCAP], float wc, float wr, int M, float ln_m, float *lab,
                                             float *conf) {
-#pragma clang fp contract(off)
   const float uc = 1.f - wc, ur = 1.f - wr;
   float v[16], top1 = 0.f;
   int best = 0;
@@ -113,9 +120,9 @@ __device__ __forceinline__ void dense_pixel(const float (&p00)[MCAP], const floa
   for (int m = 0; m < 16; ++m) {
     v[m] = 0.f;
     if (m < MCAP && m < M) {
-      const float top = __builtin_fmaf(wc, p01[m], uc * p00[m]);
-      const float bot = __builtin_fmaf(wc, p11[m], uc * p10[m]);
-      v[m] = __builtin_fmaf(wr, bot, ur * top);
+      const float top = dense_lerp(wc, uc, p00[m], p01[m]);
+      const float bot = dense_lerp(wc, uc, p10[m], p11[m]);
+      v[m] = dense_lerp(wr, ur, top, bot);
       if (m == 0 || v[m] > top1) top1 = v[m], best = m;  // strict: a tie keeps the lowest class
     }
   }
@@ -232,18 +239,22 @@ __global__ __launch_bounds__(DN_BLOCK) void labelmap_dense_kernel(DenseArgs a) {
   }
 }
 
-template <typename LAB, int KIND, bool BATCH>
-auto dense_kernel_m(int M) {
-  return M <= 4 ? labelmap_dense_kernel<LAB, KIND, 4, BATCH>
-                : M <= 8 ? labelmap_dense_kernel<LAB, KIND, 8, BATCH> : labelmap_dense_kernel<LAB, KIND, 16, BATCH>;
-}
+// The instantiation of either kernel family for a label dtype, a confidence kind (-1: none) and M classes: pick(LAB{}, KIND,
+// MCAP), the two numbers as integral constants, MCAP the smallest of 4 / 8 / 16 that holds M.
+template <int V>
+using int_c = std::integral_constant<int, V>;
 
-template <typename LAB, bool BATCH>
-auto dense_kernel(int kind, int M) {
-  return kind < 0 ? dense_kernel_m<LAB, -1, BATCH>(M)
-                  : kind == CRW_CONF_MAXPROB ? dense_kernel_m<LAB, CRW_CONF_MAXPROB, BATCH>(M)
-                  : kind == CRW_CONF_MARGIN ? dense_kernel_m<LAB, CRW_CONF_MARGIN, BATCH>(M)
-                                            : dense_kernel_m<LAB, CRW_CONF_ENTROPY, BATCH>(M);
+template <typename PICK>
+auto kernel_for(int label_dtype, int kind, int M, PICK pick) {
+  const auto by_m = [&](auto lab, auto k) {
+    return M > 4 ? (M <= 8 ? pick(lab, k, int_c<8>{}) : pick(lab, k, int_c<16>{})) : pick(lab, k, int_c<4>{});
+  };
+  const auto by_kind = [&](auto lab) {
+    return kind < 0 ? by_m(lab, int_c<-1>{})
+                    : kind == CRW_CONF_MAXPROB ? by_m(lab, int_c<CRW_CONF_MAXPROB>{})
+                    : kind == CRW_CONF_MARGIN ? by_m(lab, int_c<CRW_CONF_MARGIN>{}) : by_m(lab, int_c<CRW_CONF_ENTROPY>{});
+  };
+  return label_dtype == CRW_DT_F32 ? by_kind(float{}) : by_kind(int8_t{});
 }
 
 // configurations a workgroup walks with one set of knots: fastest or tied of 1 / 2 / 4 / 8 at G = 60, 410 x 3200, 5 - 17 % ahead of
@@ -261,29 +272,39 @@ int batch_chunk(int G) {
   return chunk < G ? chunk : G;
 }
 
-// Both entry points behind their signatures: the argument checks, the kernel's arguments, the launch.  `chunk`: the
-// configurations a workgroup walks (the one-map entry point: G = 1, chunk = 1).
-template <bool BATCH>
-int dense_launch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
-                 int label_dtype, float *conf, size_t ld, size_t map_stride, int chunk, crw_stream_t stream) {
-  clear_stale_error();
+// The arguments the dense and the ordered entry points share: checked (CRW_EINVAL), then written into `a`.  lab_phase and
+// conf_vec are the dense kernels'; the ordered ones do not read them.
+int dense_args(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
+               int label_dtype, float *conf, size_t ld, size_t map_stride, int chunk, DenseArgs &a) {
   constexpr int MAX_SIDE = 1 << 22;  // 2 * side < 2^24: the weights' numerators and denominators are exact in fp32
   if (!L || !labels || G < 1 || G > 65535 || T < 1 || N < 1 || M < 2 || M > 16 || rows < 1 || cols < 1 || rows > MAX_SIDE ||
       cols > MAX_SIDE || !dtype_ok(label_dtype) || conf_kind < -1 || conf_kind > CRW_CONF_ENTROPY ||
       (conf_kind == -1) != (conf == nullptr) || ld < (size_t)cols || map_stride < (size_t)(rows - 1) * ld + (size_t)cols ||
       ((uintptr_t)L & 3) || ((uintptr_t)conf & 3) || (label_dtype == CRW_DT_F32 && ((uintptr_t)labels & 3)))
     return CRW_EINVAL;  // (a slice's base is configuration 0's plus whole elements: 4-byte aligned when that is)
-  DenseArgs a;
   a.L = L, a.lab = labels, a.conf = conf, a.ld = ld;
   a.T = T, a.N = N, a.M = M, a.rows = rows, a.cols = cols, a.flip = flip != 0;
   a.lab_phase = (int)(((uintptr_t)labels / elem(label_dtype)) & (DN_LANE_PIX - 1));
   a.conf_vec = conf && (int)(((uintptr_t)conf / 4) & (DN_LANE_PIX - 1)) == a.lab_phase;
   a.ln_m = logf((float)M);
   a.l_stride = (size_t)T * N * M, a.map_stride = map_stride, a.G = G, a.chunk = chunk;
+  return CRW_OK;
+}
+
+// Both entry points behind their signatures: the argument checks, the kernel's arguments, the launch.  `chunk`: the
+// configurations a workgroup walks (the one-map entry point: G = 1, chunk = 1).
+template <bool BATCH>
+int dense_launch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
+                 int label_dtype, float *conf, size_t ld, size_t map_stride, int chunk, crw_stream_t stream) {
+  clear_stale_error();
+  DenseArgs a;
+  if (const int st = dense_args(L, G, T, N, M, rows, cols, flip, conf_kind, labels, label_dtype, conf, ld, map_stride, chunk, a)) return st;
   // a row's groups: ceil((cols + phase) / 4) <= (cols + 3 + 3) / 4
   const unsigned groups = ((unsigned)cols + 2 * (DN_LANE_PIX - 1)) / DN_LANE_PIX;
   const dim3 grid(((unsigned)rows + DN_ROWS - 1) / DN_ROWS, (groups + WAVE - 1) / WAVE, ((unsigned)G + chunk - 1) / chunk);
-  const auto kernel = label_dtype == CRW_DT_F32 ? dense_kernel<float, BATCH>(conf_kind, M) : dense_kernel<int8_t, BATCH>(conf_kind, M);
+  const auto kernel = kernel_for(label_dtype, conf_kind, M, [](auto lab, auto kind, auto mcap) {
+    return labelmap_dense_kernel<decltype(lab), kind(), mcap(), BATCH>;
+  });
   hipLaunchKernelGGL(kernel, grid, dim3(DN_BLOCK), 0, (hipStream_t)stream, a);
   return check_launch();
 }
@@ -353,32 +374,29 @@ __device__ __forceinline__ void load_ordered(const float *__restrict__ row, uint
     if (s < S) p[s] = row[order_at(order, s)];
 }
 
-// dense_pixel's interpolated values for the first S entries of the four rows -- ITS three lines, the roundings written out the
-// same way, contraction off: on rows permuted by load_ordered, e[s] is bit for bit the v[order[s]] dense_pixel computes (fmaf and
-// a rounded product leave the compiler no choice; dense_pixel itself hands out no v, and its text stays as the dense kernels
-// were verified with).  In two halves, because a lane's column never changes: the first two lines once per pair of node rows
+// dense_pixel's interpolated values for the first S entries of the four rows -- its three dense_lerp steps: on rows permuted by
+// load_ordered, e[s] is bit for bit the v[order[s]] dense_pixel computes (one text, and fmaf and a rounded product leave the
+// compiler no choice).  In two halves, because a lane's column never changes: the first two steps once per pair of node rows
 // (ordered_sides), the third once per pixel (ordered_values).
 template <int SCAP>
 __device__ __forceinline__ void ordered_sides(const float (&p00)[SCAP], const float (&p01)[SCAP], const float (&p10)[SCAP],
                                               const float (&p11)[SCAP], float wc, int S, float (&top)[SCAP], float (&bot)[SCAP]) {
-#pragma clang fp contract(off)
   const float uc = 1.f - wc;
 #pragma unroll
   for (int s = 0; s < SCAP; ++s) {
     top[s] = bot[s] = 0.f;
     if (s < S) {
-      top[s] = __builtin_fmaf(wc, p01[s], uc * p00[s]);
-      bot[s] = __builtin_fmaf(wc, p11[s], uc * p10[s]);
+      top[s] = dense_lerp(wc, uc, p00[s], p01[s]);
+      bot[s] = dense_lerp(wc, uc, p10[s], p11[s]);
     }
   }
 }
 
 template <int SCAP>
 __device__ __forceinline__ void ordered_values(const float (&top)[SCAP], const float (&bot)[SCAP], float wr, int S, float (&e)[SCAP]) {
-#pragma clang fp contract(off)
   const float ur = 1.f - wr;
 #pragma unroll
-  for (int s = 0; s < SCAP; ++s) e[s] = s < S ? __builtin_fmaf(wr, bot[s], ur * top[s]) : -INFINITY;  // beyond S: never a maximum
+  for (int s = 0; s < SCAP; ++s) e[s] = s < S ? dense_lerp(wr, ur, top[s], bot[s]) : -INFINITY;  // beyond S: never a maximum
 }
 
 // lane `l` (uniform) of a value every lane holds, dead lanes included
@@ -481,19 +499,6 @@ __global__ __launch_bounds__(WAVE) void labelmap_ordered_kernel(OrderedArgs a) {
   lab[0] = (LAB)order_at(a.order, state);
 }
 
-template <typename LAB, int KIND>
-auto ordered_kernel_m(int M) {
-  return M <= 4 ? labelmap_ordered_kernel<LAB, KIND, 4> : M <= 8 ? labelmap_ordered_kernel<LAB, KIND, 8> : labelmap_ordered_kernel<LAB, KIND, 16>;
-}
-
-template <typename LAB>
-auto ordered_kernel(int kind, int M) {
-  return kind < 0 ? ordered_kernel_m<LAB, -1>(M)
-                  : kind == CRW_CONF_MAXPROB ? ordered_kernel_m<LAB, CRW_CONF_MAXPROB>(M)
-                  : kind == CRW_CONF_MARGIN ? ordered_kernel_m<LAB, CRW_CONF_MARGIN>(M)
-                                            : ordered_kernel_m<LAB, CRW_CONF_ENTROPY>(M);
-}
-
 // CRW_ORDERED_BACK (read per call): 1 = the backward scan with one word in flight, the other arm of tools/ordered_timing.py's
 // A/B.  The maps do not depend on it.
 int ordered_back() {
@@ -508,18 +513,14 @@ size_t ordered_ws_bytes(int G, int rows, int cols) {
   return (size_t)G * rows * ordered_ws_ld(cols) * sizeof(uint16_t);
 }
 
-// Both entry points behind their signatures.  The argument checks are dense_launch's (repeated, its text is left alone), then
-// the order's and the workspace's; nothing is launched unless all pass.
+// Both entry points behind their signatures.  The argument checks are dense_args', then the order's and the workspace's;
+// nothing is launched unless all pass.
 int ordered_launch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, const int *order, int S, int conf_kind,
                    void *labels, int label_dtype, float *conf, size_t ld, size_t map_stride, void *ws, size_t ws_bytes,
                    crw_stream_t stream) {
   clear_stale_error();
-  constexpr int MAX_SIDE = 1 << 22;
-  if (!L || !labels || G < 1 || G > 65535 || T < 1 || N < 1 || M < 2 || M > 16 || rows < 1 || cols < 1 || rows > MAX_SIDE ||
-      cols > MAX_SIDE || !dtype_ok(label_dtype) || conf_kind < -1 || conf_kind > CRW_CONF_ENTROPY ||
-      (conf_kind == -1) != (conf == nullptr) || ld < (size_t)cols || map_stride < (size_t)(rows - 1) * ld + (size_t)cols ||
-      ((uintptr_t)L & 3) || ((uintptr_t)conf & 3) || (label_dtype == CRW_DT_F32 && ((uintptr_t)labels & 3)))
-    return CRW_EINVAL;
+  OrderedArgs a;
+  if (const int st = dense_args(L, G, T, N, M, rows, cols, flip, conf_kind, labels, label_dtype, conf, ld, map_stride, 1, a.d)) return st;
   if (!order || S < 2 || S > M || !ws || ((uintptr_t)ws & 1)) return CRW_EINVAL;
   uint64_t packed = 0;
   unsigned seen = 0;
@@ -529,15 +530,11 @@ int ordered_launch(const float *L, int G, int T, int N, int M, int rows, int col
     packed |= (uint64_t)order[s] << (4 * s);
   }
   if (ws_bytes < ordered_ws_bytes(G, rows, cols)) return CRW_EWORKSPACE;
-  OrderedArgs a;
-  a.d.L = L, a.d.lab = labels, a.d.conf = conf, a.d.ld = ld;
-  a.d.T = T, a.d.N = N, a.d.M = M, a.d.rows = rows, a.d.cols = cols, a.d.flip = flip != 0;
-  a.d.lab_phase = 0, a.d.conf_vec = 0;
-  a.d.ln_m = logf((float)M);
-  a.d.l_stride = (size_t)T * N * M, a.d.map_stride = map_stride, a.d.G = G, a.d.chunk = 1;
   a.order = packed, a.S = S, a.ws = static_cast<uint16_t *>(ws), a.ws_ld = ordered_ws_ld(cols), a.back = ordered_back();
   const dim3 grid((unsigned)(a.ws_ld / WAVE), (unsigned)G);
-  const auto kernel = label_dtype == CRW_DT_F32 ? ordered_kernel<float>(conf_kind, M) : ordered_kernel<int8_t>(conf_kind, M);
+  const auto kernel = kernel_for(label_dtype, conf_kind, M, [](auto lab, auto kind, auto mcap) {
+    return labelmap_ordered_kernel<decltype(lab), kind(), mcap()>;
+  });
   hipLaunchKernelGGL(kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, a);
   return check_launch();
 }

@@ -294,7 +294,7 @@ def test_header_and_binding_declare_the_confidence_entry_points():
 def test_a_library_without_the_confidence_entry_points_is_named_stale(monkeypatch):
     import crw_hip
     crw_hip.lib()
-    monkeypatch.setattr(crw_hip, "_has_confidence", False)
+    monkeypatch.setitem(crw_hip._present, "confidence", False)
     with pytest.raises(RuntimeError, match="stale libcrw_hip.so.*crw_labelprop_confidence.*rebuild"):
         crw_hip._confidence_lib()
 

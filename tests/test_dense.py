@@ -186,7 +186,7 @@ def test_header_and_binding_declare_the_dense_entry_point_at_abi_8():
 def test_a_library_without_the_dense_entry_point_is_named_stale(monkeypatch):
     import crw_hip
     crw_hip.lib()
-    monkeypatch.setattr(crw_hip, "_has_dense", False)
+    monkeypatch.setitem(crw_hip._present, "dense", False)
     with pytest.raises(RuntimeError, match="stale libcrw_hip.so.*crw_labelmap_dense.*rebuild"):
         crw_hip._dense_lib()
 

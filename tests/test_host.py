@@ -470,3 +470,19 @@ def test_bench_plain_run_and_output_dump(tmp_path, monkeypatch):
     assert s.ndim == 1 and 0 < s.size < big.numel() and np.all(np.diff(s) > 0)
     np.testing.assert_array_equal(np.load(tmp_path / "a" / "labels.npy"), np.arange(6, dtype=np.float32))
     assert float(np.load(tmp_path / "a" / "loss.npy")) == 0.5
+
+
+@pytest.mark.parametrize("group", ["sweep", "confidence", "dense", "dense_batch", "horizons", "sliding", "ordered"])
+def test_an_optional_entry_point_group_is_told_and_named_when_the_library_lacks_it(group, monkeypatch):
+    """The groups came at ABI 8 without a bump, so a build from before one of them still loads: `has_<group>()` tells, and
+    `_<group>_lib()` names the stale library and every entry point of the group."""
+    import crw_hip
+    names = getattr(crw_hip, f"{group.upper()}_ENTRY_POINTS")
+    has, checked_lib = getattr(crw_hip, f"has_{group}"), getattr(crw_hip, f"_{group}_lib")
+    assert names and set(names) <= set(crw_hip.SIGNATURES) and crw_hip.OPTIONAL_ENTRY_POINTS[group] is names
+    assert has() is True and checked_lib() is crw_hip.lib()
+    monkeypatch.setitem(crw_hip._present, group, False)
+    assert has() is False
+    with pytest.raises(RuntimeError, match="stale libcrw_hip.so.*rebuild") as err:
+        checked_lib()
+    assert all(name in str(err.value) for name in names)

@@ -190,7 +190,7 @@ def test_header_binding_and_status_codes_at_abi_8():
 def test_a_library_without_the_ordered_entry_points_is_named_stale(monkeypatch):
     import crw_hip
     crw_hip.lib()
-    monkeypatch.setattr(crw_hip, "_has_ordered", False)
+    monkeypatch.setitem(crw_hip._present, "ordered", False)
     with pytest.raises(RuntimeError, match="stale libcrw_hip.so.*crw_labelmap_ordered.*rebuild"):
         crw_hip._ordered_lib()
 

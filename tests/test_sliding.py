@@ -206,7 +206,7 @@ def test_header_and_binding_declare_the_sliding_entry_points_at_abi_8():
 def test_a_library_without_the_sliding_entry_points_is_named_stale(monkeypatch):
     import crw_hip
     crw_hip.lib()
-    monkeypatch.setattr(crw_hip, "_has_sliding", False)
+    monkeypatch.setitem(crw_hip._present, "sliding", False)
     W, I = torch.zeros(3, 2, 4), torch.zeros(3, 2, 4, dtype=torch.int32)
     for call in (lambda: crw_hip.labelprop_gather(torch.zeros(4), W, I, 4, 4, 3, cxt_size=2, context="sliding"),
                  lambda: crw_hip.labelprop_propagate_batch(torch.zeros(4), W[None], I, 4, 4, 3, cxt_size=2, context="sliding")):

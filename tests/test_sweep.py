@@ -335,7 +335,7 @@ def test_a_library_without_the_sweep_entry_points_is_named_stale(monkeypatch):
     """The three entry points came at ABI 8 without a bump, so an older build still loads: the wrappers must say what is wrong."""
     import crw_hip
     crw_hip.lib()
-    monkeypatch.setattr(crw_hip, "_has_sweep", False)
+    monkeypatch.setitem(crw_hip._present, "sweep", False)
     assert not crw_hip.has_sweep()
     for call in (lambda: crw_hip.labelprop_topk_scores(torch.zeros(4, 4, 8), 2, 2, 0.1, 2),
                  lambda: crw_hip.labelprop_sweep_weights(torch.zeros(3, 2, 4), (1, 2)),
