@@ -35,6 +35,8 @@
  *                             in one launch                                       runs test_all.py per setting, nearest maps)
  *   crw_labelmap_ordered[_batch]  the same interpolated probabilities decoded      (no twin: no script of the reference uses the
  *                             under a layer order, a DP per pixel column          order of the layers down a trace)
+ *   crw_labelmap_ordered_joint[_batch]  that decode over two passes' rows, per pixel  (no twin: test_all.py:146-159 merges the two
+ *                             the surer pass's: an order-preserving merge          label maps by a class rule)
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HBM) unless its name ends in _host;
@@ -64,7 +66,8 @@ extern "C" {
  * (crw_hip.has_confidence()); then crw_labelmap_dense (crw_hip.has_dense()); then crw_labelmap_dense_batch
  * (crw_hip.has_dense_batch()); then crw_horizons_ws_bytes, crw_horizons (crw_hip.has_horizons()); then
  * crw_labelprop_propagate_sliding, crw_labelprop_propagate_sliding_batch (crw_hip.has_sliding()); then
- * crw_labelmap_ordered_workspace, crw_labelmap_ordered, crw_labelmap_ordered_batch (crw_hip.has_ordered()).  The ONE place the number is
+ * crw_labelmap_ordered_workspace, crw_labelmap_ordered, crw_labelmap_ordered_batch (crw_hip.has_ordered()); then
+ * crw_labelmap_ordered_joint, crw_labelmap_ordered_joint_batch (crw_hip.has_joint()).  The ONE place the number is
  * written: crw_abi_version() returns it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
 #define CRW_ABI_VERSION 8
@@ -344,6 +347,33 @@ int crw_labelmap_ordered(const float *L, int T, int N, int M, int rows, int cols
 int crw_labelmap_ordered_batch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, const int *order_host,
                                int S, int conf_kind, void *labels, int label_dtype, float *conf, size_t ld, size_t map_stride,
                                void *ws, size_t ws_bytes, crw_stream_t stream);
+
+/* The ordered decode over the evidence of two passes, merged BEFORE the decode -- an order-preserving merge of a forward and a
+ * reverse pass.  Two sources k = a, b: L_k [T_k*N, M] soft labels under a cols_k-wide map; the [rows] x [ncols] output window is the
+ * columns col0_k ... col0_k + ncols - 1 of it, mirrored with flip_k as crw_labelmap_dense mirrors them.  N, M, rows, the order, the
+ * confidence kind and the outputs are shared.  At output pixel (r, x), bit for bit in fp32:
+ *   v_k, conf_k = what crw_labelmap_dense(L_k, T_k, N, M, rows, cols_k, flip_k, conf_kind) computes at pixel (r, col0_k + x)
+ *                 (the same device function, the same three lerp steps);
+ *   took = conf_b > conf_a  -- crw_merge_confidence's comparison: a tie keeps a, and so does a NaN on either side;
+ *   e[r][s] = (took ? v_b : v_a)[order[s]];   then crw_labelmap_ordered's recurrence, tie rules and backtrack, unchanged;
+ *   conf[r][x] = took ? conf_b : conf_a  -- what crw_merge_confidence writes for the two dense confidence maps.
+ * The labels of a column never step back in `order`, whatever `took` does down the column.  conf_kind is mandatory (-1:
+ * CRW_EINVAL); conf may be NULL: the labels alone are written.  ws: crw_labelmap_ordered_workspace(G, rows, ncols) bytes, as for
+ * crw_labelmap_ordered (too few -> CRW_EWORKSPACE).  Per source: L_k non-null and 4-byte aligned (the two may be one pointer),
+ * T_k >= 1, 1 <= cols_k <= 2^22, 0 <= col0_k, col0_k + ncols <= cols_k; the window, order_host, ws and every other limit:
+ * crw_labelmap_ordered's with cols = ncols -- all refused (CRW_EINVAL) before anything is launched.  One launch, the ordered
+ * kernel's shape: a lane per column, a wave per 64 columns; plain vector stores, no atomics, bit-reproducible. */
+int crw_labelmap_ordered_joint(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb, int Tb, int cols_b,
+                               int col0_b, int flip_b, int N, int M, int rows, int ncols, const int *order_host, int S,
+                               int conf_kind, void *labels, int label_dtype, float *conf, size_t ld, void *ws, size_t ws_bytes,
+                               crw_stream_t stream);
+/* crw_labelmap_ordered_joint for the G configurations of a sweep in ONE launch: L_k [G, T_k*N, M], configuration g's windows at
+ * labels + g * map_stride and conf + g * map_stride as for crw_labelmap_ordered_batch, one order and one geometry for all.  Slice g
+ * is bit-identical to crw_labelmap_ordered_joint(La + g*Ta*N*M, ..., Lb + g*Tb*N*M, ...) written into the same window. */
+int crw_labelmap_ordered_joint_batch(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb, int Tb, int cols_b,
+                                     int col0_b, int flip_b, int G, int N, int M, int rows, int ncols, const int *order_host, int S,
+                                     int conf_kind, void *labels, int label_dtype, float *conf, size_t ld, size_t map_stride,
+                                     void *ws, size_t ws_bytes, crw_stream_t stream);
 
 /* building blocks exported for tests and the roofline bench --------------------------------- */
 /* Weight gradient of the CNN encoder's linear head (nn.Linear(128, 128), src/encoder.py:40,55; autograd of

@@ -71,6 +71,9 @@ SIGNATURES = {
     "crw_labelmap_ordered_workspace": (_c_sz, [_c_int, _c_int, _c_int]),
     "crw_labelmap_ordered": (_c_int, [_p] + [_c_int] * 6 + [_p, _c_int, _c_int, _p, _c_int, _p, _c_sz, _p, _c_sz, _p]),
     "crw_labelmap_ordered_batch": (_c_int, [_p] + [_c_int] * 7 + [_p, _c_int, _c_int, _p, _c_int, _p, _c_sz, _c_sz, _p, _c_sz, _p]),
+    "crw_labelmap_ordered_joint": (_c_int, ([_p] + [_c_int] * 4) * 2 + [_c_int] * 4 + [_p, _c_int, _c_int, _p, _c_int, _p, _c_sz, _p, _c_sz, _p]),
+    "crw_labelmap_ordered_joint_batch": (_c_int, ([_p] + [_c_int] * 4) * 2 + [_c_int] * 5 + [_p, _c_int, _c_int, _p, _c_int, _p, _c_sz, _c_sz, _p,
+                                                  _c_sz, _p]),
     "crw_linear128_wgrad_ws_bytes": (_c_sz, [_c_int]),
     "crw_linear128_wgrad": (_c_int, [_p, _p, _p, _c_int, _p, _c_sz, _p]),
     "crw_adam_step": (_c_int, [_p, _p, _p, _p, ctypes.c_long, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
@@ -160,13 +163,16 @@ SLIDING_ENTRY_POINTS = ("crw_labelprop_propagate_sliding", "crw_labelprop_propag
 # likewise: depth-ordered label maps (`has_ordered()`)
 ORDERED_ENTRY_POINTS = ("crw_labelmap_ordered_workspace", "crw_labelmap_ordered", "crw_labelmap_ordered_batch")
 
+# likewise: the ordered decode over two passes' rows, the order-preserving merge (`has_joint()`)
+JOINT_ENTRY_POINTS = ("crw_labelmap_ordered_joint", "crw_labelmap_ordered_joint_batch")
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 
 # group -> its entry points.  `has_<group>()` tells whether the loaded library exports them, `_<group>_lib()` is lib() or the
 # error that names the stale library
 OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_ENTRY_POINTS, "dense": DENSE_ENTRY_POINTS,
                          "dense_batch": DENSE_BATCH_ENTRY_POINTS, "horizons": HORIZONS_ENTRY_POINTS,
-                         "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS}
+                         "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS, "joint": JOINT_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -222,6 +228,7 @@ has_dense_batch, _dense_batch_lib = _optional("dense_batch", "the batched dense 
 has_horizons, _horizons_lib = _optional("horizons", "the horizon entry points")
 has_sliding, _sliding_lib = _optional("sliding", "the sliding-context entry points")
 has_ordered, _ordered_lib = _optional("ordered", "the depth-ordered label map's entry points")
+has_joint, _joint_lib = _optional("joint", "the joint ordered label map's entry points")
 
 
 def check_context(context):
@@ -897,11 +904,29 @@ def _window(t, name, lead, rows, cols, dtype, device):
 _ARGMAX = object()  # `_labelmap`'s order for the arg-max maps (None is a caller's order like any other: `check_order` refuses it)
 
 
-def _labelmap(L, G, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace=None):
-    """The four label-map functions behind their signatures.  G None: one map, no leading axis, otherwise the `_batch` form;
+def _source(src, lead, N, M, ncols, device, joint):
+    """One source of `_labelmap`, (L, T, cols, col0, flip) -> the same with L contiguous and the numbers ints, checked."""
+    L, T, cols, col0, flip = src
+    T, cols, col0 = int(T), int(cols), int(col0)
+    if T < 1 or not 1 <= cols <= DENSE_MAX_SIDE:
+        raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={T}, N={N}, cols={cols})")
+    if L.numel() != (lead[0] if lead else 1) * T * N * M or L.dtype != torch.float32:
+        raise ValueError(f"L must be float32 {[*lead, T * N, M]} (got {L.dtype} {tuple(L.shape)})")
+    if joint and (col0 < 0 or col0 + ncols > cols):
+        raise ValueError(f"the window's columns col0 ... col0 + ncols - 1 must lie in the source's 0 ... cols - 1 (got col0={col0}, "
+                         f"ncols={ncols}, cols={cols})")
+    if L.device != device:
+        raise ValueError(f"the two sources must live on one device (got {device} and {L.device})")
+    return L.contiguous(), T, cols, col0, bool(flip)
+
+
+def _labelmap(sources, G, N, M, rows, cols, order, confidence, dtype, out, out_conf, workspace=None):
+    """The six label-map functions behind their signatures.  sources: one (L, T, cols, 0, flip), or `labelmap_ordered_joint`'s two
+    (L, T, cols, col0, flip) under a window of `cols` columns.  G None: one map, no leading axis, otherwise the `_batch` form;
     order _ARGMAX: `labelmap_dense`, otherwise `labelmap_ordered`'s decode under it (`workspace`: its alone)."""
+    joint = len(sources) == 2
     code = -1 if confidence is None else _conf_kind(confidence)
-    T, N, M, rows, cols = int(T), int(N), int(M), int(rows), int(cols)
+    N, M, rows, cols = int(N), int(M), int(rows), int(cols)
     lead = () if G is None else (int(G),)
     if lead and not 1 <= lead[0] <= 65535:
         raise ValueError(f"G must be in 1 ... 65535 (got {lead[0]})")
@@ -909,39 +934,44 @@ def _labelmap(L, G, T, N, M, rows, cols, order, confidence, flip, dtype, out, ou
         raise ValueError(f"M must be in 2 ... 16 (got {M})")
     if order is not _ARGMAX:
         order = check_order(order, M)
-    if T < 1 or N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
-        raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={T}, N={N}, rows={rows}, cols={cols})")
-    if L.numel() != (lead[0] if lead else 1) * T * N * M or L.dtype != torch.float32:
-        raise ValueError(f"L must be float32 {[*lead, T * N, M]} (got {L.dtype} {tuple(L.shape)})")
+    if joint and confidence is None:
+        raise ValueError("the joint map needs a confidence kind: it takes, per pixel, the surer source's row")
+    if N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
+        raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={sources[0][1]}, N={N}, rows={rows}, cols={cols})")
+    device = sources[0][0].device
+    sources = [_source(src, lead, N, M, cols, device, joint) for src in sources]
     if dtype not in (torch.float32, torch.int8):
         raise ValueError(f"dtype must be torch.float32 or torch.int8 (got {dtype})")
     if out_conf is not None and confidence is None:
         raise ValueError("out_conf needs a confidence kind")
     if out is None:
-        out = torch.empty(*lead, rows, cols, dtype=dtype, device=L.device)
+        out = torch.empty(*lead, rows, cols, dtype=dtype, device=device)
     if out_conf is None and confidence is not None:
-        out_conf = torch.empty(*lead, rows, cols, dtype=torch.float32, device=L.device)
-    ld, map_stride = _window(out, "out", lead, rows, cols, dtype, L.device)
+        out_conf = torch.empty(*lead, rows, cols, dtype=torch.float32, device=device)
+    ld, map_stride = _window(out, "out", lead, rows, cols, dtype, device)
     if out_conf is not None:
-        cld, cstride = _window(out_conf, "out_conf", lead, rows, cols, torch.float32, L.device)
+        cld, cstride = _window(out_conf, "out_conf", lead, rows, cols, torch.float32, device)
         if cld != ld and rows > 1:
             raise ValueError(f"out and out_conf must share one pitch (got {out.stride(-2)} and {out_conf.stride(-2)})")
         if cstride != map_stride:  # (equal by construction for one map)
             raise ValueError(f"out and out_conf must share one map stride (got {out.stride(0)} and {out_conf.stride(0)})")
-    L = L.contiguous()
-    if not L.is_cuda:
+    if device.type != "cuda":
         maps, confs = (out, out_conf) if lead else (out[None], None if out_conf is None else out_conf[None])
-        for g, Lg in enumerate(L.view(-1, T * N, M)):
-            if order is _ARGMAX:
-                lab, conf = _labelmap_dense_cpu(Lg, T, N, M, rows, cols, confidence, flip)
+        for g in range(lead[0] if lead else 1):
+            slices = [(L.view(-1, T * N, M)[g], T, width, col0, flip) for L, T, width, col0, flip in sources]
+            if joint:
+                lab, conf = _labelmap_joint_cpu(*slices, N, M, rows, cols, order, confidence)
+            elif order is _ARGMAX:
+                lab, conf = _labelmap_dense_cpu(*slices[0][:2], N, M, rows, cols, confidence, slices[0][4])
             else:
-                lab, conf = _labelmap_ordered_cpu(Lg, T, N, M, rows, cols, order, confidence, flip)
+                lab, conf = _labelmap_ordered_cpu(*slices[0][:2], N, M, rows, cols, order, confidence, slices[0][4])
             maps[g].copy_(lab.to(dtype))
             if confs is not None:
                 confs[g].copy_(conf)
         return out, out_conf
-    # the C signatures: L, [G,] geometry, [order, S,] windows, [map_stride,] [workspace, its bytes,] stream
-    geometry = (T, N, M, rows, cols, int(bool(flip)))
+    # the C signatures: the source(s), [G,] geometry, [order, S,] windows, [map_stride,] [workspace, its bytes,] stream
+    L, T, _, _, flip = sources[0]
+    geometry = (T, N, M, rows, cols, int(flip))
     windows = (code, _ptr(out), _dt(out), _ptr(out_conf), ld)
     if order is _ARGMAX:
         if lead:
@@ -950,14 +980,21 @@ def _labelmap(L, G, T, N, M, rows, cols, order, confidence, flip, dtype, out, ou
         else:
             _check(_dense_lib().crw_labelmap_dense(_ptr(L), *geometry, *windows, _stream()), "crw_labelmap_dense")
         return out, out_conf
-    clib = _ordered_lib()
+    clib = _joint_lib() if joint else _ordered_lib()
     if workspace is None:
-        workspace = torch.empty(clib.crw_labelmap_ordered_workspace(*lead or (1,), rows, cols), dtype=torch.uint8, device=L.device)
-    elif workspace.device != L.device or not workspace.is_contiguous():
-        raise ValueError(f"workspace must be a contiguous tensor on {L.device} (got {workspace.device})")
+        workspace = torch.empty(clib.crw_labelmap_ordered_workspace(*lead or (1,), rows, cols), dtype=torch.uint8, device=device)
+    elif workspace.device != device or not workspace.is_contiguous():
+        raise ValueError(f"workspace must be a contiguous tensor on {device} (got {workspace.device})")
     decode = ((ctypes.c_int * len(order))(*order), len(order))
     tail = (_ptr(workspace), workspace.numel() * workspace.element_size(), _stream())
-    if lead:
+    if joint:
+        both = [v for Lk, Tk, width, col0, flipk in sources for v in (_ptr(Lk), Tk, width, col0, int(flipk))]
+        if lead:
+            _check(clib.crw_labelmap_ordered_joint_batch(*both, *lead, N, M, rows, cols, *decode, *windows, map_stride, *tail),
+                   "crw_labelmap_ordered_joint_batch")
+        else:
+            _check(clib.crw_labelmap_ordered_joint(*both, N, M, rows, cols, *decode, *windows, *tail), "crw_labelmap_ordered_joint")
+    elif lead:
         _check(clib.crw_labelmap_ordered_batch(_ptr(L), *lead, *geometry, *decode, *windows, map_stride, *tail), "crw_labelmap_ordered_batch")
     else:
         _check(clib.crw_labelmap_ordered(_ptr(L), *geometry, *decode, *windows, *tail), "crw_labelmap_ordered")
@@ -974,7 +1011,7 @@ def labelmap_dense(L, T, N, M, rows, cols, *, confidence=None, flip=False, dtype
     else that is not contiguous raises ValueError.  Device tensors: one launch of crw_labelmap_dense, nothing synchronises, the
     interpolated probabilities are never written; CPU tensors: the same integer knots, fp32 weights, arithmetic and tie rule in
     torch."""
-    return _labelmap(L, None, T, N, M, rows, cols, _ARGMAX, confidence, flip, dtype, out, out_conf)
+    return _labelmap([(L, T, cols, 0, flip)], None, N, M, rows, cols, _ARGMAX, confidence, dtype, out, out_conf)
 
 
 def labelmap_dense_batch(L, G, T, N, M, rows, cols, *, confidence=None, flip=False, dtype=torch.int8, out=None, out_conf=None):
@@ -984,7 +1021,7 @@ def labelmap_dense_batch(L, G, T, N, M, rows, cols, *, confidence=None, flip=Fal
     column windows ``maps[:, :, a:b]`` of wider [G, rows, width] tensors (one pitch and one map stride for both), anything else
     that is not contiguous raises ValueError.  Device tensors: ONE launch of crw_labelmap_dense_batch, nothing synchronises; CPU
     tensors: a loop of `labelmap_dense`'s CPU route over the configurations."""
-    return _labelmap(L, G, T, N, M, rows, cols, _ARGMAX, confidence, flip, dtype, out, out_conf)
+    return _labelmap([(L, T, cols, 0, flip)], G, N, M, rows, cols, _ARGMAX, confidence, dtype, out, out_conf)
 
 
 def _interpolated(L, T, N, M, rows, cols, flip):
@@ -1043,7 +1080,7 @@ def labelmap_ordered(L, T, N, M, rows, cols, order, *, confidence=None, flip=Fal
     `labelmap_ordered_workspace(1, rows, cols)` bytes for the back-pointers (default: allocated per call; a short one raises
     CrwError CRW_EWORKSPACE).  Device tensors: one launch of crw_labelmap_ordered, nothing synchronises; CPU tensors: the same
     recurrence and tie rules in torch (a loop over rows, tensors over [S, cols]) on the CPU route's own interpolated values."""
-    return _labelmap(L, None, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace)
+    return _labelmap([(L, T, cols, 0, flip)], None, N, M, rows, cols, order, confidence, dtype, out, out_conf, workspace)
 
 
 def labelmap_ordered_batch(L, G, T, N, M, rows, cols, order, *, confidence=None, flip=False, dtype=torch.int8, out=None,
@@ -1052,11 +1089,13 @@ def labelmap_ordered_batch(L, G, T, N, M, rows, cols, order, *, confidence=None,
     [G, rows, cols], conf | None); slice g is `labelmap_ordered(L[g], ...)` bit for bit.  out / out_conf / dtype: as for
     `labelmap_dense_batch`; workspace: at least `labelmap_ordered_workspace(G, rows, cols)` bytes.  Device tensors: ONE launch of
     crw_labelmap_ordered_batch; CPU tensors: a loop of `labelmap_ordered`'s CPU route."""
-    return _labelmap(L, G, T, N, M, rows, cols, order, confidence, flip, dtype, out, out_conf, workspace)
+    return _labelmap([(L, T, cols, 0, flip)], G, N, M, rows, cols, order, confidence, dtype, out, out_conf, workspace)
 
 
-def _labelmap_ordered_cpu(L, T, N, M, rows, cols, order, confidence, flip):
-    v = _interpolated(L, T, N, M, rows, cols, flip)  # `_labelmap_dense_cpu`'s values
+def _ordered_decode(v, order):
+    """The recurrence, tie rules and back-track of `labelmap_ordered` on interpolated values v [rows, cols, M] -> labels int64
+    [rows, cols].  The ONE text of the CPU routes: `labelmap_ordered`'s and `labelmap_ordered_joint`'s."""
+    rows, cols, _ = v.shape
     S = len(order)
     e = v[:, :, order].permute(0, 2, 1).contiguous()  # [rows, S, cols]
     D = e[0].clone()
@@ -1072,7 +1111,48 @@ def _labelmap_ordered_cpu(L, T, N, M, rows, cols, order, confidence, flip):
         states[r] = state
         state = torch.where(new[r] & (idx <= state[None]), idx, 0).max(0).values  # the highest new maximum <= state
     states[0] = state
-    return torch.tensor(order)[states], _interpolated_confidence(v, confidence)
+    return torch.tensor(order)[states]
+
+
+def _labelmap_ordered_cpu(L, T, N, M, rows, cols, order, confidence, flip):
+    v = _interpolated(L, T, N, M, rows, cols, flip)  # `_labelmap_dense_cpu`'s values
+    return _ordered_decode(v, order), _interpolated_confidence(v, confidence)
+
+
+# ------------------------------------------------------------------------------ joint ordered label maps
+def labelmap_ordered_joint(a, b, N, M, rows, ncols, order, *, confidence, dtype=torch.float32, out=None, out_conf=None,
+                           workspace=None):
+    """An order-preserving merge of two passes: `labelmap_ordered`'s decode over, per pixel, the interpolated row of the SURER
+    source -> (labels [rows, ncols], conf [rows, ncols]).  a, b: the sources, each (L, T, cols, col0, flip) -- soft labels L
+    [T*N, M] under a map of `cols` columns, of which the window is the columns col0 ... col0 + ncols - 1, mirrored with flip as
+    `labelmap_dense` mirrors them (N, M, rows and `order` are shared; the two may be one tensor).  Per pixel, with v_k and conf_k
+    what `labelmap_dense(L_k, T_k, N, M, rows, cols_k, confidence=confidence, flip=flip_k)` computes at column col0_k + x: b's row
+    where conf_b > conf_a strictly, a's elsewhere (a tie, a NaN) -- `merge_confidence`'s rule --, then ONE dynamic programme down
+    the column.  The labels never step back in `order` down a column, which a per-pixel merge of two ordered maps cannot promise;
+    conf is `merge_confidence`'s of the two dense confidence maps, bit for bit.  confidence: the kind, mandatory.  dtype / out /
+    out_conf / workspace (`labelmap_ordered_workspace(1, rows, ncols)` bytes): as for `labelmap_ordered`.  Device tensors: one
+    launch of crw_labelmap_ordered_joint, nothing synchronises; CPU tensors: the same selection and `labelmap_ordered`'s CPU
+    recurrence in torch."""
+    return _labelmap([a, b], None, N, M, rows, ncols, order, confidence, dtype, out, out_conf, workspace)
+
+
+def labelmap_ordered_joint_batch(a, b, G, N, M, rows, ncols, order, *, confidence, dtype=torch.int8, out=None, out_conf=None,
+                                 workspace=None):
+    """`labelmap_ordered_joint` for the G configurations of a sweep at once: each source's L is [G, T*N, M] -> (labels
+    [G, rows, ncols], conf); slice g is `labelmap_ordered_joint` on the sources' slices g, bit for bit.  out / out_conf / dtype /
+    workspace: as for `labelmap_ordered_batch`.  Device tensors: ONE launch of crw_labelmap_ordered_joint_batch; CPU tensors: a
+    loop of the CPU route."""
+    return _labelmap([a, b], G, N, M, rows, ncols, order, confidence, dtype, out, out_conf, workspace)
+
+
+def _labelmap_joint_cpu(a, b, N, M, rows, ncols, order, confidence):
+    vs, confs = [], []
+    for L, T, cols, col0, flip in (a, b):
+        v = _interpolated(L, T, N, M, rows, cols, flip)[:, col0:col0 + ncols]  # `_labelmap_dense_cpu`'s values in the window
+        vs.append(v)
+        confs.append(_interpolated_confidence(v, confidence))
+    took = confs[1] > confs[0]  # `merge_confidence`'s comparison
+    return _ordered_decode(torch.where(took[:, :, None], vs[1], vs[0]), order), torch.where(took, confs[1], confs[0])
 
 
 def gemm_f32(A, B, C=None, transA=False, transB=False, beta=False):

@@ -21,7 +21,8 @@
 // crw_labelmap_ordered[_batch] (the second half of this file) decode the same interpolated probabilities under a layer order: per
 // pixel column the labelling that is monotone in `order` and maximises the sum of the probabilities it picks -- a dynamic
 // programme down the column, a lane per column.  They live here because they read the pixels through knot, load_row and
-// dense_pixel of this file; their own text starts at "ordered label maps".
+// dense_pixel of this file; their own text starts at "ordered label maps".  crw_labelmap_ordered_joint[_batch] (the end of the file)
+// are that decode over the interpolated rows of TWO passes, per pixel the surer one's: "joint ordered label maps".
 #include <cstdlib>
 #include <type_traits>
 
@@ -272,11 +273,12 @@ int batch_chunk(int G) {
   return chunk < G ? chunk : G;
 }
 
+constexpr int MAX_SIDE = 1 << 22;  // 2 * side < 2^24: the weights' numerators and denominators are exact in fp32
+
 // The arguments the dense and the ordered entry points share: checked (CRW_EINVAL), then written into `a`.  lab_phase and
 // conf_vec are the dense kernels'; the ordered ones do not read them.
 int dense_args(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, int conf_kind, void *labels,
                int label_dtype, float *conf, size_t ld, size_t map_stride, int chunk, DenseArgs &a) {
-  constexpr int MAX_SIDE = 1 << 22;  // 2 * side < 2^24: the weights' numerators and denominators are exact in fp32
   if (!L || !labels || G < 1 || G > 65535 || T < 1 || N < 1 || M < 2 || M > 16 || rows < 1 || cols < 1 || rows > MAX_SIDE ||
       cols > MAX_SIDE || !dtype_ok(label_dtype) || conf_kind < -1 || conf_kind > CRW_CONF_ENTROPY ||
       (conf_kind == -1) != (conf == nullptr) || ld < (size_t)cols || map_stride < (size_t)(rows - 1) * ld + (size_t)cols ||
@@ -403,6 +405,54 @@ __device__ __forceinline__ void ordered_values(const float (&top)[SCAP], const f
 __device__ __forceinline__ int lane_int(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 __device__ __forceinline__ float lane_float(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
+// One row of the scan: D[r-1] -> D[r] under e[r], and the row's back-pointer word.  Adds, compares and selects only: nothing
+// here can contract, nothing branches.  A state beyond S has e = -inf, so its D is -inf from row 0 on: never a prefix maximum,
+// never the last state.
+template <int MCAP>
+__device__ __forceinline__ unsigned ordered_step(float (&D)[MCAP], const float (&e)[MCAP]) {
+  float best = D[0];
+  unsigned word = 1u;
+  D[0] = e[0] + best;
+#pragma unroll
+  for (int s = 1; s < MCAP; ++s) {
+    const bool up = D[s] > best;  // strict: the lowest state that attains the prefix maximum
+    best = up ? D[s] : best;
+    word |= up ? 1u << s : 0u;
+    D[s] = e[s] + best;
+  }
+  return word;
+}
+
+// The backward scan of a live lane: the last state from D[rows-1], then up the column through the lane's own words; lab and ws
+// are the lane's column (row 0), `back` OrderedArgs'.
+template <typename LAB, int MCAP>
+__device__ __forceinline__ void ordered_backtrack(const float (&D)[MCAP], LAB *lab, size_t ld, const uint16_t *ws, size_t ws_ld,
+                                                  uint64_t order, int back, int rows) {
+  int state = 0;
+  float top = D[0];
+#pragma unroll
+  for (int s = 1; s < MCAP; ++s)
+    if (D[s] > top) top = D[s], state = s;  // strict: the lowest state that attains the maximum (beyond S: -inf)
+  int r = rows - 1;
+  if (back != 1)
+    for (; r >= OD_BACK; r -= OD_BACK) {  // rows r ... r - 7, all >= 1: their words first, then the chain through them
+      unsigned words[OD_BACK];
+#pragma unroll
+      for (int k = 0; k < OD_BACK; ++k) words[k] = ws[(size_t)(r - k) * ws_ld];
+#pragma unroll
+      for (int k = 0; k < OD_BACK; ++k) {
+        lab[(size_t)(r - k) * ld] = (LAB)order_at(order, state);
+        state = 31 - __builtin_clz(words[k] & ((2u << state) - 1u));
+      }
+    }
+  for (; r >= 1; --r) {
+    lab[(size_t)r * ld] = (LAB)order_at(order, state);
+    const unsigned word = ws[(size_t)r * ws_ld] & ((2u << state) - 1u);  // bit 0 is set: never empty
+    state = 31 - __builtin_clz(word);
+  }
+  lab[0] = (LAB)order_at(order, state);
+}
+
 // KIND: a CRW_CONF_* kind, or -1 for no confidence map; MCAP: 4, 8 or 16 >= M >= S
 template <typename LAB, int KIND, int MCAP>
 __global__ __launch_bounds__(WAVE) void labelmap_ordered_kernel(OrderedArgs a) {
@@ -455,48 +505,12 @@ __global__ __launch_bounds__(WAVE) void labelmap_ordered_kernel(OrderedArgs a) {
           dense_pixel<KIND, MCAP>(p00, p01, p10, p11, wc, wr, M, d.ln_m, &argmax_label, &cf);
           conf[(size_t)r * d.ld] = cf;
         }
-        // adds, compares and selects only: nothing here can contract, nothing branches.  A state beyond S has e = -inf, so its
-        // D is -inf from row 0 on: never a prefix maximum, never the last state
-        float best = D[0];
-        unsigned word = 1u;
-        D[0] = e[0] + best;
-#pragma unroll
-        for (int s = 1; s < MCAP; ++s) {
-          const bool up = D[s] > best;  // strict: the lowest state that attains the prefix maximum
-          best = up ? D[s] : best;
-          word |= up ? 1u << s : 0u;
-          D[s] = e[s] + best;
-        }
-        ws[(size_t)r * a.ws_ld] = (uint16_t)word;
+        ws[(size_t)r * a.ws_ld] = (uint16_t)ordered_step(D, e);
         ++rr;
       } while (rr < rn && lane_int(ki, rr) == i0);
     }
   }
-  if (!live) return;
-
-  int state = 0;
-  float top = D[0];
-#pragma unroll
-  for (int s = 1; s < MCAP; ++s)
-    if (D[s] > top) top = D[s], state = s;  // strict: the lowest state that attains the maximum (beyond S: -inf)
-  int r = rows - 1;
-  if (a.back != 1)
-    for (; r >= OD_BACK; r -= OD_BACK) {  // rows r ... r - 7, all >= 1: their words first, then the chain through them
-      unsigned words[OD_BACK];
-#pragma unroll
-      for (int k = 0; k < OD_BACK; ++k) words[k] = ws[(size_t)(r - k) * a.ws_ld];
-#pragma unroll
-      for (int k = 0; k < OD_BACK; ++k) {
-        lab[(size_t)(r - k) * d.ld] = (LAB)order_at(a.order, state);
-        state = 31 - __builtin_clz(words[k] & ((2u << state) - 1u));
-      }
-    }
-  for (; r >= 1; --r) {
-    lab[(size_t)r * d.ld] = (LAB)order_at(a.order, state);
-    const unsigned word = ws[(size_t)r * a.ws_ld] & ((2u << state) - 1u);  // bit 0 is set: never empty
-    state = 31 - __builtin_clz(word);
-  }
-  lab[0] = (LAB)order_at(a.order, state);
+  if (live) ordered_backtrack(D, lab, d.ld, ws, a.ws_ld, a.order, a.back, rows);
 }
 
 // CRW_ORDERED_BACK (read per call): 1 = the backward scan with one word in flight, the other arm of tools/ordered_timing.py's
@@ -513,14 +527,10 @@ size_t ordered_ws_bytes(int G, int rows, int cols) {
   return (size_t)G * rows * ordered_ws_ld(cols) * sizeof(uint16_t);
 }
 
-// Both entry points behind their signatures.  The argument checks are dense_args', then the order's and the workspace's;
-// nothing is launched unless all pass.
-int ordered_launch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, const int *order, int S, int conf_kind,
-                   void *labels, int label_dtype, float *conf, size_t ld, size_t map_stride, void *ws, size_t ws_bytes,
-                   crw_stream_t stream) {
-  clear_stale_error();
-  OrderedArgs a;
-  if (const int st = dense_args(L, G, T, N, M, rows, cols, flip, conf_kind, labels, label_dtype, conf, ld, map_stride, 1, a.d)) return st;
+// The order and the workspace of an ordered decode over the window a.d describes (G, M, rows, cols): checked (CRW_EINVAL,
+// CRW_EWORKSPACE), then written into `a`.
+int ordered_decode_args(const int *order, int S, void *ws, size_t ws_bytes, OrderedArgs &a) {
+  const int M = a.d.M;
   if (!order || S < 2 || S > M || !ws || ((uintptr_t)ws & 1)) return CRW_EINVAL;
   uint64_t packed = 0;
   unsigned seen = 0;
@@ -529,8 +539,20 @@ int ordered_launch(const float *L, int G, int T, int N, int M, int rows, int col
     seen |= 1u << order[s];
     packed |= (uint64_t)order[s] << (4 * s);
   }
-  if (ws_bytes < ordered_ws_bytes(G, rows, cols)) return CRW_EWORKSPACE;
-  a.order = packed, a.S = S, a.ws = static_cast<uint16_t *>(ws), a.ws_ld = ordered_ws_ld(cols), a.back = ordered_back();
+  if (ws_bytes < ordered_ws_bytes(a.d.G, a.d.rows, a.d.cols)) return CRW_EWORKSPACE;
+  a.order = packed, a.S = S, a.ws = static_cast<uint16_t *>(ws), a.ws_ld = ordered_ws_ld(a.d.cols), a.back = ordered_back();
+  return CRW_OK;
+}
+
+// Both entry points behind their signatures.  The argument checks are dense_args', then the order's and the workspace's;
+// nothing is launched unless all pass.
+int ordered_launch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip, const int *order, int S, int conf_kind,
+                   void *labels, int label_dtype, float *conf, size_t ld, size_t map_stride, void *ws, size_t ws_bytes,
+                   crw_stream_t stream) {
+  clear_stale_error();
+  OrderedArgs a;
+  if (const int st = dense_args(L, G, T, N, M, rows, cols, flip, conf_kind, labels, label_dtype, conf, ld, map_stride, 1, a.d)) return st;
+  if (const int st = ordered_decode_args(order, S, ws, ws_bytes, a)) return st;
   const dim3 grid((unsigned)(a.ws_ld / WAVE), (unsigned)G);
   const auto kernel = kernel_for(label_dtype, conf_kind, M, [](auto lab, auto kind, auto mcap) {
     return labelmap_ordered_kernel<decltype(lab), kind(), mcap()>;
@@ -556,4 +578,185 @@ extern "C" int crw_labelmap_ordered(const float *L, int T, int N, int M, int row
                                     crw_stream_t stream) {
   return crw::ordered_launch(L, 1, T, N, M, rows, cols, flip, order, S, conf_kind, labels, label_dtype, conf, ld, (size_t)rows * ld,
                              ws, ws_bytes, stream);
+}
+
+// ------------------------------------------------------------------------------------------------------ joint ordered label maps
+// The ordered decode over the evidence of TWO passes, merged before the decode: per pixel the interpolated row of the surer source
+// -- crw_merge_confidence's rule, source b where conf_b > conf_a strictly, source a otherwise (a tie, a NaN) -- and ONE dynamic
+// programme down the column over the selected rows.  A per-pixel merge of two monotone maps need not be monotone; this map is, by
+// construction, and its conf is the confidence merge's bit for bit.
+//
+// A source is a pass's soft labels with its own geometry along the columns: L [G][T*N*M], T frames under a `cols`-wide map of which
+// the window is the columns col0 ... col0 + ncols - 1, mirrored with flip as crw_labelmap_dense mirrors them.  (The forward side
+// of a corrected tail is a shorter item's whole map, its reverse side the tail columns of the full item's.)  N, M, rows, the order
+// and the outputs are shared, so the wave's row knots serve both sources; a lane has two column knots.
+//
+// Shape: the ordered kernel's -- a lane per column, a wave per 64 columns and configuration, the loads outside the loop over a
+// run of rows, the same step, back-pointer word, workspace layout and backward scan (ordered_step, ordered_backtrack).  Per run a
+// lane keeps each source's node rows lerped along the columns (ordered_sides: its column weight never changes), whole for the
+// confidence and permuted by `order` for the scan: 8 arrays of MCAP floats.  Per row: two whole interpolated rows and their
+// confidences, the comparison, then ONE third lerp step per state on the selected source's sides -- every value is dense_pixel's
+// (the same three dense_lerp steps on the same operands).  Register arrays are indexed by unrolled loops only.
+namespace crw {
+namespace {
+
+struct JointSource {
+  const float *L;   // configuration 0's
+  size_t l_stride;  // T * N * M
+  int T, cols, col0, flip;
+};
+
+struct JointArgs {
+  OrderedArgs o;  // o.d: the shared window (cols = ncols), N, M, rows and outputs; its L, T, flip and l_stride are unused
+  JointSource a, b;
+};
+
+// What a lane keeps of one source: the two frames its column lies between and the weight between them.
+struct JointColumn {
+  const float *f0, *f1;  // node 0's rows of frames j0, j1
+  float wc;
+  int vec;
+};
+
+__device__ __forceinline__ JointColumn joint_column(const JointSource &s, int g, long x, bool live, int N, int M) {
+  JointColumn k;
+  const float *L = s.L + (size_t)g * s.l_stride;
+  int j0 = 0;
+  k.wc = 0.f;
+  if (live) {
+    const int c = s.col0 + (int)x;
+    knot(s.flip ? s.cols - 1 - c : c, s.T, s.cols, &j0, &k.wc);
+  }
+  const int j1 = j0 + 1 < s.T ? j0 + 1 : s.T - 1;
+  k.f0 = L + (size_t)j0 * N * M, k.f1 = L + (size_t)j1 * N * M;
+  k.vec = ((M & 3) == 0 && !((uintptr_t)L & 15)) ? 4 : ((M & 1) == 0 && !((uintptr_t)L & 7)) ? 2 : 1;
+  return k;
+}
+
+// A source's sides for the run between node rows i0 / i1: dense_pixel's first two lerp steps, on the whole rows (top, bot: M
+// entries) and on the rows permuted by `order` (qtop, qbot: S entries).
+template <int MCAP>
+__device__ __forceinline__ void joint_sides(const JointColumn &k, int i0, int i1, int M, uint64_t order, int S, float (&top)[MCAP],
+                                            float (&bot)[MCAP], float (&qtop)[MCAP], float (&qbot)[MCAP]) {
+  const float *n00 = k.f0 + (size_t)i0 * M, *n01 = k.f1 + (size_t)i0 * M;
+  const float *n10 = k.f0 + (size_t)i1 * M, *n11 = k.f1 + (size_t)i1 * M;
+  float q00[MCAP], q01[MCAP], q10[MCAP], q11[MCAP];
+  float p00[MCAP], p01[MCAP], p10[MCAP], p11[MCAP];
+  load_ordered(n00, order, S, q00), load_ordered(n01, order, S, q01);
+  load_ordered(n10, order, S, q10), load_ordered(n11, order, S, q11);
+  load_row(n00, M, k.vec, p00), load_row(n01, M, k.vec, p01);
+  load_row(n10, M, k.vec, p10), load_row(n11, M, k.vec, p11);
+  ordered_sides(q00, q01, q10, q11, k.wc, S, qtop, qbot);
+  ordered_sides(p00, p01, p10, p11, k.wc, M, top, bot);
+}
+
+// The confidence of a pixel's whole interpolated row: dense_pixel's third lerp step and its confidence_of.
+template <int KIND, int MCAP>
+__device__ __forceinline__ float joint_confidence(const float (&top)[MCAP], const float (&bot)[MCAP], float wr, int M, float ln_m) {
+  const float ur = 1.f - wr;
+  float v[16];
+#pragma unroll
+  for (int m = 0; m < 16; ++m) {
+    v[m] = 0.f;
+    if (m < MCAP && m < M) v[m] = dense_lerp(wr, ur, top[m < MCAP ? m : 0], bot[m < MCAP ? m : 0]);
+  }
+  return confidence_of<KIND>(v, M, ln_m);
+}
+
+// KIND: a CRW_CONF_* kind (there is no joint map without one); MCAP: 4, 8 or 16 >= M >= S
+template <typename LAB, int KIND, int MCAP>
+__global__ __launch_bounds__(WAVE) void labelmap_ordered_joint_kernel(JointArgs a) {
+  const OrderedArgs &o = a.o;
+  const DenseArgs &d = o.d;
+  const int M = d.M, N = d.N, S = o.S, rows = d.rows;
+  // kernel_for's choice of MCAP and the order's check, said to the compiler: confidence_of walks 16 classes behind `m < M`, and
+  // without this the row loop keeps the 16 - MCAP steps that can never run (about 190 -> 125 instructions per row at MCAP = 4 with
+  // maxprob, 338 -> 227 us per call at 410 x 8192: tools/joint_timing.py)
+  __builtin_assume(M <= MCAP && S <= M);
+  const int lane = threadIdx.x, g = blockIdx.y;
+  const long x = (long)blockIdx.x * WAVE + lane;
+  const bool live = x < d.cols;  // a dead lane holds row knots and touches no memory
+  LAB *lab = static_cast<LAB *>(d.lab) + (size_t)g * d.map_stride + (live ? x : 0);
+  float *conf = d.conf ? d.conf + (size_t)g * d.map_stride + (live ? x : 0) : nullptr;  // null: the labels alone
+  uint16_t *ws = o.ws + (size_t)g * rows * o.ws_ld + (live ? x : 0);
+  const JointColumn ka = joint_column(a.a, g, x, live, N, M), kb = joint_column(a.b, g, x, live, N, M);
+
+  float D[MCAP];  // D[-1] = 0, as in labelmap_ordered_kernel
+#pragma unroll
+  for (int s = 0; s < MCAP; ++s) D[s] = 0.f;
+  for (int r0 = 0; r0 < rows; r0 += OD_CHUNK) {
+    int ki = 0;  // row r0 + lane's knot and weight, both sources'
+    float kw = 0.f;
+    if (r0 + lane < rows) knot(r0 + lane, N, rows, &ki, &kw);
+    const int rn = rows - r0 < OD_CHUNK ? rows - r0 : OD_CHUNK;
+    if (!live) continue;
+    for (int rr = 0; rr < rn;) {  // a run of rows between the same two node rows
+      const int i0 = lane_int(ki, rr), i1 = i0 + 1 < N ? i0 + 1 : N - 1;
+      float ta[MCAP], ba[MCAP], qta[MCAP], qba[MCAP], tb[MCAP], bb[MCAP], qtb[MCAP], qbb[MCAP];
+      joint_sides(ka, i0, i1, M, o.order, S, ta, ba, qta, qba);
+      joint_sides(kb, i0, i1, M, o.order, S, tb, bb, qtb, qbb);
+      do {  // no load in here, for labelmap_ordered_kernel's reason
+        const int r = r0 + rr;
+        const float wr = lane_float(kw, rr);
+        const float ca = joint_confidence<KIND>(ta, ba, wr, M, d.ln_m), cb = joint_confidence<KIND>(tb, bb, wr, M, d.ln_m);
+        const bool took = cb > ca;  // crw_merge_confidence's comparison: a tie and a NaN keep source a
+        if (conf) conf[(size_t)r * d.ld] = took ? cb : ca;
+        float top[MCAP], bot[MCAP], e[MCAP];
+#pragma unroll
+        for (int s = 0; s < MCAP; ++s) top[s] = took ? qtb[s] : qta[s], bot[s] = took ? qbb[s] : qba[s];
+        ordered_values(top, bot, wr, S, e);
+        ws[(size_t)r * o.ws_ld] = (uint16_t)ordered_step(D, e);
+        ++rr;
+      } while (rr < rn && lane_int(ki, rr) == i0);
+    }
+  }
+  if (live) ordered_backtrack(D, lab, d.ld, ws, o.ws_ld, o.order, o.back, rows);
+}
+
+// A source's own arguments: checked (CRW_EINVAL), then written into `s`.
+int joint_source(const float *L, int T, int cols, int col0, int flip, int N, int M, int ncols, JointSource &s) {
+  if (!L || ((uintptr_t)L & 3) || T < 1 || cols < 1 || cols > MAX_SIDE || col0 < 0 || col0 > cols || ncols > cols - col0) return CRW_EINVAL;
+  s.L = L, s.l_stride = (size_t)T * N * M, s.T = T, s.cols = cols, s.col0 = col0, s.flip = flip != 0;
+  return CRW_OK;
+}
+
+// Both entry points behind their signatures.  The checks of the shared arguments are dense_args' on the window (a confidence kind
+// is mandatory, the map of it is not), then each source's, the order's and the workspace's; nothing is launched unless all pass.
+int joint_launch(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb, int Tb, int cols_b, int col0_b,
+                 int flip_b, int G, int N, int M, int rows, int ncols, const int *order, int S, int conf_kind, void *labels,
+                 int label_dtype, float *conf, size_t ld, size_t map_stride, void *ws, size_t ws_bytes, crw_stream_t stream) {
+  clear_stale_error();
+  JointArgs a;
+  if (conf_kind < 0 || conf_kind > CRW_CONF_ENTROPY) return CRW_EINVAL;
+  if (const int st = dense_args(La, G, Ta, N, M, rows, ncols, flip_a, conf ? conf_kind : -1, labels, label_dtype, conf, ld, map_stride,
+                                1, a.o.d))
+    return st;
+  if (const int st = joint_source(La, Ta, cols_a, col0_a, flip_a, N, M, ncols, a.a)) return st;
+  if (const int st = joint_source(Lb, Tb, cols_b, col0_b, flip_b, N, M, ncols, a.b)) return st;
+  if (const int st = ordered_decode_args(order, S, ws, ws_bytes, a.o)) return st;
+  const dim3 grid((unsigned)(a.o.ws_ld / WAVE), (unsigned)G);
+  const auto kernel = kernel_for(label_dtype, conf_kind, M, [](auto lab, auto kind, auto mcap) {
+    return labelmap_ordered_joint_kernel<decltype(lab), (kind() < 0 ? 0 : kind()), mcap()>;  // (kind -1 never reaches here)
+  });
+  hipLaunchKernelGGL(kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, a);
+  return check_launch();
+}
+
+}  // namespace
+}  // namespace crw
+
+extern "C" int crw_labelmap_ordered_joint_batch(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb, int Tb,
+                                                int cols_b, int col0_b, int flip_b, int G, int N, int M, int rows, int ncols,
+                                                const int *order, int S, int conf_kind, void *labels, int label_dtype, float *conf,
+                                                size_t ld, size_t map_stride, void *ws, size_t ws_bytes, crw_stream_t stream) {
+  return crw::joint_launch(La, Ta, cols_a, col0_a, flip_a, Lb, Tb, cols_b, col0_b, flip_b, G, N, M, rows, ncols, order, S, conf_kind,
+                           labels, label_dtype, conf, ld, map_stride, ws, ws_bytes, stream);
+}
+
+extern "C" int crw_labelmap_ordered_joint(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb, int Tb,
+                                          int cols_b, int col0_b, int flip_b, int N, int M, int rows, int ncols, const int *order,
+                                          int S, int conf_kind, void *labels, int label_dtype, float *conf, size_t ld, void *ws,
+                                          size_t ws_bytes, crw_stream_t stream) {
+  return crw::joint_launch(La, Ta, cols_a, col0_a, flip_a, Lb, Tb, cols_b, col0_b, flip_b, 1, N, M, rows, ncols, order, S, conf_kind,
+                           labels, label_dtype, conf, ld, (size_t)rows * ld, ws, ws_bytes, stream);
 }

@@ -73,8 +73,8 @@ merge_reverse_batch = merge_reverse
 
 def _check_options(confidence, merge, upsample, decode='argmax', order=None, nclasses=None):
     """`segment`'s and `segment_sweep`'s checks of their options -> `order` as a list (None unless decode='ordered')."""
-    if merge not in ('rule', 'confidence'):
-        raise ValueError(f"merge must be 'rule' or 'confidence' (got {merge!r})")
+    if merge not in ('rule', 'confidence', 'ordered'):
+        raise ValueError(f"merge must be 'rule' or 'confidence' (got {merge!r}), or 'ordered' with decode='ordered'")
     if upsample not in ('nearest', 'bilinear'):
         raise ValueError(f"upsample must be 'nearest' or 'bilinear' (got {upsample!r})")
     if confidence is not None and confidence not in crw_hip.CONF_KINDS:
@@ -83,6 +83,10 @@ def _check_options(confidence, merge, upsample, decode='argmax', order=None, ncl
         raise ValueError("merge='confidence' needs a confidence kind (confidence='maxprob', 'margin' or 'entropy')")
     if decode not in ('argmax', 'ordered'):
         raise ValueError(f"decode must be 'argmax' or 'ordered' (got {decode!r})")
+    if merge == 'ordered' and decode != 'ordered':
+        raise ValueError("merge='ordered' needs decode='ordered' (it is that decode, over the two passes' probabilities)")
+    if merge == 'ordered' and confidence is None:
+        raise ValueError("merge='ordered' needs a confidence kind (per pixel it reads the surer pass's probabilities)")
     if decode == 'argmax':
         if order is not None:
             raise ValueError("order needs decode='ordered'")
@@ -105,14 +109,17 @@ def _write_nearest(res, seq, out, out_conf, flip):
 
 
 def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run, write,
-                    lead=(), dtype=torch.float32, **extra):
+                    lead=(), dtype=torch.float32, joint=None, **extra):
     """The passes of `segment` and `segment_sweep`, behind their argument checks -> their result dict (plus ``extra``).
     run(seq, seg_ref, use_last): the variant's `propagate` call -> (pred, xent, change, ...).
     write(res, seq, out, out_conf, flip): puts what `run` returned into a column window of the label map (and of the confidence
     map, None unless ``want``), mirrored along the columns with ``flip``.
     The maps are allocated ONCE at [*lead, rows, n_rg * rg_len] (labels ``dtype``, confidence float32) and every pass writes its
     own column window: the forward pass its radargram's, a correction the last ``px`` columns of it -- only after everything of it
-    that can raise succeeded --, the reverse pass its radargram's, mirrored.  No list of maps, no cat, no flip of a map."""
+    that can raise succeeded --, the reverse pass its radargram's, mirrored.  No list of maps, no cat, no flip of a map.
+    merge='ordered': every pass that succeeded also leaves its soft labels res[3] and its geometry (frames, map width), the reverse
+    pass decodes no map of its own, and joint(a, b, N, out, out_conf) writes a column window of ``pred`` / ``conf`` from two
+    sources (L, T, cols, col0, flip) -- a radargram's, or the head and the tail of one whose correction succeeded."""
     T, (H, W), (oh, ow) = seq_length, patch_size, overlap
     N = dataset[0].shape[1]
     rg_len = T * (W - ow) + ow
@@ -128,10 +135,14 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
 
     forward, forward_conf = new_maps()
     xents, changes = [], []
+    keep = use_last and merge == 'ordered'
+    fwd_src, tail_src = {}, {}  # radargram -> (L, frames, map width) of its forward pass / of its correction
     for t, i in enumerate(idx):
         seq = dataset[i].to(device)
         res = run(seq, seg[:rg_h, rg_len * t:rg_len * t + W], False)
         write(res, seq, *window((forward, forward_conf), rg_len * t, rg_len * (t + 1)), False)
+        if keep:
+            fwd_src[t] = (res[3], seq.shape[0], rg_len)
         xents.append(res[1])
         changes.append(res[2])
 
@@ -146,6 +157,8 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
                 a, b = rg_len * (t + 1) - px, rg_len * (t + 1)
                 res = run(seq, seg[:, a:a + W], False)
                 write(res, seq, *window((forward, forward_conf), a, b), False)  # labels and confidence: both or neither
+                if keep:
+                    tail_src[t] = (res[3], seq.shape[0], px)
             except crw_hip.CrwError as e:
                 # ... but a failure of the HIP path itself (CRW_EHIP: launch failure / GPU fault, CRW_EWORKSPACE) is not a data
                 # problem: the reference's bare `except` would hide a poisoned device context behind an uncorrected map.
@@ -159,13 +172,24 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
 
     final, final_conf = forward, forward_conf
     if use_last:
-        rev, rev_conf = new_maps()
+        rev, rev_conf = new_maps()  # merge='ordered': the merged maps themselves, there is no reverse map
         seg_rev = torch.flip(seg.unfold(1, rg_len, rg_len), (-1,)).reshape(rows, -1)
         for t, i in enumerate(idx):
             seq = dataset[i].to(device)
             res = run(seq, seg_rev[:, rg_len * t:rg_len * t + W], True)
-            write(res, seq, *window((rev, rev_conf), rg_len * t, rg_len * (t + 1)), True)
-        if merge == 'confidence':
+            if not keep:
+                write(res, seq, *window((rev, rev_conf), rg_len * t, rg_len * (t + 1)), True)
+                continue
+            a, b = rg_len * t, rg_len * (t + 1)
+            px = tail_src[t][2] if t in tail_src else 0
+            back = (res[3], seq.shape[0], rg_len)
+            if px < rg_len:  # the radargram, or the head of a corrected one
+                joint((*fwd_src[t], 0, False), (*back, 0, True), N, *window((rev, rev_conf), a, b - px))
+            if px:  # the corrected tail: the shortened item's whole map against the last px columns of the reverse pass's
+                joint((*tail_src[t], 0, False), (*back, rg_len - px, True), N, *window((rev, rev_conf), b - px, b))
+        if keep:
+            final, final_conf = rev, rev_conf
+        elif merge == 'confidence':
             final, final_conf, _ = crw_hip.merge_confidence(forward, forward_conf, rev, rev_conf)
         else:
             final = merge_reverse(forward, rev, dataset_id)
@@ -193,7 +217,10 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     merge: how the reverse pass (``use_last``) enters ``pred``.  'rule': the reference's class rule (`merge_reverse`), defined for
     dataset ids 0, 1 and 3; ``conf`` is the reverse pass's exactly where the rule wrote its label.  'confidence': per pixel, the
     pass that is surer (`crw_hip.merge_confidence`: the reverse pass where its confidence is strictly larger) -- needs no class
-    semantics, so any ``dataset_id`` is accepted; needs ``confidence``.
+    semantics, so any ``dataset_id`` is accepted; needs ``confidence``.  'ordered' (needs decode='ordered' and ``confidence``; any
+    ``dataset_id``): the two passes are merged BEFORE the decode -- per pixel the interpolated probabilities of the surer pass
+    (that same rule), one `crw_hip.labelmap_ordered_joint` per radargram (two where a correction succeeded: head and tail), no
+    reverse map is decoded; ``conf``, ``forward`` and ``forward_conf`` are merge='confidence''s bit for bit.
     upsample: how a pass's [N, T] nodes become pixels.  'nearest': the reference's -- arg-max per node, then Resize(NEAREST), every
     class boundary on the node grid.  'bilinear': the upstream routine's order (imported/crw.py:124-127) -- the pass's soft labels
     interpolated bilinearly to pixels and arg-maxed after that (`crw_hip.labelmap_dense`, one kernel per pass, straight into the
@@ -205,7 +232,8 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     (`crw_hip.labelmap_ordered` where 'argmax' calls `labelmap_dense`; same passes, corrections, exception policy and merges;
     ``conf`` / ``forward_conf`` unchanged, they do not depend on the decode).  The dict then gains ``decode`` and ``order``.
     The guarantee: every pass's window is monotone in ``order`` down every column, so ``forward`` is, and ``pred`` without a
-    reverse pass; after merge='rule' / 'confidence' the merged ``pred`` takes pixels of two monotone maps and need not be."""
+    reverse pass; after merge='rule' / 'confidence' the merged ``pred`` takes pixels of two monotone maps and need not be; with
+    merge='ordered' ``pred`` is monotone in ``order`` down every column."""
     order = _check_options(confidence, merge, upsample, decode, order, nclasses)
     want = confidence is not None
     extra = dict(decode=decode, order=order) if order else {}
@@ -223,8 +251,11 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
         kw = dict(confidence=confidence) if want else {}  # `propagate` returns a fourth entry only when asked
         write = _write_nearest
     run = lambda seq, seg_ref, last: propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=last, **kw)
+
+    def joint(a, b, N, out, out_conf):  # merge='ordered': a column window of pred / conf from two passes' soft labels
+        crw_hip.labelmap_ordered_joint(a, b, N, nclasses, *out.shape, order, confidence=confidence, out=out, out_conf=out_conf)
     return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
-                           write, **extra)
+                           write, joint=joint, **extra)
 
 
 @torch.no_grad()
@@ -244,7 +275,8 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     [G, rows, n_rg * rg_len] and every pass writes its column window of all G maps with one `crw_hip.labelmap_dense_batch`.
     It holds G-map tensors at once: with confidence, 5 bytes per pixel and configuration for the forward maps, as much again for
     the reverse pass's and for the merge's result.  decode / order: `segment`'s, one ``order`` for the G configurations, every
-    pass ONE `crw_hip.labelmap_ordered_batch`; slice g stays `segment`'s for ``sweep.configs[g]`` under the same options."""
+    pass ONE `crw_hip.labelmap_ordered_batch`; slice g stays `segment`'s for ``sweep.configs[g]`` under the same options.
+    merge='ordered': `segment`'s, every window ONE `crw_hip.labelmap_ordered_joint_batch` for the G configurations."""
     order = _check_options(confidence, merge, upsample, decode, order, nclasses)
     extra = dict(decode=decode, order=order) if order else {}
     if merge == 'rule' and dataset_id not in (0, 1, 3) and use_last:
@@ -265,8 +297,12 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
         kw = dict(confidence=confidence) if want else {}  # `propagate_sweep` returns a fourth entry only when asked
         write = _write_nearest
     run = lambda seq, seg_ref, last: propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=last, **kw)
+
+    def joint(a, b, N, out, out_conf):  # merge='ordered': ONE launch per window for the G configurations
+        crw_hip.labelmap_ordered_joint_batch(a, b, G, N, nclasses, *out.shape[1:], order, confidence=confidence, dtype=torch.int8,
+                                             out=out, out_conf=out_conf)
     return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
-                           write, lead=(G,), dtype=torch.int8, configs=list(sweep.configs), **extra)
+                           write, lead=(G,), dtype=torch.int8, joint=joint, configs=list(sweep.configs), **extra)
 
 
 @torch.no_grad()

@@ -20,7 +20,9 @@ interpolated bilinearly to pixels and arg-maxed after that (``inference.segment(
 ``"upsample": "bilinear"``) instead of the reference's arg-max + nearest stretch; ``--decode ordered --order K [K ...]`` (with
 ``--upsample bilinear``): every pixel column is decoded as a whole -- the labelling that never steps back in the order given, top
 to bottom, and collects the most probability (``inference.segment(..., decode='ordered', order=...)``; no per-dataset default;
-``--report_json`` gains ``"decode"`` and ``"order"``); ``--horizons``: after the confusion matrix (and the calibration table), the
+``--report_json`` gains ``"decode"`` and ``"order"``); ``--merge ordered`` (with ``--decode ordered`` and ``--confidence``): the reverse
+pass of ``--use_last`` enters BEFORE the decode -- per pixel the interpolated probabilities of the surer pass, one decode per
+column -- so the merged map keeps the order too (``inference.segment(..., merge='ordered')``); ``--horizons``: after the confusion matrix (and the calibration table), the
 horizon table of ``inference.horizons`` -- per class, in how many columns the layer was found, missed or invented, and the error of
 its top, bottom and thickness -- with ``--min_run N`` (default 3: runs of fewer equal labels down a column are no layer), ``--tol
 ROWS`` (default 2), ``--row_spacing X`` / ``--row_unit NAME`` (the printed distances are rows * X, in NAME); ``--save_horizons``
@@ -91,8 +93,9 @@ def get_args_parser():
     p.add_argument('--iou', action='store_true', help='also print the per-class IoU table')
     p.add_argument('--confidence', default=None, choices=('maxprob', 'margin', 'entropy'),
                    help='per-pixel confidence of the label map and its calibration table')
-    p.add_argument('--merge', default='rule', choices=('rule', 'confidence'),
-                   help="how --use_last merges the reverse pass: the reference's class rule, or per pixel the surer pass")
+    p.add_argument('--merge', default='rule', choices=('rule', 'confidence', 'ordered'),
+                   help="how --use_last merges the reverse pass: the reference's class rule, per pixel the surer pass, or (--decode "
+                        "ordered) one decode per column over the surer pass's probabilities, which keeps the order")
     p.add_argument('--bins', default=10, type=int, metavar='B', help='confidence bins of the calibration table (1 ... 64)')
     p.add_argument('--save_conf', action='store_true', help='write confidence_map.pt (needs --confidence)')
     p.add_argument('--upsample', default='nearest', choices=('nearest', 'bilinear'),
@@ -160,6 +163,8 @@ def check_decode_flags(args):
         raise SystemExit('--decode ordered needs --upsample bilinear and --order K [K ...] (the classes from top to bottom)')
     if args.decode != 'ordered' and args.order:
         raise SystemExit('--order needs --decode ordered')
+    if args.merge == 'ordered' and (args.decode != 'ordered' or args.confidence is None):
+        raise SystemExit('--merge ordered needs --decode ordered and --confidence {maxprob,margin,entropy}')
     return args
 
 

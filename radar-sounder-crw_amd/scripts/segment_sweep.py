@@ -15,7 +15,8 @@ prints every full report; ``--report_json FILE`` writes all of them with the gri
 ``predicted_map_r{r}_t{t}_k{k}.pt`` (int8, the forward map test_all.py saves) per configuration.
 ``--upsample bilinear`` / ``--confidence KIND`` / ``--merge confidence`` / ``--bins B``: ``segment_all.py``'s flags, for all
 configurations at once (``inference.segment_sweep``'s arguments; the G dense maps of a pass are one kernel launch); likewise
-``--decode ordered --order K [K ...]`` (one order for all configurations; ``--report_json`` gains ``"decode"`` and ``"order"``).  With
+``--decode ordered --order K [K ...]`` (one order for all configurations; ``--report_json`` gains ``"decode"`` and ``"order"``) and
+``--merge ordered`` (with both of ``--decode ordered`` and ``--confidence``: the order-preserving merge of the reverse pass).  With
 ``--confidence`` every configuration's line gains its ECE and AURC (``inference.calibration_sweep``), the best configuration's
 calibration table follows its matrix, ``--report_json`` gains a ``calibration`` entry per configuration, and ``--select`` also
 takes ``ece`` and ``aurc`` -- lower is better: the smallest wins, ties go to the first in the grid's order, a NaN never wins
@@ -84,8 +85,9 @@ def get_args_parser(horizons=False):
     p.add_argument('--save_maps', action='store_true', help='save every predicted_map_r{r}_t{t}_k{k}.pt (int8)')
     p.add_argument('--confidence', default=None, choices=('maxprob', 'margin', 'entropy'),
                    help='per-pixel confidence of every label map and its calibration (ECE / AURC columns)')
-    p.add_argument('--merge', default='rule', choices=('rule', 'confidence'),
-                   help="how --use_last merges the reverse pass: the reference's class rule, or per pixel the surer pass")
+    p.add_argument('--merge', default='rule', choices=('rule', 'confidence', 'ordered'),
+                   help="how --use_last merges the reverse pass: the reference's class rule, per pixel the surer pass, or (--decode "
+                        "ordered) one decode per column over the surer pass's probabilities, which keeps the order")
     p.add_argument('--bins', default=10, type=int, metavar='B', help='confidence bins of the calibration (1 ... 64)')
     p.add_argument('--upsample', default='nearest', choices=('nearest', 'bilinear'),
                    help="node labels to pixels: the reference's arg-max + nearest, or soft labels interpolated bilinearly, then arg-max")
