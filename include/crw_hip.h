@@ -37,6 +37,8 @@
  *                             under a layer order, a DP per pixel column          order of the layers down a trace)
  *   crw_labelmap_ordered_joint[_batch]  that decode over two passes' rows, per pixel  (no twin: test_all.py:146-159 merges the two
  *                             the surer pass's: an order-preserving merge          label maps by a class rule)
+ *   crw_labelmap_ordered[_joint]_posterior  the posterior of those decodes over the  (no twin)
+ *                             monotone paths: confidence and horizon error bars
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HBM) unless its name ends in _host;
@@ -67,7 +69,8 @@ extern "C" {
  * (crw_hip.has_dense_batch()); then crw_horizons_ws_bytes, crw_horizons (crw_hip.has_horizons()); then
  * crw_labelprop_propagate_sliding, crw_labelprop_propagate_sliding_batch (crw_hip.has_sliding()); then
  * crw_labelmap_ordered_workspace, crw_labelmap_ordered, crw_labelmap_ordered_batch (crw_hip.has_ordered()); then
- * crw_labelmap_ordered_joint, crw_labelmap_ordered_joint_batch (crw_hip.has_joint()).  The ONE place the number is
+ * crw_labelmap_ordered_joint, crw_labelmap_ordered_joint_batch (crw_hip.has_joint()); then crw_labelmap_posterior_workspace,
+ * crw_labelmap_ordered_posterior, crw_labelmap_ordered_joint_posterior (crw_hip.has_posterior()).  The ONE place the number is
  * written: crw_abi_version() returns it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
 #define CRW_ABI_VERSION 8
@@ -374,6 +377,46 @@ int crw_labelmap_ordered_joint_batch(const float *La, int Ta, int cols_a, int co
                                      int col0_b, int flip_b, int G, int N, int M, int rows, int ncols, const int *order_host, int S,
                                      int conf_kind, void *labels, int label_dtype, float *conf, size_t ld, size_t map_stride,
                                      void *ws, size_t ws_bytes, crw_stream_t stream);
+
+/* Posterior confidence and horizon error bars of an ordered map: the order constraint that defines the decode, read as a
+ * distribution.  Per output column, with e[r][s] EXACTLY the evidence crw_labelmap_ordered decodes (the same device functions;
+ * order, S, flip and the windows as there) and f[r][s] = max(e[r][s], floor), 2^-20 <= floor <= 0.25 (seed frames are one-hot, L
+ * holds exact zeros): a path x is monotone, x_0 <= ... <= x_{rows-1} over the states 0 ... S-1, starts and ends anywhere, weighs
+ * W(x) = prod_r f[r][x_r], and P(x) = W(x) / sum W.  gamma[r][s] = P(x_r = s).  For k = 1 ... S-1 the boundary B_k is the first
+ * row with x_r >= k, `rows` if there is none: P(B_k <= r) = sum_{s >= k} gamma[r][s].
+ *   post[r][c]     = gamma[r][pos(label[r][c])], pos the position in `order`; the labels are an INPUT (the window a decode wrote,
+ *                    label_dtype CRW_DT_I8 or CRW_DT_F32, pitch ld, never written); a label outside `order` gives 0.  In [0, 1].
+ *   hz[0][k-1][c]  = b^_k, the pick: the first row whose label's position is >= k, `rows` if none (an integer held in fp32)
+ *   hz[1][k-1][c]  = E[B_k]
+ *   hz[2][k-1][c]  = sqrt(E[(B_k - b^_k)^2]), the error bar of the pick, centred on the pick
+ * post: a [rows] x [cols] window of pitch ld (the labels' pitch); hz: fp32 [3][S-1] rows of cols values, row q*(S-1) + k-1 at
+ * hz + (q*(S-1) + k-1) * hz_ld, hz_ld >= cols -- the column window of a [3, S-1, width] tensor.  Either may be NULL, not both.
+ * Arithmetic, fp32, forward-backward down the column, rescaled every row, contraction off, prefix sums upwards from state 0, suffix
+ * sums downwards from state S-1:
+ *   a[0][s] = f[0][s];  a[r][s] = f[r][s] * sum_{s' <= s} A[r-1][s'];  A[r][s] = a[r][s] * (1 / sum_s a[r][s])
+ *   b[rows-1][s] = 1;   b[r-1][s] = sum_{s' >= s} f[r][s'] * (b[r][s'] * (1 / b[r][0]))  (b[r][0] is b[r]'s largest entry)
+ *   gamma[r][s] = A[r][s] b[r][s] * (1 / Z_r),  Z_r = sum_s A[r][s] b[r][s]
+ *   P(B_k = r+1) = ((sum_{s < k} A[r][s]) * b[r][k]) * (1 / Z_r)  (r = rows-1: the boundary is absent);  P(B_k = 0) = sum_{s >= k} gamma[0][s]
+ *   E[B_k] = sum_r (r+1) P(B_k = r+1);  E[(B_k - b^_k)^2] = sum_r (r+1 - b^_k)^2 P(B_k = r+1) + b^_k^2 P(B_k = 0), rows bottom to top.
+ * Every output is a sum of products of non-negative numbers.  A column whose evidence contradicts `order` over some 126 / log2(1 /
+ * floor) rows in a row can underflow fp32 (Z_r < 2^-126): its gamma and boundary terms of that row read 0, never NaN.
+ * ws: crw_labelmap_posterior_workspace(rows, cols, S) bytes (4 * rows * S * cols rounded up to 64 columns; 0 for a bad shape), 4-byte
+ * aligned, the normalised forward messages [row][state][column]; what it held before is never read.  Every limit and refusal of
+ * crw_labelmap_ordered applies (CRW_EINVAL); in addition floor out of range (a NaN included), both outputs NULL, post / hz / ws
+ * unaligned, hz_ld < cols -> CRW_EINVAL; too few bytes -> CRW_EWORKSPACE; all before anything is launched.  One launch, a lane per
+ * column, a wave per 64 columns, two scans of `rows` steps in series; plain vector stores, no atomics, bit-reproducible. */
+size_t crw_labelmap_posterior_workspace(int rows, int cols, int S);
+int crw_labelmap_ordered_posterior(const float *L, int T, int N, int M, int rows, int cols, int flip, const int *order_host, int S,
+                                   float floor, const void *labels, int label_dtype, size_t ld, float *post, float *hz, size_t hz_ld,
+                                   void *ws, size_t ws_bytes, crw_stream_t stream);
+/* The same posterior over crw_labelmap_ordered_joint's evidence: e[r][s] = (took ? v_b : v_a)[order[s]], took = conf_b > conf_a on
+ * the dense confidences of conf_kind (mandatory), the sources and the window as there (cols = ncols).  One kernel text and one
+ * text per scan step serve both entry points: with both sources the same tensor and geometry (a tie keeps source a) the outputs
+ * equal crw_labelmap_ordered_posterior's bit for bit.  Refusals: crw_labelmap_ordered_joint's and the posterior's. */
+int crw_labelmap_ordered_joint_posterior(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb, int Tb,
+                                         int cols_b, int col0_b, int flip_b, int N, int M, int rows, int ncols, const int *order_host,
+                                         int S, int conf_kind, float floor, const void *labels, int label_dtype, size_t ld,
+                                         float *post, float *hz, size_t hz_ld, void *ws, size_t ws_bytes, crw_stream_t stream);
 
 /* building blocks exported for tests and the roofline bench --------------------------------- */
 /* Weight gradient of the CNN encoder's linear head (nn.Linear(128, 128), src/encoder.py:40,55; autograd of

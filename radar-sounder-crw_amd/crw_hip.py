@@ -74,6 +74,10 @@ SIGNATURES = {
     "crw_labelmap_ordered_joint": (_c_int, ([_p] + [_c_int] * 4) * 2 + [_c_int] * 4 + [_p, _c_int, _c_int, _p, _c_int, _p, _c_sz, _p, _c_sz, _p]),
     "crw_labelmap_ordered_joint_batch": (_c_int, ([_p] + [_c_int] * 4) * 2 + [_c_int] * 5 + [_p, _c_int, _c_int, _p, _c_int, _p, _c_sz, _c_sz, _p,
                                                   _c_sz, _p]),
+    "crw_labelmap_posterior_workspace": (_c_sz, [_c_int, _c_int, _c_int]),
+    "crw_labelmap_ordered_posterior": (_c_int, [_p] + [_c_int] * 6 + [_p, _c_int, _c_f, _p, _c_int, _c_sz, _p, _p, _c_sz, _p, _c_sz, _p]),
+    "crw_labelmap_ordered_joint_posterior": (_c_int, ([_p] + [_c_int] * 4) * 2 + [_c_int] * 4 + [_p, _c_int, _c_int, _c_f, _p, _c_int, _c_sz, _p,
+                                                      _p, _c_sz, _p, _c_sz, _p]),
     "crw_linear128_wgrad_ws_bytes": (_c_sz, [_c_int]),
     "crw_linear128_wgrad": (_c_int, [_p, _p, _p, _c_int, _p, _c_sz, _p]),
     "crw_adam_step": (_c_int, [_p, _p, _p, _p, ctypes.c_long, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
@@ -166,13 +170,17 @@ ORDERED_ENTRY_POINTS = ("crw_labelmap_ordered_workspace", "crw_labelmap_ordered"
 # likewise: the ordered decode over two passes' rows, the order-preserving merge (`has_joint()`)
 JOINT_ENTRY_POINTS = ("crw_labelmap_ordered_joint", "crw_labelmap_ordered_joint_batch")
 
+# likewise: the posterior of the ordered decodes, confidence and horizon error bars (`has_posterior()`)
+POSTERIOR_ENTRY_POINTS = ("crw_labelmap_posterior_workspace", "crw_labelmap_ordered_posterior", "crw_labelmap_ordered_joint_posterior")
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 
 # group -> its entry points.  `has_<group>()` tells whether the loaded library exports them, `_<group>_lib()` is lib() or the
 # error that names the stale library
 OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_ENTRY_POINTS, "dense": DENSE_ENTRY_POINTS,
                          "dense_batch": DENSE_BATCH_ENTRY_POINTS, "horizons": HORIZONS_ENTRY_POINTS,
-                         "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS, "joint": JOINT_ENTRY_POINTS}
+                         "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS, "joint": JOINT_ENTRY_POINTS,
+                         "posterior": POSTERIOR_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -229,6 +237,7 @@ has_horizons, _horizons_lib = _optional("horizons", "the horizon entry points")
 has_sliding, _sliding_lib = _optional("sliding", "the sliding-context entry points")
 has_ordered, _ordered_lib = _optional("ordered", "the depth-ordered label map's entry points")
 has_joint, _joint_lib = _optional("joint", "the joint ordered label map's entry points")
+has_posterior, _posterior_lib = _optional("posterior", "the ordered maps' posterior entry points")
 
 
 def check_context(context):
@@ -1153,6 +1162,145 @@ def _labelmap_joint_cpu(a, b, N, M, rows, ncols, order, confidence):
         confs.append(_interpolated_confidence(v, confidence))
     took = confs[1] > confs[0]  # `merge_confidence`'s comparison
     return _ordered_decode(torch.where(took[:, :, None], vs[1], vs[0]), order), torch.where(took, confs[1], confs[0])
+
+
+# ------------------------------------------------------------------------------ posterior of the ordered label maps
+POSTERIOR_FLOOR = 1e-4                      # the default floor under the evidence (seed frames are one-hot: L holds exact zeros)
+POSTERIOR_FLOOR_RANGE = (2.0 ** -20, 0.25)
+
+
+def check_floor(floor):
+    """`floor` of the posterior calls -> a float in 2^-20 ... 0.25 (ValueError otherwise, a NaN included)."""
+    floor = float(floor)
+    if not POSTERIOR_FLOOR_RANGE[0] <= floor <= POSTERIOR_FLOOR_RANGE[1]:
+        raise ValueError(f"floor must lie in 2^-20 ... 0.25 (got {floor})")
+    return floor
+
+
+def labelmap_posterior_workspace(rows, cols, S):
+    """Bytes of workspace `labelmap_ordered_posterior` / `labelmap_ordered_joint_posterior` need on the device: the normalised
+    forward messages, 4 * rows * S * (cols rounded up to 64)."""
+    return _posterior_lib().crw_labelmap_posterior_workspace(int(rows), int(cols), int(S))
+
+
+def _posterior(sources, N, M, rows, cols, order, labels, confidence, floor, out, out_hz, workspace):
+    """The two posterior functions behind their signatures; sources as for `_labelmap`."""
+    joint = len(sources) == 2
+    N, M, rows, cols = int(N), int(M), int(rows), int(cols)
+    if not 2 <= M <= 16:
+        raise ValueError(f"M must be in 2 ... 16 (got {M})")
+    order = check_order(order, M)
+    S = len(order)
+    floor = check_floor(floor)
+    if joint and confidence is None:
+        raise ValueError("the joint posterior needs the confidence kind the joint map was decoded with")
+    code = _conf_kind(confidence) if joint else -1
+    if N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
+        raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={sources[0][1]}, N={N}, rows={rows}, cols={cols})")
+    device = sources[0][0].device
+    sources = [_source(src, (), N, M, cols, device, joint) for src in sources]
+    if labels.dtype not in (torch.float32, torch.int8):
+        raise ValueError(f"labels must be torch.float32 or torch.int8 (got {labels.dtype})")
+    ld, _ = _window(labels, "labels", (), rows, cols, labels.dtype, device)
+    if out is None:  # the labels' pitch, which the window of `post` shares
+        out = torch.empty((rows - 1) * ld + cols, dtype=torch.float32, device=device).as_strided((rows, cols), (ld, 1))
+    if _window(out, "out", (), rows, cols, torch.float32, device)[0] != ld and rows > 1:
+        raise ValueError(f"labels and out must share one pitch (got {labels.stride(-2)} and {out.stride(-2)})")
+    if out_hz is None:
+        out_hz = torch.empty(3, S - 1, cols, dtype=torch.float32, device=device)
+    if tuple(out_hz.shape) != (3, S - 1, cols) or out_hz.dtype != torch.float32 or out_hz.device != device:
+        raise ValueError(f"out_hz must be float32 {[3, S - 1, cols]} on {device} (got {out_hz.dtype} {tuple(out_hz.shape)} on {out_hz.device})")
+    hz_ld = out_hz.stride(1) if S > 2 else (out_hz.stride(0) if out_hz.stride(0) >= cols else cols)
+    if (cols > 1 and out_hz.stride(2) != 1) or hz_ld < cols or out_hz.stride(0) != (S - 1) * hz_ld:
+        raise ValueError(f"out_hz must be a [3, S-1, cols] tensor or the column window hz[:, :, a:b] of a wider one (stride {out_hz.stride()})")
+    if device.type != "cuda":
+        if joint:
+            vs = [_interpolated(L, T, N, M, rows, width, flip)[:, col0:col0 + cols] for L, T, width, col0, flip in sources]
+            confs = [_interpolated_confidence(v, confidence) for v in vs]
+            v = torch.where((confs[1] > confs[0])[:, :, None], vs[1], vs[0])  # `_labelmap_joint_cpu`'s selection
+        else:
+            L, T, _, _, flip = sources[0]
+            v = _interpolated(L, T, N, M, rows, cols, flip)
+        post, hz = _ordered_posterior(v, order, labels, floor)
+        out.copy_(post), out_hz.copy_(hz)
+        return out, out_hz
+    clib = _posterior_lib()
+    need = clib.crw_labelmap_posterior_workspace(rows, cols, S)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    elif workspace.device != device or not workspace.is_contiguous():
+        raise ValueError(f"workspace must be a contiguous tensor on {device} (got {workspace.device})")
+    decode = ((ctypes.c_int * S)(*order), S)
+    tail = (floor, _ptr(labels), _dt(labels), ld, _ptr(out), _ptr(out_hz), hz_ld, _ptr(workspace),
+            workspace.numel() * workspace.element_size(), _stream())
+    if joint:
+        both = [v for Lk, Tk, width, col0, flipk in sources for v in (_ptr(Lk), Tk, width, col0, int(flipk))]
+        _check(clib.crw_labelmap_ordered_joint_posterior(*both, N, M, rows, cols, *decode, code, *tail), "crw_labelmap_ordered_joint_posterior")
+    else:
+        L, T, _, _, flip = sources[0]
+        _check(clib.crw_labelmap_ordered_posterior(_ptr(L), T, N, M, rows, cols, int(flip), *decode, *tail), "crw_labelmap_ordered_posterior")
+    return out, out_hz
+
+
+def labelmap_ordered_posterior(L, T, N, M, rows, cols, order, labels, *, flip=False, floor=POSTERIOR_FLOOR, out=None, out_hz=None,
+                               workspace=None):
+    """The confidence that belongs to `labelmap_ordered`'s map -> (post float32 [rows, cols], hz float32 [3, S-1, cols]).  Over the
+    monotone paths of a pixel column (positions in `order` that never step back; any start, any end), with the evidence the decode
+    adds up -- the interpolated probabilities e[r][s], here floored, f = max(e, floor) with 2^-20 <= floor <= 0.25, and MULTIPLIED
+    down the path -- as independent per-row evidence: post[r][c] is the posterior probability of the label that `labels` holds at
+    (r, c) (0 for a label outside `order`), and for the boundary B_k of layer k = 1 ... S-1 (the first row at position >= k, `rows`
+    if none) hz[0][k-1] is the pick b^_k read from `labels`, hz[1][k-1] its posterior mean E[B_k] and hz[2][k-1] the error bar of
+    the pick, sqrt(E[(B_k - b^_k)^2]).  labels: the map a decode wrote, int8 or float32 [rows, cols], an INPUT (it may be a column
+    window of a wider map).  out / out_hz: tensors to write into; out shares the labels' pitch, out_hz may be the window
+    ``hz[:, :, a:b]`` of a [3, S-1, width] tensor.  workspace: at least `labelmap_posterior_workspace(rows, cols, S)` bytes
+    (default: allocated per call).  Device tensors: one launch of crw_labelmap_ordered_posterior (a normalised forward-backward in
+    fp32, include/crw_hip.h), nothing synchronises; CPU tensors: the same recurrences in torch on the CPU route's interpolated
+    values."""
+    return _posterior([(L, T, cols, 0, flip)], N, M, rows, cols, order, labels, None, floor, out, out_hz, workspace)
+
+
+def labelmap_ordered_joint_posterior(a, b, N, M, rows, ncols, order, labels, *, confidence, floor=POSTERIOR_FLOOR, out=None,
+                                     out_hz=None, workspace=None):
+    """`labelmap_ordered_posterior` over the evidence `labelmap_ordered_joint` decodes: per pixel the interpolated row of the surer
+    of the two sources a, b (each (L, T, cols, col0, flip); `confidence`: the kind, mandatory) -> (post [rows, ncols], hz
+    [3, S-1, ncols]).  With both sources the same tensor and geometry it equals `labelmap_ordered_posterior` bit for bit."""
+    return _posterior([a, b], N, M, rows, ncols, order, labels, confidence, floor, out, out_hz, workspace)
+
+
+def _ordered_posterior(v, order, labels, floor):
+    """The recurrences of crw_labelmap_ordered_posterior (include/crw_hip.h) in fp32 torch on interpolated values v [rows, cols, M]
+    and a label map [rows, cols] -> (post [rows, cols], hz [3, S-1, cols]).  The ONE text of the two CPU routes."""
+    rows, cols, _ = v.shape
+    S = len(order)
+    f = v[:, :, order].permute(0, 2, 1).clamp(min=floor).contiguous()  # [rows, S, cols]
+    A = torch.empty(rows, S, cols)
+    prev = torch.zeros(S, cols)
+    prev[0] = 1
+    for r in range(rows):
+        a = f[r] * prev.cumsum(0)
+        prev = A[r] = a * (1 / a.sum(0))
+    lab = labels.to(torch.float32)
+    pos = torch.full((rows, cols), -1, dtype=torch.int64)
+    for s, k in enumerate(order):
+        pos[lab == k] = s
+    ks = torch.arange(1, S)[:, None, None]
+    reached = pos[None] >= ks  # [S-1, rows, cols]
+    pick = torch.where(reached.any(1), reached.to(torch.int8).argmax(1), rows).to(torch.float32)  # the first row at position >= k
+    b = torch.ones(S, cols)
+    m1, m2 = torch.zeros(S - 1, cols), torch.zeros(S - 1, cols)
+    post = torch.empty(rows, cols)
+    for r in range(rows - 1, -1, -1):
+        g = A[r] * b
+        Z = g.sum(0)
+        inv = torch.where(Z >= 2.0 ** -126, 1 / Z, torch.zeros(()))
+        g = g * inv
+        post[r] = torch.where(pos[r] >= 0, g.gather(0, pos[r].clamp(min=0)[None])[0], torch.zeros(())).clamp(max=1)
+        p = A[r].cumsum(0)[:-1] * b[1:] * inv  # the boundary enters at row r + 1
+        m1 += (r + 1) * p
+        m2 += (r + 1 - pick) ** 2 * p
+        b = (f[r] * (b * (1 / b[0]))).flip(0).cumsum(0).flip(0)
+    m2 += pick ** 2 * g.flip(0).cumsum(0).flip(0)[1:]  # P(B_k = 0) = sum_{s >= k} gamma[0][s]
+    return post, torch.stack([pick, m1, m2.sqrt()])
 
 
 def gemm_f32(A, B, C=None, transA=False, transB=False, beta=False):

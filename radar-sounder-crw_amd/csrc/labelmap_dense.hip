@@ -23,6 +23,8 @@
 // programme down the column, a lane per column.  They live here because they read the pixels through knot, load_row and
 // dense_pixel of this file; their own text starts at "ordered label maps".  crw_labelmap_ordered_joint[_batch] (the end of the file)
 // are that decode over the interpolated rows of TWO passes, per pixel the surer one's: "joint ordered label maps".
+// crw_labelmap_ordered_posterior / crw_labelmap_ordered_joint_posterior (after those) are the posterior over the monotone paths that
+// the order defines, on the same evidence: per-pixel confidence of a decoded map and per-column error bars of its horizons.
 #include <cstdlib>
 #include <type_traits>
 
@@ -527,11 +529,10 @@ size_t ordered_ws_bytes(int G, int rows, int cols) {
   return (size_t)G * rows * ordered_ws_ld(cols) * sizeof(uint16_t);
 }
 
-// The order and the workspace of an ordered decode over the window a.d describes (G, M, rows, cols): checked (CRW_EINVAL,
-// CRW_EWORKSPACE), then written into `a`.
-int ordered_decode_args(const int *order, int S, void *ws, size_t ws_bytes, OrderedArgs &a) {
+// The order of a decode over the M classes of a.d: checked (CRW_EINVAL), then packed into `a`.
+int ordered_order(const int *order, int S, OrderedArgs &a) {
   const int M = a.d.M;
-  if (!order || S < 2 || S > M || !ws || ((uintptr_t)ws & 1)) return CRW_EINVAL;
+  if (!order || S < 2 || S > M) return CRW_EINVAL;
   uint64_t packed = 0;
   unsigned seen = 0;
   for (int s = 0; s < S; ++s) {
@@ -539,8 +540,17 @@ int ordered_decode_args(const int *order, int S, void *ws, size_t ws_bytes, Orde
     seen |= 1u << order[s];
     packed |= (uint64_t)order[s] << (4 * s);
   }
+  a.order = packed, a.S = S;
+  return CRW_OK;
+}
+
+// The order and the workspace of an ordered decode over the window a.d describes (G, M, rows, cols): checked (CRW_EINVAL,
+// CRW_EWORKSPACE), then written into `a`.
+int ordered_decode_args(const int *order, int S, void *ws, size_t ws_bytes, OrderedArgs &a) {
+  if (!ws || ((uintptr_t)ws & 1)) return CRW_EINVAL;
+  if (const int st = ordered_order(order, S, a)) return st;
   if (ws_bytes < ordered_ws_bytes(a.d.G, a.d.rows, a.d.cols)) return CRW_EWORKSPACE;
-  a.order = packed, a.S = S, a.ws = static_cast<uint16_t *>(ws), a.ws_ld = ordered_ws_ld(a.d.cols), a.back = ordered_back();
+  a.ws = static_cast<uint16_t *>(ws), a.ws_ld = ordered_ws_ld(a.d.cols), a.back = ordered_back();
   return CRW_OK;
 }
 
@@ -759,4 +769,329 @@ extern "C" int crw_labelmap_ordered_joint(const float *La, int Ta, int cols_a, i
                                           size_t ws_bytes, crw_stream_t stream) {
   return crw::joint_launch(La, Ta, cols_a, col0_a, flip_a, Lb, Tb, cols_b, col0_b, flip_b, 1, N, M, rows, ncols, order, S, conf_kind,
                            labels, label_dtype, conf, ld, (size_t)rows * ld, ws, ws_bytes, stream);
+}
+
+// ------------------------------------------------------------------------------------------- posterior of the ordered label maps
+// The confidence that belongs to the ordered decode: the posterior over the monotone paths of a column, with the interpolated
+// probabilities as independent per-row evidence (include/crw_hip.h has the definition, DESIGN.md section 3d the bound).  With
+// f[r][s] = max(e[r][s], floor), e the evidence labelmap_ordered_kernel / labelmap_ordered_joint_kernel decode (the same device
+// functions: ordered_sides, ordered_values, joint_sides, joint_confidence), per column in fp32:
+//   forward   a[0][s] = f[0][s],  a[r][s] = f[r][s] sum_{s' <= s} A[r-1][s'],  A[r] = a[r] * (1 / sum_s a[r][s]);
+//   backward  b[rows-1][s] = 1,   b[r-1][s] = sum_{s' >= s} f[r][s'] B[r][s'],  B[r] = b[r] * (1 / b[r][0])  (b does not increase with
+//             s: b[r][0] is its largest entry);
+//   gamma[r][s] = A[r][s] b[r][s] / Z_r,  Z_r = sum_s A[r][s] b[r][s];
+//   P(B_k = r+1) = (sum_{s < k} A[r][s]) b[r][k] / Z_r  (the boundary of layer k enters at row r+1: x_r < k <= x_{r+1}; r = rows-1: it
+//   never enters),  P(B_k = 0) = sum_{s >= k} gamma[0][s].
+// Every output is a sum of products of non-negative numbers: nothing cancels, so a relative error of the evidence stays a relative
+// error of the outputs.  Prefix sums run upwards from state 0, suffix sums downwards from state S-1, contraction is off.
+//
+// Shape: the ordered kernel's -- a lane per column, a wave per 64 columns, the node rows loaded once per run of rows -- except that
+// no lane is ever masked off around a scan (see the kernel: the lanes behind the window repeat its last column).  ONE kernel
+// text for both entry points (KIND -1: one source, no selection), one text per scan step (posterior_forward_step,
+// posterior_backward_step).  Forward scan: A in registers, its S values per row stored to the workspace [row][state][column rounded
+// up to 64] -- a wave's store of one state is one 256-byte segment.  Backward scan: the runs of rows bottom to top, f recomputed, b
+// carried, A read back one row ahead of its use (the load is issued before the row's stores), gamma formed, post stored, the 2 (S-1)
+// moments accumulated.  The picks b^_k come from one pass over the column's labels before the scans.  A lane reads only what it
+// wrote: whatever the workspace held before is never read.
+namespace crw {
+namespace {
+
+struct PosteriorArgs {
+  JointArgs j;     // j.o.d: the window; d.lab the labels (READ), d.conf / o.ws / o.back unused; j.b unused by the single call
+  float floor;
+  float *post;     // [rows] x [cols] window, pitch d.ld; may be null
+  float *hz;       // [3][S-1] rows of cols values, pitch hz_ld; may be null
+  size_t hz_ld;
+  float *alpha;    // [rows][S][a_ld]
+  size_t a_ld;     // cols rounded up to a multiple of 64
+};
+
+// A source's sides for the run between node rows i0 / i1, the rows permuted by `order` alone: what labelmap_ordered_kernel keeps.
+template <int MCAP>
+__device__ __forceinline__ void column_sides(const JointColumn &k, int i0, int i1, int M, uint64_t order, int S, float (&qtop)[MCAP],
+                                             float (&qbot)[MCAP]) {
+  float q00[MCAP], q01[MCAP], q10[MCAP], q11[MCAP];
+  load_ordered(k.f0 + (size_t)i0 * M, order, S, q00), load_ordered(k.f1 + (size_t)i0 * M, order, S, q01);
+  load_ordered(k.f0 + (size_t)i1 * M, order, S, q10), load_ordered(k.f1 + (size_t)i1 * M, order, S, q11);
+  ordered_sides(q00, q01, q10, q11, k.wc, S, qtop, qbot);
+}
+
+// What a lane keeps of a run of rows: source a's sides (KIND -1: those alone), or both sources' as labelmap_ordered_joint_kernel.
+template <int KIND, int MCAP>
+struct PosteriorSides {
+  float qta[MCAP], qba[MCAP], ta[MCAP], ba[MCAP], qtb[MCAP], qbb[MCAP], tb[MCAP], bb[MCAP];
+
+  __device__ __forceinline__ void load(const JointColumn &ka, const JointColumn &kb, int i0, int i1, int M, uint64_t order, int S) {
+    if (KIND >= 0) {
+      joint_sides(ka, i0, i1, M, order, S, ta, ba, qta, qba);
+      joint_sides(kb, i0, i1, M, order, S, tb, bb, qtb, qbb);
+    } else {
+      column_sides(ka, i0, i1, M, order, S, qta, qba);
+    }
+  }
+
+  // f[r][s] of the row with weight wr: the decode's e[r][s] (the joint kernel's selection with a KIND), floored; 0 beyond S.
+  __device__ __forceinline__ void evidence(float wr, int M, int S, float ln_m, float floor, float (&f)[MCAP]) const {
+    float top[MCAP], bot[MCAP], e[MCAP];
+    bool took = false;
+    if (KIND >= 0) {
+      const float ca = joint_confidence<(KIND >= 0 ? KIND : 0)>(ta, ba, wr, M, ln_m);
+      const float cb = joint_confidence<(KIND >= 0 ? KIND : 0)>(tb, bb, wr, M, ln_m);
+      took = cb > ca;  // crw_merge_confidence's comparison: a tie and a NaN keep source a
+    }
+#pragma unroll
+    for (int s = 0; s < MCAP; ++s) top[s] = took ? qtb[s] : qta[s], bot[s] = took ? qbb[s] : qba[s];
+    ordered_values(top, bot, wr, S, e);
+#pragma unroll
+    for (int s = 0; s < MCAP; ++s) f[s] = s < S ? fmaxf(e[s], floor) : 0.f;
+  }
+};
+
+// One row of the forward scan: A[r-1] -> A[r] under f[r].  Row 0 enters with A = (1, 0, ...): every prefix sum is 1.
+template <int MCAP>
+__device__ __forceinline__ void posterior_forward_step(float (&A)[MCAP], const float (&f)[MCAP]) {
+#pragma clang fp contract(off)
+  float run = 0.f, sum = 0.f;
+#pragma unroll
+  for (int s = 0; s < MCAP; ++s) {
+    run += A[s];
+    A[s] = f[s] * run;
+    sum += A[s];
+  }
+  const float inv = 1.f / sum;  // sum >= f[S-1] * (the prefix over every state) > 0
+#pragma unroll
+  for (int s = 0; s < MCAP; ++s) A[s] *= inv;
+}
+
+// One row of the backward scan, row r: from b[r] (`b`), A[r] and f[r] -> gamma[r], the terms of the moments that belong to "the
+// boundary enters at row r + 1", and b[r-1] (left in `b`).  pick[k] = b^_k.  Z_r < 2^-126 (the column's evidence contradicts the
+// order over so many rows that A and b share no state fp32 can hold) gives gamma = 0 and no terms, not a NaN.
+template <int MCAP>
+__device__ __forceinline__ void posterior_backward_step(float (&b)[MCAP], const float (&A)[MCAP], const float (&f)[MCAP], int r,
+                                                        const int (&pick)[MCAP], float (&gamma)[MCAP], float (&m1)[MCAP],
+                                                        float (&m2)[MCAP]) {
+#pragma clang fp contract(off)
+  float Z = 0.f;
+#pragma unroll
+  for (int s = 0; s < MCAP; ++s) {
+    gamma[s] = A[s] * b[s];
+    Z += gamma[s];
+  }
+  const float inv = Z >= 0x1p-126f ? 1.f / Z : 0.f;  // (the reciprocal of a subnormal can be infinite)
+#pragma unroll
+  for (int s = 0; s < MCAP; ++s) gamma[s] *= inv;
+  const float at = (float)(r + 1);
+  float below = 0.f;  // sum_{s < k} A[r][s]
+#pragma unroll
+  for (int k = 1; k < MCAP; ++k) {
+    below += A[k - 1];
+    const float p = below * b[k] * inv;  // (b[k] = 0 beyond S)
+    const float off = at - (float)pick[k];
+    m1[k] += at * p;
+    m2[k] += off * off * p;
+  }
+  const float binv = 1.f / b[0];  // b[0] >= f * B of the row below's largest entry > 0
+  float run = 0.f;
+#pragma unroll
+  for (int s = MCAP - 1; s >= 0; --s) {
+    run += f[s] * (b[s] * binv);
+    b[s] = run;
+  }
+}
+
+// The position of a label in `order`, -1 outside it (a label that is no integer included).
+template <typename LAB>
+__device__ __forceinline__ int label_position(LAB v, uint64_t order, int S) {
+  const int code = std::is_same<LAB, float>::value ? code_f32((float)v) : (int)v;
+  int pos = -1;
+  for (int s = 0; s < S; ++s)
+    if (order_at(order, s) == code) pos = s;
+  return pos;
+}
+
+// KIND: -1 for crw_labelmap_ordered_posterior, a CRW_CONF_* kind for the joint call; MCAP: 4, 8 or 16 >= M >= S
+template <typename LAB, int KIND, int MCAP>
+__global__ __launch_bounds__(WAVE) void labelmap_posterior_kernel(PosteriorArgs a) {
+  const OrderedArgs &o = a.j.o;
+  const DenseArgs &d = o.d;
+  const int M = d.M, N = d.N, S = o.S, rows = d.rows;
+  __builtin_assume(M <= MCAP && S <= M && S >= 2);
+  const int lane = threadIdx.x;
+  const long x = (long)blockIdx.x * WAVE + lane;
+  // A lane behind the window's last column runs both scans on that last column: it keeps its own workspace slots (the workspace
+  // is 64 columns wide per wave) and stores post where that column's lane stores it, the same bits.  So EXEC is full from the first
+  // row step to the last, and the row knots one lane computes and the others read (readlane) sit in registers that no copy under
+  // a partial EXEC mask ever touches.  With `if (!live) continue` around the scans the compiler is free to move a lane's knots
+  // through another register while the lanes behind the window are masked off, and what readlane then takes from those lanes is
+  // garbage (seen at MCAP = 16 with a confidence kind, the one instantiation that parks the knots in AGPRs: wild node-row addresses
+  // in a 1-column window).
+  const bool live = x < d.cols;
+  const long xc = live ? x : d.cols - 1;
+  const LAB *__restrict__ lab = static_cast<const LAB *>(d.lab) + xc;
+  float *__restrict__ post = a.post ? a.post + xc : nullptr;
+  float *__restrict__ ws = a.alpha + x;  // x < a_ld
+  const size_t a_ld = a.a_ld, a_row = (size_t)S * a_ld;
+  const JointColumn ka = joint_column(a.j.a, 0, xc, true, N, M);
+  const JointColumn kb = KIND >= 0 ? joint_column(a.j.b, 0, xc, true, N, M) : ka;
+  PosteriorSides<KIND, MCAP> sides;
+  float f[MCAP];
+
+  // the picks: b^_k = the first row whose label's position is >= k (walked bottom to top: the last assignment is the first row)
+  int pick[MCAP];
+#pragma unroll
+  for (int k = 0; k < MCAP; ++k) pick[k] = rows;
+  if (a.hz)
+    for (int r = rows - 1; r >= 0; --r) {
+      const int pos = label_position(lab[(size_t)r * d.ld], o.order, S);
+#pragma unroll
+      for (int k = 1; k < MCAP; ++k) pick[k] = pos >= k ? r : pick[k];
+    }
+
+  // forward
+  float A[MCAP];
+#pragma unroll
+  for (int s = 0; s < MCAP; ++s) A[s] = s == 0 ? 1.f : 0.f;
+  for (int r0 = 0; r0 < rows; r0 += OD_CHUNK) {
+    int ki = 0;  // row r0 + lane's knot and weight, as in labelmap_ordered_kernel
+    float kw = 0.f;
+    if (r0 + lane < rows) knot(r0 + lane, N, rows, &ki, &kw);
+    const int rn = rows - r0 < OD_CHUNK ? rows - r0 : OD_CHUNK;
+    for (int rr = 0; rr < rn;) {  // a run of rows between the same two node rows
+      const int i0 = lane_int(ki, rr), i1 = i0 + 1 < N ? i0 + 1 : N - 1;
+      sides.load(ka, kb, i0, i1, M, o.order, S);
+      do {  // no load in here, for labelmap_ordered_kernel's reason
+        sides.evidence(lane_float(kw, rr), M, S, d.ln_m, a.floor, f);
+        posterior_forward_step(A, f);
+        float *row = ws + (size_t)(r0 + rr) * a_row;
+#pragma unroll
+        for (int s = 0; s < MCAP; ++s)
+          if (s < S) row[(size_t)s * a_ld] = A[s];
+        ++rr;
+      } while (rr < rn && lane_int(ki, rr) == i0);
+    }
+  }
+
+  // backward: the same runs bottom to top.  `An`, `ln`: row r - 1's A and label, loaded while row r is worked on
+  float b[MCAP], gamma[MCAP], m1[MCAP], m2[MCAP], An[MCAP];
+  LAB ln = LAB(0);
+#pragma unroll
+  for (int s = 0; s < MCAP; ++s) b[s] = s < S ? 1.f : 0.f, gamma[s] = m1[s] = m2[s] = An[s] = 0.f;
+  {
+    const float *row = ws + (size_t)(rows - 1) * a_row;
+#pragma unroll
+    for (int s = 0; s < MCAP; ++s)
+      if (s < S) An[s] = row[(size_t)s * a_ld];
+    if (post) ln = lab[(size_t)(rows - 1) * d.ld];
+  }
+  for (int r0 = (rows - 1) / OD_CHUNK * OD_CHUNK; r0 >= 0; r0 -= OD_CHUNK) {
+    int ki = 0;
+    float kw = 0.f;
+    if (r0 + lane < rows) knot(r0 + lane, N, rows, &ki, &kw);
+    const int rn = rows - r0 < OD_CHUNK ? rows - r0 : OD_CHUNK;
+    for (int rr = rn - 1; rr >= 0;) {
+      const int i0 = lane_int(ki, rr), i1 = i0 + 1 < N ? i0 + 1 : N - 1;
+      sides.load(ka, kb, i0, i1, M, o.order, S);
+      do {
+        const int r = r0 + rr;
+        float Ar[MCAP];
+#pragma unroll
+        for (int s = 0; s < MCAP; ++s) Ar[s] = An[s];
+        const LAB lr = ln;
+        if (r > 0) {  // the row above: issued before this row's store
+          const float *row = ws + (size_t)(r - 1) * a_row;
+#pragma unroll
+          for (int s = 0; s < MCAP; ++s)
+            if (s < S) An[s] = row[(size_t)s * a_ld];
+          if (post) ln = lab[(size_t)(r - 1) * d.ld];
+        }
+        sides.evidence(lane_float(kw, rr), M, S, d.ln_m, a.floor, f);
+        posterior_backward_step(b, Ar, f, r, pick, gamma, m1, m2);
+        if (post) {
+          const int pos = label_position(lr, o.order, S);
+          float p = 0.f;
+#pragma unroll
+          for (int s = 0; s < MCAP; ++s) p = s == pos ? gamma[s] : p;
+          post[(size_t)r * d.ld] = fminf(p, 1.f);  // (the lanes behind the window: the last column's value again, to its address)
+        }
+        --rr;
+      } while (rr >= 0 && lane_int(ki, rr) == i0);
+    }
+  }
+
+  if (live && a.hz) {  // gamma is row 0's: P(B_k = 0) = sum_{s >= k} gamma[0][s], which closes the second moment
+#pragma clang fp contract(off)
+    float *hz = a.hz + x;
+    const size_t plane = (size_t)(S - 1) * a.hz_ld;
+    float above = 0.f;
+#pragma unroll
+    for (int k = MCAP - 1; k >= 1; --k) {
+      above += gamma[k];
+      if (k < S) {
+        const float at = (float)pick[k];
+        hz[(size_t)(k - 1) * a.hz_ld] = at;
+        hz[plane + (size_t)(k - 1) * a.hz_ld] = m1[k];
+        hz[2 * plane + (size_t)(k - 1) * a.hz_ld] = sqrtf(m2[k] + at * at * above);
+      }
+    }
+  }
+}
+
+size_t posterior_ws_bytes(int rows, int cols, int S) {
+  if (rows < 1 || cols < 1 || S < 2 || S > 16) return 0;
+  return (size_t)rows * S * ordered_ws_ld(cols) * sizeof(float);
+}
+
+// Both entry points behind their signatures (Lb null: the single call, conf_kind -1).  The checks are the decode's -- dense_args' on
+// the window, each source's, the order's -- then the posterior's own; nothing is launched unless all pass.
+int posterior_launch(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb, int Tb, int cols_b, int col0_b,
+                     int flip_b, int N, int M, int rows, int ncols, const int *order, int S, int conf_kind, float floor,
+                     const void *labels, int label_dtype, size_t ld, float *post, float *hz, size_t hz_ld, void *ws, size_t ws_bytes,
+                     crw_stream_t stream) {
+  clear_stale_error();
+  PosteriorArgs a;
+  const bool joint = conf_kind >= 0;
+  if (conf_kind < -1 || conf_kind > CRW_CONF_ENTROPY) return CRW_EINVAL;
+  if (const int st = dense_args(La, 1, Ta, N, M, rows, ncols, flip_a, -1, const_cast<void *>(labels), label_dtype, nullptr, ld,
+                                (size_t)(rows > 0 ? rows : 1) * ld, 1, a.j.o.d))
+    return st;
+  if (const int st = joint_source(La, Ta, cols_a, col0_a, flip_a, N, M, ncols, a.j.a)) return st;
+  a.j.b = a.j.a;
+  if (joint)
+    if (const int st = joint_source(Lb, Tb, cols_b, col0_b, flip_b, N, M, ncols, a.j.b)) return st;
+  if (const int st = ordered_order(order, S, a.j.o)) return st;
+  if (!(floor >= 0x1p-20f && floor <= 0.25f)) return CRW_EINVAL;  // (a NaN fails both)
+  if ((!post && !hz) || ((uintptr_t)post & 3) || ((uintptr_t)hz & 3) || (hz && hz_ld < (size_t)ncols) || !ws || ((uintptr_t)ws & 3))
+    return CRW_EINVAL;
+  if (ws_bytes < posterior_ws_bytes(rows, ncols, S)) return CRW_EWORKSPACE;
+  a.j.o.ws = nullptr, a.j.o.ws_ld = 0, a.j.o.back = 0;
+  a.floor = floor, a.post = post, a.hz = hz, a.hz_ld = hz_ld;
+  a.alpha = static_cast<float *>(ws), a.a_ld = ordered_ws_ld(ncols);
+  const dim3 grid((unsigned)(a.a_ld / WAVE));
+  const auto kernel = kernel_for(label_dtype, conf_kind, M, [](auto lab, auto kind, auto mcap) {
+    return labelmap_posterior_kernel<decltype(lab), kind(), mcap()>;
+  });
+  hipLaunchKernelGGL(kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, a);
+  return check_launch();
+}
+
+}  // namespace
+}  // namespace crw
+
+extern "C" size_t crw_labelmap_posterior_workspace(int rows, int cols, int S) { return crw::posterior_ws_bytes(rows, cols, S); }
+
+extern "C" int crw_labelmap_ordered_posterior(const float *L, int T, int N, int M, int rows, int cols, int flip, const int *order,
+                                              int S, float floor, const void *labels, int label_dtype, size_t ld, float *post,
+                                              float *hz, size_t hz_ld, void *ws, size_t ws_bytes, crw_stream_t stream) {
+  return crw::posterior_launch(L, T, cols, 0, flip, nullptr, 0, 0, 0, 0, N, M, rows, cols, order, S, -1, floor, labels, label_dtype, ld,
+                               post, hz, hz_ld, ws, ws_bytes, stream);
+}
+
+extern "C" int crw_labelmap_ordered_joint_posterior(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb,
+                                                    int Tb, int cols_b, int col0_b, int flip_b, int N, int M, int rows, int ncols,
+                                                    const int *order, int S, int conf_kind, float floor, const void *labels,
+                                                    int label_dtype, size_t ld, float *post, float *hz, size_t hz_ld, void *ws,
+                                                    size_t ws_bytes, crw_stream_t stream) {
+  if (conf_kind < 0) return CRW_EINVAL;  // mandatory, as for crw_labelmap_ordered_joint
+  return crw::posterior_launch(La, Ta, cols_a, col0_a, flip_a, Lb, Tb, cols_b, col0_b, flip_b, N, M, rows, ncols, order, S, conf_kind,
+                               floor, labels, label_dtype, ld, post, hz, hz_ld, ws, ws_bytes, stream);
 }

@@ -71,8 +71,16 @@ _reverse_rule_mask_batch = _reverse_rule_mask  # [G, rows, cols] maps, configura
 merge_reverse_batch = merge_reverse
 
 
-def _check_options(confidence, merge, upsample, decode='argmax', order=None, nclasses=None):
+def _check_options(confidence, merge, upsample, decode='argmax', order=None, nclasses=None, posterior=False, use_last=False,
+                   floor=None):
     """`segment`'s and `segment_sweep`'s checks of their options -> `order` as a list (None unless decode='ordered')."""
+    if posterior:
+        if decode != 'ordered':
+            raise ValueError("posterior=True needs decode='ordered' (it is the posterior of that decode's monotone paths)")
+        if use_last and merge != 'ordered':
+            raise ValueError("posterior=True with use_last needs merge='ordered': merge='rule' / 'confidence' take pixels of two "
+                             "decodes, and no one posterior describes the merged map")
+        crw_hip.check_floor(floor)
     if merge not in ('rule', 'confidence', 'ordered'):
         raise ValueError(f"merge must be 'rule' or 'confidence' (got {merge!r}), or 'ordered' with decode='ordered'")
     if upsample not in ('nearest', 'bilinear'):
@@ -109,7 +117,7 @@ def _write_nearest(res, seq, out, out_conf, flip):
 
 
 def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run, write,
-                    lead=(), dtype=torch.float32, joint=None, **extra):
+                    lead=(), dtype=torch.float32, joint=None, posterior=0, **extra):
     """The passes of `segment` and `segment_sweep`, behind their argument checks -> their result dict (plus ``extra``).
     run(seq, seg_ref, use_last): the variant's `propagate` call -> (pred, xent, change, ...).
     write(res, seq, out, out_conf, flip): puts what `run` returned into a column window of the label map (and of the confidence
@@ -119,7 +127,10 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
     that can raise succeeded --, the reverse pass its radargram's, mirrored.  No list of maps, no cat, no flip of a map.
     merge='ordered': every pass that succeeded also leaves its soft labels res[3] and its geometry (frames, map width), the reverse
     pass decodes no map of its own, and joint(a, b, N, out, out_conf) writes a column window of ``pred`` / ``conf`` from two
-    sources (L, T, cols, col0, flip) -- a radargram's, or the head and the tail of one whose correction succeeded."""
+    sources (L, T, cols, col0, flip) -- a radargram's, or the head and the tail of one whose correction succeeded.
+    posterior: 0, or S = len(order) (`segment` alone).  ``post`` [rows, width] and ``horizon`` [3, S-1, width] are then allocated
+    once as well, and the call that writes a window of ``pred`` also gets the same window of the two, as the keyword
+    post=(post window, horizon window): `write` without a reverse pass, `joint` with one (``pred`` is then the joint calls')."""
     T, (H, W), (oh, ow) = seq_length, patch_size, overlap
     N = dataset[0].shape[1]
     rg_len = T * (W - ow) + ow
@@ -136,11 +147,16 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
     forward, forward_conf = new_maps()
     xents, changes = [], []
     keep = use_last and merge == 'ordered'
+    if posterior:
+        post, horizon = new(torch.float32), torch.empty(3, posterior - 1, n_rg * rg_len, dtype=torch.float32, device=device)
+        extra.update(post=post, horizon=horizon)
+    pwin = lambda a, b, mine: dict(post=(post[:, a:b], horizon[:, :, a:b])) if posterior and mine else {}
     fwd_src, tail_src = {}, {}  # radargram -> (L, frames, map width) of its forward pass / of its correction
     for t, i in enumerate(idx):
         seq = dataset[i].to(device)
         res = run(seq, seg[:rg_h, rg_len * t:rg_len * t + W], False)
-        write(res, seq, *window((forward, forward_conf), rg_len * t, rg_len * (t + 1)), False)
+        write(res, seq, *window((forward, forward_conf), rg_len * t, rg_len * (t + 1)), False,
+              **pwin(rg_len * t, rg_len * (t + 1), not keep))
         if keep:
             fwd_src[t] = (res[3], seq.shape[0], rg_len)
         xents.append(res[1])
@@ -156,7 +172,7 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
                 seq = dataset.get_smaller_item(idx[t], small).to(device)  # first `small` columns; shortens the dataset
                 a, b = rg_len * (t + 1) - px, rg_len * (t + 1)
                 res = run(seq, seg[:, a:a + W], False)
-                write(res, seq, *window((forward, forward_conf), a, b), False)  # labels and confidence: both or neither
+                write(res, seq, *window((forward, forward_conf), a, b), False, **pwin(a, b, not keep))  # labels and confidence: both or neither
                 if keep:
                     tail_src[t] = (res[3], seq.shape[0], px)
             except crw_hip.CrwError as e:
@@ -184,9 +200,9 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
             px = tail_src[t][2] if t in tail_src else 0
             back = (res[3], seq.shape[0], rg_len)
             if px < rg_len:  # the radargram, or the head of a corrected one
-                joint((*fwd_src[t], 0, False), (*back, 0, True), N, *window((rev, rev_conf), a, b - px))
+                joint((*fwd_src[t], 0, False), (*back, 0, True), N, *window((rev, rev_conf), a, b - px), **pwin(a, b - px, True))
             if px:  # the corrected tail: the shortened item's whole map against the last px columns of the reverse pass's
-                joint((*tail_src[t], 0, False), (*back, rg_len - px, True), N, *window((rev, rev_conf), b - px, b))
+                joint((*tail_src[t], 0, False), (*back, rg_len - px, True), N, *window((rev, rev_conf), b - px, b), **pwin(b - px, b, True))
         if keep:
             final, final_conf = rev, rev_conf
         elif merge == 'confidence':
@@ -204,7 +220,7 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
 @torch.no_grad()
 def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap, pos_embed=False,
             correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
-            decode='argmax', order=None):
+            decode='argmax', order=None, posterior=False, floor=crw_hip.POSTERIOR_FLOOR):
     """dataset: RGDataset (full, overlapping items); seg: reference segmentation [rows, W_rg].
     -> dict(pred [rows, n_rg * rg_len] float labels after the optional reverse merge,
             forward: the forward (+ corrected) map the reference saves as int8 (test_all.py:128),
@@ -233,17 +249,29 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     ``conf`` / ``forward_conf`` unchanged, they do not depend on the decode).  The dict then gains ``decode`` and ``order``.
     The guarantee: every pass's window is monotone in ``order`` down every column, so ``forward`` is, and ``pred`` without a
     reverse pass; after merge='rule' / 'confidence' the merged ``pred`` takes pixels of two monotone maps and need not be; with
-    merge='ordered' ``pred`` is monotone in ``order`` down every column."""
-    order = _check_options(confidence, merge, upsample, decode, order, nclasses)
+    merge='ordered' ``pred`` is monotone in ``order`` down every column.
+    posterior (needs decode='ordered'; with ``use_last`` also merge='ordered', so that every window of ``pred`` is ONE decode's
+    output): the confidence that belongs to the decode.  The dict gains ``post`` float32 [rows, n_rg * rg_len], the posterior
+    probability of every pixel's label in ``pred`` over the monotone paths of its column, ``horizon`` float32 [3, S-1, n_rg *
+    rg_len] -- per boundary and column the pick, its posterior mean and the error bar of the pick, in rows -- and ``floor``, the floor
+    under the evidence (`crw_hip.labelmap_ordered_posterior` / `labelmap_ordered_joint_posterior`, called on the window a decode just
+    wrote: the forward pass, a corrected tail after it succeeded, the joint calls).  Every other entry is bit for bit what it is
+    without the option."""
+    order = _check_options(confidence, merge, upsample, decode, order, nclasses, posterior, use_last, floor)
     want = confidence is not None
     extra = dict(decode=decode, order=order) if order else {}
+    if posterior:
+        extra['floor'] = float(floor)
     if upsample == 'bilinear':
         kw = dict(soft=True)
 
-        def write(res, seq, out, out_conf, flip):  # res[3]: the pass's soft labels L [T*N, M]
+        def write(res, seq, out, out_conf, flip, post=None):  # res[3]: the pass's soft labels L [T*N, M]
             if order:
                 crw_hip.labelmap_ordered(res[3], *seq.shape[:2], nclasses, *out.shape, order, confidence=confidence, flip=flip,
                                          out=out, out_conf=out_conf)
+                if post is not None:
+                    crw_hip.labelmap_ordered_posterior(res[3], *seq.shape[:2], nclasses, *out.shape, order, out, flip=flip, floor=floor,
+                                                       out=post[0], out_hz=post[1])
             else:
                 crw_hip.labelmap_dense(res[3], *seq.shape[:2], nclasses, *out.shape, confidence=confidence, flip=flip, out=out,
                                        out_conf=out_conf)
@@ -252,10 +280,13 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
         write = _write_nearest
     run = lambda seq, seg_ref, last: propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=last, **kw)
 
-    def joint(a, b, N, out, out_conf):  # merge='ordered': a column window of pred / conf from two passes' soft labels
+    def joint(a, b, N, out, out_conf, post=None):  # merge='ordered': a column window of pred / conf from two passes' soft labels
         crw_hip.labelmap_ordered_joint(a, b, N, nclasses, *out.shape, order, confidence=confidence, out=out, out_conf=out_conf)
+        if post is not None:
+            crw_hip.labelmap_ordered_joint_posterior(a, b, N, nclasses, *out.shape, order, out, confidence=confidence, floor=floor,
+                                                     out=post[0], out_hz=post[1])
     return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
-                           write, joint=joint, **extra)
+                           write, joint=joint, posterior=len(order) if posterior else 0, **extra)
 
 
 @torch.no_grad()
@@ -409,6 +440,33 @@ def calibration(pred, conf, seg, dataset_id, remove_unc=True, unc_seg=None, ncla
     counts, conf_sum, dropped = crw_hip.calibration(seg, pred, conf.to(pred.device), K, bins=bins, **mask)
     host = torch.cat([counts.reshape(-1), conf_sum.view(torch.int64), dropped]).cpu()  # the one copy: 3 * bins + 3 numbers
     return _calibration_of(host, conf_sum.numel(), K)
+
+
+def horizon_bars(horizon, seg, order, z=2.0, slack=1.0):
+    """Do the error bars cover the truth?  ``horizon`` [3, S-1, width] (``segment(..., posterior=True)['horizon']``: pick, posterior
+    mean, error bar of the pick) against the reference segmentation ``seg`` [rows, width] -> ``metrics.HorizonBars``.  The
+    reference's boundary k = 1 ... S-1 of a column is the first row whose class's position in ``order`` is >= k (a class outside
+    ``order`` has none); per boundary, over the columns in which the reference has it: their number, the MAE of the pick, the mean
+    error bar, and the share with |reference - pick| <= z * bar + slack.  Torch ops where ``horizon`` lives; 4 (S-1) numbers go to
+    the host."""
+    from metrics import HorizonBars
+    S = len(order)
+    if horizon.dim() != 3 or horizon.shape[0] != 3 or horizon.shape[1] != S - 1 or seg.dim() != 2 or seg.shape[1] != horizon.shape[2]:
+        raise ValueError(f'horizon must be [3, {S - 1}, width] and seg [rows, width] (got {tuple(horizon.shape)} and {tuple(seg.shape)})')
+    seg = seg.to(horizon.device)
+    rows = seg.shape[0]
+    pos = torch.full(seg.shape, -1, dtype=torch.int64, device=seg.device)
+    for s, k in enumerate(order):
+        pos[seg == k] = s
+    reached = pos[None] >= torch.arange(1, S, device=seg.device)[:, None, None]                  # [S-1, rows, width]
+    ref = torch.where(reached.any(1), reached.to(torch.int8).argmax(1), rows).to(torch.float64)  # the first such row
+    has = ref < rows
+    miss = (ref - horizon[0].double()).abs()
+    inside = miss <= z * horizon[2].double() + slack
+    zero = torch.zeros((), dtype=torch.float64, device=seg.device)
+    sums = torch.stack([has.sum(1).double(), torch.where(has, miss, zero).sum(1), torch.where(has, horizon[2].double(), zero).sum(1),
+                        (has & inside).sum(1).double()]).cpu()
+    return HorizonBars(*sums.numpy(), rows=rows, z=z, slack=slack)
 
 
 def evaluate_sweep(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None):

@@ -298,6 +298,42 @@ class Horizons:
         return text
 
 
+class HorizonBars:
+    """Error bars of the ordered decode's horizon picks against a reference (``inference.horizon_bars``), per boundary k = 1 ...
+    S-1 over the ``n`` columns in which the reference has the boundary: ``mae`` of the pick, ``mean_bar`` (the mean error bar,
+    sqrt(E[(B_k - pick)^2]) under the decode's posterior) and ``coverage``, the share of those columns whose reference boundary lies
+    within z * bar + slack rows of the pick; all in rows, NaN where n = 0.  Built from the four per-boundary sums."""
+
+    def __init__(self, n, sum_abs, sum_bar, n_inside, rows, z=2.0, slack=1.0):
+        self.n = np.asarray(n, dtype=np.float64).round().astype(np.int64).reshape(-1)
+        self.n_inside = np.asarray(n_inside, dtype=np.float64).round().astype(np.int64).reshape(-1)
+        if self.n.shape != self.n_inside.shape or (self.n < 0).any() or (self.n_inside < 0).any() or (self.n_inside > self.n).any():
+            raise ValueError("n and n_inside must be one count per boundary with 0 <= n_inside <= n")
+        ratio = lambda num: np.divide(np.asarray(num, dtype=np.float64).reshape(-1), self.n, out=np.full(self.n.shape, np.nan),
+                                      where=self.n > 0)
+        self.mae, self.mean_bar, self.coverage = ratio(sum_abs), ratio(sum_bar), ratio(self.n_inside)
+        self.rows, self.z, self.slack = int(rows), float(z), float(slack)
+
+    @property
+    def mean_coverage(self):
+        """The unweighted mean of the boundaries' coverage over the boundaries the reference has; NaN when there is none."""
+        v = self.coverage[self.n > 0]
+        return float(v.mean()) if v.size else float("nan")
+
+    def to_dict(self):
+        lst = lambda a: [float(v) for v in a]
+        return dict(rows=self.rows, z=self.z, slack=self.slack, n=[int(v) for v in self.n], n_inside=[int(v) for v in self.n_inside],
+                    mae=lst(self.mae), mean_bar=lst(self.mean_bar), coverage=lst(self.coverage), mean_coverage=self.mean_coverage)
+
+    def __str__(self, digits=2):
+        num = lambda v, d=digits: "{:>10}".format("-") if v != v else "{:>10.{d}f}".format(v, d=d)
+        text = "Horizon error bars (inside: |reference - pick| <= {:g} x bar + {:g} rows):\n".format(self.z, self.slack)
+        text += "{:>8} {:>9} {:>10} {:>10} {:>10}\n\n".format("boundary", "columns", "mae", "mean bar", "inside")
+        for k in range(self.n.shape[0]):
+            text += "{:>8} {:>9} {} {} {}\n".format(k + 1, int(self.n[k]), num(self.mae[k]), num(self.mean_bar[k]), num(self.coverage[k], 3))
+        return text + "\n{:>8} {:>9} {:>10} {:>10} {}\n".format("mean", "", "", "", num(self.mean_coverage, 3))
+
+
 def _infer_K(gt, pred):
     top = max(float(torch.as_tensor(gt).max()), float(torch.as_tensor(pred).max())) if torch.as_tensor(gt).numel() else 1.0
     if not top == top or top >= 16:

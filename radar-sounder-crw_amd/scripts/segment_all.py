@@ -26,7 +26,13 @@ column -- so the merged map keeps the order too (``inference.segment(..., merge=
 horizon table of ``inference.horizons`` -- per class, in how many columns the layer was found, missed or invented, and the error of
 its top, bottom and thickness -- with ``--min_run N`` (default 3: runs of fewer equal labels down a column are no layer), ``--tol
 ROWS`` (default 2), ``--row_spacing X`` / ``--row_unit NAME`` (the printed distances are rows * X, in NAME); ``--save_horizons``
-writes the picks as ``horizons.pt`` (int32 [2, 3, K, cols], CPU); ``--report_json`` gains a ``horizons`` key.  Without these flags
+writes the picks as ``horizons.pt`` (int32 [2, 3, K, cols], CPU); ``--report_json`` gains a ``horizons`` key; ``--posterior`` (with
+``--decode ordered``; with ``--use_last`` also ``--merge ordered``): the confidence that belongs to the ordered decode -- per pixel
+the posterior probability of its label over the monotone paths of its column, per layer boundary and column an error bar of the
+pick (``inference.segment(..., posterior=True, floor=X)``, ``--floor X``: the floor under the evidence, default 1e-4); after the
+other tables, the calibration table of that map and the error-bar table of ``inference.horizon_bars`` (how often the reference's
+boundary lies within 2 bars + 1 row of the pick); ``--save_posterior`` writes ``posterior_map.pt`` (float32) and ``horizon_bars.pt``
+(float32 [3, S-1, cols]: pick, posterior mean, error bar); ``--report_json`` gains a ``posterior`` key.  Without these flags
 the output is what it was.
 Differences from the scripts:
   * plots are not drawn;
@@ -110,10 +116,32 @@ def get_args_parser():
     p.add_argument('--row_spacing', default=1.0, type=float, metavar='X', help='distance between two rows, for the printed errors')
     p.add_argument('--row_unit', default='rows', metavar='NAME', help='the unit --row_spacing is given in')
     p.add_argument('--save_horizons', action='store_true', help='write horizons.pt, the picks (needs --horizons)')
+    p.add_argument('--posterior', action='store_true',
+                   help="the ordered decode's own confidence: per-pixel posterior and horizon error bars (needs --decode ordered)")
+    p.add_argument('--floor', default=None, type=float, metavar='X', help='floor under the evidence of --posterior (2^-20 ... 0.25; 1e-4)')
+    p.add_argument('--save_posterior', action='store_true', help='write posterior_map.pt and horizon_bars.pt (needs --posterior)')
     return p
 
 
 HORIZON_FLAGS = ('horizons', 'min_run', 'tol', 'row_spacing', 'row_unit', 'save_horizons')
+POSTERIOR_FLAGS = ('posterior', 'floor', 'save_posterior')
+
+
+def check_posterior_flags(args):
+    """The flags around ``--posterior``."""
+    if (args.save_posterior or args.floor is not None) and not args.posterior:
+        raise SystemExit('--floor and --save_posterior need --posterior')
+    if not args.posterior:
+        return args
+    if args.single or args.decode != 'ordered':
+        raise SystemExit('--posterior needs --decode ordered (and is not available with --single)')
+    if args.use_last and args.merge != 'ordered':
+        raise SystemExit('--posterior with --use_last needs --merge ordered')
+    if args.floor is None:
+        args.floor = 1e-4
+    if not 2.0 ** -20 <= args.floor <= 0.25:
+        raise SystemExit(f'--floor {args.floor}: 2^-20 ... 0.25')
+    return args
 
 
 def check_horizon_flags(args):
@@ -205,7 +233,7 @@ def load_data(args):
 def main(args):
     from imported.labelprop import LabelPropVOS_CRW
     tim = time.time()
-    args = check_horizon_flags(check_confidence_flags(with_defaults(args)))
+    args = check_posterior_flags(check_horizon_flags(check_confidence_flags(with_defaults(args))))
     # without --confidence the four flags that go with it do nothing, and the line reads as it did before they existed
     hidden = () if args.confidence else ('confidence', 'merge', 'bins', 'save_conf')
     if args.upsample == 'nearest':  # likewise
@@ -216,6 +244,8 @@ def main(args):
         hidden += ('context',)
     if args.decode == 'argmax':  # likewise
         hidden += ('decode', 'order')
+    if not args.posterior:  # likewise
+        hidden += POSTERIOR_FLAGS
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -243,7 +273,8 @@ def main(args):
                                 correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device,
                                 **(dict(confidence=args.confidence, merge=args.merge) if args.confidence else {}),
                                 **(dict(upsample=args.upsample) if args.upsample != 'nearest' else {}),
-                                **(dict(decode=args.decode, order=args.order) if args.decode != 'argmax' else {}))
+                                **(dict(decode=args.decode, order=args.order) if args.decode != 'argmax' else {}),
+                                **(dict(posterior=True, floor=args.floor) if args.posterior else {}))
         if correction:
             print('Change point for each radargram:', out['change_idx'])
         final, forward = out['pred'], out['forward']
@@ -252,6 +283,9 @@ def main(args):
     torch.save(forward.to(torch.int8), os.path.join(args.output_folder, 'predicted_map.pt'))
     if args.save_conf:
         torch.save(out['conf'].cpu(), os.path.join(args.output_folder, 'confidence_map.pt'))
+    if args.save_posterior:
+        torch.save(out['post'].cpu(), os.path.join(args.output_folder, 'posterior_map.pt'))
+        torch.save(out['horizon'].cpu(), os.path.join(args.output_folder, 'horizon_bars.pt'))
     if device.type == 'cuda':
         torch.cuda.synchronize()
     t_inference = time.time() - tim
@@ -282,6 +316,15 @@ def main(args):
     if args.iou:
         print('')
         print(report.iou_str())
+    pcal = bars = None
+    if args.posterior:
+        pcal = inference.calibration(final, out['post'], seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
+                                     unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses, bins=args.bins)
+        bars = inference.horizon_bars(out['horizon'], seg[:, :cols], out['order'])
+        print('')
+        print(f'Calibration (posterior of the ordered decode, floor {args.floor:g}):')
+        print(pcal)
+        print(bars)
     t_all = time.time() - tim
     print('\nTime elapsed (inference + metrics):', t_all)
     if args.report_json:
@@ -299,6 +342,8 @@ def main(args):
             d['calibration'] = dict(cal.to_dict(), kind=args.confidence, merge=args.merge)
         if hz is not None:
             d['horizons'] = hz.to_dict()
+        if pcal is not None:
+            d['posterior'] = dict(floor=args.floor, calibration=pcal.to_dict(), horizon_bars=bars.to_dict())
         with open(args.report_json, 'w') as f:
             json.dump(d, f, indent=1)
     return report
