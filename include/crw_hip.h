@@ -454,6 +454,9 @@ int crw_enc_pack_input_map(const float *x, int P, int C, int H, int W, uint16_t 
  *         activation of the layer below, [P][100][cout]) is 0; bias ignored.
  * (cin, cout) in {(32,64),(64,128),(128,128),(128,64),(64,32)}.  Outputs: planes y_hi/y_lo and/or
  * y_f32 [P][100][cout] (fp32); y_lo may be NULL when only the hi plane of the result is needed.
+ * gap (and gap_part of crw_enc_conv3x3_map) is produced by the kernels in which one wave owns all pixels of its channels: cout = 128
+ * (every split), cout = 64 at split 1; any other request for it is refused with CRW_EINVAL before anything is launched -- never
+ * CRW_OK with gap left unwritten.  Outputs are complete in stream order; what they held before is never read.
  * dgap (mode 1 only, may be NULL): fused ReLU + global-average-pool backward -- the input gradient
  * is dgap[P][cin] / 100 where x_hi (then the FORWARD activation plane of that layer) is non-zero;
  * x_lo is ignored. */

@@ -1372,11 +1372,17 @@ __global__ __launch_bounds__(256) void gap_bwd_kernel(const float *__restrict__ 
   }
 }
 
+// The pooled sums leave conv3x3_kernel's epilogue only where a wave owns all row tiles of its channels (WM == 1 there: 128 output
+// channels, or 64 on the 4-wave kernel).  With the row tiles split over waves nothing would write `gap`: refused, not left unwritten.
+template <int COUT, int NW>
+constexpr bool conv_gap_ok() { return NW / ((COUT / 16 >= NW) ? NW : COUT / 16) == 1; }
+
 template <int C>
 constexpr size_t conv_lds_bytes(int npl) { return (size_t)(npl - 1) * PLANE_ROWS * crs<C>() + (size_t)NPAD * crs<C>(); }
 
 template <int SPLIT, int CIN, int COUT, int MODE, int NW>
 int launch_conv_nw(const ConvArgs &a, hipStream_t s) {
+  if (MODE == 0 && a.gap && !conv_gap_ok<COUT, NW>()) return CRW_EINVAL;
   constexpr int CMAX = CIN > COUT ? CIN : COUT;
   size_t lds = conv_lds_bytes<CMAX>(SPLIT == 3 ? 2 : 1);
 #ifdef CRW_CONV_STAMPS
@@ -1400,6 +1406,7 @@ constexpr int MT_SMALL = 4;  // row tiles of the small-edge-tile launch (tiles w
 template <int SPLIT, int CIN, int COUT, int MODE, int MTL>
 int launch_conv_map_cls(const ConvArgs &a, hipStream_t s) {
   constexpr int CMAX = CIN > COUT ? CIN : COUT, NW = (SPLIT == 3 ? 8 : 4);
+  if (MODE == 0 && a.gap && !conv_gap_ok<COUT, NW>()) return CRW_EINVAL;
   const size_t lds = (size_t)(SPLIT == 3 ? 2 : 1) * NPAD * row_stride<CMAX>();
   static bool attr = false;
   if (!attr && lds > 64 * 1024) {
