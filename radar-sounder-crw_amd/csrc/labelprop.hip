@@ -316,22 +316,28 @@ __global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_k
   }
 }
 
-template <int CSTEPS, int NCH>
-int launch_topk_mfma_n(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int chunkcand, int pf,
-                       float *W, int32_t *I, int raw, hipStream_t s) {
-  const size_t lds = (size_t)TK_Q * chunkcand * 4;
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void *)labelprop_topk_mfma_kernel<CSTEPS, NCH>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
-        hipSuccess) {
+// launch of a kernel whose dynamic LDS may pass the 64 KiB a kernel gets unasked: the limit is raised to 150 KiB once per kernel
+// (`Kern` is a template argument, so every instantiation has its own flag)
+template <auto Kern, class... Args>
+int launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+  static bool raised = false;
+  if (!raised) {
+    if (hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
       g_last_hip_error = (int)hipGetLastError();
       return CRW_EHIP;
     }
-    attr = true;
+    raised = true;
   }
-  hipLaunchKernelGGL((labelprop_topk_mfma_kernel<CSTEPS, NCH>), dim3((N + TK_Q - 1) / TK_Q, T - first_frame), dim3(TK_NT), lds, s, ehat, T, N,
-                     cxt, radius, temp, knn, first_frame, chunkcand, pf, W, I, raw);
+  hipLaunchKernelGGL(Kern, grid, block, lds, s, args...);
   return check_launch();
+}
+
+template <int CSTEPS, int NCH>
+int launch_topk_mfma_n(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int chunkcand, int pf,
+                       float *W, int32_t *I, int raw, hipStream_t s) {
+  return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH>>(dim3((N + TK_Q - 1) / TK_Q, T - first_frame), dim3(TK_NT),
+                                                                 (size_t)TK_Q * chunkcand * 4, s, ehat, T, N, cxt, radius, temp, knn,
+                                                                 first_frame, chunkcand, pf, W, I, raw);
 }
 
 // max_nf context frames of max_bi in-band keys: in one piece, or -- when the scores of a 16-query tile fill more than half a CU's LDS --
@@ -374,6 +380,54 @@ __device__ inline void st_l2(float *p, float v) {
 // -- slide_row() below; false: the indices are label rows as they stand (cxt unused).
 __device__ inline int slide_row(int i, int n, int N, int cxt) { return (i >= N && n > cxt + 1) ? i + (n - cxt - 1) * N : i; }
 
+// ---- the pieces every propagation kernel below shares: the tie rule and the frame-0 rule of "same operations in the same order per
+// output, bit-identical L and pred" exist ONCE.  (The role kernels and the ring gathers stay separate texts: merged into one
+// template / one function they measured 1 - 3 % slower, profiles/labelprop_refactor_timing.log.) ----
+// pred[q, n] of the queries q0, q0 + step, ..: the arg-max of row q of frame n's [N, M] soft labels at `frame`.  The first maximum
+// wins (strict >, the lowest class on ties: torch.argmax on distinct values).  ld reads one element: L2Load from L in the global
+// kernel, PlainLoad (an LDS read) everywhere else.
+struct PlainLoad {
+  __device__ float operator()(const float *p) const { return *p; }
+};
+struct L2Load {
+  __device__ float operator()(const float *p) const { return ld_l2(p); }
+};
+template <class Load>
+__device__ __forceinline__ void argmax_rows(float *pred, int T, int N, int M, int n, int q0, int step, const float *frame, Load ld) {
+  for (int q = q0; q < N; q += step) {
+    const float *row = frame + q * M;
+    float bv = ld(row);
+    int bi = 0;
+    for (int c = 1; c < M; ++c) {
+      const float v = ld(row + c);
+      if (v > bv) { bv = v; bi = c; }
+    }
+    pred[(long)q * T + n] = (float)bi;
+  }
+}
+
+// frame 0: with a seed its one-hot rows go to L and the seed to pred[:, 0]; without one L holds the frame already (the caller's).
+// COPY: either way a copy goes to l0 in LDS (a template argument, not a test of l0: the LDS store must follow L's load on every
+// path, or hipcc carries that load as outstanding and puts s_waitcnt vmcnt(0) in front of the per-frame arg-max loops).  L2: agent-scope stores and loads (the kernels whose later frames read L back through L2), plain
+// ones otherwise.
+template <bool L2, bool COPY>
+__device__ __forceinline__ void init_frame0(const float *seed, float *L, float *pred, float *l0, int T, int N, int M, int tid, int nt) {
+  if (COPY || seed)
+    for (int it = tid; it < N * M; it += nt) {
+      float v;
+      if (seed) {
+        v = seed[it / M] == (float)(it % M) ? 1.f : 0.f;
+        if (L2) st_l2(L + it, v);
+        else L[it] = v;
+      } else {
+        v = L2 ? ld_l2(L + it) : L[it];
+      }
+      if (COPY) l0[it] = v;
+    }
+  if (seed)
+    for (int q = tid; q < N; q += nt) pred[(long)q * T] = seed[q];
+}
+
 template <bool SLIDE>
 __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__restrict__ seed,
                                                                 const float *__restrict__ W,
@@ -381,13 +435,7 @@ __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__r
                                                                 int knn, int first_frame, float *L,
                                                                 float *__restrict__ pred, int cxt) {
   const int tid = threadIdx.x, nt = blockDim.x;
-  if (seed) {
-    for (int it = tid; it < N * M; it += nt) {
-      const int q = it / M, c = it % M;
-      st_l2(L + it, seed[q] == (float)c ? 1.f : 0.f);
-    }
-    for (int q = tid; q < N; q += nt) pred[(long)q * T] = seed[q];
-  }
+  init_frame0<true, false>(seed, L, pred, nullptr, T, N, M, tid, nt);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   for (int n = first_frame; n < T; ++n) {
@@ -404,16 +452,7 @@ __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__r
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    for (int q = tid; q < N; q += nt) {
-      const float *row = L + ((long)n * N + q) * M;
-      float bv = ld_l2(row);
-      int bi = 0;
-      for (int c = 1; c < M; ++c) {
-        const float v = ld_l2(row + c);
-        if (v > bv) { bv = v; bi = c; }
-      }
-      pred[(long)q * T + n] = (float)bi;
-    }
+    argmax_rows(pred, T, N, M, n, tid, nt, L + (long)n * N * M, L2Load());
   }
 }
 
@@ -435,18 +474,7 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
   const int tid = threadIdx.x, NM = N * M, KN = knn * N;
   float *l0 = sm, *ring = l0 + NM, *wbuf = ring + (long)R * NM;  // [NM], [R][NM], [2][KN]
   int *ibuf = reinterpret_cast<int *>(wbuf + 2 * KN);              // [2][KN]
-  for (int it = tid; it < NM; it += GATHER_NT) {
-    float v;
-    if (seed) {
-      v = seed[it / M] == (float)(it % M) ? 1.f : 0.f;
-      st_l2(L + it, v);
-    } else {
-      v = ld_l2(L + it);
-    }
-    l0[it] = v;
-  }
-  if (seed)
-    for (int q = tid; q < N; q += GATHER_NT) pred[(long)q * T] = seed[q];
+  init_frame0<true, true>(seed, L, pred, l0, T, N, M, tid, GATHER_NT);
   for (int e = tid; e < KN; e += GATHER_NT) {
     wbuf[(first_frame & 1) * KN + e] = W[e];
     ibuf[(first_frame & 1) * KN + e] = I[e];
@@ -512,16 +540,7 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
       }
     }
     __syncthreads();
-    for (int q = tid; q < N; q += GATHER_NT) {
-      const float *row = slot + q * M;
-      float bv = row[0];
-      int bi = 0;
-      for (int c = 1; c < M; ++c) {
-        const float v = row[c];
-        if (v > bv) { bv = v; bi = c; }
-      }
-      pred[(long)q * T + n] = (float)bi;
-    }
+    argmax_rows(pred, T, N, M, n, tid, GATHER_NT, slot, PlainLoad());
   }
 }
 
@@ -537,7 +556,7 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
 //     in flight from global memory and copy them into a double-buffered LDS slot two frames ahead; one more wave takes the
 //     arg-max / pred store of the previous frame.  The per-frame barrier waits for LDS traffic only (lds_barrier): global loads and
 //     stores stay in flight across frames, where labelprop_gather_lds_kernel's __syncthreads() drained them every frame (2.4 us per frame at cfg5).
-//   tail kernel: a workgroup per frame n > cxt, all at once, labels gathered from L in global memory (complete since the prefix).
+//   tail kernel (labelprop_tail_batch_kernel): a workgroup per frame n > cxt, all at once, labels gathered from L in global memory (complete since the prefix).
 // Same operations in the same order per output as the kernels above: bit-identical L and pred.
 constexpr int PX_PF = 16, PX_NT = 512;  // list entries per loader lane and frame (a frame's lists: knn * N <= 64 * PX_PF); threads at most
 __device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -565,18 +584,8 @@ __global__ __launch_bounds__(PX_NT) void labelprop_prefix_kernel(const float *__
   int2 *pl = reinterpret_cast<int2 *>(lab + (((long)(last_frame + 1) * NM + 1) & ~1L));
 
   // labels of the frames before first_frame: frame 0 from the seed when given, the rest from L (filled by the caller)
-  for (int it = tid; it < first_frame * NM; it += (int)blockDim.x) {
-    float v;
-    if (seed && it < NM) {
-      v = seed[it / M] == (float)(it % M) ? 1.f : 0.f;
-      L[it] = v;
-    } else {
-      v = L[it];
-    }
-    lab[it] = v;
-  }
-  if (seed)
-    for (int q = tid; q < N; q += (int)blockDim.x) pred[(long)q * T] = seed[q];
+  init_frame0<false, true>(seed, L, pred, lab, T, N, M, tid, (int)blockDim.x);
+  for (int it = NM + tid; it < first_frame * NM; it += (int)blockDim.x) lab[it] = L[it];
 
   float pw[PX_PF];
   int pi[PX_PF];
@@ -660,31 +669,13 @@ __global__ __launch_bounds__(PX_NT) void labelprop_prefix_kernel(const float *__
         svc_load(f + 2 + D);
       }
     } else if (f > first_frame) {  // arg-max of the previous frame (first maximum wins, like torch.argmax on distinct values)
-      for (int qq = at; qq < N; qq += 64) {
-        const float *row = lab + ((long)(f - 1) * N + qq) * M;
-        float bv = row[0];
-        int bi = 0;
-        for (int cc = 1; cc < M; ++cc) {
-          const float x = row[cc];
-          if (x > bv) { bv = x; bi = cc; }
-        }
-        pred[(long)qq * T + f - 1] = (float)bi;
-      }
+      argmax_rows(pred, T, N, M, f - 1, at, 64, lab + (long)(f - 1) * NM, PlainLoad());
     }
     turn = turn + 1 == D ? 0 : turn + 1;
     lds_barrier();
   }
   if (amax) {
-    for (int qq = at; qq < N; qq += 64) {
-      const float *row = lab + ((long)last_frame * N + qq) * M;
-      float bv = row[0];
-      int bi = 0;
-      for (int cc = 1; cc < M; ++cc) {
-        const float x = row[cc];
-        if (x > bv) { bv = x; bi = cc; }
-      }
-      pred[(long)qq * T + last_frame] = (float)bi;
-    }
+    argmax_rows(pred, T, N, M, last_frame, at, 64, lab + (long)last_frame * NM, PlainLoad());
   }
 }
 
@@ -714,16 +705,7 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
   int2 *pl = reinterpret_cast<int2 *>(lab + (((long)(R + 1) * NM + 1) & ~1L));  // [2][KNP] (index, weight bits), slot = frame & 1
 
   // frame 0 (from the seed when given) and the frames before first_frame that a frame of this call can read: the last cxt of them
-  for (int it = tid; it < NM; it += (int)blockDim.x) {
-    float v;
-    if (seed) {
-      v = seed[it / M] == (float)(it % M) ? 1.f : 0.f;
-      L[it] = v;
-    } else {
-      v = L[it];
-    }
-    lab[it] = v;
-  }
+  init_frame0<false, true>(seed, L, pred, lab, T, N, M, tid, (int)blockDim.x);
   {
     const int fl = max(1, first_frame - cxt);
     for (int it = tid; it < (first_frame - fl) * NM; it += (int)blockDim.x) {
@@ -731,8 +713,6 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
       lab[NM + ((f - 1) % R) * NM + r] = L[(long)f * NM + r];
     }
   }
-  if (seed)
-    for (int q = tid; q < N; q += (int)blockDim.x) pred[(long)q * T] = seed[q];
 
   float pw[PX_PF];
   int pi[PX_PF];
@@ -833,16 +813,7 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
         svc_load(f + 2 + D);
       }
     } else if (f > first_frame) {  // arg-max of the previous frame (first maximum wins); its slot is next written R - 1 phases on
-      for (int qq = at; qq < N; qq += 64) {
-        const float *row = lab + pslot + qq * M;
-        float bv = row[0];
-        int bi = 0;
-        for (int cc = 1; cc < M; ++cc) {
-          const float x = row[cc];
-          if (x > bv) { bv = x; bi = cc; }
-        }
-        pred[(long)qq * T + f - 1] = (float)bi;
-      }
+      argmax_rows(pred, T, N, M, f - 1, at, 64, lab + pslot, PlainLoad());
     }
     turn = turn + 1 == D ? 0 : turn + 1;
     next_shift(f + 1);
@@ -851,60 +822,7 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
     lds_barrier();
   }
   if (amax) {
-    for (int qq = at; qq < N; qq += 64) {
-      const float *row = lab + pslot + qq * M;
-      float bv = row[0];
-      int bi = 0;
-      for (int cc = 1; cc < M; ++cc) {
-        const float x = row[cc];
-        if (x > bv) { bv = x; bi = cc; }
-      }
-      pred[(long)qq * T + last_frame] = (float)bi;
-    }
-  }
-}
-
-// frames t0 .. T-1, none of which reads a label this launch writes: a workgroup per frame, neighbours' labels from L (global memory)
-constexpr int TAIL_NT = 256, TAIL_CH = 16;
-__global__ __launch_bounds__(TAIL_NT) void labelprop_tail_kernel(const float *__restrict__ W, const int32_t *__restrict__ I, int T, int N,
-                                                                 int M, int knn, int first_frame, int t0, float *L,
-                                                                 float *__restrict__ pred) {
-  extern __shared__ __attribute__((aligned(16))) float slot[];  // [N * M]
-  const int tid = threadIdx.x, NM = N * M, n = t0 + blockIdx.x;
-  const float *Wn = W + (long)(n - first_frame) * knn * N;
-  const int32_t *In = I + (long)(n - first_frame) * knn * N;
-  const int row_lim = n * N - 1;
-  for (int it = tid; it < NM; it += TAIL_NT) {
-    const int q = it / M, c = it % M;
-    float p = 0.f;
-    for (int j0 = 0; j0 < knn; j0 += TAIL_CH) {
-      int idx[TAIL_CH];
-      float w[TAIL_CH], v[TAIL_CH];
-#pragma unroll
-      for (int u = 0; u < TAIL_CH; ++u) {
-        const int jj = min(j0 + u, knn - 1);
-        idx[u] = min(max(In[jj * N + q], 0), row_lim);
-        w[u] = Wn[jj * N + q];
-      }
-#pragma unroll
-      for (int u = 0; u < TAIL_CH; ++u) v[u] = L[(long)idx[u] * M + c];
-#pragma unroll
-      for (int u = 0; u < TAIL_CH; ++u)
-        if (j0 + u < knn) p += v[u] * w[u];
-    }
-    L[((long)n * N + q) * M + c] = p;
-    slot[it] = p;
-  }
-  __syncthreads();
-  for (int q = tid; q < N; q += TAIL_NT) {
-    const float *row = slot + q * M;
-    float bv = row[0];
-    int bi = 0;
-    for (int c = 1; c < M; ++c) {
-      const float x = row[c];
-      if (x > bv) { bv = x; bi = c; }
-    }
-    pred[(long)q * T + n] = (float)bi;
+    argmax_rows(pred, T, N, M, last_frame, at, 64, lab + pslot, PlainLoad());
   }
 }
 
@@ -963,18 +881,7 @@ __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float
   L += (long)g * T * NM;
   pred += (long)g * N * T;
   float *l0 = sm, *ring = l0 + NM;  // [NM], [R][NM]
-  for (int it = tid; it < NM; it += nt) {
-    float v;
-    if (seed) {
-      v = seed[it / M] == (float)(it % M) ? 1.f : 0.f;
-      st_l2(L + it, v);
-    } else {
-      v = ld_l2(L + it);
-    }
-    l0[it] = v;
-  }
-  if (seed)
-    for (int q = tid; q < N; q += nt) pred[(long)q * T] = seed[q];
+  init_frame0<true, true>(seed, L, pred, l0, T, N, M, tid, nt);
   __syncthreads();
   const int RNM = R * NM;
   for (int n = first_frame; n <= last_frame; ++n) {
@@ -1017,20 +924,13 @@ __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float
       slot[it] = p;
     }
     __syncthreads();  // frame n's labels are in LDS; its slot is next written R frames (barriers) later
-    for (int q = tid; q < N; q += nt) {
-      const float *row = slot + q * M;
-      float bv = row[0];
-      int bi = 0;
-      for (int c = 1; c < M; ++c) {
-        const float x = row[c];
-        if (x > bv) { bv = x; bi = c; }
-      }
-      pred[(long)q * T + n] = (float)bi;
-    }
+    argmax_rows(pred, T, N, M, n, tid, nt, slot, PlainLoad());
   }
 }
 
-// labelprop_tail_kernel over (frame, configuration)
+// frames t0 .. T-1 of configuration g = blockIdx.y, none of which reads a label this launch writes: a workgroup per (frame,
+// configuration), neighbours' labels from L (global memory).  One configuration (crw_labelprop_propagate): gridDim.y = 1, i_stride unused.
+constexpr int TAIL_NT = 256, TAIL_CH = 16;
 __global__ __launch_bounds__(TAIL_NT) void labelprop_tail_batch_kernel(const float *__restrict__ W, const int32_t *__restrict__ I,
                                                                        long i_stride, int T, int N, int M, int knn, int first_frame,
                                                                        int t0, float *L, float *__restrict__ pred) {
@@ -1063,16 +963,7 @@ __global__ __launch_bounds__(TAIL_NT) void labelprop_tail_batch_kernel(const flo
     slot[it] = p;
   }
   __syncthreads();
-  for (int q = tid; q < N; q += TAIL_NT) {
-    const float *row = slot + q * M;
-    float bv = row[0];
-    int bi = 0;
-    for (int c = 1; c < M; ++c) {
-      const float x = row[c];
-      if (x > bv) { bv = x; bi = c; }
-    }
-    pred[(long)q * T + n] = (float)bi;
-  }
+  argmax_rows(pred, T, N, M, n, tid, TAIL_NT, slot, PlainLoad());
 }
 
 // xent[a, i] = logsumexp_c A_i[c, a] - A_i[a, a],  A_i[c, a] = <ehat[i,c,0:C-1], ehat[i,a,1:C]> / 0.1
@@ -1176,15 +1067,62 @@ int topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, 
   return check_launch();
 }
 
+// what every propagation entry point refuses (each adds its own: cxt_size, G, the knn cap)
+bool bad_propagate_args(const float *W, const int32_t *I, const float *L, const float *pred, int T, int N, int M, int knn, int first_frame) {
+  return !W || !I || !L || !pred || T < 2 || N < 1 || M < 1 || knn < 1 || first_frame < 1 || first_frame >= T;
+}
+
+// the split of the reference rule: frames from t0 on read no label of the call -- one frame alone, or every frame beyond the context
+// bound; the chained frames are first_frame .. t0 - 1 (none when t0 == first_frame)
+int chain_end(int T, int first_frame, int cxt_size) {
+  return (T - first_frame == 1) ? first_frame : (first_frame > cxt_size + 1 ? first_frame : (cxt_size + 1 < T ? cxt_size + 1 : T));
+}
+
+// frames t0 .. T - 1 of G configurations, all at once (nothing to do when t0 == T)
+int launch_tail(const float *W, const int32_t *I, long i_stride, int G, int T, int N, int M, int knn, int first_frame, int t0, float *L,
+                float *pred, hipStream_t s) {
+  if (t0 >= T) return CRW_OK;
+  hipLaunchKernelGGL(labelprop_tail_batch_kernel, dim3(T - t0, G), dim3(TAIL_NT), (size_t)N * M * 4, s, W, I, i_stride, T, N, M, knn,
+                     first_frame, t0, L, pred);
+  return check_launch();
+}
+
+// the role kernels (labelprop_prefix_kernel, labelprop_slide_kernel): compute waves (64 outputs each) + 1..4 list loaders (fewer
+// when the outputs need more compute waves) + the arg-max wave; nlab frames of labels and the two list slots in LDS
+int chain_ncw(long NM) { return (int)((NM + 63) / 64); }
+int chain_nld(long NM) { return PX_NT / 64 - 1 - chain_ncw(NM) < 4 ? PX_NT / 64 - 1 - chain_ncw(NM) : 4; }
+size_t chain_lds(long nlab, long NM) { return (size_t)(((nlab * NM + 1) & ~1L) * 4 + 16L * 64 * PX_PF); }
+// ... and where it can run: the neighbours in registers (32 spill), at most 6 compute waves (N * M <= 384: a loader and the arg-max wave
+// beside them), a frame's lists in the loader's registers, the labels within the 150 KiB
+bool chain_fits(int knn, long NM, long KN, size_t lds) { return knn <= 24 && chain_nld(NM) >= 1 && KN <= 64 * PX_PF && lds <= 150 * 1024; }
+
+// KP = knn rounded up to the register instances.  RING: the slide kernel (every frame chained, `last` unused), else the prefix kernel
+// over frames first_frame .. last (cxt, R unused)
+template <int KP, bool RING>
+int launch_chain_kp(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int last, int cxt, int R,
+                    size_t lds, float *L, float *pred, hipStream_t s) {
+  const int ncw = chain_ncw((long)N * M);
+  const dim3 block((ncw + chain_nld((long)N * M) + 1) * 64);
+  if constexpr (RING)
+    return launch_big_lds<labelprop_slide_kernel<KP>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, cxt, R, L, pred, ncw);
+  else
+    return launch_big_lds<labelprop_prefix_kernel<KP>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, last, L, pred, ncw);
+}
+template <bool RING>
+int launch_chain(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int last, int cxt, int R,
+                 size_t lds, float *L, float *pred, hipStream_t s) {
+  if (knn <= 8) return launch_chain_kp<8, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, s);
+  if (knn <= 16) return launch_chain_kp<16, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, s);
+  return launch_chain_kp<24, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, s);
+}
+
 // the one-workgroup walk over any lists (crw_labelprop_gather; SLIDE: the general route of crw_labelprop_propagate_sliding, the
 // indices translated in the kernel)
 template <bool SLIDE>
 int launch_gather(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int cxt, float *L,
                   float *pred, crw_stream_t stream) {
   crw::clear_stale_error();
-  if (!W || !I || !L || !pred || T < 2 || N < 1 || M < 1 || knn < 1 || first_frame < 1 || first_frame >= T ||
-      (!seed && first_frame < 1))
-    return CRW_EINVAL;
+  if (bad_propagate_args(W, I, L, pred, T, N, M, knn, first_frame)) return CRW_EINVAL;
   // LDS-resident form when the lists of a frame fit the prefetch registers and at least a few frames fit the ring
   const long NM = (long)N * M, KN = (long)knn * N;
   const long budget = 150 * 1024 - 16 * KN;  // bytes left for frame 0 + the ring after the two (weight, index) list copies
@@ -1193,18 +1131,8 @@ int launch_gather(const float *seed, const float *W, const int32_t *I, int T, in
   static const char *force_global = getenv("CRW_LABELPROP_GATHER_GLOBAL");  // diagnostics: the L2-round-trip kernel
   if (KN <= (long)GATHER_NT * GATHER_PF && R >= 4 && (long)T * N < (1L << 30) / M && !force_global) {
     const size_t lds = (size_t)(4 * (NM * (R + 1) + 4 * KN));
-    static bool attr = false;
-    if (!attr) {
-      if (hipFuncSetAttribute((const void *)labelprop_gather_lds_kernel<SLIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
-          hipSuccess) {
-        g_last_hip_error = (int)hipGetLastError();
-        return CRW_EHIP;
-      }
-      attr = true;
-    }
-    hipLaunchKernelGGL(labelprop_gather_lds_kernel<SLIDE>, dim3(1), dim3(GATHER_NT), lds, (hipStream_t)stream, seed, W, I, T, N, M,
-                       knn, first_frame, L, pred, (int)R, cxt);
-    return check_launch();
+    return launch_big_lds<labelprop_gather_lds_kernel<SLIDE>>(dim3(1), dim3(GATHER_NT), lds, (hipStream_t)stream, seed, W, I, T, N, M, knn,
+                                                              first_frame, L, pred, (int)R, cxt);
   }
   hipLaunchKernelGGL(labelprop_gather_kernel<SLIDE>, dim3(1), dim3(1024), 0, (hipStream_t)stream, seed, W, I, T, N, M, knn,
                      first_frame, L, pred, cxt);
@@ -1216,41 +1144,21 @@ template <bool SLIDE>
 int launch_propagate_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M, int knn,
                            int first_frame, int cxt_size, float *L, float *pred, crw_stream_t stream) {
   crw::clear_stale_error();
-  if (!W || !I || !L || !pred || G < 1 || G > 65535 || T < 2 || N < 1 || M < 1 || knn < 1 || knn > MAX_KNN || first_frame < 1 ||
-      first_frame >= T || cxt_size < 1)
-    return CRW_EINVAL;
+  if (bad_propagate_args(W, I, L, pred, T, N, M, knn, first_frame) || G < 1 || G > 65535 || knn > MAX_KNN || cxt_size < 1) return CRW_EINVAL;
   const long NM = (long)N * M;
   if ((long)T * N >= (1L << 30) / M || NM * 4 > 30 * 1024) return CRW_EINVAL;  // 32-bit label offsets; frame 0 + a ring of >= 4 frames in LDS
-  // the split of crw_labelprop_propagate: frames from t0 on read no label of this call
-  const int t0 = SLIDE ? T
-                       : (T - first_frame == 1) ? first_frame : (first_frame > cxt_size + 1 ? first_frame : (cxt_size + 1 < T ? cxt_size + 1 : T));
-  const int last = t0 - 1;
+  const int t0 = SLIDE ? T : chain_end(T, first_frame, cxt_size), last = t0 - 1;
   hipStream_t s = (hipStream_t)stream;
   if (last >= first_frame || seed) {  // (no chained frame: the kernel writes frame 0 from the seed and returns)
     long R = (150L * 1024) / (4 * NM) - 1;
     if (R > last + 1) R = last + 1;
     if (R < 2) R = 2;
-    static bool attr = false;
-    if (!attr) {
-      if (hipFuncSetAttribute((const void *)labelprop_chain_batch_kernel<SLIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) !=
-          hipSuccess) {
-        g_last_hip_error = (int)hipGetLastError();
-        return CRW_EHIP;
-      }
-      attr = true;
-    }
     const int nt = (int)(NM >= 1024 ? 1024 : (NM + 63) / 64 * 64);
-    hipLaunchKernelGGL(labelprop_chain_batch_kernel<SLIDE>, dim3(G), dim3(nt), (size_t)(4 * NM * (R + 1)), s, seed, W, I, (long)i_stride, T, N, M,
-                       knn, first_frame, last, L, pred, (int)R, cxt_size);
-    const int rc = check_launch();
+    const int rc = launch_big_lds<labelprop_chain_batch_kernel<SLIDE>>(dim3(G), dim3(nt), (size_t)(4 * NM * (R + 1)), s, seed, W, I, (long)i_stride,
+                                                                       T, N, M, knn, first_frame, last, L, pred, (int)R, cxt_size);
     if (rc != CRW_OK) return rc;
   }
-  if (t0 < T) {
-    hipLaunchKernelGGL(labelprop_tail_batch_kernel, dim3(T - t0, G), dim3(TAIL_NT), (size_t)NM * 4, s, W, I, (long)i_stride, T, N, M, knn,
-                       first_frame, t0, L, pred);
-    return check_launch();
-  }
-  return CRW_OK;
+  return launch_tail(W, I, (long)i_stride, G, T, N, M, knn, first_frame, t0, L, pred, s);
 }
 
 }  // namespace
@@ -1280,81 +1188,36 @@ int crw_labelprop_gather(const float *seed, const float *W, const int32_t *I, in
 int crw_labelprop_propagate(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame,
                             int cxt_size, float *L, float *pred, crw_stream_t stream) {
   crw::clear_stale_error();
-  if (!W || !I || !L || !pred || T < 2 || N < 1 || M < 1 || knn < 1 || first_frame < 1 || first_frame >= T || cxt_size < 1)
-    return CRW_EINVAL;
+  if (bad_propagate_args(W, I, L, pred, T, N, M, knn, first_frame) || cxt_size < 1) return CRW_EINVAL;
   const long NM = (long)N * M, KN = (long)knn * N;
-  // frames from t0 on read no label of this call: one frame alone, or every frame beyond the context bound
-  const int t0 = (T - first_frame == 1) ? first_frame : (first_frame > cxt_size + 1 ? first_frame : (cxt_size + 1 < T ? cxt_size + 1 : T));
-  const int last = t0 - 1;  // the chained frames first_frame .. last (none when last < first_frame)
+  const int t0 = chain_end(T, first_frame, cxt_size), last = t0 - 1;  // the chained frames first_frame .. last (none when last < first_frame)
   static const bool seq = getenv("CRW_LABELPROP_GATHER_SEQ") && getenv("CRW_LABELPROP_GATHER_SEQ")[0] == '1';  // A/B: one-workgroup walk
-  // chained frames: compute waves + 1..4 list loaders (fewer when the outputs need more compute waves) + the arg-max wave
-  const int ncw = (int)((NM + 63) / 64), nld = PX_NT / 64 - 1 - ncw < 4 ? PX_NT / 64 - 1 - ncw : 4;
-  const size_t px_lds = (size_t)((((long)(last + 1) * NM + 1) & ~1L) * 4 + 16L * 64 * PX_PF);
-  const bool px_ok = last < first_frame || (knn <= 24 /* 32 neighbours in registers spill */ && nld >= 1 && KN <= 64 * PX_PF &&
-                                            px_lds <= 150 * 1024);
+  const size_t px_lds = chain_lds(last + 1, NM);  // every chained frame's labels, direct addressing
+  const bool px_ok = last < first_frame ? !seed  // (a seed and no chained frame: the general kernel initialises frame 0)
+                                        : chain_fits(knn, NM, KN, px_lds);
   if (seq || !px_ok || NM * 4 > 60 * 1024 || (long)T * N >= (1L << 30) / M)
     return crw_labelprop_gather(seed, W, I, T, N, M, knn, first_frame, L, pred, stream);
   hipStream_t s = (hipStream_t)stream;
   if (last >= first_frame) {
-    static bool attr[3] = {false, false, false};  // dynamic-LDS limit raised, per instantiation
-    auto launch = [&](auto kern, int which) -> int {
-      if (!attr[which]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
-          g_last_hip_error = (int)hipGetLastError();
-          return CRW_EHIP;
-        }
-        attr[which] = true;
-      }
-      hipLaunchKernelGGL(kern, dim3(1), dim3((ncw + nld + 1) * 64), px_lds, s, seed, W, I, T, N, M, knn, first_frame, last, L, pred, ncw);
-      return check_launch();
-    };
-    int rc;
-    if (knn <= 8) rc = launch(labelprop_prefix_kernel<8>, 0);
-    else if (knn <= 16) rc = launch(labelprop_prefix_kernel<16>, 1);
-    else rc = launch(labelprop_prefix_kernel<24>, 2);
+    const int rc = launch_chain<false>(seed, W, I, T, N, M, knn, first_frame, last, 0, 0, px_lds, L, pred, s);
     if (rc != CRW_OK) return rc;
-  } else if (seed) {  // a seed with a later first frame and no chained frame: the general kernel initialises frame 0
-    return crw_labelprop_gather(seed, W, I, T, N, M, knn, first_frame, L, pred, stream);
   }
-  if (t0 < T) {
-    hipLaunchKernelGGL(labelprop_tail_kernel, dim3(T - t0), dim3(TAIL_NT), (size_t)NM * 4, s, W, I, T, N, M, knn, first_frame, t0, L, pred);
-    return check_launch();
-  }
-  return CRW_OK;
+  return launch_tail(W, I, 0, 1, T, N, M, knn, first_frame, t0, L, pred, s);
 }
 
 int crw_labelprop_propagate_sliding(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame,
                                     int cxt_size, float *L, float *pred, crw_stream_t stream) {
   crw::clear_stale_error();
-  if (!W || !I || !L || !pred || T < 2 || N < 1 || M < 1 || knn < 1 || first_frame < 1 || first_frame >= T || cxt_size < 1)
-    return CRW_EINVAL;
+  if (bad_propagate_args(W, I, L, pred, T, N, M, knn, first_frame) || cxt_size < 1) return CRW_EINVAL;
   const long NM = (long)N * M, KN = (long)knn * N;
-  // the ring kernel: frame 0 + min(cxt + 1, T - 1) ring slots + the two list slots within the 150 KiB; at most 6 compute waves (one
-  // list loader and the arg-max wave beside them); a frame's lists in the loader's registers.
+  // the ring kernel where frame 0 + min(cxt + 1, T - 1) ring slots fit.
   // CRW_LABELPROP_SLIDING_GENERAL=1 (read per call): the general kernels instead (A/B, tools/sliding_timing.py)
   const char *gen = getenv("CRW_LABELPROP_SLIDING_GENERAL");
   const long R = cxt_size + 1 < T - 1 ? cxt_size + 1 : T - 1;
-  const size_t lds = (size_t)((((R + 1) * NM + 1) & ~1L) * 4 + 16L * 64 * PX_PF);
-  const bool ring = !(gen && gen[0] == '1') && knn <= 24 /* 32 neighbours in registers spill */ && NM <= 384 && KN <= 64 * PX_PF &&
-                    lds <= 150 * 1024 && (long)T * N < (1L << 30) / M;
+  const size_t lds = chain_lds(R + 1, NM);
+  const bool ring = !(gen && gen[0] == '1') && chain_fits(knn, NM, KN, lds) && (long)T * N < (1L << 30) / M;
   if (!ring) return launch_gather<true>(seed, W, I, T, N, M, knn, first_frame, cxt_size, L, pred, stream);
-  const int ncw = (int)((NM + 63) / 64), nld = PX_NT / 64 - 1 - ncw < 4 ? PX_NT / 64 - 1 - ncw : 4;
-  static bool attr[3] = {false, false, false};  // dynamic-LDS limit raised, per instantiation
-  auto launch = [&](auto kern, int which) -> int {
-    if (!attr[which]) {
-      if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
-        g_last_hip_error = (int)hipGetLastError();
-        return CRW_EHIP;
-      }
-      attr[which] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(1), dim3((ncw + nld + 1) * 64), lds, (hipStream_t)stream, seed, W, I, T, N, M, knn, first_frame, cxt_size,
-                       (int)R, L, pred, ncw);
-    return check_launch();
-  };
-  if (knn <= 8) return launch(labelprop_slide_kernel<8>, 0);
-  if (knn <= 16) return launch(labelprop_slide_kernel<16>, 1);
-  return launch(labelprop_slide_kernel<24>, 2);
+  return launch_chain<true>(seed, W, I, T, N, M, knn, first_frame, T - 1, cxt_size, (int)R, lds, L, pred, (hipStream_t)stream);
 }
 
 int crw_labelprop_sweep_weights(const float *V, int F, int kcap, int N, const int *knns, int nk, float *W, crw_stream_t stream) {

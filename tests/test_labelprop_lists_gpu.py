@@ -68,7 +68,7 @@ def test_topk_lists_against_fp64(hip, shape, temp):
 # (T, N, C, M, cxt, radius, knn, grid_w): the lists of one shape per route of test_labelprop_propagate_equals_the_one_workgroup_walk,
 # with a scrambled seed.  crw_labelprop_propagate chains the frames 1 .. cxt in labelprop_prefix_kernel<8 / 16 / 24> when knn <= 24 and
 # the N * M outputs of a frame fit 6 compute waves (N * M <= 384; M is chosen to stay below that where the prefix kernel is meant),
-# and runs every later frame in labelprop_tail_kernel; otherwise it calls crw_labelprop_gather, which takes labelprop_gather_lds_kernel
+# and runs every later frame in labelprop_tail_batch_kernel (one configuration); otherwise it calls crw_labelprop_gather, which takes labelprop_gather_lds_kernel
 # when knn * N <= 2048 and at least 4 frames fit its LDS ring, else labelprop_gather_kernel.  crw_labelprop_propagate_batch always
 # runs labelprop_chain_batch_kernel + labelprop_tail_batch_kernel.
 GATHER_CASES = [

@@ -41,6 +41,13 @@ VARIANTS = [
     ("CRW_LABELPROP_TOPK_CHUNKS", "1", PARITY, "labelprop_topk_on_matrix_cores or labelprop_matches_oracle_mcords_shape or propagate_matches_reference"),
     # label-propagation top-k on the vector kernel where the default scores on the fp32 matrix cores (csrc/labelprop.hip)
     ("CRW_LABELPROP_TOPK_VALU", "1", PARITY, "labelprop_matches_oracle_mcords_shape or labelprop_edge_cases or propagate_matches_reference"),
+    # the one-workgroup walk on the global-memory kernel (csrc/labelprop.hip labelprop_gather_kernel, the fallback for lists past the
+    # LDS-ring form) as the thing the role kernel + tail, and the ring role kernel, are held to bit for bit: small shapes only
+    ("CRW_LABELPROP_GATHER_GLOBAL", "1", PARITY,
+     "labelprop_propagate_equals_the_one_workgroup_walk and (14-10-16-3-3-4-5-1 or 3-9-8-2-1-2-3-1 or 30-24-32-2-1-6-24-1)"),
+    # (the -k words are meant to pick exactly three of test_sliding_gpu.CASES: "window of one frame", "first translated frame is the
+    # last, T = cxt + 3" and "knn 4 (8 registers)"; a new case name with one of these words joins this child run)
+    ("CRW_LABELPROP_GATHER_GLOBAL", "1", "tests/test_sliding_gpu.py", "every_route and (window or first or (knn and 8))"),
 ]
 
 
