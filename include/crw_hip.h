@@ -37,8 +37,8 @@
  *                             under a layer order, a DP per pixel column          order of the layers down a trace)
  *   crw_labelmap_ordered_joint[_batch]  that decode over two passes' rows, per pixel  (no twin: test_all.py:146-159 merges the two
  *                             the surer pass's: an order-preserving merge          label maps by a class rule)
- *   crw_labelmap_ordered[_joint]_posterior  the posterior of those decodes over the  (no twin)
- *                             monotone paths: confidence and horizon error bars
+ *   crw_labelmap_ordered[_joint]_posterior[_batch]  the posterior of those decodes over  (no twin)
+ *                             the monotone paths: confidence and horizon error bars
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (HBM) unless its name ends in _host;
@@ -70,7 +70,9 @@ extern "C" {
  * crw_labelprop_propagate_sliding, crw_labelprop_propagate_sliding_batch (crw_hip.has_sliding()); then
  * crw_labelmap_ordered_workspace, crw_labelmap_ordered, crw_labelmap_ordered_batch (crw_hip.has_ordered()); then
  * crw_labelmap_ordered_joint, crw_labelmap_ordered_joint_batch (crw_hip.has_joint()); then crw_labelmap_posterior_workspace,
- * crw_labelmap_ordered_posterior, crw_labelmap_ordered_joint_posterior (crw_hip.has_posterior()).  The ONE place the number is
+ * crw_labelmap_ordered_posterior, crw_labelmap_ordered_joint_posterior (crw_hip.has_posterior()); then
+ * crw_labelmap_posterior_workspace_batch, crw_labelmap_ordered_posterior_batch, crw_labelmap_ordered_joint_posterior_batch
+ * (crw_hip.has_posterior_batch()).  The ONE place the number is
  * written: crw_abi_version() returns it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
 #define CRW_ABI_VERSION 8
@@ -417,6 +419,26 @@ int crw_labelmap_ordered_joint_posterior(const float *La, int Ta, int cols_a, in
                                          int cols_b, int col0_b, int flip_b, int N, int M, int rows, int ncols, const int *order_host,
                                          int S, int conf_kind, float floor, const void *labels, int label_dtype, size_t ld,
                                          float *post, float *hz, size_t hz_ld, void *ws, size_t ws_bytes, crw_stream_t stream);
+/* The two posteriors for the G configurations of a sweep in ONE launch (the configuration is a grid dimension of the same kernel;
+ * the one-map calls are G = 1 of the same launcher): L / La / Lb [G, T*N, M] as for crw_labelmap_ordered_batch / _joint_batch.
+ * Configuration g reads its labels at labels + g * map_stride (elements of the label type) and writes post + g * map_stride, its
+ * [3][S-1] rows of hz at hz + g * hz_stride, and uses slice g of ws (crw_labelmap_posterior_workspace_batch(G, rows, cols, S) bytes:
+ * G times the one-map call's, 0 for a bad shape or a product that does not fit a size_t) -- so maps[:, :, a:b] of [G, rows, width]
+ * tensors and hz[:, :, :, a:b] of a [G, 3, S-1, width] tensor are valid operands.  One order, one floor and one geometry serve all
+ * configurations.  Slice g is bit-identical to the one-map entry point called on slice g's operands and the same window.  Every
+ * refusal of the one-map calls applies; in addition G < 1 (or > 65535), map_stride < (rows - 1) * ld + cols, hz_stride < 3 * (S - 1) *
+ * hz_ld when hz is given, and slices whose extent overflows a size_t -> CRW_EINVAL; too few workspace bytes -> CRW_EWORKSPACE; all
+ * before anything is launched. */
+size_t crw_labelmap_posterior_workspace_batch(int G, int rows, int cols, int S);
+int crw_labelmap_ordered_posterior_batch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip,
+                                         const int *order_host, int S, float floor, const void *labels, int label_dtype, size_t ld,
+                                         size_t map_stride, float *post, float *hz, size_t hz_ld, size_t hz_stride, void *ws,
+                                         size_t ws_bytes, crw_stream_t stream);
+int crw_labelmap_ordered_joint_posterior_batch(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb, int Tb,
+                                               int cols_b, int col0_b, int flip_b, int G, int N, int M, int rows, int ncols,
+                                               const int *order_host, int S, int conf_kind, float floor, const void *labels,
+                                               int label_dtype, size_t ld, size_t map_stride, float *post, float *hz, size_t hz_ld,
+                                               size_t hz_stride, void *ws, size_t ws_bytes, crw_stream_t stream);
 
 /* building blocks exported for tests and the roofline bench --------------------------------- */
 /* Weight gradient of the CNN encoder's linear head (nn.Linear(128, 128), src/encoder.py:40,55; autograd of

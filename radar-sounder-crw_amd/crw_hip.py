@@ -78,6 +78,11 @@ SIGNATURES = {
     "crw_labelmap_ordered_posterior": (_c_int, [_p] + [_c_int] * 6 + [_p, _c_int, _c_f, _p, _c_int, _c_sz, _p, _p, _c_sz, _p, _c_sz, _p]),
     "crw_labelmap_ordered_joint_posterior": (_c_int, ([_p] + [_c_int] * 4) * 2 + [_c_int] * 4 + [_p, _c_int, _c_int, _c_f, _p, _c_int, _c_sz, _p,
                                                       _p, _c_sz, _p, _c_sz, _p]),
+    "crw_labelmap_posterior_workspace_batch": (_c_sz, [_c_int] * 4),
+    "crw_labelmap_ordered_posterior_batch": (_c_int, [_p] + [_c_int] * 7 + [_p, _c_int, _c_f, _p, _c_int, _c_sz, _c_sz, _p, _p, _c_sz, _c_sz, _p,
+                                                      _c_sz, _p]),
+    "crw_labelmap_ordered_joint_posterior_batch": (_c_int, ([_p] + [_c_int] * 4) * 2 + [_c_int] * 5 + [_p, _c_int, _c_int, _c_f, _p, _c_int,
+                                                            _c_sz, _c_sz, _p, _p, _c_sz, _c_sz, _p, _c_sz, _p]),
     "crw_linear128_wgrad_ws_bytes": (_c_sz, [_c_int]),
     "crw_linear128_wgrad": (_c_int, [_p, _p, _p, _c_int, _p, _c_sz, _p]),
     "crw_adam_step": (_c_int, [_p, _p, _p, _p, ctypes.c_long, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
@@ -173,6 +178,10 @@ JOINT_ENTRY_POINTS = ("crw_labelmap_ordered_joint", "crw_labelmap_ordered_joint_
 # likewise: the posterior of the ordered decodes, confidence and horizon error bars (`has_posterior()`)
 POSTERIOR_ENTRY_POINTS = ("crw_labelmap_posterior_workspace", "crw_labelmap_ordered_posterior", "crw_labelmap_ordered_joint_posterior")
 
+# likewise: those posteriors for the G configurations of a sweep in one launch (`has_posterior_batch()`)
+POSTERIOR_BATCH_ENTRY_POINTS = ("crw_labelmap_posterior_workspace_batch", "crw_labelmap_ordered_posterior_batch",
+                                "crw_labelmap_ordered_joint_posterior_batch")
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 
 # group -> its entry points.  `has_<group>()` tells whether the loaded library exports them, `_<group>_lib()` is lib() or the
@@ -180,7 +189,7 @@ CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame 
 OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_ENTRY_POINTS, "dense": DENSE_ENTRY_POINTS,
                          "dense_batch": DENSE_BATCH_ENTRY_POINTS, "horizons": HORIZONS_ENTRY_POINTS,
                          "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS, "joint": JOINT_ENTRY_POINTS,
-                         "posterior": POSTERIOR_ENTRY_POINTS}
+                         "posterior": POSTERIOR_ENTRY_POINTS, "posterior_batch": POSTERIOR_BATCH_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -238,6 +247,7 @@ has_sliding, _sliding_lib = _optional("sliding", "the sliding-context entry poin
 has_ordered, _ordered_lib = _optional("ordered", "the depth-ordered label map's entry points")
 has_joint, _joint_lib = _optional("joint", "the joint ordered label map's entry points")
 has_posterior, _posterior_lib = _optional("posterior", "the ordered maps' posterior entry points")
+has_posterior_batch, _posterior_batch_lib = _optional("posterior_batch", "the batched posterior entry points")
 
 
 def check_context(context):
@@ -1183,10 +1193,53 @@ def labelmap_posterior_workspace(rows, cols, S):
     return _posterior_lib().crw_labelmap_posterior_workspace(int(rows), int(cols), int(S))
 
 
-def _posterior(sources, N, M, rows, cols, order, labels, confidence, floor, out, out_hz, workspace):
-    """The two posterior functions behind their signatures; sources as for `_labelmap`."""
+def labelmap_posterior_workspace_batch(G, rows, cols, S):
+    """Bytes of workspace ONE launch of `labelmap_ordered_posterior_batch` / `labelmap_ordered_joint_posterior_batch` needs for G
+    configurations: G times `labelmap_posterior_workspace(rows, cols, S)`."""
+    return _posterior_batch_lib().crw_labelmap_posterior_workspace_batch(int(G), int(rows), int(cols), int(S))
+
+
+POSTERIOR_BATCH_WS = 2 << 30  # bytes of workspace the batched posterior calls allocate at most (CRW_POSTERIOR_BATCH_WS, read per call)
+
+
+def posterior_batch_chunks(G, rows, cols, S):
+    """How the batched posterior calls issue G configurations when they allocate their own workspace: the configurations per
+    launch, as few launches as fit CRW_POSTERIOR_BATCH_WS bytes (default 2 GiB) of workspace, at least one configuration each."""
+    one = labelmap_posterior_workspace(rows, cols, S)
+    text = os.environ.get("CRW_POSTERIOR_BATCH_WS", str(POSTERIOR_BATCH_WS))
+    try:
+        cap = int(text)
+    except ValueError:
+        cap = 0
+    if cap < 1:
+        raise ValueError(f"CRW_POSTERIOR_BATCH_WS must be a positive number of bytes (got {text!r})")
+    per = min(int(G), max(1, cap // one)) if one else int(G)
+    return [min(per, int(G) - g) for g in range(0, int(G), per)]
+
+
+def _hz_window(out_hz, lead, S, cols, device):
+    """out_hz [*lead, 3, S-1, cols]: contiguous, or the column window hz[..., a:b] of a wider tensor -> (pitch between its rows,
+    elements between configurations)."""
+    shape = (*lead, 3, S - 1, cols)
+    if tuple(out_hz.shape) != shape or out_hz.dtype != torch.float32 or out_hz.device != device:
+        raise ValueError(f"out_hz must be float32 {list(shape)} on {device} (got {out_hz.dtype} {tuple(out_hz.shape)} on {out_hz.device})")
+    hz_ld = out_hz.stride(-2) if S > 2 else (out_hz.stride(-3) if out_hz.stride(-3) >= cols else cols)
+    if (cols > 1 and out_hz.stride(-1) != 1) or hz_ld < cols or out_hz.stride(-3) != (S - 1) * hz_ld:
+        raise ValueError(f"out_hz must be a {list(shape)} tensor or the column window hz[..., a:b] of a wider one (stride {out_hz.stride()})")
+    hz_stride = out_hz.stride(0) if lead and lead[0] > 1 else 3 * (S - 1) * hz_ld
+    if hz_stride < 3 * (S - 1) * hz_ld:
+        raise ValueError(f"out_hz: configurations overlap (stride {out_hz.stride()})")
+    return hz_ld, hz_stride
+
+
+def _posterior(sources, G, N, M, rows, cols, order, labels, confidence, floor, out, out_hz, workspace):
+    """The four posterior functions behind their signatures; sources as for `_labelmap`.  G None: one map, no leading axis,
+    otherwise the `_batch` form."""
     joint = len(sources) == 2
     N, M, rows, cols = int(N), int(M), int(rows), int(cols)
+    lead = () if G is None else (int(G),)
+    if lead and not 1 <= lead[0] <= 65535:
+        raise ValueError(f"G must be in 1 ... 65535 (got {lead[0]})")
     if not 2 <= M <= 16:
         raise ValueError(f"M must be in 2 ... 16 (got {M})")
     order = check_order(order, M)
@@ -1198,47 +1251,70 @@ def _posterior(sources, N, M, rows, cols, order, labels, confidence, floor, out,
     if N < 1 or not 1 <= rows <= DENSE_MAX_SIDE or not 1 <= cols <= DENSE_MAX_SIDE:
         raise ValueError(f"need T, N >= 1 and 1 <= rows, cols <= 2^22 (got T={sources[0][1]}, N={N}, rows={rows}, cols={cols})")
     device = sources[0][0].device
-    sources = [_source(src, (), N, M, cols, device, joint) for src in sources]
+    sources = [_source(src, lead, N, M, cols, device, joint) for src in sources]
     if labels.dtype not in (torch.float32, torch.int8):
         raise ValueError(f"labels must be torch.float32 or torch.int8 (got {labels.dtype})")
-    ld, _ = _window(labels, "labels", (), rows, cols, labels.dtype, device)
-    if out is None:  # the labels' pitch, which the window of `post` shares
-        out = torch.empty((rows - 1) * ld + cols, dtype=torch.float32, device=device).as_strided((rows, cols), (ld, 1))
-    if _window(out, "out", (), rows, cols, torch.float32, device)[0] != ld and rows > 1:
+    ld, map_stride = _window(labels, "labels", lead, rows, cols, labels.dtype, device)
+    if out is None:  # the labels' pitch (and map stride), which the window of `post` shares
+        span = (rows - 1) * ld + cols
+        out = torch.empty(((lead[0] - 1) * map_stride if lead else 0) + span, dtype=torch.float32, device=device)
+        out = out.as_strided((*lead, rows, cols), (*((map_stride,) if lead else ()), ld, 1))
+    old, ostride = _window(out, "out", lead, rows, cols, torch.float32, device)
+    if old != ld and rows > 1:
         raise ValueError(f"labels and out must share one pitch (got {labels.stride(-2)} and {out.stride(-2)})")
+    if ostride != map_stride:  # (equal by construction for one map)
+        raise ValueError(f"labels and out must share one map stride (got {labels.stride(0)} and {out.stride(0)})")
     if out_hz is None:
-        out_hz = torch.empty(3, S - 1, cols, dtype=torch.float32, device=device)
-    if tuple(out_hz.shape) != (3, S - 1, cols) or out_hz.dtype != torch.float32 or out_hz.device != device:
-        raise ValueError(f"out_hz must be float32 {[3, S - 1, cols]} on {device} (got {out_hz.dtype} {tuple(out_hz.shape)} on {out_hz.device})")
-    hz_ld = out_hz.stride(1) if S > 2 else (out_hz.stride(0) if out_hz.stride(0) >= cols else cols)
-    if (cols > 1 and out_hz.stride(2) != 1) or hz_ld < cols or out_hz.stride(0) != (S - 1) * hz_ld:
-        raise ValueError(f"out_hz must be a [3, S-1, cols] tensor or the column window hz[:, :, a:b] of a wider one (stride {out_hz.stride()})")
+        out_hz = torch.empty(*lead, 3, S - 1, cols, dtype=torch.float32, device=device)
+    hz_ld, hz_stride = _hz_window(out_hz, lead, S, cols, device)
     if device.type != "cuda":
-        if joint:
-            vs = [_interpolated(L, T, N, M, rows, width, flip)[:, col0:col0 + cols] for L, T, width, col0, flip in sources]
-            confs = [_interpolated_confidence(v, confidence) for v in vs]
-            v = torch.where((confs[1] > confs[0])[:, :, None], vs[1], vs[0])  # `_labelmap_joint_cpu`'s selection
-        else:
-            L, T, _, _, flip = sources[0]
-            v = _interpolated(L, T, N, M, rows, cols, flip)
-        post, hz = _ordered_posterior(v, order, labels, floor)
-        out.copy_(post), out_hz.copy_(hz)
+        posts, hzs, labs = (out, out_hz, labels) if lead else (out[None], out_hz[None], labels[None])
+        for g in range(lead[0] if lead else 1):
+            slices = [(L.view(-1, T * N, M)[g], T, width, col0, flip) for L, T, width, col0, flip in sources]
+            if joint:
+                vs = [_interpolated(L, T, N, M, rows, width, flip)[:, col0:col0 + cols] for L, T, width, col0, flip in slices]
+                confs = [_interpolated_confidence(v, confidence) for v in vs]
+                v = torch.where((confs[1] > confs[0])[:, :, None], vs[1], vs[0])  # `_labelmap_joint_cpu`'s selection
+            else:
+                L, T, _, _, flip = slices[0]
+                v = _interpolated(L, T, N, M, rows, cols, flip)
+            post, hz = _ordered_posterior(v, order, labs[g], floor)
+            posts[g].copy_(post), hzs[g].copy_(hz)
         return out, out_hz
-    clib = _posterior_lib()
-    need = clib.crw_labelmap_posterior_workspace(rows, cols, S)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=device)
-    elif workspace.device != device or not workspace.is_contiguous():
+    clib = _posterior_batch_lib() if lead else _posterior_lib()
+    if workspace is not None and (workspace.device != device or not workspace.is_contiguous()):
         raise ValueError(f"workspace must be a contiguous tensor on {device} (got {workspace.device})")
     decode = ((ctypes.c_int * S)(*order), S)
-    tail = (floor, _ptr(labels), _dt(labels), ld, _ptr(out), _ptr(out_hz), hz_ld, _ptr(workspace),
-            workspace.numel() * workspace.element_size(), _stream())
-    if joint:
-        both = [v for Lk, Tk, width, col0, flipk in sources for v in (_ptr(Lk), Tk, width, col0, int(flipk))]
-        _check(clib.crw_labelmap_ordered_joint_posterior(*both, N, M, rows, cols, *decode, code, *tail), "crw_labelmap_ordered_joint_posterior")
-    else:
-        L, T, _, _, flip = sources[0]
-        _check(clib.crw_labelmap_ordered_posterior(_ptr(L), T, N, M, rows, cols, int(flip), *decode, *tail), "crw_labelmap_ordered_posterior")
+    if not lead:
+        if workspace is None:
+            workspace = torch.empty(clib.crw_labelmap_posterior_workspace(rows, cols, S), dtype=torch.uint8, device=device)
+        tail = (floor, _ptr(labels), _dt(labels), ld, _ptr(out), _ptr(out_hz), hz_ld, _ptr(workspace),
+                workspace.numel() * workspace.element_size(), _stream())
+        if joint:
+            both = [v for Lk, Tk, width, col0, flipk in sources for v in (_ptr(Lk), Tk, width, col0, int(flipk))]
+            _check(clib.crw_labelmap_ordered_joint_posterior(*both, N, M, rows, cols, *decode, code, *tail), "crw_labelmap_ordered_joint_posterior")
+        else:
+            L, T, _, _, flip = sources[0]
+            _check(clib.crw_labelmap_ordered_posterior(_ptr(L), T, N, M, rows, cols, int(flip), *decode, *tail), "crw_labelmap_ordered_posterior")
+        return out, out_hz
+    # the G configurations: one launch over the caller's workspace, or as few as fit CRW_POSTERIOR_BATCH_WS bytes of our own
+    chunks = [lead[0]] if workspace is not None else posterior_batch_chunks(lead[0], rows, cols, S)
+    if workspace is None:
+        workspace = torch.empty(clib.crw_labelmap_posterior_workspace_batch(chunks[0], rows, cols, S), dtype=torch.uint8, device=device)
+    g0 = 0
+    for n in chunks:  # (a slice of n configurations is the batch call on the operands' slices: the strides stay)
+        sl = slice(g0, g0 + n)
+        tail = (floor, _ptr(labels[sl]), _dt(labels), ld, map_stride, _ptr(out[sl]), _ptr(out_hz[sl]), hz_ld, hz_stride, _ptr(workspace),
+                workspace.numel() * workspace.element_size(), _stream())
+        if joint:
+            both = [v for Lk, Tk, width, col0, flipk in sources for v in (_ptr(Lk.view(lead[0], -1)[sl]), Tk, width, col0, int(flipk))]
+            _check(clib.crw_labelmap_ordered_joint_posterior_batch(*both, n, N, M, rows, cols, *decode, code, *tail),
+                   "crw_labelmap_ordered_joint_posterior_batch")
+        else:
+            L, T, _, _, flip = sources[0]
+            _check(clib.crw_labelmap_ordered_posterior_batch(_ptr(L.view(lead[0], -1)[sl]), n, T, N, M, rows, cols, int(flip), *decode, *tail),
+                   "crw_labelmap_ordered_posterior_batch")
+        g0 += n
     return out, out_hz
 
 
@@ -1256,7 +1332,7 @@ def labelmap_ordered_posterior(L, T, N, M, rows, cols, order, labels, *, flip=Fa
     (default: allocated per call).  Device tensors: one launch of crw_labelmap_ordered_posterior (a normalised forward-backward in
     fp32, include/crw_hip.h), nothing synchronises; CPU tensors: the same recurrences in torch on the CPU route's interpolated
     values."""
-    return _posterior([(L, T, cols, 0, flip)], N, M, rows, cols, order, labels, None, floor, out, out_hz, workspace)
+    return _posterior([(L, T, cols, 0, flip)], None, N, M, rows, cols, order, labels, None, floor, out, out_hz, workspace)
 
 
 def labelmap_ordered_joint_posterior(a, b, N, M, rows, ncols, order, labels, *, confidence, floor=POSTERIOR_FLOOR, out=None,
@@ -1264,7 +1340,29 @@ def labelmap_ordered_joint_posterior(a, b, N, M, rows, ncols, order, labels, *, 
     """`labelmap_ordered_posterior` over the evidence `labelmap_ordered_joint` decodes: per pixel the interpolated row of the surer
     of the two sources a, b (each (L, T, cols, col0, flip); `confidence`: the kind, mandatory) -> (post [rows, ncols], hz
     [3, S-1, ncols]).  With both sources the same tensor and geometry it equals `labelmap_ordered_posterior` bit for bit."""
-    return _posterior([a, b], N, M, rows, ncols, order, labels, confidence, floor, out, out_hz, workspace)
+    return _posterior([a, b], None, N, M, rows, ncols, order, labels, confidence, floor, out, out_hz, workspace)
+
+
+def labelmap_ordered_posterior_batch(L, G, T, N, M, rows, cols, order, labels, *, flip=False, floor=POSTERIOR_FLOOR, out=None, out_hz=None,
+                                     workspace=None):
+    """`labelmap_ordered_posterior` for the G configurations of a sweep's pass at once (one order, one floor, one geometry): L
+    [G, T*N, M], labels [G, rows, cols] (int8 as `labelmap_ordered_batch` writes them, or float32; they may be the column windows
+    ``maps[:, :, a:b]`` of wider maps) -> (post float32 [G, rows, cols], hz float32 [G, 3, S-1, cols]); slice g is
+    `labelmap_ordered_posterior(L[g], ..., labels[g])` bit for bit.  out shares the labels' pitch and map stride; out_hz may be the
+    window ``hz[:, :, :, a:b]`` of a [G, 3, S-1, width] tensor.  workspace: at least `labelmap_posterior_workspace_batch(G, rows,
+    cols, S)` bytes, then ONE launch of crw_labelmap_ordered_posterior_batch (the configuration is a grid dimension of the one-map
+    kernel).  Without it the call allocates at most CRW_POSTERIOR_BATCH_WS bytes (read per call, default 2 GiB; a sweep's window of
+    410 x 3200 x 4 is 21 MB per configuration) and issues the configurations in as few launches as fit (`posterior_batch_chunks`),
+    at least one configuration each; the outputs do not depend on the split.  CPU tensors: a loop of the one-map CPU route."""
+    return _posterior([(L, T, cols, 0, flip)], G, N, M, rows, cols, order, labels, None, floor, out, out_hz, workspace)
+
+
+def labelmap_ordered_joint_posterior_batch(a, b, G, N, M, rows, ncols, order, labels, *, confidence, floor=POSTERIOR_FLOOR, out=None,
+                                           out_hz=None, workspace=None):
+    """`labelmap_ordered_joint_posterior` for the G configurations of a sweep at once: each source's L is [G, T*N, M], labels
+    [G, rows, ncols] -> (post [G, rows, ncols], hz [G, 3, S-1, ncols]); slice g is the one-map call on the sources' slices g, bit
+    for bit.  out / out_hz / workspace and the split over launches: as for `labelmap_ordered_posterior_batch`."""
+    return _posterior([a, b], G, N, M, rows, ncols, order, labels, confidence, floor, out, out_hz, workspace)
 
 
 def _ordered_posterior(v, order, labels, floor):

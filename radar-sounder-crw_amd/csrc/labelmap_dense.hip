@@ -24,7 +24,8 @@
 // dense_pixel of this file; their own text starts at "ordered label maps".  crw_labelmap_ordered_joint[_batch] (the end of the file)
 // are that decode over the interpolated rows of TWO passes, per pixel the surer one's: "joint ordered label maps".
 // crw_labelmap_ordered_posterior / crw_labelmap_ordered_joint_posterior (after those) are the posterior over the monotone paths that
-// the order defines, on the same evidence: per-pixel confidence of a decoded map and per-column error bars of its horizons.
+// the order defines, on the same evidence: per-pixel confidence of a decoded map and per-column error bars of its horizons; their
+// _batch forms serve the G configurations of a sweep in one launch of the same kernel.
 #include <cstdlib>
 #include <type_traits>
 
@@ -792,17 +793,19 @@ extern "C" int crw_labelmap_ordered_joint(const float *La, int Ta, int cols_a, i
 // up to 64] -- a wave's store of one state is one 256-byte segment.  Backward scan: the runs of rows bottom to top, f recomputed, b
 // carried, A read back one row ahead of its use (the load is issued before the row's stores), gamma formed, post stored, the 2 (S-1)
 // moments accumulated.  The picks b^_k come from one pass over the column's labels before the scans.  A lane reads only what it
-// wrote: whatever the workspace held before is never read.
+// wrote: whatever the workspace held before is never read.  The _batch entry points are the same kernel with the configuration
+// as blockIdx.y (a sweep's window is 50 waves, its G = 60 configurations 3000): slice g of L, of the label / post maps, of hz and
+// of the workspace; the one-map entry points are G = 1 of the same launcher.
 namespace crw {
 namespace {
 
 struct PosteriorArgs {
   JointArgs j;     // j.o.d: the window; d.lab the labels (READ), d.conf / o.ws / o.back unused; j.b unused by the single call
   float floor;
-  float *post;     // [rows] x [cols] window, pitch d.ld; may be null
-  float *hz;       // [3][S-1] rows of cols values, pitch hz_ld; may be null
-  size_t hz_ld;
-  float *alpha;    // [rows][S][a_ld]
+  float *post;     // configuration 0's [rows] x [cols] window, pitch d.ld, d.map_stride between configurations; may be null
+  float *hz;       // configuration 0's [3][S-1] rows of cols values, pitch hz_ld; may be null
+  size_t hz_ld, hz_stride;  // hz_stride: between configurations
+  float *alpha;    // [G][rows][S][a_ld]
   size_t a_ld;     // cols rounded up to a multiple of 64
 };
 
@@ -916,7 +919,7 @@ __global__ __launch_bounds__(WAVE) void labelmap_posterior_kernel(PosteriorArgs 
   const DenseArgs &d = o.d;
   const int M = d.M, N = d.N, S = o.S, rows = d.rows;
   __builtin_assume(M <= MCAP && S <= M && S >= 2);
-  const int lane = threadIdx.x;
+  const int lane = threadIdx.x, g = blockIdx.y;  // the configuration is a grid dimension, as in labelmap_ordered_kernel
   const long x = (long)blockIdx.x * WAVE + lane;
   // A lane behind the window's last column runs both scans on that last column: it keeps its own workspace slots (the workspace
   // is 64 columns wide per wave) and stores post where that column's lane stores it, the same bits.  So EXEC is full from the first
@@ -927,12 +930,12 @@ __global__ __launch_bounds__(WAVE) void labelmap_posterior_kernel(PosteriorArgs 
   // in a 1-column window).
   const bool live = x < d.cols;
   const long xc = live ? x : d.cols - 1;
-  const LAB *__restrict__ lab = static_cast<const LAB *>(d.lab) + xc;
-  float *__restrict__ post = a.post ? a.post + xc : nullptr;
-  float *__restrict__ ws = a.alpha + x;  // x < a_ld
   const size_t a_ld = a.a_ld, a_row = (size_t)S * a_ld;
-  const JointColumn ka = joint_column(a.j.a, 0, xc, true, N, M);
-  const JointColumn kb = KIND >= 0 ? joint_column(a.j.b, 0, xc, true, N, M) : ka;
+  const LAB *__restrict__ lab = static_cast<const LAB *>(d.lab) + (size_t)g * d.map_stride + xc;
+  float *__restrict__ post = a.post ? a.post + (size_t)g * d.map_stride + xc : nullptr;
+  float *__restrict__ ws = a.alpha + (size_t)g * rows * a_row + x;  // x < a_ld
+  const JointColumn ka = joint_column(a.j.a, g, xc, true, N, M);
+  const JointColumn kb = KIND >= 0 ? joint_column(a.j.b, g, xc, true, N, M) : ka;
   PosteriorSides<KIND, MCAP> sides;
   float f[MCAP];
 
@@ -1020,7 +1023,7 @@ __global__ __launch_bounds__(WAVE) void labelmap_posterior_kernel(PosteriorArgs 
 
   if (live && a.hz) {  // gamma is row 0's: P(B_k = 0) = sum_{s >= k} gamma[0][s], which closes the second moment
 #pragma clang fp contract(off)
-    float *hz = a.hz + x;
+    float *hz = a.hz + (size_t)g * a.hz_stride + x;
     const size_t plane = (size_t)(S - 1) * a.hz_ld;
     float above = 0.f;
 #pragma unroll
@@ -1041,18 +1044,32 @@ size_t posterior_ws_bytes(int rows, int cols, int S) {
   return (size_t)rows * S * ordered_ws_ld(cols) * sizeof(float);
 }
 
-// Both entry points behind their signatures (Lb null: the single call, conf_kind -1).  The checks are the decode's -- dense_args' on
-// the window, each source's, the order's -- then the posterior's own; nothing is launched unless all pass.
+// G slices of `each` elements of `size` bytes: false when their extent in bytes does not fit a size_t.
+bool slices_fit(int G, size_t each, size_t size) { return each <= SIZE_MAX / size / (size_t)G; }
+
+// What the one-map calls pass for the strides between configurations: one map's rows, one [3][S-1] block of hz rows.
+size_t one_map(int rows, size_t ld) { return (size_t)(rows > 0 ? rows : 1) * ld; }
+size_t one_hz(int S, size_t hz_ld) { return 3 * (size_t)(S > 1 ? S - 1 : 1) * hz_ld; }
+
+size_t posterior_ws_bytes_batch(int G, int rows, int cols, int S) {
+  const size_t one = posterior_ws_bytes(rows, cols, S);
+  if (G < 1 || !one || !slices_fit(G, one, 1)) return 0;
+  return (size_t)G * one;
+}
+
+// The four entry points behind their signatures (Lb null: the single calls, conf_kind -1; G = 1 with one map's extent as
+// map_stride: the one-map calls).  The checks are the decode's -- dense_args' on the G windows, each source's, the order's -- then
+// the posterior's own; nothing is launched unless all pass.
 int posterior_launch(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb, int Tb, int cols_b, int col0_b,
-                     int flip_b, int N, int M, int rows, int ncols, const int *order, int S, int conf_kind, float floor,
-                     const void *labels, int label_dtype, size_t ld, float *post, float *hz, size_t hz_ld, void *ws, size_t ws_bytes,
-                     crw_stream_t stream) {
+                     int flip_b, int G, int N, int M, int rows, int ncols, const int *order, int S, int conf_kind, float floor,
+                     const void *labels, int label_dtype, size_t ld, size_t map_stride, float *post, float *hz, size_t hz_ld,
+                     size_t hz_stride, void *ws, size_t ws_bytes, crw_stream_t stream) {
   clear_stale_error();
   PosteriorArgs a;
   const bool joint = conf_kind >= 0;
   if (conf_kind < -1 || conf_kind > CRW_CONF_ENTROPY) return CRW_EINVAL;
-  if (const int st = dense_args(La, 1, Ta, N, M, rows, ncols, flip_a, -1, const_cast<void *>(labels), label_dtype, nullptr, ld,
-                                (size_t)(rows > 0 ? rows : 1) * ld, 1, a.j.o.d))
+  if (const int st = dense_args(La, G, Ta, N, M, rows, ncols, flip_a, -1, const_cast<void *>(labels), label_dtype, nullptr, ld,
+                                map_stride, 1, a.j.o.d))
     return st;
   if (const int st = joint_source(La, Ta, cols_a, col0_a, flip_a, N, M, ncols, a.j.a)) return st;
   a.j.b = a.j.a;
@@ -1062,11 +1079,18 @@ int posterior_launch(const float *La, int Ta, int cols_a, int col0_a, int flip_a
   if (!(floor >= 0x1p-20f && floor <= 0.25f)) return CRW_EINVAL;  // (a NaN fails both)
   if ((!post && !hz) || ((uintptr_t)post & 3) || ((uintptr_t)hz & 3) || (hz && hz_ld < (size_t)ncols) || !ws || ((uintptr_t)ws & 3))
     return CRW_EINVAL;
-  if (ws_bytes < posterior_ws_bytes(rows, ncols, S)) return CRW_EWORKSPACE;
+  // the G slices: hz's hold their [3][S-1] rows, and no slice's address wraps round
+  if (hz && (!slices_fit(3 * (S - 1), hz_ld, sizeof(float)) || hz_stride < 3 * (size_t)(S - 1) * hz_ld)) return CRW_EINVAL;
+  if (!slices_fit(G, map_stride, sizeof(float)) || !slices_fit(G, hz ? hz_stride : 1, sizeof(float)) ||
+      !slices_fit(G, a.j.a.l_stride, sizeof(float)) || !slices_fit(G, a.j.b.l_stride, sizeof(float)))
+    return CRW_EINVAL;
+  const size_t need = posterior_ws_bytes_batch(G, rows, ncols, S);
+  if (!need) return CRW_EINVAL;
+  if (ws_bytes < need) return CRW_EWORKSPACE;
   a.j.o.ws = nullptr, a.j.o.ws_ld = 0, a.j.o.back = 0;
-  a.floor = floor, a.post = post, a.hz = hz, a.hz_ld = hz_ld;
+  a.floor = floor, a.post = post, a.hz = hz, a.hz_ld = hz_ld, a.hz_stride = hz_stride;
   a.alpha = static_cast<float *>(ws), a.a_ld = ordered_ws_ld(ncols);
-  const dim3 grid((unsigned)(a.a_ld / WAVE));
+  const dim3 grid((unsigned)(a.a_ld / WAVE), (unsigned)G);
   const auto kernel = kernel_for(label_dtype, conf_kind, M, [](auto lab, auto kind, auto mcap) {
     return labelmap_posterior_kernel<decltype(lab), kind(), mcap()>;
   });
@@ -1082,8 +1106,20 @@ extern "C" size_t crw_labelmap_posterior_workspace(int rows, int cols, int S) { 
 extern "C" int crw_labelmap_ordered_posterior(const float *L, int T, int N, int M, int rows, int cols, int flip, const int *order,
                                               int S, float floor, const void *labels, int label_dtype, size_t ld, float *post,
                                               float *hz, size_t hz_ld, void *ws, size_t ws_bytes, crw_stream_t stream) {
-  return crw::posterior_launch(L, T, cols, 0, flip, nullptr, 0, 0, 0, 0, N, M, rows, cols, order, S, -1, floor, labels, label_dtype, ld,
-                               post, hz, hz_ld, ws, ws_bytes, stream);
+  return crw::posterior_launch(L, T, cols, 0, flip, nullptr, 0, 0, 0, 0, 1, N, M, rows, cols, order, S, -1, floor, labels, label_dtype, ld,
+                               crw::one_map(rows, ld), post, hz, hz_ld, crw::one_hz(S, hz_ld), ws, ws_bytes, stream);
+}
+
+extern "C" size_t crw_labelmap_posterior_workspace_batch(int G, int rows, int cols, int S) {
+  return crw::posterior_ws_bytes_batch(G, rows, cols, S);
+}
+
+extern "C" int crw_labelmap_ordered_posterior_batch(const float *L, int G, int T, int N, int M, int rows, int cols, int flip,
+                                                    const int *order, int S, float floor, const void *labels, int label_dtype,
+                                                    size_t ld, size_t map_stride, float *post, float *hz, size_t hz_ld,
+                                                    size_t hz_stride, void *ws, size_t ws_bytes, crw_stream_t stream) {
+  return crw::posterior_launch(L, T, cols, 0, flip, nullptr, 0, 0, 0, 0, G, N, M, rows, cols, order, S, -1, floor, labels, label_dtype, ld,
+                               map_stride, post, hz, hz_ld, hz_stride, ws, ws_bytes, stream);
 }
 
 extern "C" int crw_labelmap_ordered_joint_posterior(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb,
@@ -1092,6 +1128,18 @@ extern "C" int crw_labelmap_ordered_joint_posterior(const float *La, int Ta, int
                                                     int label_dtype, size_t ld, float *post, float *hz, size_t hz_ld, void *ws,
                                                     size_t ws_bytes, crw_stream_t stream) {
   if (conf_kind < 0) return CRW_EINVAL;  // mandatory, as for crw_labelmap_ordered_joint
-  return crw::posterior_launch(La, Ta, cols_a, col0_a, flip_a, Lb, Tb, cols_b, col0_b, flip_b, N, M, rows, ncols, order, S, conf_kind,
-                               floor, labels, label_dtype, ld, post, hz, hz_ld, ws, ws_bytes, stream);
+  return crw::posterior_launch(La, Ta, cols_a, col0_a, flip_a, Lb, Tb, cols_b, col0_b, flip_b, 1, N, M, rows, ncols, order, S, conf_kind,
+                               floor, labels, label_dtype, ld, crw::one_map(rows, ld), post, hz, hz_ld, crw::one_hz(S, hz_ld), ws,
+                               ws_bytes, stream);
+}
+
+extern "C" int crw_labelmap_ordered_joint_posterior_batch(const float *La, int Ta, int cols_a, int col0_a, int flip_a, const float *Lb,
+                                                          int Tb, int cols_b, int col0_b, int flip_b, int G, int N, int M, int rows,
+                                                          int ncols, const int *order, int S, int conf_kind, float floor,
+                                                          const void *labels, int label_dtype, size_t ld, size_t map_stride,
+                                                          float *post, float *hz, size_t hz_ld, size_t hz_stride, void *ws,
+                                                          size_t ws_bytes, crw_stream_t stream) {
+  if (conf_kind < 0) return CRW_EINVAL;  // mandatory, as for crw_labelmap_ordered_joint_batch
+  return crw::posterior_launch(La, Ta, cols_a, col0_a, flip_a, Lb, Tb, cols_b, col0_b, flip_b, G, N, M, rows, ncols, order, S, conf_kind,
+                               floor, labels, label_dtype, ld, map_stride, post, hz, hz_ld, hz_stride, ws, ws_bytes, stream);
 }

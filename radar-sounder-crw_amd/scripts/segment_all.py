@@ -129,7 +129,7 @@ POSTERIOR_FLAGS = ('posterior', 'floor', 'save_posterior')
 
 def check_posterior_flags(args):
     """The flags around ``--posterior``."""
-    if (args.save_posterior or args.floor is not None) and not args.posterior:
+    if (getattr(args, 'save_posterior', False) or args.floor is not None) and not args.posterior:  # (segment_sweep.py has no --save_posterior)
         raise SystemExit('--floor and --save_posterior need --posterior')
     if not args.posterior:
         return args

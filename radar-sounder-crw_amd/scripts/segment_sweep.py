@@ -22,7 +22,15 @@ calibration table follows its matrix, ``--report_json`` gains a ``calibration`` 
 takes ``ece`` and ``aurc`` -- lower is better: the smallest wins, ties go to the first in the grid's order, a NaN never wins
 unless every score is NaN.  ``--horizons`` (with ``--min_run N``, default 3, and ``--tol ROWS``, default 2): every configuration's
 line gains the mean top MAE of its horizons (``inference.horizons_sweep``; rows), ``--report_json`` a ``horizons`` entry per
-configuration, and ``--select`` also takes ``horizon_mae`` (offered only with ``--horizons``) -- the lowest wins, by the same rules.  Without these flags the script prints and writes what it did before them.
+configuration, and ``--select`` also takes ``horizon_mae`` (offered only with ``--horizons``) -- the lowest wins, by the same rules.
+``--posterior`` (with ``--decode ordered``; with ``--use_last`` also ``--merge ordered``; ``--floor X``, default 1e-4): the ordered
+decode's own confidence for all configurations at once (``inference.segment_sweep(..., posterior=True)``).  Every configuration's
+line gains the ECE of its posterior map and its mean bar coverage (``inference.horizon_bars_sweep``: the share of columns whose
+reference boundary lies within 2 bars + 1 row of the pick, averaged over the boundaries); the best configuration's posterior
+calibration table and error-bar table follow its other tables, as ``segment_all.py --posterior`` prints them; ``--report_json``
+gains a ``posterior`` entry per configuration and ``floor``; and ``--select`` also takes ``post_ece`` and ``post_aurc`` (offered
+only with ``--posterior``) -- the lowest wins, by the same rules.  Without these flags the script prints and writes what it did
+before them.
 CRW_SWEEP_PER_CONFIG=1: the label propagation as a loop over the configurations (same maps; the A/B arm)."""
 import argparse
 import json
@@ -48,11 +56,14 @@ SELECT = {'macro_f1': lambda r: r.macro['f1'], 'weighted_f1': lambda r: r.weight
 SELECT_CAL = {'ece': lambda c: c.ece, 'aurc': lambda c: c.aurc}
 # score of the horizons (``--horizons``): lower is better
 SELECT_HORIZON = {'horizon_mae': lambda h: h.mean_mae('top')}
+# scores of the posterior map's calibration (``--posterior``): lower is better
+SELECT_POST = {'post_ece': lambda c: c.ece, 'post_aurc': lambda c: c.aurc}
+POSTERIOR_FLAGS = ('posterior', 'floor')
 
 
-def get_args_parser(horizons=False):
+def get_args_parser(horizons=False, posterior=False):
     """``horizons``: whether ``--horizons`` is on the command line -- only then is there a horizon score to select by, and only
-    then does ``--select`` offer ``horizon_mae``."""
+    then does ``--select`` offer ``horizon_mae``.  ``posterior``: likewise for ``--posterior`` and ``post_ece`` / ``post_aurc``."""
     p = argparse.ArgumentParser('CRW label-propagation sweep (launch_test_batch.sh over test_all.py)', add_help=True)
     p.add_argument('--model', default=None, type=int, help='0=CNN,1=Resnet18')
     p.add_argument('--dataset', default=None, type=int, help='0=MCORDS1,1=Miguel,3=SHARAD')
@@ -77,9 +88,10 @@ def get_args_parser(horizons=False):
     p.add_argument('--seg_path', default=None, help='reference segmentation .pt file')
     p.add_argument('--unc_seg_path', default=None, help="dataset 0's map with the uncertain class 4 (the reference's dataset id 2)")
     p.add_argument('--synthetic', default=None, nargs=2, type=int, metavar=('H', 'W'))
-    p.add_argument('--select', default='macro_f1', choices=sorted(SELECT) + sorted(SELECT_CAL) + (sorted(SELECT_HORIZON) if horizons else []),
+    p.add_argument('--select', default='macro_f1', choices=sorted(SELECT) + sorted(SELECT_CAL) + (sorted(SELECT_HORIZON) if horizons else [])
+                   + (sorted(SELECT_POST) if posterior else []),
                    help='the score the best configuration is picked by (ece, aurc: the lowest, need --confidence; horizon_mae: the '
-                        'lowest, needs --horizons)')
+                        'lowest, needs --horizons; post_ece, post_aurc: the lowest, need --posterior)')
     p.add_argument('--reports', action='store_true', help='print the full report of every configuration')
     p.add_argument('--report_json', default=None, metavar='FILE')
     p.add_argument('--save_maps', action='store_true', help='save every predicted_map_r{r}_t{t}_k{k}.pt (int8)')
@@ -98,6 +110,10 @@ def get_args_parser(horizons=False):
     p.add_argument('--horizons', action='store_true', help="the mean top MAE of every configuration's horizons (a column)")
     p.add_argument('--min_run', default=3, type=int, metavar='N', help='shortest run of equal labels down a column that is a layer')
     p.add_argument('--tol', default=2, type=int, metavar='ROWS', help='a pick within this many rows counts as right')
+    p.add_argument('--posterior', action='store_true',
+                   help="the ordered decode's own confidence for every configuration: ECE of the posterior map and mean bar coverage "
+                        "(two columns; needs --decode ordered)")
+    p.add_argument('--floor', default=None, type=float, metavar='X', help='floor under the evidence of --posterior (2^-20 ... 0.25; 1e-4)')
     return p
 
 
@@ -113,7 +129,14 @@ def check_confidence_flags(args):
         raise SystemExit(f'--select {args.select} needs --horizons')
     if args.horizons and (args.min_run < 1 or args.tol < 0):
         raise SystemExit('--min_run is at least 1, --tol at least 0')
-    return segment_all.check_decode_flags(args)
+    return check_posterior_flags(segment_all.check_decode_flags(args))
+
+
+def check_posterior_flags(args):
+    """The flags around ``--posterior``: `segment_all.check_posterior_flags`' checks and messages, and the scores that need it."""
+    if not args.posterior and args.select in SELECT_POST:
+        raise SystemExit(f'--select {args.select} needs --posterior')
+    return segment_all.check_posterior_flags(args)
 
 
 def pick_best(scores, lower_is_better=False):
@@ -156,6 +179,8 @@ def main(args):
         hidden += ('context',)
     if args.decode == 'argmax':  # likewise
         hidden += ('decode', 'order')
+    if not args.posterior:  # likewise
+        hidden += POSTERIOR_FLAGS
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -175,7 +200,8 @@ def main(args):
                                   correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device,
                                   **(dict(confidence=args.confidence, merge=args.merge) if args.confidence else {}),
                                   **(dict(upsample=args.upsample) if args.upsample != 'nearest' else {}),
-                                  **(dict(decode=args.decode, order=args.order) if args.decode != 'argmax' else {}))
+                                  **(dict(decode=args.decode, order=args.order) if args.decode != 'argmax' else {}),
+                                  **(dict(posterior=True, floor=args.floor) if args.posterior else {}))
     if correction:
         print('Change point for each radargram:', out['change_idx'])
     final, forward = out['pred'], out['forward']
@@ -201,18 +227,28 @@ def main(args):
         hzs = inference.horizons_sweep(final, seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
                                        unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses,
                                        min_run=args.min_run, tol=args.tol)
+    pcals = bars = None
+    if args.posterior:
+        pcals = inference.calibration_sweep(final, out['post'], seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
+                                            unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses, bins=args.bins)
+        bars = inference.horizon_bars_sweep(out['horizon'], seg[:, :cols], out['order'])
     print('{:>6} {:>7} {:>4} {:>9} {:>9} {:>11} {:>9}'.format('radius', 'temp', 'knn', 'accuracy', 'macro f1', 'weighted f1', 'mean iou')
-          + (' {:>8} {:>8}'.format('ece', 'aurc') if cals else '') + (' {:>11}'.format('horizon mae') if hzs else ''))
+          + (' {:>8} {:>8}'.format('ece', 'aurc') if cals else '') + (' {:>11}'.format('horizon mae') if hzs else '')
+          + (' {:>8} {:>9}'.format('post ece', 'bar cover') if pcals else ''))
     for g, (cfg, r) in enumerate(zip(sweep.configs, reports)):
         print('{:>6} {:>7g} {:>4} {:>9.4f} {:>9.4f} {:>11.4f} {:>9.4f}'.format(cfg['RADIUS'], cfg['TEMP'], cfg['KNN'], r.accuracy,
                                                                                r.macro['f1'], r.weighted['f1'], r.mean_iou)
               + (' {:>8.4f} {:>8.4f}'.format(cals[g].ece, cals[g].aurc) if cals else '')
-              + (' {:>11.4f}'.format(hzs[g].mean_mae('top')) if hzs else ''))
+              + (' {:>11.4f}'.format(hzs[g].mean_mae('top')) if hzs else '')
+              + (' {:>8.4f} {:>9.4f}'.format(pcals[g].ece, bars[g].mean_coverage) if pcals else ''))
         if args.reports:
             print(r)
             print(r.matrix_str())
             print('')
-    if args.select in SELECT_HORIZON:
+    if args.select in SELECT_POST:
+        scores = [float(SELECT_POST[args.select](c)) for c in pcals]
+        best = pick_best(scores, lower_is_better=True)
+    elif args.select in SELECT_HORIZON:
         scores = [float(SELECT_HORIZON[args.select](h)) for h in hzs]
         best = pick_best(scores, lower_is_better=True)
     elif args.select in SELECT_CAL:
@@ -232,6 +268,11 @@ def main(args):
     if hzs:
         print('')
         print(hzs[best])
+    if pcals:
+        print('')
+        print(f'Calibration (posterior of the ordered decode, floor {args.floor:g}):')
+        print(pcals[best])
+        print(bars[best])
     t_all = time.time() - tim
     print('\nTime elapsed (inference + metrics):', t_all)
     if args.report_json:
@@ -248,6 +289,10 @@ def main(args):
         if hzs:
             for c, h in zip(d['configs'], hzs):
                 c['horizons'] = h.to_dict()
+        if pcals:
+            for c, cal, b in zip(d['configs'], pcals, bars):
+                c['posterior'] = dict(calibration=cal.to_dict(), horizon_bars=b.to_dict())
+            d['floor'] = args.floor
         if args.upsample != 'nearest':
             d['upsample'] = args.upsample
         if args.context != 'reference':
@@ -261,4 +306,4 @@ def main(args):
 
 if __name__ == '__main__':
     torch.manual_seed(11)  # the scripts seed at import (test_all.py:14)
-    main(get_args_parser(horizons='--horizons' in sys.argv[1:]).parse_args())
+    main(get_args_parser(horizons='--horizons' in sys.argv[1:], posterior='--posterior' in sys.argv[1:]).parse_args())
