@@ -36,6 +36,38 @@ def test_library_exports_every_declared_symbol():
     assert lib.crw_walk_state_bytes(1, 8, 200, 2) > lib.crw_walk_state_bytes(1, 8, 200, 1) > 0
 
 
+def test_every_device_entry_point_is_banded_or_windowed():
+    """Every entry point of include/crw_hip.h that takes a device pointer is in exactly one of the two tables of tests/stale_ref.py:
+    BANDED (-> the test file that runs it between guard bands) or WINDOWED_ELSEWHERE (the evaluation kernels -> the test that runs
+    them inside a wider, poisoned map).  The only other entry points are pure host queries -- no pointer among their parameters --
+    and the two whose pointers are host arrays.  Each named file exists and names the entry point (its C name, or the binding's
+    wrapper of that name), so that a table cannot claim what no test does; a new entry point fails here until it is covered."""
+    import stale_ref as sr
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "crw_hip.h")).read(), flags=re.S)
+    decls = dict(re.findall(r"\b(crw_[a-z0-9_]+)\s*\(([^()]*)\)", header))
+    assert len(decls) > 100 and "crw_walk_fwd" in decls and "crw_abi_version" in decls
+    tables = (set(sr.BANDED), set(sr.WINDOWED_ELSEWHERE), set(sr.HOST_ONLY), set(sr.HOST_POINTERS))
+    for i, a in enumerate(tables):
+        for b in tables[i + 1:]:
+            assert not a & b, ("listed twice", a & b)
+    listed = set().union(*tables)
+    assert listed == set(decls), ("not decided where it is covered", set(decls) - listed, "no such entry point", listed - set(decls))
+    for name, params in decls.items():
+        takes_pointer = "*" in params
+        if name in sr.HOST_ONLY:
+            assert not takes_pointer, (name, "takes a pointer: it is no pure host query")
+        elif name not in sr.HOST_POINTERS:
+            assert takes_pointer, (name, "takes no pointer: list it under HOST_ONLY")
+    assert set(sr.HOST_POINTERS) == {"crw_pelt_rbf", "crw_rn_timing_read"}      # host arrays by the header's own words; no third
+    for table, how in ((sr.BANDED, "run_banded"), (sr.WINDOWED_ELSEWHERE, None)):
+        for name, path in table.items():
+            text = open(os.path.join(ROOT, path)).read()
+            if how:
+                assert how in text and re.search(rf"\blib\.{name}\b", text), (name, path, "does not call it under run_banded")
+            else:
+                assert name in text or re.search(rf"\b{name[len('crw_'):]}\(", text), (name, path, "does not name it")
+
+
 def test_build_hook_with_and_without_a_prebuilt_library():
     """`__graft_entry__.build()` is the driver's "does it build" check: it must succeed on a tree that already holds the
     library and on one that does not (fresh clone: *.so is git-ignored), and the ABI number it checks is the header's."""
