@@ -442,45 +442,68 @@ def test_map_backward_kernels_match_torch(hip, split):
     torch.testing.assert_close(val(gh, gl), want_g, rtol=1e-5 if split == 3 else 1e-2, atol=1e-7 if split == 3 else 1e-4)
 
 
+_BASELINE_ITEM = {}
+
+
+def _baseline_item_and_free_reference():
+    """The P = 2016 item, its seeded weights and the free-running fp64 step on the device (PyTorch ops), computed once for the three
+    arithmetics of the test below and left unchanged: namespace(c, loss, A, emb, grads)."""
+    if not _BASELINE_ITEM:
+        import types
+        import encoder as crw_encoder
+        import dataset as crw_dataset
+        from test_cnn_forced_gpu import forced_reference
+        ds = crw_dataset.RGDataset.synthetic(512, 1024, 32, (16, 16), (8, 0), seed=11)
+        item = ds[1][None].contiguous()  # [1, 32, 63, 16, 16]
+        torch.manual_seed(11)
+        sd = {k: v.detach().clone() for k, v in crw_encoder.CNN(False).state_dict().items()}
+        c = types.SimpleNamespace(seq=item, sd=sd, tau=0.01, pe=False, is_map=False)
+        ref, grads = forced_reference(c, None)
+        _BASELINE_ITEM["ref"] = types.SimpleNamespace(c=c, loss=ref.loss.item(), A=ref.A.detach(), emb=ref.emb.detach(),
+                                                      grads={k: g.detach() for k, g in grads.items()})
+    return _BASELINE_ITEM["ref"]
+
+
 @pytest.mark.parametrize("convs", ["bf16x3", "mixed", "bf16"])
-def test_full_model_at_baseline_shape_vs_oracle(hip, convs):
+def test_full_model_at_baseline_shape_vs_oracle(hip, convs, monkeypatch):
     """One item of BASELINE configs[2] ([T,N] = [32,63], 16x16 patches, 2016 patches through the whole HIP conv
-    trunk + affinity + walk) against the CPU oracle.  Forward: loss within 1e-4 relative (the north_star tolerance)
-    in EVERY conv arithmetic ("mixed" runs the default's forward: the same loss and logits bit for bit).  Backward: "bf16x3" (hi/lo
-    pairs, the default) every parameter gradient within 2 % of its scale and > 0.9999 cosine; "mixed" (opt-in: the backward kernels
-    on the hi planes alone) within 2 % and > 0.9995; "bf16" (plain bf16 operands both ways, opt-in) within 5 % and > 0.999."""
-    import model as crw_model
-    import encoder as crw_encoder
-    import dataset as crw_dataset
-    from oracle import crw_oracle as orc
-    ds = crw_dataset.RGDataset.synthetic(512, 1024, 32, (16, 16), (8, 0), seed=11)
-    item = ds[1][None].contiguous()  # [1, 32, 63, 16, 16]
-    torch.manual_seed(11)
-    enc = crw_encoder.CNN(False)
-    enc.hip_convs = convs
-    sd = {k: v.detach().clone().requires_grad_(True) for k, v in enc.state_dict().items()}
-    torch.set_num_threads(min(16, len(os.sched_getaffinity(0))))
-    loss_ref, _, _ = orc.crw_forward_torch(item, sd, 0.01)
-    loss_ref.backward()
-    net = crw_model.CRW(enc, 0.01, False).cuda()
-    loss, A = net(item.cuda())
-    assert abs(loss.item() - loss_ref.item()) <= 1e-4 * abs(loss_ref.item())
-    loss.backward()
+    trunk + affinity + walk) against the oracle in fp64 (on the device, PyTorch ops).  Forward: loss within 1e-4 relative (the
+    north_star tolerance) in EVERY conv arithmetic ("mixed" runs the default's forward: the same loss and logits bit for bit), the
+    logits and the features within the arithmetic's bars of tests/cnn_forced_ref.py.  Backward, free-running reference: "bf16x3"
+    (hi/lo pairs, the default) every parameter gradient within 2 % of its scale and > 0.9999 cosine; "mixed" (opt-in: the backward
+    kernels on the hi planes alone) within 2 % and > 0.9995; "bf16" (plain bf16 operands both ways, opt-in) within 5 % and > 0.999.
+    Backward, reference forced with the device's own conv3..conv5 gates (tests/test_cnn_forced_gpu.py): dx3 and every entry of the
+    gradients of conv3..conv5 and fc within the same bars."""
+    import cnn_forced_ref as fr
+    from test_cnn_forced_gpu import BACKWARD, device_step, forced_reference, measure, report
+    free = _baseline_item_and_free_reference()
+    c = free.c
+    run, = device_step(hip, monkeypatch, c, convs)
+    loss, A = run.loss, run.A
+    assert abs(loss.item() - free.loss) <= 1e-4 * abs(free.loss)
+    fwd = {"A": float((A.double() - free.A).abs().max()) * c.tau, "features": fr.rel_err(run.feats, free.emb.reshape(run.feats.shape))}
+    report("P2016 free-running", convs, fwd, ("features", "A"))
+    for k, v in fwd.items():
+        assert v <= fr.bars_for(convs, "P2016")[k], (k, v)
     cos_min, rel_max = {"bf16x3": (0.9999, 2e-2), "mixed": (0.9995, 2e-2), "bf16": (0.999, 5e-2)}[convs]
     worst = (1.0, 0.0)
-    for k, p in enc.named_parameters():
-        r = sd[k].grad.double().flatten()
-        gq = p.grad.cpu().double().flatten()
+    for k, gq in run.grads.items():
+        r = free.grads[k].flatten()
+        gq = gq.double().flatten()
         cos = torch.dot(r, gq) / (r.norm() * gq.norm() + 1e-300)
         worst = (min(worst[0], cos.item()), max(worst[1], ((gq - r).abs().max() / r.abs().max()).item()))
         assert cos > cos_min, (k, cos.item())
         assert (gq - r).abs().max() <= rel_max * r.abs().max(), k
-    print(f"convs = {convs}: loss error {abs(loss.item() - loss_ref.item()) / abs(loss_ref.item()):.2e} relative; worst gradient cosine "
+    print(f"convs = {convs}: loss error {abs(loss.item() - free.loss) / abs(free.loss):.2e} relative; worst gradient cosine "
           f"{worst[0]:.6f}, worst max-entry error {worst[1]:.2e} of the gradient's scale")
+    ref, gref = forced_reference(c, run.rec.gates)
+    err = measure(c, run, ref, gref)
+    report("P2016 forced", convs, err, BACKWARD)
+    for k in BACKWARD:
+        assert err[k] <= fr.bars_for(convs, "P2016")[k], (k, err[k])
     if convs == "mixed":  # the forward is the default's
-        enc.hip_convs = "bf16x3"
-        loss2, A2 = net(item.cuda())
-        assert loss2.item() == loss.item() and torch.equal(A2, A)
+        run2, = device_step(hip, monkeypatch, c, "bf16x3")
+        assert run2.loss.item() == loss.item() and torch.equal(run2.A, A)
 
 
 @pytest.mark.parametrize("stride", [1, 2])
@@ -690,23 +713,20 @@ def _well_posed_front_inputs(P, cin, h, w, w1, b1, w2, b2, g):
     products); conv2 runs on bf16 hi/lo pairs (8-bit significands: |lo| <= 2^-9 |hi|, the lo.lo product is dropped and each lo is
     itself rounded: 3 * 2^-18 on the sum of absolute products) with fp32 accumulation (256 * 2^-24), plus conv1's error carried
     through.  Patches with an unsafe pool1 / ReLU1 decision are redrawn; dy is set to zero at the pooled outputs whose
-    pool2 / ReLU2 decision is unsafe, so that whichever way it goes moves nothing."""
+    pool2 / ReLU2 decision is unsafe, so that whichever way it goes moves nothing.  (The bounds themselves: tests/cnn_forced_ref.py,
+    which carries them on through conv3..conv5.)"""
     import torch.nn.functional as TF
+    from cnn_forced_ref import fp32_conv_bound, front_bounds
     w1, b1, w2, b2 = (t.detach() for t in (w1, b1, w2, b2))
     keep = []
     while sum(k.shape[0] for k in keep) < P:
         x = torch.randn(P, cin, h, w, generator=g)
         pre1 = TF.conv2d(x.double(), w1, b1, padding=1)
-        e1 = 64 * 2.0 ** -24 * (TF.conv2d(x.double().abs(), w1.abs(), b1.abs(), padding=1))
+        e1 = fp32_conv_bound(x.double().abs(), w1, b1, 64)
         keep.append(x[_pool_decisions_safe(pre1, e1).flatten(1).all(1)])
     x = torch.cat(keep)[:P]
-    xd = x.double()
-    e1 = 64 * 2.0 ** -24 * TF.conv2d(xd.abs(), w1.abs(), b1.abs(), padding=1)
-    a1 = TF.max_pool2d(TF.relu(TF.conv2d(xd, w1, b1, padding=1)), 2, 1)
-    pre2 = TF.conv2d(a1, w2, b2, padding=1)
-    e2 = (3 * 2.0 ** -18 + 256 * 2.0 ** -24) * TF.conv2d(a1, w2.abs(), b2.abs(), padding=1) + \
-        TF.conv2d(TF.max_pool2d(e1, 2, 1), w2.abs(), None, padding=1)
-    safe = _pool_decisions_safe(pre2, e2)  # [P,32,h-6,w-6]
+    f = front_bounds(x.double(), w1, b1, w2, b2)
+    safe = _pool_decisions_safe(f.pre2, f.e2)  # [P,32,h-6,w-6]
     dy = torch.randn(P, (h - 6) * (w - 6), 32, generator=g)
     return x, dy * safe.permute(0, 2, 3, 1).reshape(dy.shape)
 
