@@ -202,12 +202,24 @@ int crw_labelprop_propagate_batch(const float *seed, const float *W, const int32
  * frames, no parallel tail.  Route: one workgroup with frame 0 and a ring of cxt_size + 1 frames in LDS when
  * (cxt_size + 2) * N * M * 4 bytes + 16 KiB of list slots <= 150 KiB, knn <= 24, N * M <= 384 and knn * N <= 1024 (there an index
  * outside [0, min(n, cxt_size + 1) * N) is clamped into it); otherwise crw_labelprop_gather's kernels with the translation done in
- * the kernel (nothing is allocated, I is not copied).  CRW_LABELPROP_SLIDING_GENERAL=1 (read per call) takes the second route. */
+ * the kernel (nothing is allocated, I is not copied).  CRW_LABELPROP_SLIDING_GENERAL=1 (read per call) takes the second route.
+ *
+ * ANCHOR MARKS (these two entry points only; the LDS of the first route does not grow for them).  A softmax weight is never
+ * negative, so a list whose slot-0 weight W[f - first_frame][0][q] is EXACTLY -inf (bits 0xFF800000, CRW_LABELPROP_ANCHOR_WEIGHT)
+ * is a mark: node q of frame f is anchored to the class its slot-0 index I[f - first_frame][0][q] names, clamped into [0, M - 1]
+ * (like every index, it never addresses out of range).  For a marked node L[f*N + q] is exactly the one-hot of the class, written
+ * as 1.0f and +0.0f, pred[q][f] is the class, the other slots of the list are ignored, and every later frame reads the clamped
+ * row.  Every other weight value -- other negative values and NaN included -- means what it meant before, and lists without a mark
+ * give the bits they gave before.  crw_labelprop_gather, crw_labelprop_propagate and crw_labelprop_propagate_batch know no mark
+ * (under the reference rule an anchor beyond frame cxt_size would change only itself).  A library older than the marks has the
+ * same entry points at the same ABI and turns the -inf into NaN: ask it with one tiny marked call (crw_hip.has_anchor_lists()). */
+#define CRW_LABELPROP_ANCHOR_WEIGHT (-__builtin_inff())
 int crw_labelprop_propagate_sliding(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame,
                                     int cxt_size, float *L, float *pred, crw_stream_t stream);
 /* G configurations at once, arguments and limits as crw_labelprop_propagate_batch: a workgroup per configuration walks ALL frames
  * first_frame .. T-1 (no second launch).  Slice g of L and pred is bit-identical to crw_labelprop_propagate_sliding on that
- * configuration's lists. */
+ * configuration's lists -- anchor marks included: the marks are configuration g's (W[g]), the classes may be shared (i_stride 0),
+ * and a configuration padded to a longer knn keeps slot 0 as a real slot (knn >= 1). */
 int crw_labelprop_propagate_sliding_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N,
                                           int M, int knn, int first_frame, int cxt_size, float *L, float *pred, crw_stream_t stream);
 

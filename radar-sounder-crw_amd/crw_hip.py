@@ -398,6 +398,64 @@ def sliding_rows(I, N, cxt_size, first_frame=1):
     return torch.where(I >= N, I + shift, I)
 
 
+ANCHOR_WEIGHT = float("-inf")  # CRW_LABELPROP_ANCHOR_WEIGHT: a slot-0 weight with these bits (0xFF800000) marks an anchored node
+
+
+def check_anchors(anchors, T, N, M):
+    """the shape, dtype and class-count rules of every `anchors=` argument"""
+    if tuple(anchors.shape) != (T, N) or anchors.dtype != torch.int8:
+        raise ValueError(f"anchors must be a [{T}, {N}] int8 tensor (got {tuple(anchors.shape)}, {anchors.dtype})")
+    if M > 127:
+        raise ValueError(f"anchors are int8: at most 127 classes (got {M})")
+
+
+def mark_anchors(W, I, anchors, M, first_frame=1):
+    """Write anchor marks into the lists of the sliding entry points, IN PLACE (include/crw_hip.h, crw_labelprop_propagate_sliding):
+    for every node q of frame f >= first_frame with 0 <= anchors[f, q] < M, the slot-0 weight becomes -inf and the slot-0 index the
+    class.  W [F, knn, N] or [G, F, knn, N] float32 and I likewise int32 (each on its own: a [G, ...] W may share one [F, knn, N] I),
+    the lists of frames first_frame .. first_frame + F - 1; anchors [T, N] int8, T >= first_frame + F.  Any other value of `anchors`
+    leaves the node free, rows before first_frame are ignored, no slot but 0 is touched.  Two selects on the slot-0 views: nothing
+    is read back from the device and nothing is allocated per anchored frame; CPU tensors work as well.  -> (W, I)"""
+    F, N = W.shape[-3], W.shape[-1]
+    if I.shape[-3:] != W.shape[-3:] or W.dim() not in (3, 4) or I.dim() not in (3, 4):
+        raise ValueError(f"W and I must be [F, knn, N] or [G, F, knn, N] lists of the same frames (got {tuple(W.shape)}, {tuple(I.shape)})")
+    if anchors.dim() != 2 or anchors.shape[1] != N or anchors.shape[0] < first_frame + F:
+        raise ValueError(f"anchors must be [T >= {first_frame + F}, {N}] (got {tuple(anchors.shape)})")
+    a = anchors[first_frame:first_frame + F].to(device=W.device, dtype=torch.int32)    # [F, N]
+    valid = (a >= 0) & (a < M)
+    w0, i0 = W.select(-2, 0), I.select(-2, 0)                                              # [..., F, N] views of slot 0
+    torch.where(valid, torch.full((), ANCHOR_WEIGHT, device=W.device, dtype=W.dtype), w0, out=w0)
+    torch.where(valid, a.to(I.dtype), i0, out=i0)
+    return W, I
+
+
+_anchor_lists = {}  # library path -> the loaded library honours anchor marks
+
+
+def has_anchor_lists():
+    """True when the loaded library honours anchor marks in the lists of the sliding entry points.  Neither the ABI number nor a
+    symbol tells: a library from before the marks has the same entry points and turns the -inf weight into NaN.  So this asks the
+    library itself, once per library: one marked call at T = 2, N = 1, M = 2 (the node of frame 1 anchored to class 1) whose row
+    must come back as the one-hot [0, 1].  False: `labelprop_gather(anchors=)` takes the segmented route."""
+    if LIB_PATH not in _anchor_lists:
+        ok = has_sliding() and torch.cuda.is_available()
+        if ok:
+            seed = torch.zeros(1, device="cuda")
+            W, I = torch.full((1, 1, 1), ANCHOR_WEIGHT, device="cuda"), torch.ones(1, 1, 1, device="cuda", dtype=torch.int32)
+            L, pred = torch.zeros(2, 2, device="cuda"), torch.zeros(1, 2, device="cuda")
+            _check(lib().crw_labelprop_propagate_sliding(_dev(seed, "seed"), _dev(W, "W"), _dev(I, "I", torch.int32), 2, 1, 2, 1, 1, 1,
+                                                         _dev(L, "L"), _dev(pred, "pred"), _stream()), "crw_labelprop_propagate_sliding")
+            ok = L[1].tolist() == [0.0, 1.0] and pred[0].tolist() == [0.0, 1.0]
+        _anchor_lists[LIB_PATH] = ok
+    return _anchor_lists[LIB_PATH]
+
+
+def anchors_segmented():
+    """CRW_ANCHORS_SEGMENTED=1 (read per call), or a library without anchor marks: anchored propagation runs as segments
+    (`_propagate_anchored`) instead of one launch on marked lists."""
+    return os.environ.get("CRW_ANCHORS_SEGMENTED") == "1" or not has_anchor_lists()
+
+
 def _propagate_anchored(seed, W, I, anchors, T, N, M, knn, first_frame, cxt_size, L, pred):
     """Anchored propagation as segments of crw_labelprop_propagate_sliding: the entry point up to the next frame that holds a
     clamped node, that frame's clamped rows of L and entries of pred overwritten, then again with seed = NULL and first_frame = that
@@ -441,8 +499,10 @@ def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_
     bitwise `labelprop_gather(seed, W, sliding_rows(I, N, cxt_size, first_frame), ...)` with cxt_size None.
     anchors (needs context='sliding'): [T, N] int8, on the device or on the host, labelled nodes inside the item -- a value in [0, M) clamps the
     node's row of L to that class's one-hot before the next frame reads it, any other value (-1; M, 127, -128 likewise) leaves it
-    free; rows of frames before first_frame are ignored.  Runs crw_labelprop_propagate_sliding once per stretch between anchored
-    frames (`_propagate_anchored`).  None: the call is what it was."""
+    free; rows of frames before first_frame are ignored.  ONE crw_labelprop_propagate_sliding call on a marked COPY of W and I
+    (`mark_anchors`; the caller's lists are left as they are -- a caller that owns its lists marks them itself and passes no
+    anchors).  CRW_ANCHORS_SEGMENTED=1 (read per call), or a library that does not know the marks (`has_anchor_lists()`): once per
+    stretch between anchored frames instead (`_propagate_anchored`), the same bits.  None: the call is what it was."""
     knn = W.shape[1]
     check_context(context)
     if context == "sliding" and cxt_size is None:
@@ -451,16 +511,15 @@ def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_
         if context != "sliding":
             raise ValueError("anchors need context='sliding' (and cxt_size): under the reference rule a late frame never reads a "
                              "label later than frame cxt_size, so an anchor there would change only itself")
-        if tuple(anchors.shape) != (T, N) or anchors.dtype != torch.int8:
-            raise ValueError(f"anchors must be a [{T}, {N}] int8 tensor (got {tuple(anchors.shape)}, {anchors.dtype})")
-        if M > 127:
-            raise ValueError(f"anchors are int8: at most 127 classes (got {M})")
+        check_anchors(anchors, T, N, M)
     if L is None:
         L = torch.empty(T * N, M, device=W.device, dtype=torch.float32)
     if pred is None:
         pred = torch.zeros(N, T, device=W.device, dtype=torch.float32)
     if anchors is not None:
-        return _propagate_anchored(seed, W, I, anchors, T, N, M, knn, int(first_frame), cxt_size, L, pred)
+        if anchors_segmented():
+            return _propagate_anchored(seed, W, I, anchors, T, N, M, knn, int(first_frame), cxt_size, L, pred)
+        W, I = mark_anchors(W.clone(), I.clone(), anchors, M, int(first_frame))
     if context == "sliding":
         _check(_sliding_lib().crw_labelprop_propagate_sliding(_dev(seed, "seed") if seed is not None else None, _dev(W, "W"),
                                                               _dev(I, "I", torch.int32), T, N, M, knn, int(first_frame), int(cxt_size),

@@ -379,6 +379,12 @@ __device__ inline void st_l2(float *p, float v) {
 // SLIDE (crw_labelprop_propagate_sliding): an index of frame n addresses the list it was scored on, [frame 0, frames n - cxt .. n - 1]
 // -- slide_row() below; false: the indices are label rows as they stand (cxt unused).
 __device__ inline int slide_row(int i, int n, int N, int cxt) { return (i >= N && n > cxt + 1) ? i + (n - cxt - 1) * N : i; }
+// An anchor mark (sliding entry points only, CRW_LABELPROP_ANCHOR_WEIGHT in the header): a slot-0 weight of exactly -inf says that
+// the node is clamped to the class its RAW slot-0 index names, clamped into [0, M - 1].  No softmax weight has these bits, so every
+// other list is read as before.  anchor_onehot: the value the clamped node's output (q, c) takes -- 1.0f or +0.0f, written as they are.
+constexpr int ANCHOR_BITS = (int)0xFF800000u;
+__device__ inline bool anchor_mark(float w0) { return __float_as_int(w0) == ANCHOR_BITS; }
+__device__ inline float anchor_onehot(int i0, int M, int c) { return c == min(max(i0, 0), M - 1) ? 1.f : 0.f; }
 
 // ---- the pieces every propagation kernel below shares: the tie rule and the frame-0 rule of "same operations in the same order per
 // output, bit-identical L and pred" exist ONCE.  (The role kernels and the ring gathers stay separate texts: merged into one
@@ -444,10 +450,12 @@ __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__r
     for (int it = tid; it < N * M; it += nt) {
       const int q = it / M, c = it % M;
       float p = 0.f;
+      const bool mk = SLIDE && anchor_mark(Wn[q]);  // an anchored node: its list is not a list -- every read goes to row 0
       for (int j = 0; j < knn; ++j) {
-        const int r = SLIDE ? slide_row(In[j * N + q], n, N, cxt) : In[j * N + q];
+        const int r = SLIDE ? (mk ? 0 : slide_row(In[j * N + q], n, N, cxt)) : In[j * N + q];
         p += ld_l2(L + (long)r * M + c) * Wn[j * N + q];
       }
+      if (mk) p = anchor_onehot(In[q], M, c);  // ... and the sum is dropped for the one-hot of its class
       st_l2(L + ((long)n * N + q) * M + c, p);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -503,6 +511,7 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
     for (int it = tid; it < NM; it += GATHER_NT) {
       const int q = it / M, c = it % M;
       float p = 0.f;
+      const bool mk = SLIDE && anchor_mark(wn[q]);  // an anchored node (slot 0 of the frame's lists in LDS): every read goes to row 0
       // GATHER_CH neighbours at a time: their (index, weight) reads and then their label reads are independent LDS round trips
       // (one neighbour after the other is two dependent round trips each: 3 of the 4 us a frame took); the sum stays in j order
       for (int j0 = 0; j0 < knn; j0 += GATHER_CH) {
@@ -511,7 +520,7 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
 #pragma unroll
         for (int u = 0; u < GATHER_CH; ++u) {
           const int jj = min(j0 + u, knn - 1);
-          idx[u] = SLIDE ? slide_row(in[jj * N + q], n, N, cxt) : in[jj * N + q];
+          idx[u] = SLIDE ? (mk ? 0 : slide_row(in[jj * N + q], n, N, cxt)) : in[jj * N + q];
           w[u] = wn[jj * N + q];
         }
 #pragma unroll
@@ -528,6 +537,7 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
         for (int u = 0; u < GATHER_CH; ++u)
           if (j0 + u < knn) p += v[u] * w[u];
       }
+      if (mk) p = anchor_onehot(in[q], M, c);  // ... and the sum is dropped for the one-hot of its class
       st_l2(L + ((long)n * N + q) * M + c, p);
       slot[it] = p;
     }
@@ -700,6 +710,9 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
   const bool compute = wave < ncw, loader = !compute && wave < nwaves - 1, amax = wave == nwaves - 1;
   const int lk = wave - ncw, at = tid - (nwaves - 1) * 64;
   constexpr int KNP = 64 * PX_PF;
+  // launch_chain sends knn to the smallest instance that holds it, so knn > KP - 8: slots j < KLO are real in every list here and
+  // need neither the clamp to the last slot nor the padding test
+  constexpr int KLO = KP - 8;
   const int RNM = R * NM;
   float *lab = sm;                                                                   // [NM] frame 0, [R][NM] the ring
   int2 *pl = reinterpret_cast<int2 *>(lab + (((long)(R + 1) * NM + 1) & ~1L));  // [2][KNP] (index, weight bits), slot = frame & 1
@@ -749,15 +762,20 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
     const int2 *ln = pl + (f & 1) * KNP;
 #pragma unroll
     for (int j = 0; j < KP; ++j) {
-      const int2 e = ln[min(j, knn - 1) * N + q];
+      const int2 e = ln[(j < KLO ? j : min(j, knn - 1)) * N + q];
       ix[j] = e.x;
       ww[j] = __int_as_float(e.y);
     }
   };
   // frame f's indices -> LDS offsets.  shift = ((f - cxt - 1) % R) * NM once the window slides, 0 before; the clamp keeps an index
   // inside the list it addresses (topk: < min(f, cxt + 1) * N), i.e. on rows before the frame's own and inside the ring
-  auto to_offsets = [&](int f, int shift, int (&ix)[KP], float (&ww)[KP]) {
+  // An anchored lane (anchor_mark on the slot-0 weight, the class from the RAW slot-0 index, before the clamp to a row below): mk and
+  // the value oh its output takes are made here, one frame ahead and behind the previous frame's stores; the frame itself pays one
+  // select on p.  The marked list's offsets stay in range like any other's, so its label reads are harmless and its sum is dropped.
+  auto to_offsets = [&](int f, int shift, int (&ix)[KP], float (&ww)[KP], int &mk, int &oh) {
     const int lim = min(f, cxt + 1) * N - 1;
+    mk = anchor_mark(ww[0]) ? -1 : 0;
+    oh = __float_as_int(anchor_onehot(ix[0], M, c));
 #pragma unroll
     for (int j = 0; j < KP; ++j) {
       const int i = min(max(ix[j], 0), lim);
@@ -767,7 +785,7 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
         if (o >= NM + RNM) o -= RNM;
       }
       ix[j] = o;
-      if (j >= knn) ww[j] = 0.f;  // padding slot: p + v * 0 = p
+      if (j >= KLO && j >= knn) ww[j] = 0.f;  // padding slot: p + v * 0 = p
     }
   };
   // running offsets (wave-uniform): shift of the frame whose offsets are made next, store slot of the frame computed next
@@ -779,9 +797,10 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
       if (shift == RNM) shift = 0;
     }
   };
+  int amk = 0, aoh = 0;  // all ones where this lane's node is anchored in the frame computed next; the bits of the value it then takes
   if (compute) {
     fetch_lists(first_frame, a, w);
-    to_offsets(first_frame, shift, a, w);
+    to_offsets(first_frame, shift, a, w, amk, aoh);
   }
   next_shift(first_frame);
   lds_barrier();  // the read of slot first_frame & 1 above comes before loader 0's svc_store(first_frame + 2) into the same slot
@@ -799,9 +818,19 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
       float p = 0.f;
 #pragma unroll
       for (int j = 0; j < KP; ++j) p += v[j] * w[j];
+      // an anchored node: exactly 1.0f / +0.0f, and every later frame and the arg-max wave read the clamped row.  A bit select on
+      // two VGPRs made a frame ahead, (amk & aoh) | (~amk & p).  Written as the instruction: from the C expression hipcc goes back to
+      // a v_cndmask on a lane mask kept in SGPRs across the barrier, which spilled four more SGPRs in this loop.
+      // (make EXTRA=-DCRW_LABELPROP_RING_NO_ANCHORS: the kernel without it, the arm tools/anchor_lists_timing.py --also measures)
+#ifndef CRW_LABELPROP_RING_NO_ANCHORS
+      asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(p) : "v"(amk), "v"(aoh), "v"(p));
+#endif
       lab[wslot + it] = p;  // the slot of frame f - R: out of every window since frame f - 1
       L[(long)f * NM + it] = p;
-      to_offsets(f + 1, shift, na, nw);
+      // nothing of the next frame's offsets is scheduled above the stores: hipcc otherwise lifts the first clamp, and with it the
+      // wait for the first list entry (an LDS round trip), in front of the remaining list reads and the LDS store
+      __builtin_amdgcn_sched_barrier(0);
+      to_offsets(f + 1, shift, na, nw, amk, aoh);
 #pragma unroll
       for (int j = 0; j < KP; ++j) {
         a[j] = na[j];
@@ -896,6 +925,8 @@ __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float
     for (int it = tid; it < NM; it += nt) {
       const int q = it / M, c = it % M;
       float p = 0.f;
+      // an anchored node: the mark is configuration g's (W), the class may be shared (I with i_stride 0); its sum is dropped
+      const bool mk = SLIDE && anchor_mark(Wn[q]);
       for (int j0 = 0; j0 < knn; j0 += PB_CH) {
         int idx[PB_CH];
         float w[PB_CH], v[PB_CH];
@@ -920,6 +951,7 @@ __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float
         for (int u = 0; u < PB_CH; ++u)
           if (j0 + u < knn) p += v[u] * w[u];
       }
+      if (mk) p = anchor_onehot(In[q], M, c);
       st_l2(L + ((long)n * N + q) * M + c, p);
       slot[it] = p;
     }

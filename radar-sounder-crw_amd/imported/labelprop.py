@@ -22,6 +22,8 @@ import torch
 import crw_hip
 
 MASK_NEG = -1e10
+ANCHORS_NEED_SLIDING = ("anchors need CONTEXT 'sliding': under the reference's index quirk a frame beyond CXT_SIZE + 1 never reads a "
+                        "label later than frame CXT_SIZE, so an anchor there would change only itself")
 
 
 class LabelPropVOS_CRW(object):
@@ -88,15 +90,22 @@ class LabelPropVOS_CRW(object):
         -> (pred [N,T] float class ids, L [T*N, M] soft labels).  grid_w: the N nodes are an (N / grid_w) x grid_w grid.
         anchors (needs CONTEXT 'sliding'): [T, N] int8, device or host, labelled nodes inside the item -- a class id in [0, nclasses)
         clamps the node's soft labels to that class before the next frame reads them, anything else (-1) leaves the node free; row 0
-        is ignored (the seed rules there).  One launch per stretch between anchored frames (`crw_hip.labelprop_gather(anchors=)`)."""
+        is ignored (the seed rules there).  The lists made here are this call's own, so the anchors are marked into them in place
+        (`crw_hip.mark_anchors`, no copy) and ONE crw_labelprop_propagate_sliding call follows; CRW_ANCHORS_SEGMENTED=1 (read per call)
+        or a library without the marks: one launch per stretch between anchored frames (`crw_hip.labelprop_gather(anchors=)`)."""
         T, N, C = feats.shape
         if anchors is not None and self.context != 'sliding':
-            raise ValueError("anchors need CONTEXT 'sliding': under the reference's index quirk a frame beyond CXT_SIZE + 1 never reads a "
-                             "label later than frame CXT_SIZE, so an anchor there would change only itself")
+            raise ValueError(ANCHORS_NEED_SLIDING)
         self._check_grid(N // grid_w, grid_w)
         self._band(N // grid_w, grid_w, feats.device)
         Wt, It = crw_hip.labelprop_topk(feats, self.cxt_size, self.radius, self.temperature, self.topk, first_frame=1, grid_w=grid_w)
-        kw = {} if anchors is None else dict(anchors=anchors)
+        kw = {}
+        if anchors is not None:
+            crw_hip.check_anchors(anchors, T, N, nclasses)
+            if crw_hip.anchors_segmented():
+                kw = dict(anchors=anchors)
+            else:
+                crw_hip.mark_anchors(Wt, It, anchors, nclasses, 1)
         L, pred = crw_hip.labelprop_gather(seed.float().contiguous(), Wt, It, T, N, nclasses, first_frame=1, cxt_size=self.cxt_size,
                                            context=self.context, **kw)
         return pred, L
@@ -130,9 +139,11 @@ class LabelPropSweep(object):
             raise RuntimeError(f"KNN={max(self.knns)} exceeds the number of nodes per frame ({h * w}); "
                                "torch.topk in the reference raises for the first frame as well")
 
-    def propagate_all(self, feats, seed, nclasses, grid_w=1, soft=False):
+    def propagate_all(self, feats, seed, nclasses, grid_w=1, soft=False, anchors=None):
         """feats [T,N,C] (normalised features), seed [N] float class ids of frame 0 -> pred [G,N,T] float class ids, G =
-        len(configs).  soft: -> (pred, L [G, T*N, M]), the soft labels of every configuration as well (the batch kernel writes them
+        len(configs).  anchors (needs context 'sliding'): `LabelPropVOS_CRW.propagate_all`'s, the same for every configuration --
+        marked in place into the W [G, ...] that `labelprop_sweep_weights` wrote and into the shared I (`crw_hip.mark_anchors`: a
+        configuration padded from a smaller knn keeps slot 0 as a real slot), then the ONE batch call as without them.  soft: -> (pred, L [G, T*N, M]), the soft labels of every configuration as well (the batch kernel writes them
         anyway; the per-configuration arm stacks its G copies) -- what `crw_hip.labelmap_dense_batch` turns into pixel maps.
 
         Per (radius, temp): ONE selection at kcap = max(knns) (`crw_hip.labelprop_topk_scores`; the lists of a smaller knn are
@@ -142,12 +153,17 @@ class LabelPropSweep(object):
         CRW_SWEEP_PER_CONFIG=1 (read per call): a loop of `LabelPropVOS_CRW.propagate_all` over the configurations on the same
         features instead -- the A/B arm of tools/sweep_timing.py, and the fallback."""
         T, N, C = feats.shape
+        if anchors is not None:
+            if self.context != 'sliding':
+                raise ValueError(ANCHORS_NEED_SLIDING)
+            crw_hip.check_anchors(anchors, T, N, nclasses)
         self._check_grid(N // grid_w, grid_w)
         seed = seed.float().contiguous()
         if os.environ.get("CRW_SWEEP_PER_CONFIG") == "1":
+            akw = {} if anchors is None else dict(anchors=anchors)
             if not soft:
-                return torch.stack([LabelPropVOS_CRW(cfg).propagate_all(feats, seed, nclasses, grid_w=grid_w)[0] for cfg in self.configs])
-            outs = [LabelPropVOS_CRW(cfg).propagate_all(feats, seed, nclasses, grid_w=grid_w) for cfg in self.configs]
+                return torch.stack([LabelPropVOS_CRW(cfg).propagate_all(feats, seed, nclasses, grid_w=grid_w, **akw)[0] for cfg in self.configs])
+            outs = [LabelPropVOS_CRW(cfg).propagate_all(feats, seed, nclasses, grid_w=grid_w, **akw) for cfg in self.configs]
             return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
         nk, kmax, F = len(self.knns), max(self.knns), T - 1
         P = len(self.radii) * len(self.temps)
@@ -160,6 +176,11 @@ class LabelPropSweep(object):
                 crw_hip.labelprop_topk_scores(feats, self.cxt_size, r, t, kmax, first_frame=1, grid_w=grid_w, out=(V, I[p]))
                 crw_hip.labelprop_sweep_weights(V, self.knns, out=W[p])
                 p += 1
+        if anchors is not None:  # before I is expanded: every (radius, temp) pair's indices take the classes, every W[g] the marks
+            if not crw_hip.has_anchor_lists():
+                raise RuntimeError(f"{crw_hip.LIB_PATH} does not honour anchor marks in the lists (a stale libcrw_hip.so): a sweep "
+                                   "cannot run as segments -- rebuild with `make -C radar-sounder-crw_amd/csrc`")
+            crw_hip.mark_anchors(W.view(P * nk, F, kmax, N), I, anchors, nclasses, 1)
         if P == 1:
             Ig = I[0]  # one list of indices shared by every configuration
         else:

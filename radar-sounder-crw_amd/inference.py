@@ -311,7 +311,7 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
 @torch.no_grad()
 def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size, overlap, pos_embed=False,
                   correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
-                  decode='argmax', order=None, **posterior_options):
+                  decode='argmax', order=None, anchors=None, **posterior_options):
     """`segment` for every configuration of ``sweep`` (LabelPropSweep, G = len(sweep.configs)) with its control flow run ONCE:
     which items are corrected, at which length (`get_smaller_item` and its permanent shortening of the dataset) and what the
     reverse pass sees depend on the features alone, never on (radius, temp, knn).  Same exception policy in the correction.
@@ -336,7 +336,13 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     float32 [G, 3, S-1, cols] and ``floor``; slice g is `segment`'s for ``sweep.configs[g]``, bit for bit.  The call that writes a
     window of ``pred`` writes the same window of the two for all G configurations (`crw_hip.labelmap_ordered_posterior_batch` /
     `labelmap_ordered_joint_posterior_batch`, as few launches as fit the workspace cap); every other entry is bit for bit what
-    it is without the option."""
+    it is without the option.
+    anchors: `segment`'s -- None, or (annot, cols), labelled traces inside the radargrams (needs a ``sweep`` under context
+    'sliding'); the same anchors in both passes and for all G configurations, the reverse pass mirrored, not together with
+    ``correction``; the dict gains ``anchor_cols``.  Slice g stays `segment`'s for ``sweep.configs[g]`` under the same anchors."""
+    if anchors is not None and correction:
+        raise ValueError("anchors and correction=True do not combine: the correction is itself a re-seed (at the change point), and "
+                         "how the two interact is not decided")
     posterior, floor = posterior_options.pop('posterior', False), posterior_options.pop('floor', crw_hip.POSTERIOR_FLOOR)
     if posterior_options:
         raise TypeError(f"segment_sweep() got an unexpected keyword argument '{next(iter(posterior_options))}'")
@@ -364,7 +370,7 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     else:
         kw = dict(confidence=confidence) if want else {}  # `propagate_sweep` returns a fourth entry only when asked
         write = _write_nearest
-    run = lambda seq, seg_ref, last: propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=last, **kw)
+    run = lambda seq, seg_ref, last, **anch: propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=last, **kw, **anch)
 
     def joint(a, b, N, out, out_conf, post=None):  # merge='ordered': ONE launch per window for the G configurations
         crw_hip.labelmap_ordered_joint_batch(a, b, G, N, nclasses, *out.shape[1:], order, confidence=confidence, dtype=torch.int8,
@@ -373,7 +379,7 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
             crw_hip.labelmap_ordered_joint_posterior_batch(a, b, G, N, nclasses, *out.shape[1:], order, out, confidence=confidence,
                                                            floor=floor, out=post[0], out_hz=post[1])
     return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
-                           write, lead=(G,), dtype=torch.int8, joint=joint, posterior=len(order) if posterior else 0,
+                           write, lead=(G,), dtype=torch.int8, joint=joint, posterior=len(order) if posterior else 0, anchors=anchors,
                            configs=list(sweep.configs), **extra)
 
 

@@ -31,6 +31,9 @@ calibration table and error-bar table follow its other tables, as ``segment_all.
 gains a ``posterior`` entry per configuration and ``floor``; and ``--select`` also takes ``post_ece`` and ``post_aurc`` (offered
 only with ``--posterior``) -- the lowest wins, by the same rules.  Without these flags the script prints and writes what it did
 before them.
+``--anchors FILE`` / ``--anchor_every K`` (with ``--context sliding``, not with ``--correction``): ``segment_all.py``'s two flags,
+the same anchors for every configuration (``inference.segment_sweep(..., anchors=(map, columns))``); one line says how many traces
+are anchored and ``--report_json`` gains ``anchors``.  Without them the output is what it was.
 CRW_SWEEP_PER_CONFIG=1: the label propagation as a loop over the configurations (same maps; the A/B arm)."""
 import argparse
 import json
@@ -114,6 +117,10 @@ def get_args_parser(horizons=False, posterior=False):
                    help="the ordered decode's own confidence for every configuration: ECE of the posterior map and mean bar coverage "
                         "(two columns; needs --decode ordered)")
     p.add_argument('--floor', default=None, type=float, metavar='X', help='floor under the evidence of --posterior (2^-20 ... 0.25; 1e-4)')
+    p.add_argument('--anchors', default=None, metavar='FILE',
+                   help='labelled traces inside the radargrams: a .pt map, < 0 = unlabelled (needs --context sliding)')
+    p.add_argument('--anchor_every', default=None, type=int, metavar='K',
+                   help="evaluation: the reference map's column at the first pixel of every K-th frame as anchors (needs --context sliding)")
     return p
 
 
@@ -168,7 +175,8 @@ def report_dict(report):
 def main(args):
     from imported.labelprop import LabelPropSweep
     tim = time.time()
-    args = check_confidence_flags(with_defaults(args))
+    args = segment_all.check_anchor_flags(check_confidence_flags(with_defaults(args)))
+    anchored = args.anchors is not None or args.anchor_every is not None
     # without --confidence / --upsample the flags that go with them do nothing, and the line reads as it did before they existed
     hidden = () if args.confidence else ('confidence', 'merge', 'bins')
     if args.upsample == 'nearest':
@@ -181,6 +189,8 @@ def main(args):
         hidden += ('decode', 'order')
     if not args.posterior:  # likewise
         hidden += POSTERIOR_FLAGS
+    if not anchored:  # likewise
+        hidden += segment_all.ANCHOR_FLAGS
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -196,12 +206,16 @@ def main(args):
     if correction and not args.dataset_full:
         print('Correction skipped: it needs --dataset_full true (the reference skips it silently here)')
         correction = False
+    anchors = segment_all.load_anchors(args, seg, rg_len) if anchored else None
+    if anchored:
+        print('Anchored traces:', len(anchors[1]))
     out = inference.segment_sweep(dataset, seg, encoder, sweep, nclasses, T, args.patch_size, args.overlap, pos_embed=args.pos_embed,
                                   correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device,
                                   **(dict(confidence=args.confidence, merge=args.merge) if args.confidence else {}),
                                   **(dict(upsample=args.upsample) if args.upsample != 'nearest' else {}),
                                   **(dict(decode=args.decode, order=args.order) if args.decode != 'argmax' else {}),
-                                  **(dict(posterior=True, floor=args.floor) if args.posterior else {}))
+                                  **(dict(posterior=True, floor=args.floor) if args.posterior else {}),
+                                  **(dict(anchors=anchors) if anchored else {}))
     if correction:
         print('Change point for each radargram:', out['change_idx'])
     final, forward = out['pred'], out['forward']
@@ -299,6 +313,9 @@ def main(args):
             d['context'] = args.context
         if args.decode != 'argmax':
             d.update(decode=args.decode, order=list(out['order']))
+        if anchored:
+            d['anchors'] = dict(traces=len(out['anchor_cols']), columns=out['anchor_cols'],
+                                source='file' if args.anchors is not None else f'every {args.anchor_every} frames of the reference map')
         with open(args.report_json, 'w') as f:
             json.dump(d, f, indent=1)
     return reports, best

@@ -213,7 +213,7 @@ def ndiag_matrix(size, n=1):
 
 
 @torch.no_grad()
-def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False):
+def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False, anchors=None):
     """`propagate` for every configuration of ``sweep`` (imported.labelprop.LabelPropSweep) at once: the encoder, the metric and
     the change point do not depend on (radius, temp, knn) and run ONCE, on the batch `propagate` gives the encoder
     ->  (labels [G,N,T] float, xent [N,T-1] (CPU), change_idx | None); labels[g] is `propagate`'s for ``sweep.configs[g]``.
@@ -221,10 +221,18 @@ def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last
     confidence / soft: the tuple grows as `propagate`'s does -- conf [G,N,T] float, then, last, the soft labels L [G, T*N, M]
     (frames in the pass's own order); conf[g] and L[g] are `propagate`'s for ``sweep.configs[g]``.  The confidence of all G
     configurations is ONE `crw_hip.labelprop_confidence` call on the stack read as G*T frames of one pass: the formula is per row,
-    and every frame g*T is a one-hot seed, which reads 1."""
+    and every frame g*T is a one-hot seed, which reads 1.
+    anchors: `propagate`'s -- [T, N] int8 in the ITEM's frame order, flipped here under ``use_last``, the same for all G
+    configurations (``sweep`` under context 'sliding'); a one-frame item ignores them."""
     if confidence is not None and confidence not in crw_hip.CONF_KINDS:
         raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
     T, N, H, W = seq.shape
+    akw = {}
+    if anchors is not None and T > 1:
+        if tuple(anchors.shape) != (T, N):
+            raise ValueError(f"anchors must be [{T}, {N}] (got {tuple(anchors.shape)})")
+        a = anchors.to(torch.int8)
+        akw = dict(anchors=(torch.flip(a, (0,)) if use_last else a).contiguous())
     feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
     G = len(sweep.configs)
     if T == 1:
@@ -238,9 +246,9 @@ def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last
     xent = crw_hip.xent_metric(feats)
     diffs = column_diffs_async(xent) if T > 2 else None
     if confidence is None and not soft:
-        pred = sweep.propagate_all(feats, seed, nclasses)
+        pred = sweep.propagate_all(feats, seed, nclasses, **akw)
     else:
-        pred, L = sweep.propagate_all(feats, seed, nclasses, soft=True)
+        pred, L = sweep.propagate_all(feats, seed, nclasses, soft=True, **akw)
     conf = None
     if confidence is not None:  # queued right behind the propagation, before the host turns to the change point
         conf = crw_hip.labelprop_confidence(L.reshape(G * T * N, nclasses), G * T, N, nclasses, confidence)  # [N, G*T]
