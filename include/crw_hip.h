@@ -72,7 +72,8 @@ extern "C" {
  * crw_labelmap_ordered_joint, crw_labelmap_ordered_joint_batch (crw_hip.has_joint()); then crw_labelmap_posterior_workspace,
  * crw_labelmap_ordered_posterior, crw_labelmap_ordered_joint_posterior (crw_hip.has_posterior()); then
  * crw_labelmap_posterior_workspace_batch, crw_labelmap_ordered_posterior_batch, crw_labelmap_ordered_joint_posterior_batch
- * (crw_hip.has_posterior_batch()).  The ONE place the number is
+ * (crw_hip.has_posterior_batch()); the conv-trunk chain of include/crw_hip_chain.h came the same way
+ * (crw_hip.has_conv_chain()).  The ONE place the number is
  * written: crw_abi_version() returns it, the ctypes binding (crw_hip.ABI_VERSION) parses it from this header, and __graft_entry__.build() / the host tests compare
  * the two. */
 #define CRW_ABI_VERSION 8

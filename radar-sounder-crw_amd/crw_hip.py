@@ -151,6 +151,11 @@ SIGNATURES = {
     "crw_gemm_bf16": (_c_int, [_p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _c_sz, _c_int, _p]),
 }
 
+# include/crw_hip_chain.h, likewise one to one: the conv-trunk chain (optional: `has_conv_chain()`)
+CHAIN_SIGNATURES = {
+    "crw_enc_conv_fwd_chain": (_c_int, [_c_int, _c_int] + [_p] * 18),
+}
+
 # entry points added at ABI 8 without a bump: a library built before them still loads, `has_sweep()` tells
 SWEEP_ENTRY_POINTS = ("crw_labelprop_topk_scores", "crw_labelprop_sweep_weights", "crw_labelprop_propagate_batch")
 
@@ -182,6 +187,9 @@ POSTERIOR_ENTRY_POINTS = ("crw_labelmap_posterior_workspace", "crw_labelmap_orde
 POSTERIOR_BATCH_ENTRY_POINTS = ("crw_labelmap_posterior_workspace_batch", "crw_labelmap_ordered_posterior_batch",
                                 "crw_labelmap_ordered_joint_posterior_batch")
 
+# likewise: conv3 -> conv4 -> conv5 of the CNN encoder in one launch (`has_conv_chain()`; without it the layers run one by one)
+CONV_CHAIN_ENTRY_POINTS = tuple(CHAIN_SIGNATURES)
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 
 # group -> its entry points.  `has_<group>()` tells whether the loaded library exports them, `_<group>_lib()` is lib() or the
@@ -189,7 +197,8 @@ CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame 
 OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_ENTRY_POINTS, "dense": DENSE_ENTRY_POINTS,
                          "dense_batch": DENSE_BATCH_ENTRY_POINTS, "horizons": HORIZONS_ENTRY_POINTS,
                          "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS, "joint": JOINT_ENTRY_POINTS,
-                         "posterior": POSTERIOR_ENTRY_POINTS, "posterior_batch": POSTERIOR_BATCH_ENTRY_POINTS}
+                         "posterior": POSTERIOR_ENTRY_POINTS, "posterior_batch": POSTERIOR_BATCH_ENTRY_POINTS,
+                         "conv_chain": CONV_CHAIN_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -205,7 +214,7 @@ def lib():
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
         missing = {n for names in OPTIONAL_ENTRY_POINTS.values() for n in names if not hasattr(handle, n)}
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES}.items():
             if name in missing:
                 continue
             fn = getattr(handle, name)
@@ -248,6 +257,7 @@ has_ordered, _ordered_lib = _optional("ordered", "the depth-ordered label map's 
 has_joint, _joint_lib = _optional("joint", "the joint ordered label map's entry points")
 has_posterior, _posterior_lib = _optional("posterior", "the ordered maps' posterior entry points")
 has_posterior_batch, _posterior_batch_lib = _optional("posterior_batch", "the batched posterior entry points")
+has_conv_chain, _conv_chain_lib = _optional("conv_chain", "the conv-trunk chain entry point")
 
 
 def check_context(context):
@@ -1565,9 +1575,14 @@ def enc_pack_input(x, split):
 
 
 def enc_conv3x3(mode, split, xh, xl, wh, wl, cout, bias=None, mask=None, planes=True, f32=False, gap=False,
-                dgap=None, lo_plane=True):
+                dgap=None, lo_plane=True, chain=None):
     """mode 0: relu(conv + bias) ; mode 1: backward-data with optional ReLU mask.  -> (yh, yl, yf, gap).
-    dgap (mode 1): the input gradient is dgap/100 gated by xh (forward activation plane), xl ignored."""
+    dgap (mode 1): the input gradient is dgap/100 gated by xh (forward activation plane), xl ignored.
+    chain (a `ConvFwdChain`): this call is one layer of conv3 -> conv4 -> conv5 and is served from the chain's one launch."""
+    if chain is not None:
+        if mode != 0 or split != 3 or mask is not None or not planes or f32 or dgap is not None:
+            raise RuntimeError("a ConvFwdChain serves the mode-0, split-3 calls of conv3, conv4 and conv5 only")
+        return chain.layer(xh, xl, wh, wl, cout, bias, gap, lo_plane)
     P, _, cin = xh.shape
     dev = xh.device
     yh = torch.empty(P, 100, cout, dtype=_BF, device=dev) if planes else None
@@ -1581,6 +1596,53 @@ def enc_conv3x3(mode, split, xh, xl, wh, wl, cout, bias=None, mask=None, planes=
                                  _dev(dgap, "dgap") if dgap is not None else None, _stream()), "crw_enc_conv3x3")
     _ev_end(ev, ("fwd", cin, cout) if mode == 0 else ("bwd", cout, cin))
     return yh, yl, yf, gp
+
+
+def conv_chain_on():
+    """Does the CNN trunk run conv3 -> conv4 -> conv5 in one launch?  Yes when the library has the chain kernel, unless
+    CRW_CONV_CHAIN=0 (read at every call: the per-layer route is the chain's A/B partner) or KERNEL_EVENTS is collecting:
+    bench.py's per-kernel roofline brackets and names the per-layer launches."""
+    return KERNEL_EVENTS is None and os.environ.get("CRW_CONV_CHAIN", "1") != "0" and has_conv_chain()
+
+
+def enc_conv_fwd_chain(x3h, x3l, packed, biases):
+    """relu(conv + bias) of conv3, conv4, conv5 on hi/lo planes in one launch -> (y3h, y3l, y4h, y4l, y5h, gap): bit for bit
+    what three mode-0 `enc_conv3x3` calls at split 3 return (conv5 with gap=True, lo_plane=False).  packed: per layer the
+    forward planes (hi, lo, ...) of `enc_pack_weights`; biases: per layer [cout] fp32."""
+    P, dev = x3h.shape[0], x3h.device
+    mk = lambda c: torch.empty(P, 100, c, dtype=_BF, device=dev)
+    y3h, y3l, y4h, y4l, y5h = mk(64), mk(64), mk(128), mk(128), mk(128)
+    gap = torch.empty(P, 128, dtype=torch.float32, device=dev)
+    w = [a for pk, b in zip(packed, biases) for a in (_bf(pk[0], "w_hi"), _bf(pk[1], "w_lo"), _dev(b, "bias"))]
+    _check(_conv_chain_lib().crw_enc_conv_fwd_chain(3, P, _bf(x3h, "x3h"), _bf(x3l, "x3l"), *w, _bf(y3h, "y3h"), _bf(y3l, "y3l"),
+                                                    _bf(y4h, "y4h"), _bf(y4l, "y4l"), _bf(y5h, "y5h"), _dev(gap, "gap"), _stream()),
+           "crw_enc_conv_fwd_chain")
+    return y3h, y3l, y4h, y4l, y5h, gap
+
+
+class ConvFwdChain:
+    """conv3 -> conv4 -> conv5 of one forward pass in one launch, handed out layer by layer: the caller makes its three mode-0
+    `enc_conv3x3` calls as ever and passes this object as `chain`.  The first call launches `enc_conv_fwd_chain` for all three
+    layers; every call returns its own layer's (yh, yl, None, gap) -- the same tensors, bit for bit, that the call would have
+    computed from the operands it names, which must be the chain's own (the previous call's planes, this layer's weights and bias)."""
+
+    def __init__(self, x3h, x3l, packed, biases):
+        self.inputs, self.packed, self.biases = [(x3h, x3l)], packed, biases
+        self.out = None
+
+    def layer(self, xh, xl, wh, wl, cout, bias, gap, lo_plane):
+        i = len(self.inputs) - 1
+        last = i == 2
+        if (i > 2 or xh is not self.inputs[i][0] or xl is not self.inputs[i][1] or wh is not self.packed[i][0]
+                or wl is not self.packed[i][1] or bias is not self.biases[i] or cout != (64, 128, 128)[i] or bool(gap) != last
+                or bool(lo_plane) == last):
+            raise RuntimeError(f"ConvFwdChain: call {i} does not name the operands of layer conv{3 + i} of this chain")
+        if self.out is None:
+            self.out = enc_conv_fwd_chain(self.inputs[0][0], self.inputs[0][1], self.packed, self.biases)
+        y3h, y3l, y4h, y4l, y5h, gp = self.out
+        yh, yl = ((y3h, y3l), (y4h, y4l), (y5h, None))[i]
+        self.inputs.append((yh, yl))
+        return yh, yl, None, (gp if last else None)
 
 
 def linear128_wgrad(dy, x):

@@ -29,6 +29,7 @@
 // registers (k-steps of 32 pixels streamed across patch boundaries), and writes its partial sums to a
 // workspace; a second kernel adds the slices in a fixed order (bitwise reproducible, no float atomics).
 #include "crw_common.h"
+#include "crw_hip_chain.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -238,97 +239,105 @@ constexpr int conv_waves_per_simd() {
 // (26 x 26 maps: 10 x 6, 6 x 10, 6 x 6); those with at most 64 go to an MTL = 4 launch whose MFMA rows are dealt to the in-map
 // pixels only (row i -> pixel (i / tw, i % tw)): 28 + 20 = 48 row tiles per 26 x 26 map instead of 63 (r02 cfg5: conv5 at 0.134 of
 // the roof against 0.20 on 10 x 10 maps).  MTL = MT keeps the 10-wide row order (pixels outside the map are computed and dropped).
-template <int SPLIT, int CIN, int COUT, int MODE, int NW, bool MAP = false, int MTL = MT>
-__global__ __launch_bounds__(NW * 64, (conv_waves_per_simd<CIN, COUT, NW, MAP>())) void conv3x3_kernel(ConvArgs a) {
-  static_assert(MAP || MTL == MT, "MTL is a MAP parameter");
-  constexpr bool REMAP = MTL < MT;
-  constexpr int NT = NW * 64;
-  constexpr int NPL = (SPLIT == 3) ? 2 : 1;
-  constexpr int CMAX = CIN > COUT ? CIN : COUT;
+//
+// The kernel is a composition of three phases -- image -> LDS; k-loop and epilogue into the staging; staged planes -> HBM -- which the
+// chain kernels further down (conv_fwd_chain_kernel) run layer after layer on one patch without leaving LDS.
+//
+// The compile-time geometry of one layer inside a workgroup of NW waves.  LO_OFF: byte offset of the lo plane (0 = the layer's
+// own, see PLANE); the chain kernels keep it the same through all their layers.
+template <int SPLIT_, int CIN_, int COUT_, int NW_, bool MAP_ = false, int MTL_ = MT, int LO_OFF = 0>
+struct ConvGeom {
+  static_assert(MAP_ || MTL_ == MT, "MTL is a MAP parameter");
+  static constexpr int SPLIT = SPLIT_, CIN = CIN_, COUT = COUT_, NW = NW_, MTL = MTL_;
+  static constexpr bool MAP = MAP_, CHAINED = LO_OFF != 0;
+  static constexpr bool REMAP = MTL < MT;
+  static constexpr int NT = NW * 64;
+  static constexpr int NPL = (SPLIT == 3) ? 2 : 1;
+  static constexpr int CMAX = CIN > COUT ? CIN : COUT;
   // LDS row strides of the input image / the output staging and byte offset of the lo plane.  MAP windows carry real
   // neighbour data in their halo rows, so the two planes cannot share a halo row: full 144-row planes on the
   // 2C+16 stride (2-way conflicts, still two workgroups per CU)
-  constexpr int RSI = MAP ? row_stride<CIN>() : crs<CIN>(), RSO = MAP ? row_stride<COUT>() : crs<COUT>();
-  constexpr int PLANE = MAP ? NPAD * row_stride<CMAX>() : PLANE_ROWS * crs<CMAX>();
-  constexpr int WN = (COUT / 16 >= NW) ? NW : COUT / 16;  // waves across the output channels
-  constexpr int WM = NW / WN;                             // waves across the pixel row tiles
-  constexpr int NTW = COUT / 16 / WN;                     // 16-wide column tiles per wave
-  constexpr int MTW = (MTL + WM - 1) / WM;                // row tiles per wave and patch (tile wm + WM*k)
-  constexpr int KCH = CIN / 32;                           // 32-deep k-steps per tap
+  static constexpr int RSI = MAP ? row_stride<CIN>() : crs<CIN>(), RSO = MAP ? row_stride<COUT>() : crs<COUT>();
+  static constexpr int PLANE = LO_OFF ? LO_OFF : (MAP ? NPAD * row_stride<CMAX>() : PLANE_ROWS * crs<CMAX>());
+  static constexpr int WN = (COUT / 16 >= NW) ? NW : COUT / 16;  // waves across the output channels
+  static constexpr int WM = NW / WN;                             // waves across the pixel row tiles
+  static constexpr int NTW = COUT / 16 / WN;                     // 16-wide column tiles per wave
+  static constexpr int MTW = (MTL + WM - 1) / WM;                // row tiles per wave and patch (tile wm + WM*k)
+  static constexpr int KCH = CIN / 32;                           // 32-deep k-steps per tap
+  static constexpr int NSTEP = 9 * KCH;
   // rows dealt out by bank residue (slot_pixel) where a wave owns all 7 row tiles; with row tiles split over waves
   // (64 / 32 output channels at 8 waves) the wave-uniform tile index costs the short epilogue more than the reads gain
   // (measured, tools/r02_conv_ab.sh: dealing by residue with split row tiles gains 2-3 % on conv4's backward-data -- 36 k-steps
   // per patch -- and nothing on the 9 / 18-step layers)
-  constexpr bool PERM = !MAP && (WM == 1 || (MODE == 1 && CIN == 128 && COUT == 64));
-  extern __shared__ __attribute__((aligned(16))) char lds[];
+  template <int MODE>
+  static constexpr bool perm() { return !MAP && (WM == 1 || (MODE == 1 && CIN == 128 && COUT == 64)); }
+};
 
-  int p0 = blockIdx.x, ty0 = 0, tx0 = 0;  // patch; MAP: origin of this workgroup's output tile in the map
-  int tw = IMG_W, npix_live = NPIX, tw_recip = 0, gap_slot = 0;
-  if constexpr (MAP) {
-    const int tile = a.tile_list[blockIdx.x % a.ncls];
-    p0 = blockIdx.x / a.ncls;
-    ty0 = (tile / a.tiles_x) * IMG_W;
-    tx0 = (tile % a.tiles_x) * IMG_W;
-    gap_slot = p0 * (a.tiles_x * a.tiles_y) + tile;
-    if constexpr (REMAP) {
-      tw = min(IMG_W, a.mw - tx0);
-      npix_live = tw * min(IMG_W, a.mh - ty0);  // <= 16 MTL by the launcher's choice of class
-      tw_recip = 65536 / tw + 1;                // (i * tw_recip) >> 16 == i / tw for i < 112, tw <= 10
-    }
+// operands of one layer (the pointer fields of ConvArgs, which see there) and, MAP only, the map's size
+struct ConvIO {
+  const uint16_t *xh, *xl, *wh, *wl;
+  const float *bias;
+  const uint16_t *maskh;
+  uint16_t *yh, *yl;
+  float *yf, *gap;
+  const float *dgap;
+  int mh, mw;
+};
+
+// what a workgroup computes: patch p0; MAP: origin of its output tile in the map and, with REMAP, the tile's live width / pixels
+struct ConvTile {
+  int p0, ty0, tx0, tw, npix_live, tw_recip, gap_slot;
+};
+
+// The thread index of a phase.  A chain runs its layers back to back in one kernel, and address arithmetic that two layers have in
+// common (pixel positions, weight-fragment offsets of equal k-steps, chunk offsets of equally wide planes) would be computed once
+// and kept in registers across k-loops that have none to spare: every phase of a chain derives its addresses anew.
+template <class G>
+__device__ __forceinline__ int phase_tid() {
+  int tid = threadIdx.x;
+  if constexpr (G::CHAINED) {
+    asm volatile("" : "+v"(tid));
+    tid &= G::NT - 1;
   }
-  (void)tw; (void)npix_live; (void)tw_recip; (void)gap_slot;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, r16 = lane & 15;
+  return tid;
+}
 
-  auto stamp = [&](int k) {  // phase timestamps, only in `make STAMPS=1` builds (tools/stamp_probe.py)
-#ifdef CRW_CONV_STAMPS
-    if (a.stamps && tid == 0) a.stamps[(long)blockIdx.x * 5 + k] = (long long)__builtin_amdgcn_s_memtime();
-#else
-    (void)k;
-#endif
-  };
-  stamp(0);
-  // ---- patch -> LDS ------------------------------------------------------------------------------
-  if constexpr (MAP) {
-    // all 144 pixels of the 12x12 window (halo included) come from the map; outside it they are zero
-    constexpr int NCH = CIN / 8, WTOT = NPAD * NCH, WIT = (WTOT + NT - 1) / NT;
-    uint4 vh[WIT], vl[WIT];
-#pragma unroll
-    for (int i = 0; i < WIT; ++i) {
-      const int c = min(tid + i * NT, WTOT - 1), wp = c / NCH, ch = c % NCH;
-      const int my = ty0 + wp / PAD_W - 1, mx = tx0 + wp % PAD_W - 1;
-      const bool ok = my >= 0 && my < a.mh && mx >= 0 && mx < a.mw;
-      const long off = (((long)p0 * a.mh + min(max(my, 0), a.mh - 1)) * a.mw + min(max(mx, 0), a.mw - 1)) * CIN + 8 * ch;
-      vh[i] = *reinterpret_cast<const uint4 *>(a.xh + off);  // unconditional, clamped (see PlaneLoad)
-      if (SPLIT == 3) vl[i] = *reinterpret_cast<const uint4 *>(a.xl + off);
-      if (!ok) vh[i] = vl[i] = uint4{0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int i = 0; i < WIT; ++i) {
-      const int c = tid + i * NT;
-      if (WTOT % NT == 0 || c < WTOT) {
-        *reinterpret_cast<uint4 *>(lds + (c / NCH) * RSI + 16 * (c % NCH)) = vh[i];
-        if (SPLIT == 3) *reinterpret_cast<uint4 *>(lds + PLANE + (c / NCH) * RSI + 16 * (c % NCH)) = vl[i];
-      }
-    }
+// ---- phase 1: patch -> LDS (the padded 12x12 image, halo zeroed) ------------------------------------
+template <class G, int MODE>
+__device__ __forceinline__ void conv_load_image(const ConvIO &a, const ConvTile &t) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];  // the workgroup's dynamic LDS: one array, whoever declares it
+  constexpr int SPLIT = G::SPLIT, CIN = G::CIN, NT = G::NT, RSI = G::RSI, PLANE = G::PLANE;
+  const int tid = phase_tid<G>(), p = G::MAP ? t.p0 : (int)blockIdx.x;
+  char *img = lds;
+  zero_halo<CIN, NT, RSI>(img, tid);
+  if (SPLIT == 3) zero_halo<CIN, NT, RSI>(img + PLANE, tid);
+  if (MODE == 1 && a.dgap) {
+    gap_planes_to_lds<CIN, NT, SPLIT, RSI>(a.xh + (long)p * NPIX * CIN, a.dgap + (long)p * CIN, img, img + PLANE, tid);
   } else {
-    const int p = p0;
-    char *img = lds;
-    zero_halo<CIN, NT, RSI>(img, tid);
-    if (SPLIT == 3) zero_halo<CIN, NT, RSI>(img + PLANE, tid);
-    if (MODE == 1 && a.dgap) {
-      gap_planes_to_lds<CIN, NT, SPLIT, RSI>(a.xh + (long)p * NPIX * CIN, a.dgap + (long)p * CIN, img, img + PLANE, tid);
-    } else {
-      PlaneLoad<CIN, NT, RSI> lh, ll;
-      lh.load(a.xh + (long)p * NPIX * CIN, tid);
-      if (SPLIT == 3) ll.load(a.xl + (long)p * NPIX * CIN, tid);
-      lh.store(img, tid);
-      if (SPLIT == 3) ll.store(img + PLANE, tid);
-    }
+    PlaneLoad<CIN, NT, RSI> lh, ll;
+    lh.load(a.xh + (long)p * NPIX * CIN, tid);
+    if (SPLIT == 3) ll.load(a.xl + (long)p * NPIX * CIN, tid);
+    lh.store(img, tid);
+    if (SPLIT == 3) ll.store(img + PLANE, tid);
   }
-  __syncthreads();
-  stamp(1);
+}
 
+// ---- phase 2: the k-loop over 9 taps x CIN / 32, then the epilogue into the staging ----------------------
+// (one function: the accumulators never leave it.  `stamp`: the phase timestamps of the diagnostic build, or a no-op.)
+// AHEAD: weight fragments are requested AHEAD k-steps before use.  DIST: activation fragments are read from LDS DIST row tiles
+// before the MFMAs that consume them (the compiler, left alone, issues them one tile = 96 cycles ahead: less than the LDS latency,
+// so a workgroup alone in its k-loop kept the matrix pipe only ~55 % busy).  The first DIST tiles of the NEXT k-step are read
+// during the last tiles of this one and carried in nah/nal.  Neither changes the order in which an output element is summed.
+template <class G, int MODE, bool PERM, int AHEAD, int DIST, class STAMP>
+__device__ __forceinline__ void conv_compute(const ConvIO &a, const ConvTile &t, STAMP &&stamp) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];  // the workgroup's dynamic LDS: one array, whoever declares it
+  constexpr int SPLIT = G::SPLIT, COUT = G::COUT, MTL = G::MTL, RSI = G::RSI, RSO = G::RSO, PLANE = G::PLANE;
+  constexpr int WN = G::WN, WM = G::WM, NTW = G::NTW, MTW = G::MTW, KCH = G::KCH, NSTEP = G::NSTEP;
+  constexpr bool MAP = G::MAP, REMAP = G::REMAP;
+  const int tid = phase_tid<G>(), lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, r16 = lane & 15;
+  const int ty0 = t.ty0, tx0 = t.tx0, tw = t.tw, npix_live = t.npix_live, tw_recip = t.tw_recip, gap_slot = t.gap_slot;
+  (void)ty0; (void)tx0; (void)tw; (void)npix_live; (void)tw_recip; (void)gap_slot;
   // row tile mt, row r16 -> interior pixel i -> LDS byte offset of this lane's 16-byte chunk of the tap-(0,0)
   // source pixel (k-chunk g); a k-step adds a wave-uniform offset (tap shift + 64 bytes per 32 channels)
   const int wm = wave / WN, wn = wave % WN;
@@ -381,14 +390,6 @@ __global__ __launch_bounds__(NW * 64, (conv_waves_per_simd<CIN, COUT, NW, MAP>()
     }
   };
 
-  constexpr int NSTEP = 9 * KCH;
-  constexpr bool OCC6 = conv_waves_per_simd<CIN, COUT, NW, MAP>() == 6;  // 80 registers: shorter look-aheads
-  constexpr int AHEAD = OCC6 ? (CIN == 32 ? 1 : 2) : 4;  // weight fragments are requested AHEAD k-steps before use
-  // Activation fragments are read from LDS DIST row tiles before the MFMAs that consume them (the compiler,
-  // left alone, issues them one tile = 96 cycles ahead: less than the LDS latency, so a workgroup alone in
-  // its k-loop kept the matrix pipe only ~55 % busy).  The first DIST tiles of the NEXT k-step are read
-  // during the last tiles of this one and carried in nah/nal.
-  constexpr int DIST = OCC6 ? (MTW < 2 ? MTW : 2) : (MTW < 3 ? MTW : 3);
   bf8 nah[DIST], nal[DIST];
 #pragma unroll
   for (int k = 0; k < DIST; ++k)
@@ -444,7 +445,8 @@ __global__ __launch_bounds__(NW * 64, (conv_waves_per_simd<CIN, COUT, NW, MAP>()
     do_step(integral_constant<bool, i == TAIL - 1>{}, step + i, bh[i], bl[i], bh[(i + AHEAD) % 5], bl[(i + AHEAD) % 5]);
   });
 
-  // ---- epilogue ----------------------------------------------------------------------------------
+  // ---- epilogue: bias + ReLU (MODE 0), the hi/lo split, the fp32 copy and the pooled means; the bf16 planes are staged in LDS
+  // as the padded 12x12 image on the row stride of COUT channels -- the layout the next layer's k-loop reads
   // C/D map: acc[k][j][r] = out[patch p0][pixel 16 (wm + WM k) + 4 g + r][channel co_w + 16 j + r16]
   float bias_r[NTW];
 #pragma unroll
@@ -453,7 +455,7 @@ __global__ __launch_bounds__(NW * 64, (conv_waves_per_simd<CIN, COUT, NW, MAP>()
   __syncthreads();  // every wave is done reading the input image: reuse LDS as the output staging
   stamp(3);
   {
-    const int p = p0;
+    const int p = MAP ? t.p0 : (int)blockIdx.x;
     char *img = lds;
     float gsum[NTW];
 #pragma unroll
@@ -527,8 +529,18 @@ __global__ __launch_bounds__(NW * 64, (conv_waves_per_simd<CIN, COUT, NW, MAP>()
       }
     }
   }
-  if (a.yh) {
-    __syncthreads();
+}
+
+// ---- phase 3: staged planes -> HBM ----------------------------------------------------------------------
+// Call behind a barrier (the staging is complete).
+template <class G, int MODE>
+__device__ __forceinline__ void conv_store(const ConvIO &a, const ConvTile &t) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];  // the workgroup's dynamic LDS: one array, whoever declares it
+  constexpr int COUT = G::COUT, NT = G::NT, NPL = G::NPL, RSO = G::RSO, PLANE = G::PLANE;
+  constexpr bool MAP = G::MAP;
+  const int tid = phase_tid<G>(), p0 = MAP ? t.p0 : (int)blockIdx.x, ty0 = t.ty0, tx0 = t.tx0;
+  (void)ty0; (void)tx0;
+  {
     // staged tiles -> global in whole 16-byte chunks; the ReLU mask of the layer below (MODE 1) is
     // applied here, 8 channels at a time, from the matching chunk of its activation plane
     constexpr int NCH = COUT / 8, TOTAL = NPIX * NCH, ITER = (TOTAL + NT - 1) / NT;
@@ -578,7 +590,132 @@ __global__ __launch_bounds__(NW * 64, (conv_waves_per_simd<CIN, COUT, NW, MAP>()
       }
     }
   }
+}
+
+// waves per SIMD and look-aheads of the stand-alone kernel (see conv_waves_per_simd): 80 registers take shorter look-aheads
+template <int CIN, int COUT, int NW, bool MAP, int MTW>
+struct ConvAhead {
+  static constexpr bool OCC6 = conv_waves_per_simd<CIN, COUT, NW, MAP>() == 6;
+  static constexpr int AHEAD = OCC6 ? (CIN == 32 ? 1 : 2) : 4;
+  static constexpr int DIST = OCC6 ? (MTW < 2 ? MTW : 2) : (MTW < 3 ? MTW : 3);
+};
+
+template <int SPLIT, int CIN, int COUT, int MODE, int NW, bool MAP = false, int MTL = MT>
+__global__ __launch_bounds__(NW * 64, (conv_waves_per_simd<CIN, COUT, NW, MAP>())) void conv3x3_kernel(ConvArgs a) {
+  using G = ConvGeom<SPLIT, CIN, COUT, NW, MAP, MTL>;
+  constexpr bool REMAP = G::REMAP, PERM = G::template perm<MODE>();
+  constexpr int NT = G::NT, RSI = G::RSI, PLANE = G::PLANE;
+  using LA = ConvAhead<CIN, COUT, NW, MAP, G::MTW>;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+
+  int p0 = blockIdx.x, ty0 = 0, tx0 = 0;  // patch; MAP: origin of this workgroup's output tile in the map
+  int tw = IMG_W, npix_live = NPIX, tw_recip = 0, gap_slot = 0;
+  if constexpr (MAP) {
+    const int tile = a.tile_list[blockIdx.x % a.ncls];
+    p0 = blockIdx.x / a.ncls;
+    ty0 = (tile / a.tiles_x) * IMG_W;
+    tx0 = (tile % a.tiles_x) * IMG_W;
+    gap_slot = p0 * (a.tiles_x * a.tiles_y) + tile;
+    if constexpr (REMAP) {
+      tw = min(IMG_W, a.mw - tx0);
+      npix_live = tw * min(IMG_W, a.mh - ty0);  // <= 16 MTL by the launcher's choice of class
+      tw_recip = 65536 / tw + 1;                // (i * tw_recip) >> 16 == i / tw for i < 112, tw <= 10
+    }
+  }
+  const ConvTile t{p0, ty0, tx0, tw, npix_live, tw_recip, gap_slot};
+  const ConvIO io{a.xh, a.xl, a.wh, a.wl, a.bias, a.maskh, a.yh, a.yl, a.yf, a.gap, a.dgap, a.mh, a.mw};
+  const int tid = threadIdx.x;
+
+  auto stamp = [&](int k) {  // phase timestamps, only in `make STAMPS=1` builds (tools/stamp_probe.py)
+#ifdef CRW_CONV_STAMPS
+    if (a.stamps && tid == 0) a.stamps[(long)blockIdx.x * 5 + k] = (long long)__builtin_amdgcn_s_memtime();
+#else
+    (void)k;
+#endif
+  };
+  stamp(0);
+  // ---- patch -> LDS ------------------------------------------------------------------------------
+  if constexpr (MAP) {
+    // all 144 pixels of the 12x12 window (halo included) come from the map; outside it they are zero
+    constexpr int NCH = CIN / 8, WTOT = NPAD * NCH, WIT = (WTOT + NT - 1) / NT;
+    uint4 vh[WIT], vl[WIT];
+#pragma unroll
+    for (int i = 0; i < WIT; ++i) {
+      const int c = min(tid + i * NT, WTOT - 1), wp = c / NCH, ch = c % NCH;
+      const int my = ty0 + wp / PAD_W - 1, mx = tx0 + wp % PAD_W - 1;
+      const bool ok = my >= 0 && my < a.mh && mx >= 0 && mx < a.mw;
+      const long off = (((long)p0 * a.mh + min(max(my, 0), a.mh - 1)) * a.mw + min(max(mx, 0), a.mw - 1)) * CIN + 8 * ch;
+      vh[i] = *reinterpret_cast<const uint4 *>(a.xh + off);  // unconditional, clamped (see PlaneLoad)
+      if (SPLIT == 3) vl[i] = *reinterpret_cast<const uint4 *>(a.xl + off);
+      if (!ok) vh[i] = vl[i] = uint4{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int i = 0; i < WIT; ++i) {
+      const int c = tid + i * NT;
+      if (WTOT % NT == 0 || c < WTOT) {
+        *reinterpret_cast<uint4 *>(lds + (c / NCH) * RSI + 16 * (c % NCH)) = vh[i];
+        if (SPLIT == 3) *reinterpret_cast<uint4 *>(lds + PLANE + (c / NCH) * RSI + 16 * (c % NCH)) = vl[i];
+      }
+    }
+  } else {
+    conv_load_image<G, MODE>(io, t);
+  }
+  __syncthreads();
+  stamp(1);
+
+  conv_compute<G, MODE, PERM, LA::AHEAD, LA::DIST>(io, t, stamp);
+  if (a.yh) {
+    __syncthreads();
+    conv_store<G, MODE>(io, t);
+  }
   stamp(4);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Chains: conv3 -> conv4 -> conv5 of one patch in ONE workgroup (hi/lo pairs only).  No layer depends on another patch, and a
+// layer's epilogue stages its planes in LDS as the very image the next layer's k-loop reads, so the activations go from layer to
+// layer in LDS: a layer's planes are still stored to HBM (the backward pass reads them), but nothing is read back, no image is
+// reloaded, and a workgroup's conv3 / conv4 phases run beside the co-resident workgroup's conv5 phase.  Every k-loop and epilogue
+// is the stand-alone kernel's (same phases, same order of summation: bit-identical results); only the look-aheads are those of
+// the 4-waves-per-SIMD build throughout.  The lo plane sits at CHAIN_LO in every layer, the LDS footprint is conv5's: two
+// workgroups per CU.
+struct ConvChainArgs {
+  ConvIO l[3];  // the layers in the order they run; l[0].xh / xl is the chain's input
+  int P;
+};
+constexpr int CHAIN_NW = 8, CHAIN_LO = PLANE_ROWS * crs<128>();
+
+// One layer of a chain on the image in LDS.  NEXT: another layer follows -- the staged planes get the zero halo of an input image
+// (the image they replace had another row stride) before the barrier behind which they are stored and read again.
+template <class G, bool NEXT>
+__device__ __forceinline__ void conv_chain_layer(const ConvIO &io, const ConvTile &t) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  constexpr int MODE = 0;
+  constexpr bool PERM = G::template perm<MODE>();
+  constexpr int DIST = G::MTW < 3 ? G::MTW : 3;
+  const int tid = phase_tid<G>();
+  conv_compute<G, MODE, PERM, 4, DIST>(io, t, [](int) {});
+  if (NEXT) {
+    zero_halo<G::COUT, G::NT, G::RSO>(lds, tid);
+    zero_halo<G::COUT, G::NT, G::RSO>(lds + G::PLANE, tid);
+  }
+  __syncthreads();
+  conv_store<G, MODE>(io, t);
+}
+
+template <int SPLIT>
+__global__ __launch_bounds__(CHAIN_NW * 64, CHAIN_NW / 2) void conv_fwd_chain_kernel(ConvChainArgs a) {
+  static_assert(SPLIT == 3, "the chains run on hi/lo pairs");
+  using G3 = ConvGeom<SPLIT, 32, 64, CHAIN_NW, false, MT, CHAIN_LO>;
+  using G4 = ConvGeom<SPLIT, 64, 128, CHAIN_NW, false, MT, CHAIN_LO>;
+  using G5 = ConvGeom<SPLIT, 128, 128, CHAIN_NW, false, MT, CHAIN_LO>;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const ConvTile t{(int)blockIdx.x, 0, 0, IMG_W, NPIX, 0, 0};
+  conv_load_image<G3, 0>(a.l[0], t);
+  __syncthreads();
+  conv_chain_layer<G3, true>(a.l[0], t);
+  conv_chain_layer<G4, true>(a.l[1], t);
+  conv_chain_layer<G5, false>(a.l[2], t);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1464,6 +1601,22 @@ int launch_conv(const ConvArgs &a, hipStream_t s) {
   return launch_conv_nw<SPLIT, CIN, COUT, MODE, (SPLIT == 3 ? 8 : 4)>(a, s);
 }
 
+// a chain kernel: one workgroup per patch on conv5's LDS footprint
+template <class K>
+int launch_chain(K kernel, bool &attr, const ConvChainArgs &a, hipStream_t s) {
+  constexpr size_t lds = conv_lds_bytes<128>(2);
+  static_assert(lds == (size_t)CHAIN_LO + NPAD * crs<128>() && 2 * lds <= 160 * 1024, "two workgroups per CU");
+  if (!attr) {
+    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+      g_last_hip_error = (int)hipGetLastError();
+      return CRW_EHIP;
+    }
+    attr = true;
+  }
+  hipLaunchKernelGGL(kernel, dim3(a.P), dim3(CHAIN_NW * 64), lds, s, a);
+  return check_launch();
+}
+
 // input channels per workgroup (one 16-channel tile per wave)
 constexpr int wgrad_nci(int cin) { return cin > 64 ? 64 : cin; }
 
@@ -1621,6 +1774,21 @@ int crw_enc_conv3x3(int mode, int split, int P, int cin, int cout, const uint16_
   CRW_CONV_CASE(64, 32)
 #undef CRW_CONV_CASE
   return CRW_EINVAL;
+}
+
+int crw_enc_conv_fwd_chain(int split, int P, const uint16_t *x_hi, const uint16_t *x_lo, const uint16_t *w3_hi,
+                           const uint16_t *w3_lo, const float *b3, const uint16_t *w4_hi, const uint16_t *w4_lo, const float *b4,
+                           const uint16_t *w5_hi, const uint16_t *w5_lo, const float *b5, uint16_t *y3_hi, uint16_t *y3_lo,
+                           uint16_t *y4_hi, uint16_t *y4_lo, uint16_t *y5_hi, float *gap, crw_stream_t stream) {
+  clear_stale_error();
+  if (split != 3 || P < 1 || !x_hi || !x_lo || !w3_hi || !w3_lo || !w4_hi || !w4_lo || !w5_hi || !w5_lo) return CRW_EINVAL;
+  if (!y3_hi || !y3_lo || !y4_hi || !y4_lo || !y5_hi) return CRW_EINVAL;
+  ConvChainArgs a{{{x_hi, x_lo, w3_hi, w3_lo, b3, nullptr, y3_hi, y3_lo, nullptr, nullptr, nullptr, 0, 0},
+                   {nullptr, nullptr, w4_hi, w4_lo, b4, nullptr, y4_hi, y4_lo, nullptr, nullptr, nullptr, 0, 0},
+                   {nullptr, nullptr, w5_hi, w5_lo, b5, nullptr, y5_hi, nullptr, nullptr, gap, nullptr, 0, 0}},
+                  P};
+  static bool attr = false;
+  return launch_chain(conv_fwd_chain_kernel<3>, attr, a, (hipStream_t)stream);
 }
 
 static int wgrad_groups(int cin) { return cin / wgrad_nci(cin); }

@@ -38,10 +38,13 @@ class _HipEncoder(torch.autograd.Function):
         # the front end also keeps its pool1 planes and pooling codes (10 KB per patch): its backward kernel then skips the
         # conv1 -> pool1 -> conv2 recomputation
         x3h, x3l, fsaved = crw_hip.enc_front_fwd(split, x, w1, b1, w2p[:2], b2, save=True)
-        y3h, y3l, _, _ = crw_hip.enc_conv3x3(0, split, x3h, x3l, packed[0][0], packed[0][1], 64, bias=b3)
-        y4h, y4l, _, _ = crw_hip.enc_conv3x3(0, split, y3h, y3l, packed[1][0], packed[1][1], 128, bias=b4)
+        # hi/lo pairs: the three layers in ONE launch, the activations handed from layer to layer in LDS (same bits); the calls
+        # below are then served from it.  CRW_CONV_CHAIN=0, bench.py's per-kernel events or plain bf16: a launch per layer
+        chain = crw_hip.ConvFwdChain(x3h, x3l, packed, (b3, b4, b5)) if split == 3 and crw_hip.conv_chain_on() else None
+        y3h, y3l, _, _ = crw_hip.enc_conv3x3(0, split, x3h, x3l, packed[0][0], packed[0][1], 64, bias=b3, chain=chain)
+        y4h, y4l, _, _ = crw_hip.enc_conv3x3(0, split, y3h, y3l, packed[1][0], packed[1][1], 128, bias=b4, chain=chain)
         y5h, _, _, gap = crw_hip.enc_conv3x3(0, split, y4h, y4l, packed[2][0], packed[2][1], 128, bias=b5, gap=True,
-                                             lo_plane=False)  # only the sign of y5 is needed later
+                                             lo_plane=False, chain=chain)  # only the sign of y5 is needed later
         ctx.split = split
         # lo planes are None for plain bf16; everything goes through save_for_backward (in-place weight updates between
         # forward and backward are detected, a second backward without retain_graph raises autograd's own error)
