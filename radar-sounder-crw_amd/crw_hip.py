@@ -156,6 +156,13 @@ CHAIN_SIGNATURES = {
     "crw_enc_conv_fwd_chain": (_c_int, [_c_int, _c_int] + [_p] * 18),
 }
 
+# include/crw_hip_restart.h, likewise: label propagation whose context restarts at an origin frame (optional: `has_anchor_restart()`)
+RESTART_SIGNATURES = {
+    "crw_labelprop_topk_origin": (_c_int, [_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f, _c_int, _c_int, _c_int, _p, _p, _p, _c_int, _p]),
+    "crw_labelprop_propagate_origin": (_c_int, [_p, _p, _p] + [_c_int] * 6 + [_p, _p, _p, _p]),
+    "crw_labelprop_propagate_origin_batch": (_c_int, [_p, _p, _p, _c_sz] + [_c_int] * 7 + [_p, _p, _p, _p]),
+}
+
 # entry points added at ABI 8 without a bump: a library built before them still loads, `has_sweep()` tells
 SWEEP_ENTRY_POINTS = ("crw_labelprop_topk_scores", "crw_labelprop_sweep_weights", "crw_labelprop_propagate_batch")
 
@@ -190,7 +197,11 @@ POSTERIOR_BATCH_ENTRY_POINTS = ("crw_labelmap_posterior_workspace_batch", "crw_l
 # likewise: conv3 -> conv4 -> conv5 of the CNN encoder in one launch (`has_conv_chain()`; without it the layers run one by one)
 CONV_CHAIN_ENTRY_POINTS = tuple(CHAIN_SIGNATURES)
 
+# likewise: the sliding rule with a per-frame origin, anchor_context='restart' (`has_anchor_restart()`)
+ANCHOR_RESTART_ENTRY_POINTS = tuple(RESTART_SIGNATURES)
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
+ANCHOR_CONTEXTS = ("clamp", "restart")  # what a fully labelled anchor trace does to the frames behind it
 
 # group -> its entry points.  `has_<group>()` tells whether the loaded library exports them, `_<group>_lib()` is lib() or the
 # error that names the stale library
@@ -198,7 +209,7 @@ OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_E
                          "dense_batch": DENSE_BATCH_ENTRY_POINTS, "horizons": HORIZONS_ENTRY_POINTS,
                          "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS, "joint": JOINT_ENTRY_POINTS,
                          "posterior": POSTERIOR_ENTRY_POINTS, "posterior_batch": POSTERIOR_BATCH_ENTRY_POINTS,
-                         "conv_chain": CONV_CHAIN_ENTRY_POINTS}
+                         "conv_chain": CONV_CHAIN_ENTRY_POINTS, "anchor_restart": ANCHOR_RESTART_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -214,7 +225,7 @@ def lib():
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
         missing = {n for names in OPTIONAL_ENTRY_POINTS.values() for n in names if not hasattr(handle, n)}
-        for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES, **RESTART_SIGNATURES}.items():
             if name in missing:
                 continue
             fn = getattr(handle, name)
@@ -258,6 +269,7 @@ has_joint, _joint_lib = _optional("joint", "the joint ordered label map's entry 
 has_posterior, _posterior_lib = _optional("posterior", "the ordered maps' posterior entry points")
 has_posterior_batch, _posterior_batch_lib = _optional("posterior_batch", "the batched posterior entry points")
 has_conv_chain, _conv_chain_lib = _optional("conv_chain", "the conv-trunk chain entry point")
+has_anchor_restart, _anchor_restart_lib = _optional("anchor_restart", "the entry points that take a per-frame origin")
 
 
 def check_context(context):
@@ -387,11 +399,92 @@ def normalize(emb):
     return ehat
 
 
-def labelprop_topk(ehat, cxt_size, radius, temp, knn, first_frame=1, grid_w=1):
-    """grid_w: the N nodes of a frame form an (N / grid_w) x grid_w grid (1 = a radargram's column of patches)"""
+def check_anchor_context(anchor_context):
+    if anchor_context not in ANCHOR_CONTEXTS:
+        raise ValueError(f"anchor_context must be one of {ANCHOR_CONTEXTS} (got {anchor_context!r})")
+    return anchor_context
+
+
+def anchor_origins(anchors, nclasses, T, first_frame=1):
+    """The policy of anchor_context='restart': origin [T] int32 (a CPU tensor) for the `origin=` arguments below.  A frame is an
+    ORIGIN when it is frame 0, or when all N of its nodes are clamped by `anchors` [T, N] int8 (a class in [0, nclasses); frames
+    before first_frame are never clamped, so they restart nothing); origin[n] is the latest origin < n, origin[0] = 0.  A partially
+    anchored frame clamps and restarts nothing.  One host read when `anchors` is a device tensor."""
+    a = anchors.detach().cpu().to(torch.int64)
+    if a.dim() != 2 or a.shape[0] != T:
+        raise ValueError(f"anchors must be [{T}, N] (got {tuple(anchors.shape)})")
+    full = ((a >= 0) & (a < int(nclasses))).all(1)
+    full[:max(int(first_frame), 1)] = False
+    latest = torch.cummax(torch.where(full, torch.arange(T), torch.zeros((), dtype=torch.int64)), 0)[0]
+    origin = torch.zeros(T, dtype=torch.int32)
+    origin[1:] = latest[:-1].to(torch.int32)
+    return origin
+
+
+def check_origin(origin, T):
+    """The chain rule of include/crw_hip_restart.h, checked on the host: origin [T] integers with origin[n] in {origin[n - 1], n - 1}
+    and 0 <= origin[n] < n for n >= 1 (origin[0] is not read).  -> the values as a list."""
+    if origin.dim() != 1 or origin.shape[0] != T or origin.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"origin must be [{T}] int32 (got {tuple(origin.shape)}, {origin.dtype})")
+    o = origin.detach().cpu().tolist()
+    for n in range(1, T):
+        if not 0 <= o[n] < n or (n > 1 and o[n] not in (o[n - 1], n - 1)):
+            raise ValueError(f"origin[{n}] = {o[n]} breaks the chain rule: it must be origin[{n - 1}] = {o[n - 1]} or {n - 1}")
+    return o
+
+
+def origin_stretches(o, T, first_frame=1):
+    """[(a, e)]: the frames a + 1 .. e (those of first_frame .. T - 1 among them) share the origin a -- the sub-items ehat[a:e + 1]
+    the segmented construction runs the entry points without origins on.  o: `check_origin`'s list."""
+    out = []
+    for n in range(max(int(first_frame), 1), T):
+        if out and out[-1][0] == o[n]:
+            out[-1][1] = n
+        else:
+            out.append([o[n], n])
+    return [tuple(x) for x in out]
+
+
+def anchors_restart_segmented():
+    """CRW_ANCHORS_RESTART_SEGMENTED=1 (read per call): every `origin=` call below is built from the entry points WITHOUT origins, one
+    call per stretch between origins on the sub-item that starts there -- the A/B arm and the device-side definition of the rule."""
+    return os.environ.get("CRW_ANCHORS_RESTART_SEGMENTED") == "1"
+
+
+def _origin_dev(origin, device):
+    return origin.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _topk_origin(ehat, cxt_size, radius, temp, k, first_frame, grid_w, WV, I, raw, origin):
+    """`labelprop_topk` / `labelprop_topk_scores` under the restart rule: crw_labelprop_topk_origin, or the segmented construction."""
+    T, N, C = ehat.shape
+    o = check_origin(origin, T)
+    if anchors_restart_segmented():
+        fn, what = (_sweep_lib().crw_labelprop_topk_scores, "crw_labelprop_topk_scores") if raw else \
+            (lib().crw_labelprop_topk_grid, "crw_labelprop_topk_grid")
+        for a, e in origin_stretches(o, T, first_frame):
+            ff = max(int(first_frame) - a, 1)
+            at = a + ff - int(first_frame)  # the stretch's first frame in the lists
+            _check(fn(_dev(ehat[a:], "ehat"), e + 1 - a, N, C, int(cxt_size), int(radius), float(temp), int(k), ff, int(grid_w),
+                      _dev(WV[at:], "W"), _dev(I[at:], "I", torch.int32), _stream()), what)
+        return WV, I
+    org = _origin_dev(origin, ehat.device)
+    _check(_anchor_restart_lib().crw_labelprop_topk_origin(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(radius), float(temp), int(k),
+                                                           int(first_frame), int(grid_w), _dev(org, "origin", torch.int32),
+                                                           _dev(WV, "W"), _dev(I, "I", torch.int32), int(raw), _stream()),
+           "crw_labelprop_topk_origin")
+    return WV, I
+
+
+def labelprop_topk(ehat, cxt_size, radius, temp, knn, first_frame=1, grid_w=1, origin=None):
+    """grid_w: the N nodes of a frame form an (N / grid_w) x grid_w grid (1 = a radargram's column of patches).
+    origin ([T] int32, `anchor_origins`): frame n scores against frame origin[n] and the frames between it and n only, as frame
+    n - origin[n] of the item that starts there (include/crw_hip_restart.h); None: every frame scores from frame 0."""
     T, N, C = ehat.shape
     W = torch.empty(T - first_frame, knn, N, device=ehat.device, dtype=torch.float32)
     I = torch.empty(T - first_frame, knn, N, device=ehat.device, dtype=torch.int32)
+    if origin is not None:
+        return _topk_origin(ehat, cxt_size, radius, temp, knn, first_frame, grid_w, W, I, 0, origin)
     _check(lib().crw_labelprop_topk_grid(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(radius), float(temp), int(knn),
                                          int(first_frame), int(grid_w), _dev(W, "W"), _dev(I, "I", torch.int32), _stream()),
            "crw_labelprop_topk_grid")
@@ -502,7 +595,33 @@ def _propagate_anchored(seed, W, I, anchors, T, N, M, knn, first_frame, cxt_size
     return L, pred
 
 
-def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_size=None, context="reference", anchors=None):
+def _propagate_origin_segmented(seed, W, I, o, T, N, M, knn, first_frame, cxt_size, L, pred):
+    """The restart rule from crw_labelprop_propagate_sliding alone: per stretch (a, e) of `origin_stretches` one call on the sub-item
+    L[a * N:(e + 1) * N] -- frame a is the sub-item's frame 0 and the caller's (seed = NULL; the seed itself only where a = 0 holds the
+    call's first frame) -- with the list slices that start at the stretch's first frame, marks and all.  pred of a sub-item goes
+    through a [N, e + 1 - a] view of one scratch buffer, the entry point's layout."""
+    fn = _sliding_lib().crw_labelprop_propagate_sliding
+    scratch = torch.empty(N * T, device=pred.device, dtype=pred.dtype)
+    if seed is not None and o[first_frame] != 0:  # no stretch starts at frame 0: the seed's frame is written here
+        L[:N] = (seed[:, None] == torch.arange(M, device=seed.device)).to(L.dtype)
+        pred[:, 0] = seed
+    for a, e in origin_stretches(o, T, first_frame):
+        Ts, ff = e + 1 - a, max(first_frame - a, 1)
+        at = a + ff - first_frame
+        first = seed is not None and a == 0
+        whole = a == 0 and Ts == T
+        part = pred if whole else scratch[:N * Ts].view(N, Ts)
+        _check(fn(_dev(seed, "seed") if first else None, _dev(W[at:], "W"), _dev(I[at:], "I", torch.int32), Ts, N, M, knn, ff,
+                  int(cxt_size), _dev(L[a * N:], "L"), _dev(part, "pred"), _stream()), "crw_labelprop_propagate_sliding")
+        if not whole:
+            pred[:, a + ff:e + 1] = part[:, ff:]
+            if first:
+                pred[:, 0] = part[:, 0]
+    return L, pred
+
+
+def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_size=None, context="reference", anchors=None,
+                     origin=None):
     """cxt_size: the context size the lists were made with by `labelprop_topk` (same first_frame) -> crw_labelprop_propagate
     (chained frames in one workgroup, the frames beyond the context bound all at once); None: any lists, one workgroup.
     context='sliding' (needs cxt_size): the indices address the frames they were scored on -- crw_labelprop_propagate_sliding,
@@ -512,11 +631,20 @@ def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_
     free; rows of frames before first_frame are ignored.  ONE crw_labelprop_propagate_sliding call on a marked COPY of W and I
     (`mark_anchors`; the caller's lists are left as they are -- a caller that owns its lists marks them itself and passes no
     anchors).  CRW_ANCHORS_SEGMENTED=1 (read per call), or a library that does not know the marks (`has_anchor_lists()`): once per
-    stretch between anchored frames instead (`_propagate_anchored`), the same bits.  None: the call is what it was."""
+    stretch between anchored frames instead (`_propagate_anchored`), the same bits.  None: the call is what it was.
+    origin (needs context='sliding'; [T] int32, `anchor_origins`): the lists are `labelprop_topk(..., origin=origin)`'s and frame n
+    reads the rows of the item that starts at origin[n] (include/crw_hip_restart.h) -- ONE crw_labelprop_propagate_origin call,
+    anchors marked as above; CRW_ANCHORS_RESTART_SEGMENTED=1 (read per call): crw_labelprop_propagate_sliding once per stretch
+    between origins on the sub-item that starts there, the same bits."""
     knn = W.shape[1]
     check_context(context)
     if context == "sliding" and cxt_size is None:
         raise ValueError("context='sliding' needs cxt_size (the context size the lists were made with)")
+    if origin is not None:
+        if context != "sliding":
+            raise ValueError("origin needs context='sliding' (and cxt_size): the restart rule is defined on the frames the lists were "
+                             "scored on")
+        o = check_origin(origin, T)
     if anchors is not None:
         if context != "sliding":
             raise ValueError("anchors need context='sliding' (and cxt_size): under the reference rule a late frame never reads a "
@@ -527,9 +655,18 @@ def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_
     if pred is None:
         pred = torch.zeros(N, T, device=W.device, dtype=torch.float32)
     if anchors is not None:
-        if anchors_segmented():
+        if origin is None and anchors_segmented():
             return _propagate_anchored(seed, W, I, anchors, T, N, M, knn, int(first_frame), cxt_size, L, pred)
         W, I = mark_anchors(W.clone(), I.clone(), anchors, M, int(first_frame))
+    if origin is not None:
+        if anchors_restart_segmented():
+            return _propagate_origin_segmented(seed, W, I, o, T, N, M, knn, int(first_frame), cxt_size, L, pred)
+        org = _origin_dev(origin, W.device)
+        _check(_anchor_restart_lib().crw_labelprop_propagate_origin(_dev(seed, "seed") if seed is not None else None, _dev(W, "W"),
+                                                                    _dev(I, "I", torch.int32), T, N, M, knn, int(first_frame),
+                                                                    int(cxt_size), _dev(org, "origin", torch.int32), _dev(L, "L"),
+                                                                    _dev(pred, "pred"), _stream()), "crw_labelprop_propagate_origin")
+        return L, pred
     if context == "sliding":
         _check(_sliding_lib().crw_labelprop_propagate_sliding(_dev(seed, "seed") if seed is not None else None, _dev(W, "W"),
                                                               _dev(I, "I", torch.int32), T, N, M, knn, int(first_frame), int(cxt_size),
@@ -547,10 +684,10 @@ def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_
     return L, pred
 
 
-def labelprop_topk_scores(ehat, cxt_size, radius, temp, kcap, first_frame=1, grid_w=1, out=None):
+def labelprop_topk_scores(ehat, cxt_size, radius, temp, kcap, first_frame=1, grid_w=1, out=None, origin=None):
     """`labelprop_topk` with the selected logits V [T-first_frame, kcap, N] instead of their softmax weights (empty slot -inf), and
     the same I: the lists of every knn <= kcap are their first knn entries (`labelprop_sweep_weights` makes the weights).
-    out: (V, I) tensors of those shapes to write into."""
+    out: (V, I) tensors of those shapes to write into.  origin: as in `labelprop_topk`."""
     T, N, C = ehat.shape
     if out is not None:
         V, I = out
@@ -559,6 +696,8 @@ def labelprop_topk_scores(ehat, cxt_size, radius, temp, kcap, first_frame=1, gri
     else:
         V = torch.empty(T - first_frame, kcap, N, device=ehat.device, dtype=torch.float32)
         I = torch.empty(T - first_frame, kcap, N, device=ehat.device, dtype=torch.int32)
+    if origin is not None:
+        return _topk_origin(ehat, cxt_size, radius, temp, kcap, first_frame, grid_w, V, I, 1, origin)
     _check(_sweep_lib().crw_labelprop_topk_scores(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(radius), float(temp), int(kcap),
                                                   int(first_frame), int(grid_w), _dev(V, "V"), _dev(I, "I", torch.int32), _stream()),
            "crw_labelprop_topk_scores")
@@ -582,13 +721,20 @@ def labelprop_sweep_weights(V, knns, out=None):
     return W
 
 
-def labelprop_propagate_batch(seed, W, I, T, N, M, first_frame=1, cxt_size=None, L=None, pred=None, context="reference"):
+def labelprop_propagate_batch(seed, W, I, T, N, M, first_frame=1, cxt_size=None, L=None, pred=None, context="reference", origin=None):
     """G configurations' `labelprop_gather(..., cxt_size=cxt_size, context=context)` in one call: W [G, T-first_frame, knn, N]; I the same shape, or
     [T-first_frame, knn, N] shared by all -> (L [G, T*N, M], pred [G, N, T]), slice g bitwise what the per-configuration call
-    gives on W[g] (shorter lists padded with zero weights).  seed None: L's frames before first_frame are filled by the caller."""
+    gives on W[g] (shorter lists padded with zero weights).  seed None: L's frames before first_frame are filled by the caller.
+    origin (needs context='sliding'): ONE [T] int32 origin array for the G configurations -- crw_labelprop_propagate_origin_batch;
+    CRW_ANCHORS_RESTART_SEGMENTED=1 (read per call): the segmented `labelprop_gather(origin=)`, configuration by configuration."""
     if cxt_size is None:
         raise ValueError("cxt_size (the context size the lists were made with) is required")
     check_context(context)
+    if origin is not None:
+        if context != "sliding":
+            raise ValueError("origin needs context='sliding' (and cxt_size): the restart rule is defined on the frames the lists were "
+                             "scored on")
+        check_origin(origin, T)
     G, F, knn = W.shape[0], W.shape[1], W.shape[2]
     if W.dim() != 4 or F != T - first_frame or W.shape[3] != N:
         raise RuntimeError(f"W must be [G, {T - first_frame}, knn, {N}] (got {tuple(W.shape)})")
@@ -606,6 +752,19 @@ def labelprop_propagate_batch(seed, W, I, T, N, M, first_frame=1, cxt_size=None,
         pred = torch.zeros(G, N, T, device=W.device, dtype=torch.float32)
     if tuple(L.shape) != (G, T * N, M) or tuple(pred.shape) != (G, N, T):
         raise RuntimeError(f"L must be {(G, T * N, M)} and pred {(G, N, T)} (got {tuple(L.shape)}, {tuple(pred.shape)})")
+    if origin is not None:
+        if anchors_restart_segmented():
+            for g in range(G):
+                labelprop_gather(seed, W[g], I[g] if stride else I, T, N, M, first_frame, L[g], pred[g], cxt_size, "sliding", origin=origin)
+            return L, pred
+        org = _origin_dev(origin, W.device)
+        _check(_anchor_restart_lib().crw_labelprop_propagate_origin_batch(_dev(seed, "seed") if seed is not None else None, _dev(W, "W"),
+                                                                          _dev(I, "I", torch.int32), stride, G, T, N, M, knn,
+                                                                          int(first_frame), int(cxt_size),
+                                                                          _dev(org, "origin", torch.int32), _dev(L, "L"),
+                                                                          _dev(pred, "pred"), _stream()),
+               "crw_labelprop_propagate_origin_batch")
+        return L, pred
     if context == "sliding":
         _check(_sliding_lib().crw_labelprop_propagate_sliding_batch(_dev(seed, "seed") if seed is not None else None, _dev(W, "W"),
                                                                     _dev(I, "I", torch.int32), stride, G, T, N, M, knn,

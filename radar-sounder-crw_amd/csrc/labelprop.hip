@@ -13,6 +13,7 @@
 // [frame 0, last cxt frames] but are applied to the untruncated label list.  The opt-in 'sliding' rule
 // (crw_labelprop_propagate_sliding) applies them to the frames they were scored on instead; the lists are the same.
 #include "crw_common.h"
+#include "crw_hip_restart.h"
 #include <cstdlib>
 
 namespace crw {
@@ -24,12 +25,17 @@ constexpr int MAX_KNN = 64;
 // query (i, j) when (i - i')^2 + (j - j')^2 < radius^2 (MaskedAttention.make, src/imported/maskedatt.py:232-245); candidates are the
 // keys of the clipped bounding box of that disc, in node order, and box keys outside the disc never score (the reference gives them
 // logit -1e10 / temp: softmax weight exactly 0).
+// ORG (crw_labelprop_topk_origin, include/crw_hip_restart.h): frame na is scored as frame n = na - a of the item that starts at its
+// origin a = origin[na] -- the key base moves to frame a, the context arithmetic runs on n, the lists go to frame na's place.
+__device__ inline int frame_origin(const int32_t *origin, int n) { return min(max(origin[n], 0), n - 1); }  // 0 <= a < n whatever it holds
+template <bool ORG>
 __global__ __launch_bounds__(256) void labelprop_topk_kernel(const float *__restrict__ ehat, int T, int N, int C,
                                                              int cxt, int radius, float temp, int knn,
                                                              int first_frame, int gw, float *__restrict__ W,
-                                                             int32_t *__restrict__ I, int raw) {
+                                                             int32_t *__restrict__ I, int raw, const int32_t *__restrict__ origin) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int q = blockIdx.x, n = blockIdx.y + first_frame;
+  const int q = blockIdx.x, na = blockIdx.y + first_frame, org = ORG ? frame_origin(origin, na) : 0, n = na - org;
+  if (ORG) ehat += (long)org * N * C;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool trunc = n > cxt + 1;
   const int nf = trunc ? cxt + 1 : n;
@@ -116,7 +122,7 @@ __global__ __launch_bounds__(256) void labelprop_topk_kernel(const float *__rest
     } else if (raw) {
       w = -INFINITY;
     }
-    const long o = ((long)(n - first_frame) * knn + tid) * N + q;
+    const long o = ((long)(na - first_frame) * knn + tid) * N + q;
     W[o] = w;
     I[o] = idx;
   }
@@ -139,16 +145,19 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // 80 - 100 context frames: 3 888 / 11 781 candidates per query).  The argument holds chunk after chunk -- the k best carried into
 // each selection come from earlier chunks, so they have the lowest indices -- and the chunk size is that of NCH = 2 (pf * max_bi
 // <= 64 * TK_NV / 2 in registers, 64 KiB of scores at 1 024 candidates: two workgroups per CU).
-template <int CSTEPS, int NCH>  // C / 16: float4 per lane and row
+template <int CSTEPS, int NCH, bool ORG>  // C / 16: float4 per lane and row; ORG: as in labelprop_topk_kernel
 __global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_kernel(const float *__restrict__ ehat, int T, int N, int cxt, int radius,
                                                                            float temp, int knn, int first_frame, int maxcand, int pf,
-                                                                           float *__restrict__ W, int32_t *__restrict__ I, int raw) {
+                                                                           float *__restrict__ W, int32_t *__restrict__ I, int raw,
+                                                                           const int32_t *__restrict__ origin) {
   constexpr int C = 16 * CSTEPS, NV = TK_NV / (NCH == 1 ? 1 : 2);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float *val = smem;  // [TK_Q][maxcand] (maxcand: candidates of ONE chunk)
   __shared__ float sel_v[TK_Q][MAX_KNN];
   __shared__ int sel_i[TK_Q][MAX_KNN];
-  const int q0 = blockIdx.x * TK_Q, nq = min(TK_Q, N - q0), n = blockIdx.y + first_frame;
+  const int q0 = blockIdx.x * TK_Q, nq = min(TK_Q, N - q0), na = blockIdx.y + first_frame;
+  const int org = ORG ? frame_origin(origin, na) : 0, n = na - org;
+  if (ORG) ehat += (long)org * N * C;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, g = lane >> 4;
   const bool trunc = n > cxt + 1;
   const int nf = trunc ? cxt + 1 : n;
@@ -308,7 +317,7 @@ __global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_k
         } else if (raw) {
           w = -INFINITY;
         }
-        const long o = ((long)(n - first_frame) * knn + lane) * N + q0 + u;
+        const long o = ((long)(na - first_frame) * knn + lane) * N + q0 + u;
         W[o] = w;
         I[o] = idx;
       }
@@ -334,23 +343,27 @@ int launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... arg
 
 template <int CSTEPS, int NCH>
 int launch_topk_mfma_n(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int chunkcand, int pf,
-                       float *W, int32_t *I, int raw, hipStream_t s) {
-  return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH>>(dim3((N + TK_Q - 1) / TK_Q, T - first_frame), dim3(TK_NT),
-                                                                 (size_t)TK_Q * chunkcand * 4, s, ehat, T, N, cxt, radius, temp, knn,
-                                                                 first_frame, chunkcand, pf, W, I, raw);
+                       float *W, int32_t *I, int raw, const int32_t *origin, hipStream_t s) {
+  const dim3 grid((N + TK_Q - 1) / TK_Q, T - first_frame);
+  const size_t lds = (size_t)TK_Q * chunkcand * 4;
+  if (origin)
+    return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH, true>>(grid, dim3(TK_NT), lds, s, ehat, T, N, cxt, radius, temp, knn,
+                                                                         first_frame, chunkcand, pf, W, I, raw, origin);
+  return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH, false>>(grid, dim3(TK_NT), lds, s, ehat, T, N, cxt, radius, temp, knn,
+                                                                        first_frame, chunkcand, pf, W, I, raw, origin);
 }
 
 // max_nf context frames of max_bi in-band keys: in one piece, or -- when the scores of a 16-query tile fill more than half a CU's LDS --
 // in two halves, so that two workgroups share a CU (CRW_LABELPROP_TOPK_CHUNKS=1: always one piece, A/B)
 template <int CSTEPS>
 int launch_topk_mfma(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int max_nf, int max_bi, float *W,
-                     int32_t *I, int raw, hipStream_t s) {
+                     int32_t *I, int raw, const int32_t *origin, hipStream_t s) {
   static const bool one = getenv("CRW_LABELPROP_TOPK_CHUNKS") && getenv("CRW_LABELPROP_TOPK_CHUNKS")[0] == '1';
   const long maxcand = (long)max_nf * max_bi;
   const int pf = (max_nf + 1) / 2;
   if (!one && CSTEPS <= 8 /* 256 channels: past 128 registers */ && (size_t)TK_Q * maxcand * 4 > 76 * 1024 && (long)pf * max_bi <= 64L * (TK_NV / 2))
-    return launch_topk_mfma_n<CSTEPS, 2>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, s);
-  return launch_topk_mfma_n<CSTEPS, 1>(ehat, T, N, cxt, radius, temp, knn, first_frame, (int)maxcand, max_nf, W, I, raw, s);
+    return launch_topk_mfma_n<CSTEPS, 2>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, origin, s);
+  return launch_topk_mfma_n<CSTEPS, 1>(ehat, T, N, cxt, radius, temp, knn, first_frame, (int)maxcand, max_nf, W, I, raw, origin, s);
 }
 
 // candidate lists past the two forms above (more than 64 * TK_NV candidates, or a tile's scores over 150 KiB): chunks of pf frames,
@@ -359,12 +372,12 @@ int launch_topk_mfma(const float *ehat, int T, int N, int cxt, int radius, float
 constexpr int TK_LONG_CAND = 64 * (TK_NV / 2);
 template <int CSTEPS>
 int launch_topk_mfma_long(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int max_nf, int max_bi,
-                          float *W, int32_t *I, int raw, hipStream_t s) {
+                          float *W, int32_t *I, int raw, const int32_t *origin, hipStream_t s) {
   static_assert(CSTEPS <= 8, "256 channels: past 128 registers");
   int pf = TK_LONG_CAND / max_bi;
   const int nch = (max_nf + pf - 1) / pf;
   pf = (max_nf + nch - 1) / nch;
-  return launch_topk_mfma_n<CSTEPS, 0>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, s);
+  return launch_topk_mfma_n<CSTEPS, 0>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, origin, s);
 }
 
 __device__ inline float ld_l2(const float *p) {
@@ -379,6 +392,12 @@ __device__ inline void st_l2(float *p, float v) {
 // SLIDE (crw_labelprop_propagate_sliding): an index of frame n addresses the list it was scored on, [frame 0, frames n - cxt .. n - 1]
 // -- slide_row() below; false: the indices are label rows as they stand (cxt unused).
 __device__ inline int slide_row(int i, int n, int N, int cxt) { return (i >= N && n > cxt + 1) ? i + (n - cxt - 1) * N : i; }
+// ORG (the crw_labelprop_propagate_origin entry points, include/crw_hip_restart.h): frame n is frame n - a of the item that starts at
+// its origin a = origin[n] -- the same translation on n - a, then a frames further down L.  a = 0: slide_row's value.
+template <bool ORG>
+__device__ inline int slide_row_at(int i, int n, int a, int N, int cxt) {
+  return ORG ? a * N + slide_row(i, n - a, N, cxt) : slide_row(i, n, N, cxt);
+}
 // An anchor mark (sliding entry points only, CRW_LABELPROP_ANCHOR_WEIGHT in the header): a slot-0 weight of exactly -inf says that
 // the node is clamped to the class its RAW slot-0 index names, clamped into [0, M - 1].  No softmax weight has these bits, so every
 // other list is read as before.  anchor_onehot: the value the clamped node's output (q, c) takes -- 1.0f or +0.0f, written as they are.
@@ -434,12 +453,12 @@ __device__ __forceinline__ void init_frame0(const float *seed, float *L, float *
     for (int q = tid; q < N; q += nt) pred[(long)q * T] = seed[q];
 }
 
-template <bool SLIDE>
+template <bool SLIDE, bool ORG>
 __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__restrict__ seed,
                                                                 const float *__restrict__ W,
                                                                 const int32_t *__restrict__ I, int T, int N, int M,
                                                                 int knn, int first_frame, float *L,
-                                                                float *__restrict__ pred, int cxt) {
+                                                                float *__restrict__ pred, int cxt, const int32_t *__restrict__ origin) {
   const int tid = threadIdx.x, nt = blockDim.x;
   init_frame0<true, false>(seed, L, pred, nullptr, T, N, M, tid, nt);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -447,12 +466,13 @@ __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__r
   for (int n = first_frame; n < T; ++n) {
     const float *Wn = W + (long)(n - first_frame) * knn * N;
     const int32_t *In = I + (long)(n - first_frame) * knn * N;
+    const int org = ORG ? frame_origin(origin, n) : 0;
     for (int it = tid; it < N * M; it += nt) {
       const int q = it / M, c = it % M;
       float p = 0.f;
       const bool mk = SLIDE && anchor_mark(Wn[q]);  // an anchored node: its list is not a list -- every read goes to row 0
       for (int j = 0; j < knn; ++j) {
-        const int r = SLIDE ? (mk ? 0 : slide_row(In[j * N + q], n, N, cxt)) : In[j * N + q];
+        const int r = SLIDE ? (mk ? 0 : slide_row_at<ORG>(In[j * N + q], n, org, N, cxt)) : In[j * N + q];
         p += ld_l2(L + (long)r * M + c) * Wn[j * N + q];
       }
       if (mk) p = anchor_onehot(In[q], M, c);  // ... and the sum is dropped for the one-hot of its class
@@ -472,12 +492,13 @@ __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__r
 // same order: bit-identical results.
 constexpr int GATHER_NT = 256, GATHER_PF = 8;  // threads; prefetch registers per thread (knn * N <= 2048)
 constexpr int GATHER_CH = 20;                  // neighbours whose LDS reads are in flight together (KNN = 20: one batch per output; 4: 0.64, 10: 0.61, 20: 0.58 ms per cfg5 pass)
-template <bool SLIDE>
+template <bool SLIDE, bool ORG>  // ORG: a restart frame's long-term frame is an ordinary row of L -- in the ring while it is recent, from L afterwards
 __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const float *__restrict__ seed,
                                                                          const float *__restrict__ W,
                                                                          const int32_t *__restrict__ I, int T, int N, int M,
                                                                          int knn, int first_frame, float *L,
-                                                                         float *__restrict__ pred, int R, int cxt) {
+                                                                         float *__restrict__ pred, int R, int cxt,
+                                                                         const int32_t *__restrict__ origin) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, NM = N * M, KN = knn * N;
   float *l0 = sm, *ring = l0 + NM, *wbuf = ring + (long)R * NM;  // [NM], [R][NM], [2][KN]
@@ -491,6 +512,7 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
   const int RNM = R * NM;
   for (int n = first_frame; n < T; ++n) {
     const int cur = n & 1;
+    const int org = ORG ? frame_origin(origin, n) : 0;
     // next frame's lists: global -> registers now, -> LDS after this frame's arithmetic (unconditional, clamped loads)
     const long nxt = (long)(min(n + 1, T - 1) - first_frame) * KN;
     float pw[GATHER_PF];
@@ -520,7 +542,7 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
 #pragma unroll
         for (int u = 0; u < GATHER_CH; ++u) {
           const int jj = min(j0 + u, knn - 1);
-          idx[u] = SLIDE ? (mk ? 0 : slide_row(in[jj * N + q], n, N, cxt)) : in[jj * N + q];
+          idx[u] = SLIDE ? (mk ? 0 : slide_row_at<ORG>(in[jj * N + q], n, org, N, cxt)) : in[jj * N + q];
           w[u] = wn[jj * N + q];
         }
 #pragma unroll
@@ -697,11 +719,21 @@ __global__ __launch_bounds__(PX_NT) void labelprop_prefix_kernel(const float *__
 // kernel's direct address i * M + c; afterwards it is that plus ((n - cxt - 1) % R) * NM, wrapped once -- one add and one compare per
 // neighbour, both kept per frame as running offsets (no division in the loop).  R = cxt + 1, not cxt: in phase n frame n is stored
 // while other lanes still read frame n - cxt, so the slot it takes must be that of frame n - cxt - 1.
-template <int KP>
+//
+// ORG (crw_labelprop_propagate_origin, include/crw_hip_restart.h): frame n is frame n' = n - a of the item that starts at its origin
+// a = origin[n].  The ring keeps its ABSOLUTE layout (frame f at slot (f - 1) % R), so the translation is the running `shift` again:
+// ((a + max(0, n' - cxt - 1)) % R) * NM, which at a restart (a = n - 1) is the offset of the slot frame n itself takes, and from
+// there advances as before once n' > cxt + 1; the clamp bound follows n'.  The long-term frame is no longer frame 0 and would leave
+// the ring after R phases, so it has a slot of its own -- TWO of them: in phase a, frame a's rows become the long-term frame of
+// phase a + 1 while other lanes still read the long-term frame of phase a.  The compute lanes of phase a store their output a second
+// time, into the slot that is NOT being read, and the roles flip at the barrier (mb, the slot of the frame whose offsets are made
+// next).  origin[] is copied to LDS once, clamped to [0, n - 1]; a sequence that breaks the chain rule (origin[n] neither origin[n - 1]
+// nor n - 1) reads rows of the wrong frames but never outside the labels in LDS: n' here is counted, at most n.
+template <int KP, bool ORG>
 __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__restrict__ seed, const float *__restrict__ W,
                                                                   const int32_t *__restrict__ I, int T, int N, int M, int knn,
                                                                   int first_frame, int cxt, int R, float *L, float *__restrict__ pred,
-                                                                  int ncw) {
+                                                                  int ncw, const int32_t *__restrict__ origin) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, NM = N * M, KN = knn * N, last_frame = T - 1;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -715,10 +747,20 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
   constexpr int KLO = KP - 8;
   const int RNM = R * NM;
   float *lab = sm;                                                                   // [NM] frame 0, [R][NM] the ring
-  int2 *pl = reinterpret_cast<int2 *>(lab + (((long)(R + 1) * NM + 1) & ~1L));  // [2][KNP] (index, weight bits), slot = frame & 1
+  // ORG: [NM] the second long-term slot and origin[T] behind the ring, in whole frames (slide_origin_frames(), the launcher's count)
+  const long nlab = ORG ? R + 2 + (T + NM - 1) / NM : R + 1;
+  int2 *pl = reinterpret_cast<int2 *>(lab + ((nlab * NM + 1) & ~1L));  // [2][KNP] (index, weight bits), slot = frame & 1
+  int *orgs = reinterpret_cast<int *>(lab + (long)(R + 2) * NM);      // (ORG only)
 
   // frame 0 (from the seed when given) and the frames before first_frame that a frame of this call can read: the last cxt of them
   init_frame0<false, true>(seed, L, pred, lab, T, N, M, tid, (int)blockDim.x);
+  int org0 = 0;  // ORG: the first frame's origin -- its rows are the first long-term frame (same lanes, after frame 0's copy)
+  if constexpr (ORG) {
+    for (int t = tid; t < T; t += (int)blockDim.x) orgs[t] = t ? frame_origin(origin, t) : 0;
+    org0 = __builtin_amdgcn_readfirstlane(frame_origin(origin, first_frame));
+    if (org0 > 0)
+      for (int it = tid; it < NM; it += (int)blockDim.x) lab[it] = L[(long)org0 * NM + it];
+  }
   {
     const int fl = max(1, first_frame - cxt);
     for (int it = tid; it < (first_frame - fl) * NM; it += (int)blockDim.x) {
@@ -772,7 +814,8 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
   // An anchored lane (anchor_mark on the slot-0 weight, the class from the RAW slot-0 index, before the clamp to a row below): mk and
   // the value oh its output takes are made here, one frame ahead and behind the previous frame's stores; the frame itself pays one
   // select on p.  The marked list's offsets stay in range like any other's, so its label reads are harmless and its sum is dropped.
-  auto to_offsets = [&](int f, int shift, int (&ix)[KP], float (&ww)[KP], int &mk, int &oh) {
+  // ORG: f is the frame's number n' in the item that starts at its origin, mb the offset of its long-term slot (0 or NM + RNM)
+  auto to_offsets = [&](int f, int shift, int mb, int (&ix)[KP], float (&ww)[KP], int &mk, int &oh) {
     const int lim = min(f, cxt + 1) * N - 1;
     mk = anchor_mark(ww[0]) ? -1 : 0;
     oh = __float_as_int(anchor_onehot(ix[0], M, c));
@@ -780,7 +823,10 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
     for (int j = 0; j < KP; ++j) {
       const int i = min(max(ix[j], 0), lim);
       int o = i * M + c;
-      if (i >= N) {
+      if constexpr (ORG) {  // two selects, no branch: as an if / else hipcc makes it a divergent branch per neighbour
+        const int os = o + shift, ow = os >= NM + RNM ? os - RNM : os;
+        o = i >= N ? ow : o + mb;
+      } else if (i >= N) {
         o += shift;
         if (o >= NM + RNM) o -= RNM;
       }
@@ -797,17 +843,41 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
       if (shift == RNM) shift = 0;
     }
   };
+  // ORG, all wave-uniform and like `shift` those of the frame whose offsets are made next: np its number in the item that starts at
+  // its origin, mb its long-term slot, rs: it restarts, i.e. the frame computed now is its origin and is stored to mb as well.
+  // next_origin(g): frame g's -> frame g + 1's, called where wslot is frame g's slot (the next slot is the restart's shift + NM)
+  int np = first_frame - org0, mb = 0;
+  bool rs = false;
+  if constexpr (ORG) shift = ((org0 + max(0, np - cxt - 1)) % R) * NM;
+  // (o1: orgs[min(g + 1, last_frame)], read from LDS a phase ahead so that its round trip is not in front of the barrier)
+  auto next_origin = [&](int g, int o1) {
+    rs = __builtin_amdgcn_readfirstlane(o1) == g;
+    if (rs) {
+      np = 1;
+      mb = mb ? 0 : NM + RNM;
+      shift = wslot + NM == NM + RNM ? 0 : wslot;
+    } else if (++np > cxt + 1) {
+      shift += NM;
+      if (shift == RNM) shift = 0;
+    }
+  };
   int amk = 0, aoh = 0;  // all ones where this lane's node is anchored in the frame computed next; the bits of the value it then takes
   if (compute) {
     fetch_lists(first_frame, a, w);
-    to_offsets(first_frame, shift, a, w, amk, aoh);
+    to_offsets(ORG ? np : first_frame, shift, mb, a, w, amk, aoh);
   }
-  next_shift(first_frame);
+  if constexpr (ORG) {
+    next_origin(first_frame, orgs[min(first_frame + 1, last_frame)]);  // (orgs[] is behind the barrier above)
+  } else {
+    next_shift(first_frame);
+  }
   lds_barrier();  // the read of slot first_frame & 1 above comes before loader 0's svc_store(first_frame + 2) into the same slot
 
   int turn = 0;       // (f - first_frame) % D
   int pslot = wslot;  // slot of frame f - 1 (the arg-max wave's)
   for (int f = first_frame; f <= last_frame; ++f) {
+    int o2 = 0;  // ORG: the origin of frame f + 2
+    if constexpr (ORG) o2 = orgs[min(f + 2, last_frame)];
     if (compute) {
       float v[KP];
 #pragma unroll
@@ -826,11 +896,14 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
       asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(p) : "v"(amk), "v"(aoh), "v"(p));
 #endif
       lab[wslot + it] = p;  // the slot of frame f - R: out of every window since frame f - 1
+      // ORG, frame f is the next frame's origin: a second store, to the long-term slot nobody reads in this phase -- and otherwise
+      // the first store again (no branch in the chain)
+      if constexpr (ORG) lab[(rs ? mb : wslot) + it] = p;
       L[(long)f * NM + it] = p;
       // nothing of the next frame's offsets is scheduled above the stores: hipcc otherwise lifts the first clamp, and with it the
       // wait for the first list entry (an LDS round trip), in front of the remaining list reads and the LDS store
       __builtin_amdgcn_sched_barrier(0);
-      to_offsets(f + 1, shift, na, nw, amk, aoh);
+      to_offsets(ORG ? np : f + 1, shift, mb, na, nw, amk, aoh);
 #pragma unroll
       for (int j = 0; j < KP; ++j) {
         a[j] = na[j];
@@ -845,9 +918,10 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
       argmax_rows(pred, T, N, M, f - 1, at, 64, lab + pslot, PlainLoad());
     }
     turn = turn + 1 == D ? 0 : turn + 1;
-    next_shift(f + 1);
+    if constexpr (!ORG) next_shift(f + 1);
     pslot = wslot;
     wslot = wslot + NM == NM + RNM ? NM : wslot + NM;
+    if constexpr (ORG) next_origin(f + 1, o2);
     lds_barrier();
   }
   if (amax) {
@@ -898,11 +972,14 @@ __global__ __launch_bounds__(256) void labelprop_sweep_weights_kernel(const floa
 // time (they do not depend on the chain); the sum runs in neighbour order from 0.f like every other propagation kernel here, and
 // padding slots (weight exactly 0, a valid index) leave it as it is: p + v * 0.f == p for the finite labels.
 constexpr int PB_CH = 16;
-template <bool SLIDE>  // slide_row() on every index before the clamp (crw_labelprop_propagate_sliding_batch)
+// SLIDE: slide_row() on every index before the clamp (crw_labelprop_propagate_sliding_batch); ORG: slide_row_at() with the frame's
+// origin, one origin array for the G configurations (crw_labelprop_propagate_origin_batch)
+template <bool SLIDE, bool ORG>
 __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float *__restrict__ seed, const float *__restrict__ W,
                                                                      const int32_t *__restrict__ I, long i_stride, int T, int N, int M,
                                                                      int knn, int first_frame, int last_frame, float *L,
-                                                                     float *__restrict__ pred, int R, int cxt) {
+                                                                     float *__restrict__ pred, int R, int cxt,
+                                                                     const int32_t *__restrict__ origin) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, nt = (int)blockDim.x, NM = N * M, KN = knn * N, g = blockIdx.x;
   W += (long)g * (T - first_frame) * KN;
@@ -921,6 +998,7 @@ __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float
     const int lo_idx = lo_f * N;               // first label-list row that is in the ring
     const int epoch_base = (n / R - 1) * RNM;  // flat offset of the older of the (at most) two ring epochs in view
     const int row_lim = n * N - 1;
+    const int org = ORG ? frame_origin(origin, n) : 0;
     float *slot = ring + (n % R) * NM;
     for (int it = tid; it < NM; it += nt) {
       const int q = it / M, c = it % M;
@@ -933,7 +1011,7 @@ __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float
 #pragma unroll
         for (int u = 0; u < PB_CH; ++u) {
           const int jj = min(j0 + u, knn - 1);
-          const int raw_i = SLIDE ? slide_row(In[jj * N + q], n, N, cxt) : In[jj * N + q];
+          const int raw_i = SLIDE ? slide_row_at<ORG>(In[jj * N + q], n, org, N, cxt) : In[jj * N + q];
           idx[u] = min(max(raw_i, 0), row_lim);  // in range whatever the lists hold (topk: < min(n, cxt + 1) * N)
           w[u] = Wn[jj * N + q];
         }
@@ -1067,8 +1145,10 @@ namespace {
 
 // one route choice for both output modes: raw = 0 softmax weights (crw_labelprop_topk_grid), 1 the selected logits
 // (crw_labelprop_topk_scores) -- the same kernels, the same selection, another last line of the epilogue
+// origin (crw_labelprop_topk_origin; NULL: every frame scores from frame 0): the route is still chosen from the whole call's
+// arguments -- a restart frame has fewer candidates than the bound the route was chosen for, never more
 int topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int knn, int first_frame, int grid_w, float *W,
-              int32_t *I, int raw, crw_stream_t stream) {
+              int32_t *I, int raw, const int32_t *origin, crw_stream_t stream) {
   crw::clear_stale_error();
   if (!ehat || !W || !I || T < 2 || N < 1 || C < 1 || cxt_size < 1 || radius < 1 || knn < 1 || knn > MAX_KNN ||
       !(temp > 0.f) || first_frame < 1 || first_frame >= T || grid_w < 1 || N % grid_w)
@@ -1084,18 +1164,22 @@ int topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, 
   const bool column = grid_w == 1 && !valu && N >= TK_Q && (((uintptr_t)ehat) & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
   if (column && (C == 64 || C == 128 || C == 256) && maxcand <= 64L * TK_NV && (size_t)TK_Q * maxcand * 4 <= 150 * 1024) {
-    if (C == 64) return launch_topk_mfma<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, s);
-    if (C == 128) return launch_topk_mfma<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, s);
-    return launch_topk_mfma<16>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, s);
+    if (C == 64) return launch_topk_mfma<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, s);
+    if (C == 128) return launch_topk_mfma<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, s);
+    return launch_topk_mfma<16>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, s);
   }
   // longer lists (radius 30 / 60 at 80 - 100 context frames): any number of chunks; a single frame's band must fit one chunk
   if (column && (C == 64 || C == 128) && max_bi <= TK_LONG_CAND) {
-    if (C == 64) return launch_topk_mfma_long<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, s);
-    return launch_topk_mfma_long<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, s);
+    if (C == 64) return launch_topk_mfma_long<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, s);
+    return launch_topk_mfma_long<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, s);
   }
   if (lds > 60 * 1024) return CRW_EINVAL;
-  hipLaunchKernelGGL(labelprop_topk_kernel, dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T,
-                     N, C, cxt_size, radius, temp, knn, first_frame, grid_w, W, I, raw);
+  if (origin)
+    hipLaunchKernelGGL(labelprop_topk_kernel<true>, dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T, N, C, cxt_size,
+                       radius, temp, knn, first_frame, grid_w, W, I, raw, origin);
+  else
+    hipLaunchKernelGGL(labelprop_topk_kernel<false>, dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T,
+                       N, C, cxt_size, radius, temp, knn, first_frame, grid_w, W, I, raw, origin);
   return check_launch();
 }
 
@@ -1130,29 +1214,38 @@ bool chain_fits(int knn, long NM, long KN, size_t lds) { return knn <= 24 && cha
 
 // KP = knn rounded up to the register instances.  RING: the slide kernel (every frame chained, `last` unused), else the prefix kernel
 // over frames first_frame .. last (cxt, R unused)
+// origin (RING only, crw_labelprop_propagate_origin): the slide kernel's ORG instance; NULL: the instance it has always been
 template <int KP, bool RING>
 int launch_chain_kp(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int last, int cxt, int R,
-                    size_t lds, float *L, float *pred, hipStream_t s) {
+                    size_t lds, float *L, float *pred, const int32_t *origin, hipStream_t s) {
   const int ncw = chain_ncw((long)N * M);
   const dim3 block((ncw + chain_nld((long)N * M) + 1) * 64);
-  if constexpr (RING)
-    return launch_big_lds<labelprop_slide_kernel<KP>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, cxt, R, L, pred, ncw);
-  else
+  if constexpr (RING) {
+    if (origin)
+      return launch_big_lds<labelprop_slide_kernel<KP, true>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, cxt, R, L, pred,
+                                                              ncw, origin);
+    return launch_big_lds<labelprop_slide_kernel<KP, false>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, cxt, R, L, pred,
+                                                             ncw, origin);
+  } else {
     return launch_big_lds<labelprop_prefix_kernel<KP>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, last, L, pred, ncw);
+  }
 }
 template <bool RING>
 int launch_chain(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int last, int cxt, int R,
-                 size_t lds, float *L, float *pred, hipStream_t s) {
-  if (knn <= 8) return launch_chain_kp<8, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, s);
-  if (knn <= 16) return launch_chain_kp<16, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, s);
-  return launch_chain_kp<24, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, s);
+                 size_t lds, float *L, float *pred, const int32_t *origin, hipStream_t s) {
+  if (knn <= 8) return launch_chain_kp<8, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, origin, s);
+  if (knn <= 16) return launch_chain_kp<16, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, origin, s);
+  return launch_chain_kp<24, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, origin, s);
 }
+// frames of LDS the slide kernel's ORG instance keeps beside the two list slots: frame 0's slot, the ring, the second long-term
+// slot, and origin[T] rounded up to whole frames
+long slide_origin_frames(long R, long T, long NM) { return R + 2 + (T + NM - 1) / NM; }
 
 // the one-workgroup walk over any lists (crw_labelprop_gather; SLIDE: the general route of crw_labelprop_propagate_sliding, the
 // indices translated in the kernel)
-template <bool SLIDE>
+template <bool SLIDE, bool ORG = false>
 int launch_gather(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int cxt, float *L,
-                  float *pred, crw_stream_t stream) {
+                  float *pred, crw_stream_t stream, const int32_t *origin = nullptr) {
   crw::clear_stale_error();
   if (bad_propagate_args(W, I, L, pred, T, N, M, knn, first_frame)) return CRW_EINVAL;
   // LDS-resident form when the lists of a frame fit the prefetch registers and at least a few frames fit the ring
@@ -1163,18 +1256,18 @@ int launch_gather(const float *seed, const float *W, const int32_t *I, int T, in
   static const char *force_global = getenv("CRW_LABELPROP_GATHER_GLOBAL");  // diagnostics: the L2-round-trip kernel
   if (KN <= (long)GATHER_NT * GATHER_PF && R >= 4 && (long)T * N < (1L << 30) / M && !force_global) {
     const size_t lds = (size_t)(4 * (NM * (R + 1) + 4 * KN));
-    return launch_big_lds<labelprop_gather_lds_kernel<SLIDE>>(dim3(1), dim3(GATHER_NT), lds, (hipStream_t)stream, seed, W, I, T, N, M, knn,
-                                                              first_frame, L, pred, (int)R, cxt);
+    return launch_big_lds<labelprop_gather_lds_kernel<SLIDE, ORG>>(dim3(1), dim3(GATHER_NT), lds, (hipStream_t)stream, seed, W, I, T, N, M, knn,
+                                                                   first_frame, L, pred, (int)R, cxt, origin);
   }
-  hipLaunchKernelGGL(labelprop_gather_kernel<SLIDE>, dim3(1), dim3(1024), 0, (hipStream_t)stream, seed, W, I, T, N, M, knn,
-                     first_frame, L, pred, cxt);
+  hipLaunchKernelGGL((labelprop_gather_kernel<SLIDE, ORG>), dim3(1), dim3(1024), 0, (hipStream_t)stream, seed, W, I, T, N, M, knn,
+                     first_frame, L, pred, cxt, origin);
   return check_launch();
 }
 
 // SLIDE: every frame is chained (last = T - 1, no tail launch), the indices translated in the kernel
-template <bool SLIDE>
+template <bool SLIDE, bool ORG = false>
 int launch_propagate_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M, int knn,
-                           int first_frame, int cxt_size, float *L, float *pred, crw_stream_t stream) {
+                           int first_frame, int cxt_size, float *L, float *pred, crw_stream_t stream, const int32_t *origin = nullptr) {
   crw::clear_stale_error();
   if (bad_propagate_args(W, I, L, pred, T, N, M, knn, first_frame) || G < 1 || G > 65535 || knn > MAX_KNN || cxt_size < 1) return CRW_EINVAL;
   const long NM = (long)N * M;
@@ -1186,8 +1279,9 @@ int launch_propagate_batch(const float *seed, const float *W, const int32_t *I, 
     if (R > last + 1) R = last + 1;
     if (R < 2) R = 2;
     const int nt = (int)(NM >= 1024 ? 1024 : (NM + 63) / 64 * 64);
-    const int rc = launch_big_lds<labelprop_chain_batch_kernel<SLIDE>>(dim3(G), dim3(nt), (size_t)(4 * NM * (R + 1)), s, seed, W, I, (long)i_stride,
-                                                                       T, N, M, knn, first_frame, last, L, pred, (int)R, cxt_size);
+    const int rc = launch_big_lds<labelprop_chain_batch_kernel<SLIDE, ORG>>(dim3(G), dim3(nt), (size_t)(4 * NM * (R + 1)), s, seed, W, I,
+                                                                            (long)i_stride, T, N, M, knn, first_frame, last, L, pred, (int)R,
+                                                                            cxt_size, origin);
     if (rc != CRW_OK) return rc;
   }
   return launch_tail(W, I, (long)i_stride, G, T, N, M, knn, first_frame, t0, L, pred, s);
@@ -1199,12 +1293,12 @@ extern "C" {
 
 int crw_labelprop_topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int knn, int first_frame,
                             int grid_w, float *W, int32_t *I, crw_stream_t stream) {
-  return topk_grid(ehat, T, N, C, cxt_size, radius, temp, knn, first_frame, grid_w, W, I, 0, stream);
+  return topk_grid(ehat, T, N, C, cxt_size, radius, temp, knn, first_frame, grid_w, W, I, 0, nullptr, stream);
 }
 
 int crw_labelprop_topk_scores(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int kcap, int first_frame,
                               int grid_w, float *V, int32_t *I, crw_stream_t stream) {
-  return topk_grid(ehat, T, N, C, cxt_size, radius, temp, kcap, first_frame, grid_w, V, I, 1, stream);
+  return topk_grid(ehat, T, N, C, cxt_size, radius, temp, kcap, first_frame, grid_w, V, I, 1, nullptr, stream);
 }
 
 int crw_labelprop_topk(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int knn,
@@ -1231,7 +1325,7 @@ int crw_labelprop_propagate(const float *seed, const float *W, const int32_t *I,
     return crw_labelprop_gather(seed, W, I, T, N, M, knn, first_frame, L, pred, stream);
   hipStream_t s = (hipStream_t)stream;
   if (last >= first_frame) {
-    const int rc = launch_chain<false>(seed, W, I, T, N, M, knn, first_frame, last, 0, 0, px_lds, L, pred, s);
+    const int rc = launch_chain<false>(seed, W, I, T, N, M, knn, first_frame, last, 0, 0, px_lds, L, pred, nullptr, s);
     if (rc != CRW_OK) return rc;
   }
   return launch_tail(W, I, 0, 1, T, N, M, knn, first_frame, t0, L, pred, s);
@@ -1249,7 +1343,36 @@ int crw_labelprop_propagate_sliding(const float *seed, const float *W, const int
   const size_t lds = chain_lds(R + 1, NM);
   const bool ring = !(gen && gen[0] == '1') && chain_fits(knn, NM, KN, lds) && (long)T * N < (1L << 30) / M;
   if (!ring) return launch_gather<true>(seed, W, I, T, N, M, knn, first_frame, cxt_size, L, pred, stream);
-  return launch_chain<true>(seed, W, I, T, N, M, knn, first_frame, T - 1, cxt_size, (int)R, lds, L, pred, (hipStream_t)stream);
+  return launch_chain<true>(seed, W, I, T, N, M, knn, first_frame, T - 1, cxt_size, (int)R, lds, L, pred, nullptr, (hipStream_t)stream);
+}
+
+// ---- include/crw_hip_restart.h: the same entry points with a per-frame origin (the ORG instances of the kernels above) ----------
+int crw_labelprop_topk_origin(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int k, int first_frame,
+                              int grid_w, const int32_t *origin, float *WV, int32_t *I, int raw, crw_stream_t stream) {
+  if (raw != 0 && raw != 1) return CRW_EINVAL;
+  return topk_grid(ehat, T, N, C, cxt_size, radius, temp, k, first_frame, grid_w, WV, I, raw, origin, stream);
+}
+
+int crw_labelprop_propagate_origin(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame,
+                                   int cxt_size, const int32_t *origin, float *L, float *pred, crw_stream_t stream) {
+  if (!origin) return crw_labelprop_propagate_sliding(seed, W, I, T, N, M, knn, first_frame, cxt_size, L, pred, stream);
+  crw::clear_stale_error();
+  if (bad_propagate_args(W, I, L, pred, T, N, M, knn, first_frame) || cxt_size < 1) return CRW_EINVAL;
+  const long NM = (long)N * M, KN = (long)knn * N;
+  // the ring kernel where its labels -- one more frame than without origins, and origin[T] -- still fit; the same switch as above
+  const char *gen = getenv("CRW_LABELPROP_SLIDING_GENERAL");
+  const long R = cxt_size + 1 < T - 1 ? cxt_size + 1 : T - 1;
+  const size_t lds = chain_lds(slide_origin_frames(R, T, NM), NM);
+  const bool ring = !(gen && gen[0] == '1') && chain_fits(knn, NM, KN, lds) && (long)T * N < (1L << 30) / M;
+  if (!ring) return launch_gather<true, true>(seed, W, I, T, N, M, knn, first_frame, cxt_size, L, pred, stream, origin);
+  return launch_chain<true>(seed, W, I, T, N, M, knn, first_frame, T - 1, cxt_size, (int)R, lds, L, pred, origin, (hipStream_t)stream);
+}
+
+int crw_labelprop_propagate_origin_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M,
+                                         int knn, int first_frame, int cxt_size, const int32_t *origin, float *L, float *pred,
+                                         crw_stream_t stream) {
+  if (!origin) return launch_propagate_batch<true>(seed, W, I, i_stride, G, T, N, M, knn, first_frame, cxt_size, L, pred, stream);
+  return launch_propagate_batch<true, true>(seed, W, I, i_stride, G, T, N, M, knn, first_frame, cxt_size, L, pred, stream, origin);
 }
 
 int crw_labelprop_sweep_weights(const float *V, int F, int kcap, int N, const int *knns, int nk, float *W, crw_stream_t stream) {

@@ -26,6 +26,19 @@ ANCHORS_NEED_SLIDING = ("anchors need CONTEXT 'sliding': under the reference's i
                         "label later than frame CXT_SIZE, so an anchor there would change only itself")
 
 
+def restart_origin(anchor_context, anchors, context, T, N, nclasses):
+    """The option checks of `anchor_context=` -> the origin array of 'restart' (`crw_hip.anchor_origins`; row 0 of the anchors is
+    the seed's and restarts nothing more than frame 0 does), None under 'clamp'."""
+    if crw_hip.check_anchor_context(anchor_context) == 'clamp':
+        return None
+    if anchors is None:
+        raise ValueError("anchor_context='restart' needs anchors: a restart happens at a fully anchored frame")
+    if context != 'sliding':
+        raise ValueError(ANCHORS_NEED_SLIDING)
+    crw_hip.check_anchors(anchors, T, N, nclasses)
+    return crw_hip.anchor_origins(anchors, nclasses, T)
+
+
 class LabelPropVOS_CRW(object):
     def __init__(self, cfg):
         self.cxt_size = cfg['CXT_SIZE']
@@ -85,24 +98,29 @@ class LabelPropVOS_CRW(object):
         crw_hip.labelprop_gather(None, Wt, It, n + 1, N, M, first_frame=n, L=L, cxt_size=self.cxt_size, context=self.context)
         return L[n * N:].reshape(N, M).t().reshape(1, M, h, w)
 
-    def propagate_all(self, feats, seed, nclasses, grid_w=1, anchors=None):
+    def propagate_all(self, feats, seed, nclasses, grid_w=1, anchors=None, anchor_context='clamp'):
         """feats [T,N,C] (normalised features), seed [N] float class ids of frame 0
         -> (pred [N,T] float class ids, L [T*N, M] soft labels).  grid_w: the N nodes are an (N / grid_w) x grid_w grid.
+        anchor_context 'restart' (needs anchors): a frame whose N nodes are all anchored is as good as a seed -- every frame behind
+        it is propagated as a frame of the item that starts there (`crw_hip.anchor_origins`, the `origin=` of `labelprop_topk` and
+        `labelprop_gather`); 'clamp': the anchors clamp and the context is what it is without them.
         anchors (needs CONTEXT 'sliding'): [T, N] int8, device or host, labelled nodes inside the item -- a class id in [0, nclasses)
         clamps the node's soft labels to that class before the next frame reads them, anything else (-1) leaves the node free; row 0
         is ignored (the seed rules there).  The lists made here are this call's own, so the anchors are marked into them in place
         (`crw_hip.mark_anchors`, no copy) and ONE crw_labelprop_propagate_sliding call follows; CRW_ANCHORS_SEGMENTED=1 (read per call)
         or a library without the marks: one launch per stretch between anchored frames (`crw_hip.labelprop_gather(anchors=)`)."""
         T, N, C = feats.shape
+        origin = restart_origin(anchor_context, anchors, self.context, T, N, nclasses)
         if anchors is not None and self.context != 'sliding':
             raise ValueError(ANCHORS_NEED_SLIDING)
         self._check_grid(N // grid_w, grid_w)
         self._band(N // grid_w, grid_w, feats.device)
-        Wt, It = crw_hip.labelprop_topk(feats, self.cxt_size, self.radius, self.temperature, self.topk, first_frame=1, grid_w=grid_w)
-        kw = {}
+        Wt, It = crw_hip.labelprop_topk(feats, self.cxt_size, self.radius, self.temperature, self.topk, first_frame=1, grid_w=grid_w,
+                                        origin=origin)
+        kw = {} if origin is None else dict(origin=origin)
         if anchors is not None:
             crw_hip.check_anchors(anchors, T, N, nclasses)
-            if crw_hip.anchors_segmented():
+            if origin is None and crw_hip.anchors_segmented():
                 kw = dict(anchors=anchors)
             else:
                 crw_hip.mark_anchors(Wt, It, anchors, nclasses, 1)
@@ -139,9 +157,10 @@ class LabelPropSweep(object):
             raise RuntimeError(f"KNN={max(self.knns)} exceeds the number of nodes per frame ({h * w}); "
                                "torch.topk in the reference raises for the first frame as well")
 
-    def propagate_all(self, feats, seed, nclasses, grid_w=1, soft=False, anchors=None):
+    def propagate_all(self, feats, seed, nclasses, grid_w=1, soft=False, anchors=None, anchor_context='clamp'):
         """feats [T,N,C] (normalised features), seed [N] float class ids of frame 0 -> pred [G,N,T] float class ids, G =
-        len(configs).  anchors (needs context 'sliding'): `LabelPropVOS_CRW.propagate_all`'s, the same for every configuration --
+        len(configs).  anchor_context: `LabelPropVOS_CRW.propagate_all`'s -- under 'restart' ONE origin array serves every selection
+        and the batch call (crw_labelprop_propagate_origin_batch).  anchors (needs context 'sliding'): `LabelPropVOS_CRW.propagate_all`'s, the same for every configuration --
         marked in place into the W [G, ...] that `labelprop_sweep_weights` wrote and into the shared I (`crw_hip.mark_anchors`: a
         configuration padded from a smaller knn keeps slot 0 as a real slot), then the ONE batch call as without them.  soft: -> (pred, L [G, T*N, M]), the soft labels of every configuration as well (the batch kernel writes them
         anyway; the per-configuration arm stacks its G copies) -- what `crw_hip.labelmap_dense_batch` turns into pixel maps.
@@ -153,6 +172,7 @@ class LabelPropSweep(object):
         CRW_SWEEP_PER_CONFIG=1 (read per call): a loop of `LabelPropVOS_CRW.propagate_all` over the configurations on the same
         features instead -- the A/B arm of tools/sweep_timing.py, and the fallback."""
         T, N, C = feats.shape
+        origin = restart_origin(anchor_context, anchors, self.context, T, N, nclasses)
         if anchors is not None:
             if self.context != 'sliding':
                 raise ValueError(ANCHORS_NEED_SLIDING)
@@ -160,7 +180,7 @@ class LabelPropSweep(object):
         self._check_grid(N // grid_w, grid_w)
         seed = seed.float().contiguous()
         if os.environ.get("CRW_SWEEP_PER_CONFIG") == "1":
-            akw = {} if anchors is None else dict(anchors=anchors)
+            akw = {} if anchors is None else dict(anchors=anchors, anchor_context=anchor_context)
             if not soft:
                 return torch.stack([LabelPropVOS_CRW(cfg).propagate_all(feats, seed, nclasses, grid_w=grid_w, **akw)[0] for cfg in self.configs])
             outs = [LabelPropVOS_CRW(cfg).propagate_all(feats, seed, nclasses, grid_w=grid_w, **akw) for cfg in self.configs]
@@ -173,7 +193,7 @@ class LabelPropSweep(object):
         p = 0
         for r in self.radii:
             for t in self.temps:
-                crw_hip.labelprop_topk_scores(feats, self.cxt_size, r, t, kmax, first_frame=1, grid_w=grid_w, out=(V, I[p]))
+                crw_hip.labelprop_topk_scores(feats, self.cxt_size, r, t, kmax, first_frame=1, grid_w=grid_w, out=(V, I[p]), origin=origin)
                 crw_hip.labelprop_sweep_weights(V, self.knns, out=W[p])
                 p += 1
         if anchors is not None:  # before I is expanded: every (radius, temp) pair's indices take the classes, every W[g] the marks
@@ -186,5 +206,5 @@ class LabelPropSweep(object):
         else:
             Ig = I[:, None].expand(P, nk, F, kmax, N).reshape(P * nk, F, kmax, N)  # (a copy: the batch takes one stride)
         L, pred = crw_hip.labelprop_propagate_batch(seed, W.view(P * nk, F, kmax, N), Ig, T, N, nclasses, first_frame=1,
-                                                    cxt_size=self.cxt_size, context=self.context)
+                                                    cxt_size=self.cxt_size, context=self.context, origin=origin)
         return (pred, L) if soft else pred

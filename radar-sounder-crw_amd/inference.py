@@ -116,8 +116,13 @@ def _write_nearest(res, seq, out, out_conf, flip):
         window[...] = torch.flip(up, (-1,)) if flip else up
 
 
+def _check_anchor_context(anchor_context, anchors):
+    if crw_hip.check_anchor_context(anchor_context) == 'restart' and anchors is None:
+        raise ValueError("anchor_context='restart' needs anchors: a restart happens at a fully anchored frame")
+
+
 def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run, write,
-                    lead=(), dtype=torch.float32, joint=None, posterior=0, anchors=None, **extra):
+                    lead=(), dtype=torch.float32, joint=None, posterior=0, anchors=None, anchor_context='clamp', **extra):
     """The passes of `segment` and `segment_sweep`, behind their argument checks -> their result dict (plus ``extra``).
     run(seq, seg_ref, use_last): the variant's `propagate` call -> (pred, xent, change, ...).
     write(res, seq, out, out_conf, flip): puts what `run` returned into a column window of the label map (and of the confidence
@@ -132,7 +137,8 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
     once as well, and the call that writes a window of ``pred`` also gets the same window of the two, as the keyword
     post=(post window, horizon window): `write` without a reverse pass, `joint` with one (``pred`` is then the joint calls').
     anchors: None, or (annot, cols) of `segment`: `run` is then called with the keyword anchors=<the radargram's [T, N] node anchors>
-    (`utils.anchor_nodes`) in both passes, and the result gains ``anchor_cols``."""
+    (`utils.anchor_nodes`) and anchor_context=``anchor_context`` in both passes, and the result gains ``anchor_cols`` and
+    ``anchor_context``."""
     T, (H, W), (oh, ow) = seq_length, patch_size, overlap
     N = dataset[0].shape[1]
     rg_len = T * (W - ow) + ow
@@ -151,8 +157,11 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
         annot, cols = anchors
         cols = sorted(int(c) for c in cols)
         per_rg = anchor_nodes(torch.as_tensor(annot)[:, :n_rg * rg_len], cols, rg_len, T, N, rg_h, W - ow)
-        anch = lambda t: dict(anchors=per_rg[t])
-        extra.update(anchor_cols=cols)
+        ckw = {} if anchor_context == 'clamp' else dict(anchor_context=anchor_context)  # (the default is not passed on: `run` may be a caller's own)
+        anch = lambda t: dict(anchors=per_rg[t], **ckw)
+        extra.update(anchor_cols=cols, anchor_context=anchor_context)
+        if anchor_context == 'restart':  # the fully labelled traces beyond the seed's: where the forward pass restarts
+            extra.update(origin_traces=sum(int((p[1:] >= 0).all(1).sum()) for p in per_rg))
     forward, forward_conf = new_maps()
     xents, changes = [], []
     keep = use_last and merge == 'ordered'
@@ -229,7 +238,7 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
 @torch.no_grad()
 def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap, pos_embed=False,
             correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
-            decode='argmax', order=None, posterior=False, floor=crw_hip.POSTERIOR_FLOOR, anchors=None):
+            decode='argmax', order=None, posterior=False, floor=crw_hip.POSTERIOR_FLOOR, anchors=None, anchor_context='clamp'):
     """dataset: RGDataset (full, overlapping items); seg: reference segmentation [rows, W_rg].
     -> dict(pred [rows, n_rg * rg_len] float labels after the optional reverse merge,
             forward: the forward (+ corrected) map the reference saves as int8 (test_all.py:128),
@@ -272,7 +281,11 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     reads them.  Both passes see the same anchors, the reverse pass mirrored (frame T - 1 - f); an anchor on a pass's own seed frame
     is ignored by that pass (``seg`` rules there) and live in the other.  Everything downstream takes the soft labels as before:
     confidence 1 at a clamped node, the maps, both decodes, the merges, the posterior.  The dict gains ``anchor_cols``.  Not
-    together with ``correction``: the correction is itself a re-seed, and how the two combine is not decided."""
+    together with ``correction``: the correction is itself a re-seed, and how the two combine is not decided.
+    anchor_context: 'clamp', or 'restart' (needs anchors) -- a fully labelled trace is as good as a seed: the frames behind it are
+    propagated as frames of the item that starts there (`LabelPropVOS_CRW.propagate_all`).  Both passes restart, the reverse pass on
+    the mirrored anchors; everything downstream is untouched.  With anchors the dict gains ``anchor_context``."""
+    _check_anchor_context(anchor_context, anchors)
     order = _check_options(confidence, merge, upsample, decode, order, nclasses, posterior, use_last, floor)
     if anchors is not None and correction:
         raise ValueError("anchors and correction=True do not combine: the correction is itself a re-seed (at the change point), and "
@@ -305,13 +318,14 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
             crw_hip.labelmap_ordered_joint_posterior(a, b, N, nclasses, *out.shape, order, out, confidence=confidence, floor=floor,
                                                      out=post[0], out_hz=post[1])
     return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
-                           write, joint=joint, posterior=len(order) if posterior else 0, anchors=anchors, **extra)
+                           write, joint=joint, posterior=len(order) if posterior else 0, anchors=anchors, anchor_context=anchor_context,
+                           **extra)
 
 
 @torch.no_grad()
 def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size, overlap, pos_embed=False,
                   correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
-                  decode='argmax', order=None, anchors=None, **posterior_options):
+                  decode='argmax', order=None, anchors=None, anchor_context='clamp', **posterior_options):
     """`segment` for every configuration of ``sweep`` (LabelPropSweep, G = len(sweep.configs)) with its control flow run ONCE:
     which items are corrected, at which length (`get_smaller_item` and its permanent shortening of the dataset) and what the
     reverse pass sees depend on the features alone, never on (radius, temp, knn).  Same exception policy in the correction.
@@ -339,7 +353,9 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     it is without the option.
     anchors: `segment`'s -- None, or (annot, cols), labelled traces inside the radargrams (needs a ``sweep`` under context
     'sliding'); the same anchors in both passes and for all G configurations, the reverse pass mirrored, not together with
-    ``correction``; the dict gains ``anchor_cols``.  Slice g stays `segment`'s for ``sweep.configs[g]`` under the same anchors."""
+    ``correction``; the dict gains ``anchor_cols``.  Slice g stays `segment`'s for ``sweep.configs[g]`` under the same anchors.
+    anchor_context: `segment`'s, one set of origins for the G configurations."""
+    _check_anchor_context(anchor_context, anchors)
     if anchors is not None and correction:
         raise ValueError("anchors and correction=True do not combine: the correction is itself a re-seed (at the change point), and "
                          "how the two interact is not decided")
@@ -380,7 +396,7 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
                                                            floor=floor, out=post[0], out_hz=post[1])
     return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
                            write, lead=(G,), dtype=torch.int8, joint=joint, posterior=len(order) if posterior else 0, anchors=anchors,
-                           configs=list(sweep.configs), **extra)
+                           anchor_context=anchor_context, configs=list(sweep.configs), **extra)
 
 
 @torch.no_grad()

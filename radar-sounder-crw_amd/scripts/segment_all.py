@@ -37,7 +37,9 @@ boundary lies within 2 bars + 1 row of the pick); ``--save_posterior`` writes ``
 reference map's shape, < 0 = unlabelled; every column with an entry >= 0 is annotated and clamps the nodes of its frame
 (``inference.segment(..., anchors=(map, columns))``); ``--anchor_every K``: an evaluation convenience, the ground-truth column at
 the first pixel of every K-th frame of each radargram as the anchors; one line says how many traces are anchored, ``--report_json``
-gains ``anchors``; the report counts anchored traces as it counts the seed traces.  Without these flags the output is what it was.
+gains ``anchors``; the report counts anchored traces as it counts the seed traces; ``--anchor_context restart`` (with either): a
+fully labelled anchor trace restarts the propagation context like a seed (``inference.segment(..., anchor_context='restart')``), one
+more line says how many of the anchored traces are such origins, ``--report_json`` gains ``anchor_context``.  Without these flags the output is what it was.
 Differences from the scripts:
   * plots are not drawn;
   * true / false flags read true / false (the scripts take any given string as true); ``--patch_size`` takes two numbers;
@@ -128,17 +130,21 @@ def get_args_parser():
                    help='labelled traces inside the radargrams: a .pt map, < 0 = unlabelled (needs --context sliding)')
     p.add_argument('--anchor_every', default=None, type=int, metavar='K',
                    help="evaluation: the reference map's column at the first pixel of every K-th frame as anchors (needs --context sliding)")
+    p.add_argument('--anchor_context', default=None, choices=('clamp', 'restart'),
+                   help='restart: a fully labelled anchor trace restarts the propagation context, like a seed (needs anchors; clamp)')
     return p
 
 
 HORIZON_FLAGS = ('horizons', 'min_run', 'tol', 'row_spacing', 'row_unit', 'save_horizons')
 POSTERIOR_FLAGS = ('posterior', 'floor', 'save_posterior')
-ANCHOR_FLAGS = ('anchors', 'anchor_every')
+ANCHOR_FLAGS = ('anchors', 'anchor_every', 'anchor_context')
 
 
 def check_anchor_flags(args):
-    """The flags ``--anchors`` and ``--anchor_every``."""
+    """The flags ``--anchors``, ``--anchor_every`` and ``--anchor_context``."""
     if args.anchors is None and args.anchor_every is None:
+        if getattr(args, 'anchor_context', None) is not None:
+            raise SystemExit('--anchor_context needs --anchors or --anchor_every')
         return args
     if args.anchors is not None and args.anchor_every is not None:
         raise SystemExit('--anchors and --anchor_every: one of the two')
@@ -288,6 +294,9 @@ def main(args):
     anchored = getattr(args, 'anchors', None) is not None or getattr(args, 'anchor_every', None) is not None
     if not anchored:  # likewise
         hidden += ANCHOR_FLAGS
+    anchor_context = getattr(args, 'anchor_context', None)
+    if anchor_context is None:  # likewise
+        hidden += ('anchor_context',)
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -320,7 +329,10 @@ def main(args):
                                 **(dict(upsample=args.upsample) if args.upsample != 'nearest' else {}),
                                 **(dict(decode=args.decode, order=args.order) if args.decode != 'argmax' else {}),
                                 **(dict(posterior=True, floor=args.floor) if args.posterior else {}),
-                                **(dict(anchors=anchors) if anchored else {}))
+                                **(dict(anchors=anchors) if anchored else {}),
+                                **(dict(anchor_context=anchor_context) if anchor_context else {}))
+        if out.get('anchor_context') == 'restart':
+            print('Origin traces:', out['origin_traces'], 'of the anchored traces (anchor_context restart)')
         if correction:
             print('Change point for each radargram:', out['change_idx'])
         final, forward = out['pred'], out['forward']
@@ -391,6 +403,10 @@ def main(args):
         if anchored:
             d['anchors'] = dict(traces=len(out['anchor_cols']), columns=out['anchor_cols'],
                                 source='file' if args.anchors is not None else f'every {args.anchor_every} frames of the reference map')
+            if anchor_context is not None:
+                d['anchor_context'] = anchor_context
+                if anchor_context == 'restart':
+                    d['anchors']['origin_traces'] = out['origin_traces']
         if pcal is not None:
             d['posterior'] = dict(floor=args.floor, calibration=pcal.to_dict(), horizon_bars=bars.to_dict())
         with open(args.report_json, 'w') as f:

@@ -33,7 +33,8 @@ only with ``--posterior``) -- the lowest wins, by the same rules.  Without these
 before them.
 ``--anchors FILE`` / ``--anchor_every K`` (with ``--context sliding``, not with ``--correction``): ``segment_all.py``'s two flags,
 the same anchors for every configuration (``inference.segment_sweep(..., anchors=(map, columns))``); one line says how many traces
-are anchored and ``--report_json`` gains ``anchors``.  Without them the output is what it was.
+are anchored and ``--report_json`` gains ``anchors``; ``--anchor_context restart``: ``segment_all.py``'s, one set of origins for
+every configuration.  Without them the output is what it was.
 CRW_SWEEP_PER_CONFIG=1: the label propagation as a loop over the configurations (same maps; the A/B arm)."""
 import argparse
 import json
@@ -121,6 +122,8 @@ def get_args_parser(horizons=False, posterior=False):
                    help='labelled traces inside the radargrams: a .pt map, < 0 = unlabelled (needs --context sliding)')
     p.add_argument('--anchor_every', default=None, type=int, metavar='K',
                    help="evaluation: the reference map's column at the first pixel of every K-th frame as anchors (needs --context sliding)")
+    p.add_argument('--anchor_context', default=None, choices=('clamp', 'restart'),
+                   help='restart: a fully labelled anchor trace restarts the propagation context, like a seed (needs anchors; clamp)')
     return p
 
 
@@ -191,6 +194,9 @@ def main(args):
         hidden += POSTERIOR_FLAGS
     if not anchored:  # likewise
         hidden += segment_all.ANCHOR_FLAGS
+    anchor_context = getattr(args, 'anchor_context', None)
+    if anchor_context is None:  # likewise
+        hidden += ('anchor_context',)
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -215,7 +221,10 @@ def main(args):
                                   **(dict(upsample=args.upsample) if args.upsample != 'nearest' else {}),
                                   **(dict(decode=args.decode, order=args.order) if args.decode != 'argmax' else {}),
                                   **(dict(posterior=True, floor=args.floor) if args.posterior else {}),
-                                  **(dict(anchors=anchors) if anchored else {}))
+                                  **(dict(anchors=anchors) if anchored else {}),
+                                  **(dict(anchor_context=anchor_context) if anchor_context else {}))
+    if out.get('anchor_context') == 'restart':
+        print('Origin traces:', out['origin_traces'], 'of the anchored traces (anchor_context restart)')
     if correction:
         print('Change point for each radargram:', out['change_idx'])
     final, forward = out['pred'], out['forward']
@@ -316,6 +325,10 @@ def main(args):
         if anchored:
             d['anchors'] = dict(traces=len(out['anchor_cols']), columns=out['anchor_cols'],
                                 source='file' if args.anchors is not None else f'every {args.anchor_every} frames of the reference map')
+            if anchor_context is not None:
+                d['anchor_context'] = anchor_context
+                if anchor_context == 'restart':
+                    d['anchors']['origin_traces'] = out['origin_traces']
         with open(args.report_json, 'w') as f:
             json.dump(d, f, indent=1)
     return reports, best

@@ -142,13 +142,16 @@ def _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last):
 
 
 @torch.no_grad()
-def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False, anchors=None):
+def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False, anchors=None,
+              anchor_context='clamp'):
     """seq [T,N,h,w]; seg_ref [rows, w] class ids of the first (or last) frame; model: encoder;
     lp: LabelPropVOS_CRW  ->  (labels [N,T] float, xent [N,T-1] (CPU), change_idx | None).
 
     anchors: None, or [T, N] int8 in the ITEM's frame order (`anchor_nodes`; flipped along T with ``seq`` under ``use_last``):
     labelled nodes inside the item, handed to ``lp.propagate_all`` (which needs CONTEXT 'sliding'); the row of the pass's seed frame
     is ignored.  A one-frame item ignores them.
+    anchor_context: 'clamp', or 'restart' (needs anchors): ``lp.propagate_all``'s option -- the context restarts at every fully
+    anchored frame, in the pass's own frame order (under ``use_last`` on the mirrored anchors).
 
     confidence: None, or a kind of `crw_hip.labelprop_confidence` ('maxprob', 'margin', 'entropy') -- the tuple then gains a
     fourth entry, conf [N,T] float on the labels' device: the confidence of every label, from the soft labels the propagation
@@ -159,6 +162,8 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, conf
     if confidence is not None and confidence not in crw_hip.CONF_KINDS:
         raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
     T, N, H, W = seq.shape
+    if crw_hip.check_anchor_context(anchor_context) == 'restart' and anchors is None:
+        raise ValueError("anchor_context='restart' needs anchors: a restart happens at a fully anchored frame")
     if anchors is not None:
         if not hasattr(lp, 'propagate_all'):
             raise ValueError("anchors need a label propagation with `propagate_all` (LabelPropVOS_CRW): the frame-by-frame protocol "
@@ -177,7 +182,8 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, conf
     diffs = column_diffs_async(xent) if T > 2 else None  # on its way to the host before the label propagation is queued
     if anchors is not None:
         a = anchors.to(torch.int8)  # left where it is: from the host (`anchor_nodes`) the frames are found without a device read
-        pred, L = lp.propagate_all(feats, seed, nclasses, anchors=(torch.flip(a, (0,)) if use_last else a).contiguous())
+        ckw = {} if anchor_context == 'clamp' else dict(anchor_context=anchor_context)
+        pred, L = lp.propagate_all(feats, seed, nclasses, anchors=(torch.flip(a, (0,)) if use_last else a).contiguous(), **ckw)
     elif hasattr(lp, 'propagate_all'):
         pred, L = lp.propagate_all(feats, seed, nclasses)
     else:  # foreign label-propagation object: reference's frame-by-frame protocol
@@ -213,7 +219,8 @@ def ndiag_matrix(size, n=1):
 
 
 @torch.no_grad()
-def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False, anchors=None):
+def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False, anchors=None,
+                    anchor_context='clamp'):
     """`propagate` for every configuration of ``sweep`` (imported.labelprop.LabelPropSweep) at once: the encoder, the metric and
     the change point do not depend on (radius, temp, knn) and run ONCE, on the batch `propagate` gives the encoder
     ->  (labels [G,N,T] float, xent [N,T-1] (CPU), change_idx | None); labels[g] is `propagate`'s for ``sweep.configs[g]``.
@@ -223,16 +230,20 @@ def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last
     configurations is ONE `crw_hip.labelprop_confidence` call on the stack read as G*T frames of one pass: the formula is per row,
     and every frame g*T is a one-hot seed, which reads 1.
     anchors: `propagate`'s -- [T, N] int8 in the ITEM's frame order, flipped here under ``use_last``, the same for all G
-    configurations (``sweep`` under context 'sliding'); a one-frame item ignores them."""
+    configurations (``sweep`` under context 'sliding'); a one-frame item ignores them.  anchor_context: `propagate`'s."""
     if confidence is not None and confidence not in crw_hip.CONF_KINDS:
         raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
     T, N, H, W = seq.shape
+    if crw_hip.check_anchor_context(anchor_context) == 'restart' and anchors is None:
+        raise ValueError("anchor_context='restart' needs anchors: a restart happens at a fully anchored frame")
     akw = {}
     if anchors is not None and T > 1:
         if tuple(anchors.shape) != (T, N):
             raise ValueError(f"anchors must be [{T}, {N}] (got {tuple(anchors.shape)})")
         a = anchors.to(torch.int8)
         akw = dict(anchors=(torch.flip(a, (0,)) if use_last else a).contiguous())
+        if anchor_context != 'clamp':
+            akw.update(anchor_context=anchor_context)
     feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
     G = len(sweep.configs)
     if T == 1:
