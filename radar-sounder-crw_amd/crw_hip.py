@@ -163,6 +163,12 @@ RESTART_SIGNATURES = {
     "crw_labelprop_propagate_origin_batch": (_c_int, [_p, _p, _p, _c_sz] + [_c_int] * 7 + [_p, _p, _p, _p]),
 }
 
+# include/crw_hip_routes.h, likewise: the route log -- which selector branch launched (optional: `has_routes()`; host pointers)
+ROUTES_SIGNATURES = {
+    "crw_routes_clear": (_c_int, []),
+    "crw_routes_read": (_c_int, [_p, _p, _c_int]),
+}
+
 # entry points added at ABI 8 without a bump: a library built before them still loads, `has_sweep()` tells
 SWEEP_ENTRY_POINTS = ("crw_labelprop_topk_scores", "crw_labelprop_sweep_weights", "crw_labelprop_propagate_batch")
 
@@ -200,6 +206,9 @@ CONV_CHAIN_ENTRY_POINTS = tuple(CHAIN_SIGNATURES)
 # likewise: the sliding rule with a per-frame origin, anchor_context='restart' (`has_anchor_restart()`)
 ANCHOR_RESTART_ENTRY_POINTS = tuple(RESTART_SIGNATURES)
 
+# likewise: the route log (`has_routes()`, `routes()`)
+ROUTES_ENTRY_POINTS = tuple(ROUTES_SIGNATURES)
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 ANCHOR_CONTEXTS = ("clamp", "restart")  # what a fully labelled anchor trace does to the frames behind it
 
@@ -209,7 +218,8 @@ OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_E
                          "dense_batch": DENSE_BATCH_ENTRY_POINTS, "horizons": HORIZONS_ENTRY_POINTS,
                          "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS, "joint": JOINT_ENTRY_POINTS,
                          "posterior": POSTERIOR_ENTRY_POINTS, "posterior_batch": POSTERIOR_BATCH_ENTRY_POINTS,
-                         "conv_chain": CONV_CHAIN_ENTRY_POINTS, "anchor_restart": ANCHOR_RESTART_ENTRY_POINTS}
+                         "conv_chain": CONV_CHAIN_ENTRY_POINTS, "anchor_restart": ANCHOR_RESTART_ENTRY_POINTS,
+                         "routes": ROUTES_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -225,7 +235,7 @@ def lib():
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
         missing = {n for names in OPTIONAL_ENTRY_POINTS.values() for n in names if not hasattr(handle, n)}
-        for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES, **RESTART_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES, **RESTART_SIGNATURES, **ROUTES_SIGNATURES}.items():
             if name in missing:
                 continue
             fn = getattr(handle, name)
@@ -270,6 +280,36 @@ has_posterior, _posterior_lib = _optional("posterior", "the ordered maps' poster
 has_posterior_batch, _posterior_batch_lib = _optional("posterior_batch", "the batched posterior entry points")
 has_conv_chain, _conv_chain_lib = _optional("conv_chain", "the conv-trunk chain entry point")
 has_anchor_restart, _anchor_restart_lib = _optional("anchor_restart", "the entry points that take a per-frame origin")
+has_routes, _routes_lib = _optional("routes", "the route log's entry points")
+
+MAX_ROUTES = 256  # csrc/crw_common.h
+
+
+def routes_read():
+    """{name: count} of the routes (the selector branches, named by CRW_ROUTE in csrc/) that launched since
+    the last `routes_clear()`, in this process.  Host work only."""
+    handle = _routes_lib()
+    names, counts = (ctypes.c_char_p * MAX_ROUTES)(), (ctypes.c_long * MAX_ROUTES)()
+    n = handle.crw_routes_read(ctypes.cast(names, _p), ctypes.cast(counts, _p), MAX_ROUTES)
+    return {names[i].decode(): counts[i] for i in range(min(n, MAX_ROUTES)) if counts[i]}
+
+
+def routes_clear():
+    _routes_lib().crw_routes_clear()
+
+
+class routes(dict):
+    """`with crw_hip.routes() as hit:` -- the counters are cleared on entry; on exit `hit` holds {name: count} of the routes the
+    block's calls took.  The names are decided on the host at launch, so no synchronisation is needed to read them."""
+
+    def __enter__(self):
+        self.clear()
+        routes_clear()
+        return self
+
+    def __exit__(self, *exc):
+        self.update(routes_read())
+        return False
 
 
 def check_context(context):

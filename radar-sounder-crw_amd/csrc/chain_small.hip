@@ -134,10 +134,13 @@ __global__ __launch_bounds__(NTH) void chain_small_kernel(const float *__restric
 template <bool BWD>
 int launch(const float *Gt, const float *F, float *X0, float *X1, int B, int K, int n, hipStream_t s) {
   if (B < 1 || K < 1 || (n != 32 && n != 64)) return CRW_EINVAL;
-  if (n == 64)
+  if (n == 64) {
+    CRW_ROUTE("chain_small.n64");
     hipLaunchKernelGGL((chain_small_kernel<64, BWD, 1024>), dim3(2 * B), dim3(1024), 0, s, Gt, F, X0, X1, B, K);
-  else
+  } else {
+    CRW_ROUTE("chain_small.n32");
     hipLaunchKernelGGL((chain_small_kernel<32, BWD, 256>), dim3(2 * B), dim3(256), 0, s, Gt, F, X0, X1, B, K);
+  }
   return check_launch();
 }
 

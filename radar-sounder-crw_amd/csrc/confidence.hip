@@ -368,8 +368,10 @@ extern "C" int crw_merge_confidence(const void *fwd_lab, const float *fwd_conf, 
   size_t head = 0;
   while (head < 16 && !aligned_at(head)) ++head;
   if (head >= 16 || head >= P) {
+    CRW_ROUTE("confidence.merge_scalar");
     a.head = 0, a.tail0 = 0;  // everything scalar
   } else {
+    CRW_ROUTE("confidence.merge_vector");
     a.head = head;
     a.tail0 = head + (P - head) / CONF_LANE_PIX * CONF_LANE_PIX;
   }

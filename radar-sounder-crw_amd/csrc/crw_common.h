@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <atomic>
 #include "crw_hip.h"
 
 namespace crw {
@@ -34,6 +35,23 @@ inline int check_launch() {
   do {                              \
     int _st = (expr);               \
     if (_st != CRW_OK) return _st;  \
+  } while (0)
+
+// ---- the route log (include/crw_hip_routes.h, routes.hip) ---------------------------------
+// CRW_ROUTE(<string literal>) stands in a host-side selector, behind argument validation and immediately in front of the launch the selector
+// decided on: the name says which code path ran (not every template integer; DESIGN.md section 8 has the table).  The site's
+// function-local static registers the name once (thread-safe: C++ static initialisation, then a mutex inside route_register);
+// every pass costs one relaxed atomic add on the host.  No allocation, no device work.
+constexpr int MAX_ROUTES = 256;
+struct RouteSite {
+  const char *name;
+  std::atomic<long> count;
+};
+RouteSite *route_register(const char *name);
+#define CRW_ROUTE(name)                                                        \
+  do {                                                                         \
+    static ::crw::RouteSite *const _crw_site = ::crw::route_register(name);    \
+    _crw_site->count.fetch_add(1, std::memory_order_relaxed);                  \
   } while (0)
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }

@@ -1534,6 +1534,8 @@ int launch_conv_nw(const ConvArgs &a, hipStream_t s) {
     }
     attr = true;
   }
+  if constexpr (NW == 4) CRW_ROUTE("conv.patch_nw4");
+  else CRW_ROUTE("conv.patch_nw8");
   hipLaunchKernelGGL((conv3x3_kernel<SPLIT, CIN, COUT, MODE, NW>), dim3(a.P), dim3(NW * 64), lds, s, a);
   return check_launch();
 }
@@ -1554,6 +1556,8 @@ int launch_conv_map_cls(const ConvArgs &a, hipStream_t s) {
     }
     attr = true;
   }
+  if constexpr (MTL == MT_SMALL) CRW_ROUTE("conv.map_small");
+  else CRW_ROUTE("conv.map_big");
   hipLaunchKernelGGL((conv3x3_kernel<SPLIT, CIN, COUT, MODE, NW, true, MTL>), dim3(a.P * a.ncls), dim3(NW * 64), lds, s, a);
   return check_launch();
 }
@@ -1613,6 +1617,7 @@ int launch_chain(K kernel, bool &attr, const ConvChainArgs &a, hipStream_t s) {
     }
     attr = true;
   }
+  CRW_ROUTE("conv.chain");
   hipLaunchKernelGGL(kernel, dim3(a.P), dim3(CHAIN_NW * 64), lds, s, a);
   return check_launch();
 }
@@ -1635,6 +1640,7 @@ int launch_wgrad(const WgradArgs &a, int nblk, hipStream_t s) {
     }
     attr = true;
   }
+  CRW_ROUTE("wgrad.gen1");
   hipLaunchKernelGGL((conv3x3_wgrad_kernel<SPLIT, CIN, COUT, NCI, NW>), dim3(nblk * (CIN / NCI) * (COUT / WG_NCO)),
                      dim3(NW * 64), lds, s, a);
   return check_launch();
@@ -1653,6 +1659,7 @@ int launch_wgrad_map(const WgradArgs &a, int nblk, hipStream_t s) {
     }
     attr = true;
   }
+  CRW_ROUTE("wgrad.map");
   hipLaunchKernelGGL((conv3x3_wgrad_kernel<SPLIT, CIN, COUT, NCI, NW, true>), dim3(nblk * (CIN / NCI) * (COUT / WG_NCO)),
                      dim3(NW * 64), lds, s, a);
   return check_launch();
@@ -1671,6 +1678,7 @@ int launch_wgrad2(const WgradArgs &a, int nslice, hipStream_t s) {
     }
     attr = true;
   }
+  CRW_ROUTE("wgrad.streamed");
   hipLaunchKernelGGL((conv3x3_wgrad2_kernel<SPLIT, CIN, COUT, DIAG>), dim3(nslice * (CIN / W2_NCI)), dim3(W2_NW * 64), lds, s, a);
   return check_launch();
 }

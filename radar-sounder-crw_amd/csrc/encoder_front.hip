@@ -1065,6 +1065,8 @@ int launch_front_fwd(void (*const (&kernels)[4])(Args), int split, const Args &a
       return CRW_EHIP;
     attr[which] = true;
   }
+  if (nt == 1024) CRW_ROUTE("front.fwd_nt1024");  // (patch and map forms alike)
+  else CRW_ROUTE("front.fwd_nt512");
   hipLaunchKernelGGL(kernels[which], dim3(nwork < 512 ? (int)nwork : 512), dim3(nt), lds, s, a);
   return check_launch();
 }
@@ -1163,9 +1165,12 @@ int crw_enc_front_bwd(int split, const float *x, int P, int cin, const float *w1
   FrontBwdArgs a{{x, w1, b1, w2_hi, w2_lo, b2, nullptr, nullptr, P, cin, const_cast<char *>(static_cast<const char *>(saved))},
                  w2b_hi, w2b_lo, dy, (float *)ws, ppb, g_front_stamps};
   static const char *force_rc = getenv("CRW_FRONT_RECOMPUTE");  // diagnostics / A-B: ignore the saved record
-  if (saved && !(force_rc && force_rc[0] == '1'))
+  if (saved && !(force_rc && force_rc[0] == '1')) {
+    CRW_ROUTE("front.bwd_saved");
     return launch_front_bwd<front_bwd_saved_kernel<1>, front_bwd_saved_kernel<3>>(split, a, nslice, lds_bytes<SavedLds>(cin), dw1,
                                                                                   db1, dw2, db2, s);
+  }
+  CRW_ROUTE("front.bwd_recompute");
   return launch_front_bwd<front_bwd_kernel<1>, front_bwd_kernel<3>>(split, a, nslice, lds_bytes<RecomputeLds>(cin, XPW, C1W), dw1,
                                                                     db1, dw2, db2, s);
 }
@@ -1190,6 +1195,7 @@ int crw_enc_front_bwd_map(int split, const float *x, int P, int cin, int H, int 
   const int upb = (units + nslice - 1) / nslice;
   nslice = (units + upb - 1) / upb;
   FrontBwdArgs a{{x, w1, b1, w2_hi, w2_lo, b2, nullptr, nullptr, P, cin, nullptr}, w2b_hi, w2b_lo, dy, (float *)ws, upb, nullptr, H, W, tx, ty};
+  CRW_ROUTE("front.bwd_tile");
   return launch_front_bwd<front_bwd_tile_kernel<1>, front_bwd_tile_kernel<3>>(split, a, nslice, lds_bytes<RecomputeLds>(cin, TXW, TCW),
                                                                               dw1, db1, dw2, db2, (hipStream_t)stream);
 }

@@ -488,8 +488,9 @@ inline bool rega_on() {
   return on;
 }
 
-// CRW_GEMM_RING5=1 (opt-in): plain-bf16 256 x 256 products on the ring of five 32-deep half-tiles instead of the two-stage ring of
-// 64-deep tiles.  Measured both ways (profiles/r04_gemm_ceiling.log, profiles/r04_gemm_ring5.log): back to back in the stand-alone
+// CRW_GEMM_RING5=1 (opt-in; launch_layout tests it ahead of the stagger branches, so the switch alone reaches mainloop_ring5, and
+// tests/test_variants.py proves that from the route log): plain-bf16 256 x 256 products on the ring of five 32-deep half-tiles
+// instead of the two-stage ring of 64-deep tiles.  Measured both ways (profiles/r04_gemm_ceiling.log, profiles/r04_gemm_ring5.log): back to back in the stand-alone
 // micro-benchmark the five-slot ring is 6 % faster (1151 against 1080 TFLOP/s), through the library from the walk it is 4-9 %
 // SLOWER in all four operand layouts and the whole N = 4096 walk takes 48.0 against 46.3 ms -- and the micro-benchmark's
 // "LDS-DMA stream + barrier" variant runs at the same 38-44 GB/s per CU with either ring: deeper prefetch does not raise what a
@@ -509,38 +510,55 @@ inline int stagger_on() {
   return on;
 }
 
+// Precedence of the switches (each branch names its route): CRW_GEMM_REGA=1 takes every plain-bf16 product
+// and puts 256-tile hi/lo pairs on the unstaggered loop; then CRW_GEMM_RING5=1 takes the plain-bf16 256-tiles -- tested BEFORE the
+// stagger branches, whose default would otherwise shadow it; then CRW_GEMM_STAGGER picks the 256-tile schedule.
 template <int SPLIT, int TB>
 int launch_layout(const GemmGroup &g, int code, hipStream_t s) {
-  if constexpr (TB == 256) {
-    if (stagger_on() == 2 && !rega_on()) switch (code) {
-        case 3: return launch_one<SPLIT, TB, true, true, false, 9>(g, s);
-        case 2: return launch_one<SPLIT, TB, true, false, false, 9>(g, s);
-        case 1: return launch_one<SPLIT, TB, false, true, false, 9>(g, s);
-        default: return launch_one<SPLIT, TB, false, false, false, 9>(g, s);
-      }
-    if (stagger_on() == 1 && !rega_on()) switch (code) {
-        case 3: return launch_one<SPLIT, TB, true, true, false, 8>(g, s);
-        case 2: return launch_one<SPLIT, TB, true, false, false, 8>(g, s);
-        case 1: return launch_one<SPLIT, TB, false, true, false, 8>(g, s);
-        default: return launch_one<SPLIT, TB, false, false, false, 8>(g, s);
-      }
-  }
   if constexpr (SPLIT == 1 && TB == 256) {
-    if (ring5_on() && !rega_on()) switch (code) {
+    if (ring5_on() && !rega_on()) {
+      CRW_ROUTE("gemm_bf16.t256_ring5");
+      switch (code) {
         case 3: return launch_one<SPLIT, TB, true, true, false, 0, true>(g, s);
         case 2: return launch_one<SPLIT, TB, true, false, false, 0, true>(g, s);
         case 1: return launch_one<SPLIT, TB, false, true, false, 0, true>(g, s);
         default: return launch_one<SPLIT, TB, false, false, false, 0, true>(g, s);
       }
+    }
+  }
+  if constexpr (TB == 256) {
+    if (stagger_on() == 2 && !rega_on()) {
+      CRW_ROUTE("gemm_bf16.t256_stagger2");
+      switch (code) {
+        case 3: return launch_one<SPLIT, TB, true, true, false, 9>(g, s);
+        case 2: return launch_one<SPLIT, TB, true, false, false, 9>(g, s);
+        case 1: return launch_one<SPLIT, TB, false, true, false, 9>(g, s);
+        default: return launch_one<SPLIT, TB, false, false, false, 9>(g, s);
+      }
+    }
+    if (stagger_on() == 1 && !rega_on()) {
+      CRW_ROUTE("gemm_bf16.t256_stagger");
+      switch (code) {
+        case 3: return launch_one<SPLIT, TB, true, true, false, 8>(g, s);
+        case 2: return launch_one<SPLIT, TB, true, false, false, 8>(g, s);
+        case 1: return launch_one<SPLIT, TB, false, true, false, 8>(g, s);
+        default: return launch_one<SPLIT, TB, false, false, false, 8>(g, s);
+      }
+    }
   }
   if constexpr (SPLIT == 1) {
-    if (rega_on()) switch (code) {
+    if (rega_on()) {
+      CRW_ROUTE("gemm_bf16.rega");
+      switch (code) {
         case 3: return launch_one<SPLIT, TB, true, true, true>(g, s);
         case 2: return launch_one<SPLIT, TB, true, false, true>(g, s);
         case 1: return launch_one<SPLIT, TB, false, true, true>(g, s);
         default: return launch_one<SPLIT, TB, false, false, true>(g, s);
       }
+    }
   }
+  if constexpr (TB == 256) CRW_ROUTE("gemm_bf16.t256_stagger0");  // every wave requests right behind the barrier
+  else CRW_ROUTE("gemm_bf16.t128");
   switch (code) {
     case 3: return launch_one<SPLIT, TB, true, true>(g, s);
     case 2: return launch_one<SPLIT, TB, true, false>(g, s);

@@ -769,18 +769,23 @@ int launch_gemm_group_f32(const GemmGroup &g, hipStream_t s) {
   if (g.nprob < 1 || g.nprob > MAX_GROUP || g.n <= 0 || g.n % 32 || g.batch < 1) return CRW_EINVAL;
   const int tile = pick_tile(g.n, (long)g.batch * g.nprob);
   dim3 grid((g.n / tile) * (g.n / tile), g.batch, g.nprob);
-  if (tile == 128)
+  if (tile == 128) {
+    CRW_ROUTE("gemm_f32.t128");
     hipLaunchKernelGGL((gemm_pad_f32_kernel<128, 128>), grid, dim3(256), 0, s, g);
-  else if (tile == 64)
+  } else if (tile == 64) {
+    CRW_ROUTE("gemm_f32.t64");
     hipLaunchKernelGGL((gemm_pad_f32_kernel<64, 64>), grid, dim3(256), 0, s, g);
-  else
+  } else {
+    CRW_ROUTE("gemm_f32.t32");
     hipLaunchKernelGGL((gemm_pad_f32_kernel<32, 32>), grid, dim3(256), 0, s, g);
+  }
   return check_launch();
 }
 
 int launch_edge_gemm(const EdgeGemm &g, int batch, hipStream_t s) {
   if (g.M < 1 || g.N < 1 || batch < 1) return CRW_EINVAL;
   dim3 grid((g.N + EB - 1) / EB, (g.M + EB - 1) / EB, batch);
+  CRW_ROUTE("gemm_f32.edge");
   hipLaunchKernelGGL(edge_gemm_kernel, grid, dim3(256), 0, s, g);
   return check_launch();
 }
@@ -820,16 +825,20 @@ int launch_affinity_tiles(const float *ehat, int B, int T, int N, int C, float t
   const bool single = tiles == 1;
   if (N <= 64) {  // one 64 x 64 tile per matrix
     const size_t lds64 = sizeof(float) * (size_t)(64 * 68 + 2 * 2 * 64 * 2);  // tile image + half-tile partials (> the operand tiles)
+    CRW_ROUTE("affinity.fwd_f32_t64");
     hipLaunchKernelGGL((affinity_tile_kernel<false, 64>), dim3(1, nmat), dim3(256), lds64, s, ehat, T, N, C, tau, A, nullptr, 1,
                        stats);
     return check_launch();
   }
-  if (affinity_on_bf16(N, C))
+  if (affinity_on_bf16(N, C)) {
+    CRW_ROUTE("affinity.fwd_bf16x6");
     hipLaunchKernelGGL(affinity_tile_kernel<true>, dim3(tiles * tiles, nmat), dim3(256), lds, s, ehat, T, N, C, tau, A,
                        (stats && !single) ? part : nullptr, tiles, (stats && single) ? stats : nullptr);
-  else
+  } else {
+    CRW_ROUTE("affinity.fwd_f32_t128");
     hipLaunchKernelGGL(affinity_tile_kernel<false>, dim3(tiles * tiles, nmat), dim3(256), lds, s, ehat, T, N, C, tau, A,
                        (stats && !single) ? part : nullptr, tiles, (stats && single) ? stats : nullptr);
+  }
   if (stats && !single) {
     const long n = 2L * nmat * N;
     hipLaunchKernelGGL(affinity_stats_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, nmat, tiles, N, stats);
@@ -846,6 +855,10 @@ int launch_affinity_bwd_tiles(const float *dA, const float *ehat, int B, int T, 
   if (N <= 64 && !(N & 3)) hipLaunchKernelGGL((affinity_bwd_tile_kernel<TNV, 64, true>), dim3(1, B * T), dim3(256), 0, s, dA, ehat, T, N, tau, dehat); \
   else if (N <= 64) hipLaunchKernelGGL((affinity_bwd_tile_kernel<TNV, 64, false>), dim3(1, B * T), dim3(256), 0, s, dA, ehat, T, N, tau, dehat);       \
   else hipLaunchKernelGGL((affinity_bwd_tile_kernel<TNV, 128, false>), grid, dim3(256), 0, s, dA, ehat, T, N, tau, dehat);
+    if (C != 32 && C != 64 && C != 128) return CRW_EINVAL;
+    if (N <= 64 && !(N & 3)) CRW_ROUTE("affinity.bwd_f32_t64");
+    else if (N <= 64) CRW_ROUTE("affinity.bwd_f32_t64_elem");
+    else CRW_ROUTE("affinity.bwd_f32_t128_elem");
     switch (C) {
       case 32: CRW_AFB(1) break;
       case 64: CRW_AFB(2) break;
@@ -856,9 +869,12 @@ int launch_affinity_bwd_tiles(const float *dA, const float *ehat, int B, int T, 
     return check_launch();
   }
   if (C == 128 && affinity_on_bf16(N, C)) {
+    CRW_ROUTE("affinity.bwd_bf16x6");
     hipLaunchKernelGGL(affinity_bwd_x6_kernel, grid, dim3(256), 0, s, dA, ehat, T, N, tau, dehat);
     return check_launch();
   }
+  if (C != 32 && C != 64 && C != 128) return CRW_EINVAL;
+  CRW_ROUTE("affinity.bwd_f32_t128");
   switch (C) {
     case 32: hipLaunchKernelGGL(affinity_bwd_tile_kernel<1>, grid, dim3(256), 0, s, dA, ehat, T, N, tau, dehat); break;
     case 64: hipLaunchKernelGGL(affinity_bwd_tile_kernel<2>, grid, dim3(256), 0, s, dA, ehat, T, N, tau, dehat); break;

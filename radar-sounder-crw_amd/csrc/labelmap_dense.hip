@@ -310,6 +310,9 @@ int dense_launch(const float *L, int G, int T, int N, int M, int rows, int cols,
   const auto kernel = kernel_for(label_dtype, conf_kind, M, [](auto lab, auto kind, auto mcap) {
     return labelmap_dense_kernel<decltype(lab), kind(), mcap(), BATCH>;
   });
+  if constexpr (!BATCH) CRW_ROUTE("dense.single");
+  else if (chunk > 1) CRW_ROUTE("dense.batch_chunked");
+  else CRW_ROUTE("dense.batch_chunk1");
   hipLaunchKernelGGL(kernel, grid, dim3(DN_BLOCK), 0, (hipStream_t)stream, a);
   return check_launch();
 }
@@ -552,6 +555,8 @@ int ordered_decode_args(const int *order, int S, void *ws, size_t ws_bytes, Orde
   if (const int st = ordered_order(order, S, a)) return st;
   if (ws_bytes < ordered_ws_bytes(a.d.G, a.d.rows, a.d.cols)) return CRW_EWORKSPACE;
   a.ws = static_cast<uint16_t *>(ws), a.ws_ld = ordered_ws_ld(a.d.cols), a.back = ordered_back();
+  if (a.back == 1) CRW_ROUTE("ordered.back_one_word");  // (the last check of every ordered decode: the launch follows)
+  else CRW_ROUTE("ordered.back_default");
   return CRW_OK;
 }
 

@@ -346,6 +346,9 @@ int launch_topk_mfma_n(const float *ehat, int T, int N, int cxt, int radius, flo
                        float *W, int32_t *I, int raw, const int32_t *origin, hipStream_t s) {
   const dim3 grid((N + TK_Q - 1) / TK_Q, T - first_frame);
   const size_t lds = (size_t)TK_Q * chunkcand * 4;
+  if constexpr (NCH == 1) CRW_ROUTE("labelprop.topk_mfma_chunks1");
+  else if constexpr (NCH == 2) CRW_ROUTE("labelprop.topk_mfma_chunks2");
+  else CRW_ROUTE("labelprop.topk_mfma_long");
   if (origin)
     return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH, true>>(grid, dim3(TK_NT), lds, s, ehat, T, N, cxt, radius, temp, knn,
                                                                          first_frame, chunkcand, pf, W, I, raw, origin);
@@ -1174,6 +1177,7 @@ int topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, 
     return launch_topk_mfma_long<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, s);
   }
   if (lds > 60 * 1024) return CRW_EINVAL;
+  CRW_ROUTE("labelprop.topk_valu");
   if (origin)
     hipLaunchKernelGGL(labelprop_topk_kernel<true>, dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T, N, C, cxt_size,
                        radius, temp, knn, first_frame, grid_w, W, I, raw, origin);
@@ -1221,12 +1225,15 @@ int launch_chain_kp(const float *seed, const float *W, const int32_t *I, int T, 
   const int ncw = chain_ncw((long)N * M);
   const dim3 block((ncw + chain_nld((long)N * M) + 1) * 64);
   if constexpr (RING) {
+    if (origin) CRW_ROUTE("labelprop.slide_ring_origin");
+    else CRW_ROUTE("labelprop.slide_ring");
     if (origin)
       return launch_big_lds<labelprop_slide_kernel<KP, true>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, cxt, R, L, pred,
                                                               ncw, origin);
     return launch_big_lds<labelprop_slide_kernel<KP, false>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, cxt, R, L, pred,
                                                              ncw, origin);
   } else {
+    CRW_ROUTE("labelprop.propagate_prefix");
     return launch_big_lds<labelprop_prefix_kernel<KP>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, last, L, pred, ncw);
   }
 }
@@ -1256,9 +1263,15 @@ int launch_gather(const float *seed, const float *W, const int32_t *I, int T, in
   static const char *force_global = getenv("CRW_LABELPROP_GATHER_GLOBAL");  // diagnostics: the L2-round-trip kernel
   if (KN <= (long)GATHER_NT * GATHER_PF && R >= 4 && (long)T * N < (1L << 30) / M && !force_global) {
     const size_t lds = (size_t)(4 * (NM * (R + 1) + 4 * KN));
+    if constexpr (ORG) CRW_ROUTE("labelprop.slide_general_origin_lds");
+    else if constexpr (SLIDE) CRW_ROUTE("labelprop.slide_general_lds");
+    else CRW_ROUTE("labelprop.gather_lds");
     return launch_big_lds<labelprop_gather_lds_kernel<SLIDE, ORG>>(dim3(1), dim3(GATHER_NT), lds, (hipStream_t)stream, seed, W, I, T, N, M, knn,
                                                                    first_frame, L, pred, (int)R, cxt, origin);
   }
+  if constexpr (ORG) CRW_ROUTE("labelprop.slide_general_origin_global");
+  else if constexpr (SLIDE) CRW_ROUTE("labelprop.slide_general_global");
+  else CRW_ROUTE("labelprop.gather_global");
   hipLaunchKernelGGL((labelprop_gather_kernel<SLIDE, ORG>), dim3(1), dim3(1024), 0, (hipStream_t)stream, seed, W, I, T, N, M, knn,
                      first_frame, L, pred, cxt, origin);
   return check_launch();
@@ -1279,6 +1292,9 @@ int launch_propagate_batch(const float *seed, const float *W, const int32_t *I, 
     if (R > last + 1) R = last + 1;
     if (R < 2) R = 2;
     const int nt = (int)(NM >= 1024 ? 1024 : (NM + 63) / 64 * 64);
+    if constexpr (ORG) CRW_ROUTE("labelprop.batch_slide_origin");
+    else if constexpr (SLIDE) CRW_ROUTE("labelprop.batch_slide");
+    else CRW_ROUTE("labelprop.batch_reference");
     const int rc = launch_big_lds<labelprop_chain_batch_kernel<SLIDE, ORG>>(dim3(G), dim3(nt), (size_t)(4 * NM * (R + 1)), s, seed, W, I,
                                                                             (long)i_stride, T, N, M, knn, first_frame, last, L, pred, (int)R,
                                                                             cxt_size, origin);
@@ -1408,9 +1424,11 @@ int crw_xent_metric(const float *ehat, int T, int N, int C, float *xent, crw_str
   if (!ehat || !xent || T < 2 || N < 1 || C < 2 || (size_t)N * 4 > 60 * 1024) return CRW_EINVAL;
   const size_t ld = (((size_t)C + 3) & ~(size_t)3) + 4, frame_lds = (2 * (size_t)N * ld + (size_t)N * N) * 4;
   if (frame_lds <= 64 * 1024) {  // a frame's features fit LDS twice: a workgroup per frame
+    CRW_ROUTE("xent.frame");
     hipLaunchKernelGGL(xent_metric_frame_kernel, dim3(T - 1), dim3(XENT_NT), frame_lds, (hipStream_t)stream, ehat, T, N, C, xent);
     return check_launch();
   }
+  CRW_ROUTE("xent.column");
   hipLaunchKernelGGL(xent_metric_kernel, dim3(N, T - 1), dim3(64), (size_t)N * 4, (hipStream_t)stream, ehat, T, N, C,
                      xent);
   return check_launch();

@@ -932,6 +932,9 @@ int rn_sums_tail(const float *in, int R, int C, double *part2, unsigned *tickets
   const int want = NS * C >= 256 ? 32 : 64;
   const int RB = (R + want - 1) / want > 0 ? (R + want - 1) / want : 1;
   const int R2 = (R + RB - 1) / RB;
+  if (mode == 1) CRW_ROUTE("rn_bn.ticket_relaxed");
+  else if (mode == 2) CRW_ROUTE("rn_bn.ticket_acqrel");
+  else CRW_ROUTE("rn_bn.ticket_fence");
   hipLaunchKernelGGL((rn_sums_tail_kernel<NS, INTERLEAVED, Tail>), dim3((C + 63) / 64, R2), dim3(1024), 0, s, in, R, C, RB, part2, tickets,
                      mode, tail);
   return check_launch();

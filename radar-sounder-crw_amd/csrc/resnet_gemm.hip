@@ -814,7 +814,10 @@ int launch_wgrad_cfg(const RnWgradArgs &a, hipStream_t s) {
 int rn_conv_bk() {
   static int bk = -1;
   if (bk < 0) {
-    const char *e = getenv("CRW_RN_BK");  // A/B knob: force the k-tile depth (64: two 64-deep stages; 32: three 32-deep stages)
+    // A/B knob of the PLAIN kernel only (rn_conv_kernel: CRW_RN_SPEC=0, and the stem's backward-data product whatever CRW_RN_SPEC
+    // says): force the k-tile depth (64: two 64-deep stages; 32: three 32-deep stages).  launch_rn_conv reads it behind the
+    // split-role branch, so with the default CRW_RN_SPEC it moves the stem backward alone.
+    const char *e = getenv("CRW_RN_BK");
     bk = e ? atoi(e) : 0;
   }
   return bk;
@@ -833,16 +836,35 @@ int launch_rn_conv(const RnConvArgs &a, hipStream_t s) {
   // a quarter fewer staged bytes per flop but one workgroup per CU, 4.98 ms; forward 3x3x128 product 87 -> 110 us): what these
   // short-k products need is the second workgroup that covers prologue and epilogue.  CRW_RN_SPEC=0 selects rn_conv_kernel.
   static const int tm = [] { const char *e = getenv("CRW_RN_TM"); return e ? atoi(e) : 128; }();  // 256: 256-patch tiles on 8 waves
-  if (tm == 256 && a.mtiles % 2 == 0 && a.mode != RN_MODE_STEM_BWD)
+  if (tm == 256 && a.mtiles % 2 == 0 && a.mode != RN_MODE_STEM_BWD) {
+    CRW_ROUTE("rn_conv.tm256");
     return wide ? launch_conv_cfg<128, 32, 2, 256>(a, s) : launch_conv_cfg<64, 32, 2, 256>(a, s);
+  }
   static const int spec = [] { const char *e = getenv("CRW_RN_SPEC"); return e ? atoi(e) : 2; }();
   if (spec && a.mode != RN_MODE_STEM_BWD) {
-    if (spec == 3) return wide ? launch_conv_spec<128, 32, 3>(a, s) : launch_conv_spec<64, 32, 3>(a, s);
-    if (spec == 4) return wide ? launch_conv_spec<128, 32, 4>(a, s) : launch_conv_spec<64, 32, 4>(a, s);
+    if (spec == 3) {
+      CRW_ROUTE("rn_conv.spec3");
+      return wide ? launch_conv_spec<128, 32, 3>(a, s) : launch_conv_spec<64, 32, 3>(a, s);
+    }
+    if (spec == 4) {
+      CRW_ROUTE("rn_conv.spec4");
+      return wide ? launch_conv_spec<128, 32, 4>(a, s) : launch_conv_spec<64, 32, 4>(a, s);
+    }
+    CRW_ROUTE("rn_conv.spec2");
     return wide ? launch_conv_spec<128, 32, 2>(a, s) : launch_conv_spec<64, 32, 2>(a, s);
   }
   int bk = rn_conv_bk();
   if (bk != 32 && bk != 64 && bk != 322) bk = a.mode == RN_MODE_STEM_BWD ? 64 : 322;
+  // (the stem backward has names of its own: it is on this kernel, at 64 deep, in every environment)
+  if (a.mode == RN_MODE_STEM_BWD) {
+    if (bk == 322) CRW_ROUTE("rn_conv.stem_bwd_bk322");
+    else if (bk == 32) CRW_ROUTE("rn_conv.stem_bwd_bk32");
+    else CRW_ROUTE("rn_conv.stem_bwd_bk64");
+  } else {
+    if (bk == 322) CRW_ROUTE("rn_conv.plain_bk322");
+    else if (bk == 32) CRW_ROUTE("rn_conv.plain_bk32");
+    else CRW_ROUTE("rn_conv.plain_bk64");
+  }
   if (bk == 322) return wide ? launch_conv_cfg<128, 32, 2>(a, s) : launch_conv_cfg<64, 32, 3>(a, s);
   if (bk == 32) return wide ? launch_conv_cfg<128, 32, 3>(a, s) : launch_conv_cfg<64, 32, 3>(a, s);
   return wide ? launch_conv_cfg<128, 64, 2>(a, s) : launch_conv_cfg<64, 64, 2>(a, s);
@@ -881,11 +903,13 @@ int launch_rn_wgrad(const RnWgradArgs &a, float *dw, hipStream_t s) {
   }
   int st;
   if (bk == 32) {
+    CRW_ROUTE("rn_wgrad.bk32");
     if (m128 && n128) st = launch_wgrad_cfg<128, 128, 32>(a, s);
     else if (m128) st = launch_wgrad_cfg<128, 64, 32>(a, s);
     else if (n128) st = launch_wgrad_cfg<64, 128, 32>(a, s);
     else st = launch_wgrad_cfg<64, 64, 32>(a, s);
   } else {
+    CRW_ROUTE("rn_wgrad.bk64");
     if (m128 && n128) st = launch_wgrad_cfg<128, 128, 64>(a, s);
     else if (m128) st = launch_wgrad_cfg<128, 64, 64>(a, s);
     else if (n128) st = launch_wgrad_cfg<64, 128, 64>(a, s);

@@ -323,6 +323,8 @@ int forward_pass(bool training, bool keep, const float *x, int P, int cin, int h
   auto fork = [&]() { return sw == s || g_side.order(s, sw) ? CRW_OK : CRW_EHIP; };
   auto join = [&]() { return sw == s || g_side.order(sw, s) ? CRW_OK : CRW_EHIP; };
   SideJoin guard{g_side, s, sw};
+  if (sw != s) CRW_ROUTE("rn_net.fwd_side_stream");
+  else CRW_ROUTE("rn_net.fwd_one_stream");
   CRW_TRY(rn_zero_tickets(pl.tickets, 2, s));
 
   // all convolution / linear weights -> hi / lo planes (forward and backward-data layouts), one launch
@@ -377,6 +379,7 @@ int forward_pass(bool training, bool keep, const float *x, int P, int cin, int h
       }
       CRW_TRY(bn_coef(pl.part, rn_stem16_blocks() * 8, 64, (double)P * pl.H1 * pl.W1, prm[5], prm[6], 1, pl.coef1, pl.stats_ws, s));
     } else {
+      CRW_ROUTE("rn_stem.gathered");
       CRW_TRY(conv(s, RN_MODE_STEM_FWD, P, pl.Hm, pl.Wm, 4, pl.H1, pl.W1, 64, 7, 2, 3, pl.xmap, pl.wsf_h, pl.wsf_l, nullptr, pl.Z1,
                    training ? pl.part : nullptr));
       CRW_TRY(bn_coef(pl.part, (pl.Ppad / 128) * 2 * pl.H1 * pl.W1, 64, (double)P * pl.H1 * pl.W1, prm[5], prm[6], 1, pl.coef1, pl.stats_ws, s));
@@ -469,6 +472,8 @@ int crw_rn_train_bwd(const float *dout, const float *x, int P, int cin, int h, i
   g_side.used = 0;
   auto fork = [&]() { return sw == s || g_side.order(s, sw) ? CRW_OK : CRW_EHIP; };  // side stream sees what the chain has produced
   SideJoin guard{g_side, s, sw};  // error paths included: the caller's stream waits for whatever the side stream still holds
+  if (sw != s) CRW_ROUTE("rn_net.bwd_side_stream");
+  else CRW_ROUTE("rn_net.bwd_one_stream");
   CRW_TRY(rn_zero_tickets(pl.tickets, 2, s));
 
   // head (one product over layer4's hl x wl map, see Plan): per-pixel weight gradients, then their mean = fc.weight's gradient
@@ -484,6 +489,8 @@ int crw_rn_train_bwd(const float *dout, const float *x, int P, int cin, int h, i
   // The separate reduce pass (10 B per element re-read from HBM) disappears: 5.04 -> 4.8 ms per step.  CRW_RN_FUSE_RED=0 keeps it.
   // (Straight from the accumulator layout -- 64-byte row pieces -- the same fusion measured SLOWER than the separate pass.)
   static const bool fuse_red = !(getenv("CRW_RN_FUSE_RED") && getenv("CRW_RN_FUSE_RED")[0] == '0');
+  if (fuse_red) CRW_ROUTE("rn_net.bwd_fused_red");
+  else CRW_ROUTE("rn_net.bwd_separate_red");
   const int rrows = pl.Ppad / 128 * 2;  // partial rows per group
   float *g = pl.g[0];                   // gradient of the current block's output
   {

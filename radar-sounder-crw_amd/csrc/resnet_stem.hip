@@ -644,6 +644,7 @@ int launch_rn_pack_stem_frag(const float *w1, uint16_t *wf, uint16_t *wt, hipStr
 int launch_rn_stem16_fwd(const float *x, int P, int cin, const float *stem, const uint16_t *wf, float *Z1, float *part, hipStream_t s) {
   const size_t lds = WFRAG_BYTES + 8 * 2 * MAP_PLANE;
   static bool set1 = false, set2 = false;
+  CRW_ROUTE("rn_stem.patch_per_wave");
   if (cin == 1) {
     if (!set1) { CRW_TRY(set_lds(rn_stem_fwd_kernel<1>, lds)); set1 = true; }
     hipLaunchKernelGGL(rn_stem_fwd_kernel<1>, dim3(rn_stem16_blocks()), dim3(512), lds, s, x, stem, wf, P, Z1, part);
@@ -678,6 +679,7 @@ int launch_rn_stem_band_fwd(const float *x, int P, int cin, int h, int w, const 
   if (!stem_band_geometry(h, w, g) || (cin != 1 && cin != 2)) return CRW_EINVAL;
   const size_t lds = WFRAG_BYTES + (size_t)8 * 2 * g.MR * g.MW * 8;
   static size_t set1 = 0, set2 = 0;  // dynamic-LDS limit raised so far, per instantiation
+  CRW_ROUTE("rn_stem.band");
   if (cin == 1) {
     if (set1 < lds) { CRW_TRY(set_lds(rn_stem_fwd_band_kernel<1>, (size_t)160 * 1024)); set1 = (size_t)160 * 1024; }
     hipLaunchKernelGGL(rn_stem_fwd_band_kernel<1>, dim3(rn_stem16_blocks()), dim3(512), lds, s, x, stem, wf, P, g, Z1, part);

@@ -348,6 +348,7 @@ int launch_softmax_fwd(const float *A, const float *stats_ext, int B, int Tm1, i
   float *rmax = stats, *rsum = stats + (long)nmat * Np, *cmax = stats + 2L * nmat * Np, *csum = stats + 3L * nmat * Np;
   const bool vec = (N % 4) == 0 && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
   if (stats_ext) {
+    CRW_ROUTE("softmax.stats_import");
     hipLaunchKernelGGL(import_stats_kernel, dim3((N + 255) / 256, nmat), dim3(256), 0, s, stats_ext, B, Tm1, N, Np, stats);
   } else {
     const dim3 grid((N + 3) / 4 + (N + 255) / 256, nmat);
@@ -355,12 +356,15 @@ int launch_softmax_fwd(const float *A, const float *stats_ext, int B, int Tm1, i
     else hipLaunchKernelGGL(stats_kernel<false>, grid, dim3(256), 0, s, A, B, Tm1, N, Np, (N + 3) / 4, rmax, rsum, cmax, csum);
   }
   const dim3 grid(Np / 4, nmat);
-  if (vec)
+  if (vec) {  // (the statistics kernel above, when it ran, took the same form)
+    CRW_ROUTE("softmax.fwd_vec");
     hipLaunchKernelGGL(softmax_write_kernel<true>, grid, dim3(256), 0, s, A, B, Tm1, N, Np, rmax, rsum, cmax, csum, F, Gt,
                        (uint16_t *)Fh, (uint16_t *)Fl, (uint16_t *)Gh, (uint16_t *)Gl);
-  else
+  } else {
+    CRW_ROUTE("softmax.fwd_scalar");
     hipLaunchKernelGGL(softmax_write_kernel<false>, grid, dim3(256), 0, s, A, B, Tm1, N, Np, rmax, rsum, cmax, csum, F, Gt,
                        (uint16_t *)Fh, (uint16_t *)Fl, (uint16_t *)Gh, (uint16_t *)Gl);
+  }
   return check_launch();
 }
 
@@ -368,10 +372,13 @@ int launch_stats_dense(const float *A, int nmat, int N, float *stats, hipStream_
   // stats_kernel with B = nmat, T-1 = 1 maps internal matrix i to caller matrix i, and Np = N makes the rows dense
   float *rmax = stats, *rsum = stats + (long)nmat * N, *cmax = stats + 2L * nmat * N, *csum = stats + 3L * nmat * N;
   const dim3 grid((N + 3) / 4 + (N + 255) / 256, nmat);
-  if ((N % 4) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0)
+  if ((N % 4) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0) {
+    CRW_ROUTE("softmax.stats_dense_vec");
     hipLaunchKernelGGL(stats_kernel<true>, grid, dim3(256), 0, s, A, nmat, 1, N, N, (N + 3) / 4, rmax, rsum, cmax, csum);
-  else
+  } else {
+    CRW_ROUTE("softmax.stats_dense_scalar");
     hipLaunchKernelGGL(stats_kernel<false>, grid, dim3(256), 0, s, A, nmat, 1, N, N, (N + 3) / 4, rmax, rsum, cmax, csum);
+  }
   return check_launch();
 }
 
@@ -383,9 +390,11 @@ int launch_softmax_bwd(const float *A, const float *stats, const float *dF, cons
   const bool vec = (N % 4) == 0 && (((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(dA)) & 15) == 0);
   const dim3 g1((N + 3) / 4 + (N + 63) / 64, nmat), g2((N + 3) / 4, nmat);
   if (vec) {
+    CRW_ROUTE("softmax.bwd_vec");
     hipLaunchKernelGGL(dots_kernel<true>, g1, dim3(256), 0, s, A, B, Tm1, N, Np, (N + 3) / 4, rmax, rsum, cmax, csum, dF, dGt, rdot, cdot);
     hipLaunchKernelGGL(softmax_bwd_write_kernel<true>, g2, dim3(256), 0, s, A, B, Tm1, N, Np, rmax, rsum, cmax, csum, dF, dGt, rdot, cdot, dA);
   } else {
+    CRW_ROUTE("softmax.bwd_scalar");
     hipLaunchKernelGGL(dots_kernel<false>, g1, dim3(256), 0, s, A, B, Tm1, N, Np, (N + 3) / 4, rmax, rsum, cmax, csum, dF, dGt, rdot, cdot);
     hipLaunchKernelGGL(softmax_bwd_write_kernel<false>, g2, dim3(256), 0, s, A, B, Tm1, N, Np, rmax, rsum, cmax, csum, dF, dGt, rdot, cdot, dA);
   }

@@ -276,8 +276,10 @@ int crw_walk_fwd(const float *A, const float *stats_ext, int B, int T, int N, in
 
   // the sequential part: Lt_{k+1} = Gt_k Lt_k, R_{k+1} = F_k R_k   (array index i holds X_{i+1})
   if (small) {
+    CRW_ROUTE("walk.fwd_persistent");
     CRW_TRY(launch_chain_small_fwd(st.Gt.f, st.F.f, st.Lt.f, st.R.f, B, K, Np, s));
   } else {
+    CRW_ROUTE("walk.fwd_gemm");
     for (int i = 1; i < K; ++i) {
       GemmGroup g{};
       g.n = Np; g.batch = B;
@@ -355,8 +357,10 @@ int crw_walk_bwd(const float *gloss, const float *A, int B, int T, int N, int ch
   }
   // the sequential part: dLt_k += Gt_k^T dLt_{k+1}, dR_k += F_k^T dR_{k+1}   (index i holds X_{i+1})
   if (small) {
+    CRW_ROUTE("walk.bwd_persistent");
     CRW_TRY(launch_chain_small_bwd(st.Gt.f, st.F.f, sc.dLt.f, sc.dR.f, B, K, Np, s));
   } else {
+    CRW_ROUTE("walk.bwd_gemm");
     for (int i = K - 2; i >= 0; --i) {
       GemmGroup g{};
       g.n = Np; g.batch = B;

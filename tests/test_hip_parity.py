@@ -1043,9 +1043,18 @@ def test_labelprop_propagate_equals_the_one_workgroup_walk(hip, T, N, C, M, cxt,
     Wt, It = hip.labelprop_topk(feats, cxt, radius, 0.1, knn, first_frame=1, grid_w=grid_w)
     for n in range(1, T):  # the bound the new entry point relies on
         assert int(It[n - 1].max()) < min(n, cxt + 1) * N
-    L0, p0 = hip.labelprop_gather(seed, Wt, It, T, N, M, first_frame=1)
-    L1, p1 = hip.labelprop_gather(seed, Wt, It, T, N, M, first_frame=1, cxt_size=cxt)
+    with hip.routes() as walk:
+        L0, p0 = hip.labelprop_gather(seed, Wt, It, T, N, M, first_frame=1)
+    with hip.routes() as hit:
+        L1, p1 = hip.labelprop_gather(seed, Wt, It, T, N, M, first_frame=1, cxt_size=cxt)
     assert torch.equal(L0, L1) and torch.equal(p0, p1)
+    # which kernels were compared (the library's own account, include/crw_hip_routes.h): the one-workgroup walk on one side; on the
+    # other the role kernel where the case's comment says so -- knn <= 24 and N * M <= 384 -- else the walk again (the last two
+    # cases; T = 2 with a seed has no chained frame and goes to the walk too).  CRW_LABELPROP_GATHER_SEQ=1 sends every case there.
+    assert len(walk) == 1 and next(iter(walk)) in ("labelprop.gather_lds", "labelprop.gather_global"), dict(walk)
+    seq = os.environ.get("CRW_LABELPROP_GATHER_SEQ", "")[:1] == "1"
+    prefix = knn <= 24 and N * M <= 384 and T > 2 and not seq
+    assert set(hit) == ({"labelprop.propagate_prefix"} if prefix else set(walk)), (dict(hit), dict(walk))
     for first in sorted({2, max(2, cxt), min(T - 1, cxt + 1), min(T - 1, cxt + 3), T - 1}):
         if first >= T:
             continue

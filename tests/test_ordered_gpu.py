@@ -61,9 +61,13 @@ def test_both_backward_scans_write_the_same_maps(hip, monkeypatch):
         T, N, M, rows, cols = shape
         L = dr.reference(shape)[0].cuda() if shape != (3, 2, 2, 16, 48) else dr.dirichlet_rows(T, N, M, seed=2).cuda()
         monkeypatch.delenv("CRW_ORDERED_BACK", raising=False)
-        want, _ = hip.labelmap_ordered(L, T, N, M, rows, cols, range(M), dtype=torch.int8)
+        with hip.routes() as hit:
+            want, _ = hip.labelmap_ordered(L, T, N, M, rows, cols, range(M), dtype=torch.int8)
+        assert dict(hit) == {"ordered.back_default": 1}, dict(hit)
         monkeypatch.setenv("CRW_ORDERED_BACK", "1")
-        got, _ = hip.labelmap_ordered(L, T, N, M, rows, cols, range(M), dtype=torch.int8)
+        with hip.routes() as hit:
+            got, _ = hip.labelmap_ordered(L, T, N, M, rows, cols, range(M), dtype=torch.int8)
+        assert dict(hit) == {"ordered.back_one_word": 1}, dict(hit)      # the switch is live
         assert torch.equal(got, want), shape
 
 

@@ -31,8 +31,9 @@ def features(T, N, C, seed):
     return torch.randn(T, N, C, generator=g)
 
 
-def check(hip, monkeypatch, emb, M, cxt, radius, temp, knn, first_frame=1, fill=None, seed_labels=None):
+def check(hip, monkeypatch, emb, M, cxt, radius, temp, knn, first_frame=1, fill=None, seed_labels=None, route=None):
     """emb [T, N, C] (CPU, raw) -> (W, I, L, pred) of the default route, after holding both routes to the definition.
+    route: what the default run's route name must start with ("labelprop.slide_ring" / "labelprop.slide_general_").
     first_frame > 1: no seed, L and pred prefilled (frames before first_frame random soft labels); fill: byte the outputs hold before."""
     T, N, C = emb.shape
     ehat = hip.normalize(emb.cuda().contiguous())
@@ -60,9 +61,15 @@ def check(hip, monkeypatch, emb, M, cxt, radius, temp, knn, first_frame=1, fill=
             monkeypatch.setenv("CRW_LABELPROP_SLIDING_GENERAL", "1")
         else:
             monkeypatch.delenv("CRW_LABELPROP_SLIDING_GENERAL", raising=False)
-        L, pred = hip.labelprop_gather(seed, W, I, T, N, M, first_frame=first_frame, L=L0.clone(), pred=p0.clone(), cxt_size=cxt,
-                                       context="sliding")
+        with hip.routes() as hit:
+            L, pred = hip.labelprop_gather(seed, W, I, T, N, M, first_frame=first_frame, L=L0.clone(), pred=p0.clone(), cxt_size=cxt,
+                                           context="sliding")
         torch.cuda.synchronize()
+        # the library's own account of the route (include/crw_hip_routes.h): one sliding launch, the switch's arm on the general kernels
+        assert len(hit) == 1 and all(k.startswith("labelprop.slide_") for k in hit), dict(hit)
+        assert not general or next(iter(hit)).startswith("labelprop.slide_general_"), dict(hit)
+        if route is not None and not general:
+            assert next(iter(hit)).startswith(route), (route, dict(hit))
         v = sr.definition_violations(gather, seed, W, R, M, first_frame, L, pred, L_init, pred_init)
         print(("general" if general else "default"), v)
         assert not any(v.values()), (general, v)
@@ -90,7 +97,9 @@ CASES = {
 @pytest.mark.parametrize("name", list(CASES))
 def test_every_route_is_the_gather_on_translated_lists(hip, monkeypatch, name):
     T, N, M, C, cxt, radius, temp, knn = CASES[name]
-    W, I, L, pred = check(hip, monkeypatch, features(T, N, C, len(name)), M, cxt, radius, temp, knn)
+    # a case named "general: ..." claims the general kernels by its shape, every other the ring kernel
+    route = "labelprop.slide_general_" if name.startswith("general:") else "labelprop.slide_ring"
+    W, I, L, pred = check(hip, monkeypatch, features(T, N, C, len(name)), M, cxt, radius, temp, knn, route=route)
     if T > cxt + 2:  # the rule matters: the reference rule's labels differ somewhere
         Lr, _ = hip.labelprop_gather((torch.arange(N) * M // N).float().cuda(), W, I, T, N, M, cxt_size=cxt)
         assert not torch.equal(L, Lr)

@@ -58,9 +58,14 @@ def test_every_kernel_shape_writes_the_same_maps(hip, monkeypatch, chunk):
     """CRW_DENSE_BATCH_CHUNK (read per call): one configuration per blockIdx.z, an uneven last chunk, one chunk for all."""
     G, (T, N, M, rows, cols) = 7, SHAPES[1]
     L = distinct_soft_labels(G, T, N, M, seed=2).cuda()
-    want = hip.labelmap_dense_batch(L, G, T, N, M, rows, cols, confidence="entropy", flip=True)
+    monkeypatch.delenv("CRW_DENSE_BATCH_CHUNK", raising=False)
+    with hip.routes() as hit:
+        want = hip.labelmap_dense_batch(L, G, T, N, M, rows, cols, confidence="entropy", flip=True)
+    assert dict(hit) == {"dense.batch_chunked": 1}, dict(hit)       # the default: four configurations per workgroup
     monkeypatch.setenv("CRW_DENSE_BATCH_CHUNK", chunk)
-    got = hip.labelmap_dense_batch(L, G, T, N, M, rows, cols, confidence="entropy", flip=True)
+    with hip.routes() as hit:
+        got = hip.labelmap_dense_batch(L, G, T, N, M, rows, cols, confidence="entropy", flip=True)
+    assert dict(hit) == {("dense.batch_chunk1" if chunk == "1" else "dense.batch_chunked"): 1}, dict(hit)   # the switch is live
     assert torch.equal(got[0], want[0]) and torch.equal(got[1].view(torch.int32), want[1].view(torch.int32))
 
 

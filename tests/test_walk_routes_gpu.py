@@ -122,8 +122,13 @@ def test_walk_dA_per_slice(hip, route, chain, kind, B, T, N):
     float64 at the tolerances the suite had, dA through `audit` at the per-slice bar of the chain, dA[:, -1] all zeros.  Both
     runs must pass the same bar.  The T = 3 rows are K = 1: no recurrence, no dGt / dF product."""
     ref = _reference(hip, kind, B, T, N)
+    must, must_not = wr.ROUTE_NAMES[route]
     for name, stats in (("own statistics", None), ("imported statistics", ref["stats"])):
-        loss, At, dA = _walk(hip, ref["A"], chain, stats)
+        with hip.routes() as hit:
+            loss, At, dA = _walk(hip, ref["A"], chain, stats)
+        # the case runs the route its row is named for (the library's own account, not the shape's promise)
+        assert set(must) <= set(hit) and not set(must_not) & set(hit), (route, sorted(hit))
+        assert ("softmax.stats_import" in hit) == (stats is not None), sorted(hit)
         _check_forward(chain, loss, At, ref)
         _check_dA(f"{route} chain {chain} {kind} {(B, T, N)} {name}", chain, kind, dA, ref)
     if route == "bf16_256" and chain == 2:
@@ -141,7 +146,10 @@ def test_walk_dA_logits_not_16_byte_aligned(hip, B, T, N):
     A.copy_(ref["A"])
     assert A.is_contiguous() and A.data_ptr() % 16 == 4 and ref["A"].data_ptr() % 16 == 0
     for name, stats in (("own statistics", None), ("imported statistics", ref["stats"])):
-        loss, At, dA = _walk(hip, A, 0, stats)
+        with hip.routes() as hit:
+            loss, At, dA = _walk(hip, A, 0, stats)
+        assert {"softmax.fwd_scalar", "softmax.bwd_scalar"} <= set(hit) and not {"softmax.fwd_vec", "softmax.bwd_vec"} & set(hit), sorted(hit)
+        assert ("walk.fwd_persistent" in hit) == (N == 64) and ("walk.fwd_gemm" in hit) == (N == 128), sorted(hit)
         _check_forward(0, loss, At, ref)
         _check_dA(f"unaligned logits {(B, T, N)} {name}", 0, "randn3", dA, ref)
 

@@ -46,6 +46,15 @@ ROUTE_TABLE = (
     ("bf16_128", (1, 2), ((2, 3, 5), (2, 7, 33), (1, 3, 96), (1, 4, 127), (1, 4, 128), (2, 5, 129), (1, 9, 250)), ("randn3", "peaked")),
     ("bf16_256", (1, 2), ((8, 10, 500),), ("peaked",)),
 )
+# the library's names (include/crw_hip_routes.h) for the rows' routes: what a case of the row must take,
+# and what it must not
+ROUTE_NAMES = {
+    "persistent": (("walk.fwd_persistent", "walk.bwd_persistent"), ("walk.fwd_gemm", "walk.bwd_gemm", "gemm_bf16.t128", "gemm_bf16.t256_stagger")),
+    "gemm_f32": (("walk.fwd_gemm", "walk.bwd_gemm"), ("walk.fwd_persistent", "walk.bwd_persistent", "gemm_bf16.t128", "gemm_bf16.t256_stagger")),
+    "bf16_128": (("walk.fwd_gemm", "walk.bwd_gemm", "gemm_bf16.t128"), ("walk.fwd_persistent", "gemm_bf16.t256_stagger", "gemm_f32.t32", "gemm_f32.t64", "gemm_f32.t128")),
+    # (the chain steps of the one large case are 2 x 2 x 8 x 2 = 64 tiles of 256: they stay on 128-tiles; its batched products fill the chip)
+    "bf16_256": (("walk.fwd_gemm", "walk.bwd_gemm", "gemm_bf16.t256_stagger"), ("walk.fwd_persistent", "gemm_f32.t32", "gemm_f32.t64", "gemm_f32.t128")),
+}
 CHAIN_MODE = {0: "none", 1: "bf16", 2: "bf16x3"}
 GLOSS = 0.7
 # peaked cases whose default seed misses the admission condition of test_walk_routes.py (the fp32 oracle itself is then no

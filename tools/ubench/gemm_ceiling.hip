@@ -6,7 +6,8 @@
 // 256 x 256 on 8 waves, one per CU), plain bf16 and hi/lo pairs, in the two operand layouts the chain uses most.
 // It prints MFMA flops executed per second (what bench.py's roofline_chain_n4096* lines quote) and the time per k-tile and CU.
 //
-//   build:  hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -I radar-sounder-crw_amd/csrc tools/ubench/gemm_ceiling.hip -o tools/ubench/gemm_ceiling
+//   build:  hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -I radar-sounder-crw_amd/csrc tools/ubench/gemm_ceiling.hip \
+//                 radar-sounder-crw_amd/csrc/routes.hip -o tools/ubench/gemm_ceiling      (routes.hip: the table behind CRW_ROUTE in launch_layout)
 //   run  :  tools/ubench/gemm_ceiling [n=4096] [batch=4]          (on the GPU box; output committed as profiles/r04_gemm_ceiling.log)
 #include <cstdio>
 #include <cstdlib>
