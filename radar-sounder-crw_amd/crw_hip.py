@@ -163,6 +163,11 @@ RESTART_SIGNATURES = {
     "crw_labelprop_propagate_origin_batch": (_c_int, [_p, _p, _p, _c_sz] + [_c_int] * 7 + [_p, _p, _p, _p]),
 }
 
+# include/crw_hip_novelty.h, likewise: context novelty, where a labelled trace would help (optional: `has_novelty()`)
+NOVELTY_SIGNATURES = {
+    "crw_labelprop_novelty": (_c_int, [_p] + [_c_int] * 7 + [_p, _p, _p, _c_int, _p]),
+}
+
 # include/crw_hip_routes.h, likewise: the route log -- which selector branch launched (optional: `has_routes()`; host pointers)
 ROUTES_SIGNATURES = {
     "crw_routes_clear": (_c_int, []),
@@ -209,6 +214,9 @@ ANCHOR_RESTART_ENTRY_POINTS = tuple(RESTART_SIGNATURES)
 # likewise: the route log (`has_routes()`, `routes()`)
 ROUTES_ENTRY_POINTS = tuple(ROUTES_SIGNATURES)
 
+# likewise: context novelty (`has_novelty()`, `labelprop_novelty`)
+NOVELTY_ENTRY_POINTS = tuple(NOVELTY_SIGNATURES)
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 ANCHOR_CONTEXTS = ("clamp", "restart")  # what a fully labelled anchor trace does to the frames behind it
 
@@ -219,7 +227,7 @@ OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_E
                          "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS, "joint": JOINT_ENTRY_POINTS,
                          "posterior": POSTERIOR_ENTRY_POINTS, "posterior_batch": POSTERIOR_BATCH_ENTRY_POINTS,
                          "conv_chain": CONV_CHAIN_ENTRY_POINTS, "anchor_restart": ANCHOR_RESTART_ENTRY_POINTS,
-                         "routes": ROUTES_ENTRY_POINTS}
+                         "routes": ROUTES_ENTRY_POINTS, "novelty": NOVELTY_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -235,7 +243,8 @@ def lib():
                                "run `make -C radar-sounder-crw_amd/csrc` (hipcc --offload-arch=gfx950)")
         handle = ctypes.CDLL(LIB_PATH)
         missing = {n for names in OPTIONAL_ENTRY_POINTS.values() for n in names if not hasattr(handle, n)}
-        for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES, **RESTART_SIGNATURES, **ROUTES_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES, **RESTART_SIGNATURES, **ROUTES_SIGNATURES,
+                                   **NOVELTY_SIGNATURES}.items():
             if name in missing:
                 continue
             fn = getattr(handle, name)
@@ -281,6 +290,7 @@ has_posterior_batch, _posterior_batch_lib = _optional("posterior_batch", "the ba
 has_conv_chain, _conv_chain_lib = _optional("conv_chain", "the conv-trunk chain entry point")
 has_anchor_restart, _anchor_restart_lib = _optional("anchor_restart", "the entry points that take a per-frame origin")
 has_routes, _routes_lib = _optional("routes", "the route log's entry points")
+has_novelty, _novelty_lib = _optional("novelty", "the context-novelty entry point")
 
 MAX_ROUTES = 256  # csrc/crw_common.h
 
@@ -742,6 +752,77 @@ def labelprop_topk_scores(ehat, cxt_size, radius, temp, kcap, first_frame=1, gri
                                                   int(first_frame), int(grid_w), _dev(V, "V"), _dev(I, "I", torch.int32), _stream()),
            "crw_labelprop_topk_scores")
     return V, I
+
+
+NOVELTY_ROUTES = {"auto": 0, "vector": 1, "matrix": 2}  # `labelprop_novelty(route=)`; the C codes 0 / 1 / 2 pass as they are
+NOVELTY_MAX_NODES = 4096
+
+
+def novelty_top(N, top=None):
+    """how many of a frame's N node novelties its score averages: max(1, N // 4) unless given"""
+    top = max(1, N // 4) if top is None else int(top)
+    if not 1 <= top <= N:
+        raise ValueError(f"top must lie in 1 .. N = {N} (got {top})")
+    return top
+
+
+def labelprop_novelty(ehat, cxt_size, radius, top=None, first_frame=1, origin=None, route="auto"):
+    """How well each node's best key in its propagation context matches it (include/crw_hip_novelty.h) -> (nov [T - first_frame, N],
+    score [T - first_frame]) on the device, one launch.  nov[n, q] = 1 - max <ehat[n, q], key> over the in-band nodes (|p - q| <
+    radius, an N x 1 grid) of the frames `labelprop_topk` scores frame n against -- frame origin[n] and the cxt_size frames before
+    n that lie behind it (origin: `anchor_origins`, as in `labelprop_topk`; None: frame 0); score[n] = the mean of the `top`
+    (default max(1, N // 4)) largest nov[n, :].  A one-frame peak of the score marks a frame whose nodes have nothing like them
+    among their keys: `suggest_frames`.  route: 'auto', 'vector', 'matrix' (or the C codes 0, 1, 2)."""
+    T, N, C = ehat.shape
+    top = novelty_top(N, top)
+    code = NOVELTY_ROUTES.get(route, route)
+    if code not in (0, 1, 2):
+        raise ValueError(f"route must be one of {tuple(NOVELTY_ROUTES)} (got {route!r})")
+    org = None
+    if origin is not None:
+        check_origin(origin, T)
+        org = _origin_dev(origin, ehat.device)
+    nov = torch.empty(T - first_frame, N, device=ehat.device, dtype=torch.float32)
+    score = torch.empty(T - first_frame, device=ehat.device, dtype=torch.float32)
+    _check(_novelty_lib().crw_labelprop_novelty(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(radius), int(first_frame), top,
+                                                None if org is None else _dev(org, "origin", torch.int32), _dev(nov, "nov"),
+                                                _dev(score, "score"), code, _stream()), "crw_labelprop_novelty")
+    return nov, score
+
+
+def suggest_frames(score, cxt_size, budget, min_gap=2, first_frame=1, anchored=None):
+    """Where to label next, from `labelprop_novelty`'s frame scores: -> [(frame, z, s)] in pick order.  Host work only (CPU tensors,
+    numpy or lists; a device tensor is copied once), usable without a GPU.
+    score [F]: entry i is frame first_frame + i.  In float64: z[n] = s[n] - median of the other scored frames within cxt_size of n
+    (a young context, just after frame 0 or a restart, lifts s for several frames; an onset is a one-frame peak); then `budget`
+    rounds of "largest z, lowest frame on ties, drop the frames within min_gap of it".  anchored: frames that are fully labelled
+    already; they and their neighbours within min_gap are dropped first.  Fewer than `budget` picks when the frames run out.
+    The z of items in which nothing emerges overlap those of weak onsets: a pick is a place to look, not a detection."""
+    import numpy as np
+    s = np.asarray(score.detach().cpu() if torch.is_tensor(score) else score, dtype=np.float64).reshape(-1)
+    F, cxt, gap, first = len(s), int(cxt_size), int(min_gap), int(first_frame)
+    if cxt < 1 or gap < 0 or int(budget) < 0 or first < 0:
+        raise ValueError(f"cxt_size >= 1, min_gap >= 0, budget >= 0 and first_frame >= 0 (got {cxt_size}, {min_gap}, {budget}, {first_frame})")
+    z = np.empty(F)
+    for i in range(F):
+        lo, hi = max(0, i - cxt), min(F - 1, i + cxt)
+        nb = np.concatenate([s[lo:i], s[i + 1:hi + 1]])
+        z[i] = s[i] - (np.median(nb) if nb.size else 0.0)
+    left = np.ones(F, bool)
+
+    def drop(frame):
+        left[max(frame - gap - first, 0):max(frame + gap + 1 - first, 0)] = False
+
+    for f in (anchored if anchored is not None else ()):
+        drop(int(f))
+    out = []
+    for _ in range(int(budget)):
+        if not left.any():
+            break
+        i = int(np.argmax(np.where(left, z, -np.inf)))         # the first maximum: the lowest frame on ties
+        out.append((first + i, float(z[i]), float(s[i])))
+        drop(first + i)
+    return out
 
 
 def labelprop_sweep_weights(V, knns, out=None):

@@ -128,6 +128,17 @@ class LabelPropVOS_CRW(object):
                                            context=self.context, **kw)
         return pred, L
 
+    def novelty(self, feats, anchors=None, anchor_context='clamp', top=None, nclasses=None):
+        """feats [T,N,C] (normalised features, a column of patches) -> (nov [T-1, N], score [T-1]) of frames 1 .. T-1 on the device:
+        how little each node's best key in this propagation's context resembles it, and the mean of each frame's `top` (default
+        max(1, N // 4)) largest (`crw_hip.labelprop_novelty`; RADIUS and CXT_SIZE are this object's, TEMP and KNN play no part).
+        anchors / anchor_context as in `propagate_all`: under 'restart' the keys of a frame start at its origin
+        (`crw_hip.anchor_origins`; nclasses as there, None: 127, the most that int8 anchors can name), under 'clamp' the anchors change no key.
+        `crw_hip.suggest_frames` turns the scores into places to label."""
+        T, N, C = feats.shape
+        origin = restart_origin(anchor_context, anchors, self.context, T, N, 127 if nclasses is None else nclasses)
+        return crw_hip.labelprop_novelty(feats, self.cxt_size, self.radius, top=top, first_frame=1, origin=origin)
+
 
 class LabelPropSweep(object):
     """Label propagation for every (RADIUS, TEMP, KNN) of a grid at one CXT_SIZE -- scripts/launch/launch_test_batch.sh runs

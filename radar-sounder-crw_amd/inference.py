@@ -122,7 +122,7 @@ def _check_anchor_context(anchor_context, anchors):
 
 
 def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run, write,
-                    lead=(), dtype=torch.float32, joint=None, posterior=0, anchors=None, anchor_context='clamp', **extra):
+                    lead=(), dtype=torch.float32, joint=None, posterior=0, anchors=None, anchor_context='clamp', forward_kw=None, **extra):
     """The passes of `segment` and `segment_sweep`, behind their argument checks -> their result dict (plus ``extra``).
     run(seq, seg_ref, use_last): the variant's `propagate` call -> (pred, xent, change, ...).
     write(res, seq, out, out_conf, flip): puts what `run` returned into a column window of the label map (and of the confidence
@@ -138,7 +138,8 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
     post=(post window, horizon window): `write` without a reverse pass, `joint` with one (``pred`` is then the joint calls').
     anchors: None, or (annot, cols) of `segment`: `run` is then called with the keyword anchors=<the radargram's [T, N] node anchors>
     (`utils.anchor_nodes`) and anchor_context=``anchor_context`` in both passes, and the result gains ``anchor_cols`` and
-    ``anchor_context``."""
+    ``anchor_context``.
+    forward_kw: further keywords for `run` in the forward pass of every full item, and nowhere else (`segment`'s suggest=)."""
     T, (H, W), (oh, ow) = seq_length, patch_size, overlap
     N = dataset[0].shape[1]
     rg_len = T * (W - ow) + ow
@@ -172,7 +173,7 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
     fwd_src, tail_src = {}, {}  # radargram -> (L, frames, map width) of its forward pass / of its correction
     for t, i in enumerate(idx):
         seq = dataset[i].to(device)
-        res = run(seq, seg[:rg_h, rg_len * t:rg_len * t + W], False, **anch(t))
+        res = run(seq, seg[:rg_h, rg_len * t:rg_len * t + W], False, **anch(t), **(forward_kw or {}))
         write(res, seq, *window((forward, forward_conf), rg_len * t, rg_len * (t + 1)), False,
               **pwin(rg_len * t, rg_len * (t + 1), not keep))
         if keep:
@@ -238,7 +239,8 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
 @torch.no_grad()
 def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap, pos_embed=False,
             correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
-            decode='argmax', order=None, posterior=False, floor=crw_hip.POSTERIOR_FLOOR, anchors=None, anchor_context='clamp'):
+            decode='argmax', order=None, posterior=False, floor=crw_hip.POSTERIOR_FLOOR, anchors=None, anchor_context='clamp', suggest=0, suggest_gap=2,
+            suggest_top=None):
     """dataset: RGDataset (full, overlapping items); seg: reference segmentation [rows, W_rg].
     -> dict(pred [rows, n_rg * rg_len] float labels after the optional reverse merge,
             forward: the forward (+ corrected) map the reference saves as int8 (test_all.py:128),
@@ -284,8 +286,21 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     together with ``correction``: the correction is itself a re-seed, and how the two combine is not decided.
     anchor_context: 'clamp', or 'restart' (needs anchors) -- a fully labelled trace is as good as a seed: the frames behind it are
     propagated as frames of the item that starts there (`LabelPropVOS_CRW.propagate_all`).  Both passes restart, the reverse pass on
-    the mirrored anchors; everything downstream is untouched.  With anchors the dict gains ``anchor_context``."""
+    the mirrored anchors; everything downstream is untouched.  With anchors the dict gains ``anchor_context``.
+    suggest: 0, or how many traces per radargram to propose for labelling next (needs a label propagation with `novelty`).  The
+    forward pass of every full item -- no correction, not the reverse pass -- also computes the context novelty of its frames on
+    the features it propagates (`propagate(novelty=True)`; suggest_top: `novelty_top`), and the dict gains ``novelty``, float32
+    [items, T] on the CPU (frame scores, 0 at the seed frame), and ``suggested``: per radargram the picks of
+    `crw_hip.suggest_frames` (suggest_gap: its min_gap) as dicts radargram, item, frame, column, columns (first, last + 1), z,
+    score -- ``column`` is the frame's first pixel column, which `utils.anchor_nodes` maps back to that frame.  ``anchors`` are
+    honoured: under 'restart' the keys start at the origins, and fully labelled frames are not proposed again, so labelling a
+    pick and passing it as an anchor gives the next picks.  A pick is a place to look, not a detection: items in which nothing
+    new appears give z as large as a weak onset's.  Every other entry is bit for bit what it is without the option."""
     _check_anchor_context(anchor_context, anchors)
+    if int(suggest) < 0 or int(suggest_gap) < 0:
+        raise ValueError(f"suggest and suggest_gap must be >= 0 (got {suggest}, {suggest_gap})")
+    if suggest and not hasattr(lp, 'novelty'):
+        raise ValueError("suggest needs a label propagation with `novelty` (LabelPropVOS_CRW)")
     order = _check_options(confidence, merge, upsample, decode, order, nclasses, posterior, use_last, floor)
     if anchors is not None and correction:
         raise ValueError("anchors and correction=True do not combine: the correction is itself a re-seed (at the change point), and "
@@ -310,16 +325,50 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     else:
         kw = dict(confidence=confidence) if want else {}  # `propagate` returns a fourth entry only when asked
         write = _write_nearest
-    run = lambda seq, seg_ref, last, **anch: propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=last, **kw, **anch)
+    novs = []  # (nov [N, T], score [T]) of every full item's forward pass, with suggest
+
+    def run(seq, seg_ref, last, novelty=False, **anch):
+        nkw = dict(novelty=True, novelty_top=suggest_top) if novelty else {}
+        res = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=last, **kw, **anch, **nkw)
+        if novelty:  # taken out again: the writers read the tuple by position
+            at = 4 if 'confidence' in kw else 3
+            novs.append(res[at])
+            res = res[:at] + res[at + 1:]
+        return res
 
     def joint(a, b, N, out, out_conf, post=None):  # merge='ordered': a column window of pred / conf from two passes' soft labels
         crw_hip.labelmap_ordered_joint(a, b, N, nclasses, *out.shape, order, confidence=confidence, out=out, out_conf=out_conf)
         if post is not None:
             crw_hip.labelmap_ordered_joint_posterior(a, b, N, nclasses, *out.shape, order, out, confidence=confidence, floor=floor,
                                                      out=post[0], out_hz=post[1])
-    return _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
-                           write, joint=joint, posterior=len(order) if posterior else 0, anchors=anchors, anchor_context=anchor_context,
-                           **extra)
+    out = _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, use_last, dataset_id, device, want, merge, run,
+                          write, joint=joint, posterior=len(order) if posterior else 0, anchors=anchors, anchor_context=anchor_context,
+                          forward_kw=dict(novelty=True) if suggest else None, **extra)
+    if suggest:
+        out.update(_suggested(novs, lp.cxt_size, int(suggest), int(suggest_gap), dataset[0].shape[1], nclasses, seq_length, patch_size,
+                              overlap, anchors))
+    return out
+
+
+def _suggested(novs, cxt_size, budget, gap, N, nclasses, seq_length, patch_size, overlap, anchors):
+    """`segment`'s ``novelty`` and ``suggested`` from the forward passes' (nov, score) pairs: ONE copy to the host, then host work."""
+    T, (H, W), (oh, ow) = seq_length, patch_size, overlap
+    step, rg_len, rg_h = W - ow, T * (W - ow) + ow, N * (H - oh) + oh
+    s = torch.stack([sc for _, sc in novs]).cpu()
+    per_rg = None
+    if anchors is not None:
+        annot, cols = anchors
+        per_rg = anchor_nodes(torch.as_tensor(annot)[:, :len(novs) * rg_len], cols, rg_len, T, N, rg_h, step)
+    suggested = []
+    for t in range(len(novs)):
+        full = [] if per_rg is None else [f for f in range(1, T) if bool(((per_rg[t][f] >= 0) & (per_rg[t][f] < nclasses)).all())]
+        picks = []
+        for f, z, sc in crw_hip.suggest_frames(s[t, 1:], cxt_size, budget, gap, 1, full):
+            first = t * rg_len + f * step
+            picks.append(dict(radargram=t, item=t * T, frame=f, column=first, columns=(first, first + step if f < T - 1 else (t + 1) * rg_len),
+                              z=z, score=sc))
+        suggested.append(picks)
+    return dict(novelty=s, suggested=suggested)
 
 
 @torch.no_grad()

@@ -39,7 +39,10 @@ reference map's shape, < 0 = unlabelled; every column with an entry >= 0 is anno
 the first pixel of every K-th frame of each radargram as the anchors; one line says how many traces are anchored, ``--report_json``
 gains ``anchors``; the report counts anchored traces as it counts the seed traces; ``--anchor_context restart`` (with either): a
 fully labelled anchor trace restarts the propagation context like a seed (``inference.segment(..., anchor_context='restart')``), one
-more line says how many of the anchored traces are such origins, ``--report_json`` gains ``anchor_context``.  Without these flags the output is what it was.
+more line says how many of the anchored traces are such origins, ``--report_json`` gains ``anchor_context``; ``--suggest_anchors K``
+(``--suggest_gap G``, ``--suggest_top R``): a fixed-width table after the report -- item, frame, columns, z, score -- of the K traces
+per radargram whose labelling the context novelty of the forward pass suggests next (``inference.segment(..., suggest=K)``; places to
+look, not detections), ``--report_json`` gains ``suggested_anchors``.  Without these flags the output is what it was.
 Differences from the scripts:
   * plots are not drawn;
   * true / false flags read true / false (the scripts take any given string as true); ``--patch_size`` takes two numbers;
@@ -132,12 +135,48 @@ def get_args_parser():
                    help="evaluation: the reference map's column at the first pixel of every K-th frame as anchors (needs --context sliding)")
     p.add_argument('--anchor_context', default=None, choices=('clamp', 'restart'),
                    help='restart: a fully labelled anchor trace restarts the propagation context, like a seed (needs anchors; clamp)')
+    p.add_argument('--suggest_anchors', default=None, type=int, metavar='K',
+                   help='also print, per radargram, the K traces whose labelling the context novelty suggests next')
+    p.add_argument('--suggest_gap', default=None, type=int, metavar='G', help='no two suggestions within G frames of each other (2)')
+    p.add_argument('--suggest_top', default=None, type=int, metavar='R',
+                   help="a frame's score averages its R most novel nodes (a quarter of the nodes)")
     return p
 
 
 HORIZON_FLAGS = ('horizons', 'min_run', 'tol', 'row_spacing', 'row_unit', 'save_horizons')
 POSTERIOR_FLAGS = ('posterior', 'floor', 'save_posterior')
 ANCHOR_FLAGS = ('anchors', 'anchor_every', 'anchor_context')
+SUGGEST_FLAGS = ('suggest_anchors', 'suggest_gap', 'suggest_top')
+
+
+def check_suggest_flags(args):
+    """The flags around ``--suggest_anchors``."""
+    k = getattr(args, 'suggest_anchors', None)
+    if k is None:
+        if getattr(args, 'suggest_gap', None) is not None or getattr(args, 'suggest_top', None) is not None:
+            raise SystemExit('--suggest_gap and --suggest_top need --suggest_anchors K')
+        return args
+    if args.single:
+        raise SystemExit('--suggest_anchors is not available with --single')
+    if k < 1:
+        raise SystemExit(f'--suggest_anchors {k}: at least 1')
+    if args.suggest_gap is None:
+        args.suggest_gap = 2
+    if args.suggest_gap < 0:
+        raise SystemExit(f'--suggest_gap {args.suggest_gap}: at least 0')
+    if args.suggest_top is not None and args.suggest_top < 1:
+        raise SystemExit(f'--suggest_top {args.suggest_top}: at least 1')
+    return args
+
+
+def suggested_table(suggested):
+    """The picks of ``inference.segment(suggest=K)`` as a fixed-width table: item, frame, columns, z, score."""
+    lines = ['Suggested anchor traces (context novelty: places to look, not detections):',
+             f"{'item':>6} {'frame':>6} {'columns':>15} {'z':>9} {'score':>9}"]
+    for picks in suggested:
+        for p in picks:
+            lines.append(f"{p['item']:>6d} {p['frame']:>6d} {'%d-%d' % (p['columns'][0], p['columns'][1] - 1):>15} {p['z']:>9.4f} {p['score']:>9.4f}")
+    return '\n'.join(lines)
 
 
 def check_anchor_flags(args):
@@ -278,6 +317,8 @@ def load_data(args):
 def main(args):
     from imported.labelprop import LabelPropVOS_CRW
     tim = time.time()
+    args = check_suggest_flags(args)
+    suggest = getattr(args, 'suggest_anchors', None)
     args = check_anchor_flags(check_posterior_flags(check_horizon_flags(check_confidence_flags(with_defaults(args)))))
     # without --confidence the four flags that go with it do nothing, and the line reads as it did before they existed
     hidden = () if args.confidence else ('confidence', 'merge', 'bins', 'save_conf')
@@ -297,6 +338,8 @@ def main(args):
     anchor_context = getattr(args, 'anchor_context', None)
     if anchor_context is None:  # likewise
         hidden += ('anchor_context',)
+    if suggest is None:  # likewise
+        hidden += SUGGEST_FLAGS
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -330,7 +373,8 @@ def main(args):
                                 **(dict(decode=args.decode, order=args.order) if args.decode != 'argmax' else {}),
                                 **(dict(posterior=True, floor=args.floor) if args.posterior else {}),
                                 **(dict(anchors=anchors) if anchored else {}),
-                                **(dict(anchor_context=anchor_context) if anchor_context else {}))
+                                **(dict(anchor_context=anchor_context) if anchor_context else {}),
+                                **(dict(suggest=suggest, suggest_gap=args.suggest_gap, suggest_top=args.suggest_top) if suggest else {}))
         if out.get('anchor_context') == 'restart':
             print('Origin traces:', out['origin_traces'], 'of the anchored traces (anchor_context restart)')
         if correction:
@@ -383,6 +427,9 @@ def main(args):
         print(f'Calibration (posterior of the ordered decode, floor {args.floor:g}):')
         print(pcal)
         print(bars)
+    if suggest:
+        print('')
+        print(suggested_table(out['suggested']))
     t_all = time.time() - tim
     print('\nTime elapsed (inference + metrics):', t_all)
     if args.report_json:
@@ -409,6 +456,9 @@ def main(args):
                     d['anchors']['origin_traces'] = out['origin_traces']
         if pcal is not None:
             d['posterior'] = dict(floor=args.floor, calibration=pcal.to_dict(), horizon_bars=bars.to_dict())
+        if suggest:
+            d['suggested_anchors'] = dict(per_radargram=suggest, min_gap=args.suggest_gap, top=args.suggest_top,
+                                          picks=[dict(p, columns=list(p['columns'])) for picks in out['suggested'] for p in picks])
         with open(args.report_json, 'w') as f:
             json.dump(d, f, indent=1)
     return report

@@ -143,7 +143,7 @@ def _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last):
 
 @torch.no_grad()
 def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False, anchors=None,
-              anchor_context='clamp'):
+              anchor_context='clamp', novelty=False, novelty_top=None):
     """seq [T,N,h,w]; seg_ref [rows, w] class ids of the first (or last) frame; model: encoder;
     lp: LabelPropVOS_CRW  ->  (labels [N,T] float, xent [N,T-1] (CPU), change_idx | None).
 
@@ -158,7 +158,12 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, conf
     wrote (the reference arg-maxes them away, src/utils.py:160); 1 in the seed column.  The labels do not depend on it.
     soft: the tuple gains, as its LAST entry, the soft labels themselves: L [T*N, M] float32 on the labels' device, node (n, t) in
     row t*N + n, frames in the pass's own order (reversed under ``use_last``, like the labels); frame 0 -- and a one-frame item --
-    is the one-hot of the seed.  What `crw_hip.labelmap_dense` turns into a pixel map."""
+    is the one-hot of the seed.  What `crw_hip.labelmap_dense` turns into a pixel map.
+    novelty: the tuple gains one entry, behind conf when that is present and before L: (nov [N,T], score [T]) float32 on the labels'
+    device, frames in the pass's own order -- `lp.novelty` on the SAME features (the encoder does not run again), under the pass's
+    anchors and anchor_context; column / entry 0 (the seed frame has no keys) is 0.  novelty_top: how many of a frame's largest
+    node novelties its score averages (None: max(1, N // 4)).  What `crw_hip.suggest_frames` reads.  The labels do not depend on
+    it."""
     if confidence is not None and confidence not in crw_hip.CONF_KINDS:
         raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
     T, N, H, W = seq.shape
@@ -170,11 +175,18 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, conf
                              "of a foreign object has no place for them")
         if T > 1 and tuple(anchors.shape) != (T, N):
             raise ValueError(f"anchors must be [{T}, {N}] (got {tuple(anchors.shape)})")
+    if novelty:
+        if not hasattr(lp, 'propagate_all') or not hasattr(lp, 'novelty'):
+            raise ValueError("novelty needs a label propagation with `propagate_all` and `novelty` (LabelPropVOS_CRW): a foreign "
+                             "object's frame-by-frame protocol does not say which keys a frame scores against")
+        crw_hip.novelty_top(N, novelty_top)
     feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
     if T == 1:  # a one-frame item (the correction step of test_all.py can ask for it): nothing to propagate, like the reference
         out = (seed[:, None].clone(), torch.zeros(N, 0), None)
         if confidence is not None:
             out += (torch.ones(N, 1, device=feats.device),)
+        if novelty:
+            out += ((torch.zeros(N, 1, device=feats.device), torch.zeros(1, device=feats.device)),)
         if soft:
             out += ((seed[:, None] == torch.arange(nclasses, device=feats.device)[None, :]).float(),)
         return out
@@ -201,11 +213,20 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, conf
             L = torch.cat(ml, 0)[..., 0].permute(0, 2, 1).reshape(T * N, nclasses).float().contiguous()
     # queued right behind the propagation, before the host turns to the change point
     conf = crw_hip.labelprop_confidence(L, T, N, nclasses, confidence) if confidence is not None else None
+    nov = None
+    if novelty:  # likewise queued behind the propagation, on the features it ran on
+        nkw = {}
+        if anchors is not None:
+            nkw = dict(anchors=(torch.flip(a, (0,)) if use_last else a).contiguous(), anchor_context=anchor_context, nclasses=nclasses)
+        nv, sc = lp.novelty(feats, top=novelty_top, **nkw)
+        nov = (torch.cat([nv.new_zeros(N, 1), nv.t()], 1), torch.cat([sc.new_zeros(1), sc]))
     # the change point is host work (PELT on T-2 samples): it runs while the GPU propagates the labels queued above
     change_idx = change_point(xent, diffs)
     out = (pred, xent.cpu(), change_idx)
     if confidence is not None:
         out += (conf,)
+    if novelty:
+        out += (nov,)
     if soft:
         out += (L,)
     return out
