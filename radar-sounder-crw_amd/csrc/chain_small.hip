@@ -126,7 +126,7 @@ __global__ __launch_bounds__(NTH) void chain_small_kernel(const float *__restric
     // LDS-only barrier: __syncthreads() would also wait (vmcnt(0)) for this step's result stores and for the
     // prefetch of the next P, i.e. one HBM round trip per step of a 29-step sequential chain.  Nothing written to
     // global memory in this kernel is read back by another lane.
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
     cur ^= 1;
   }
 }

@@ -76,6 +76,10 @@ __device__ inline float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+// Workgroup barrier that makes LDS traffic visible but does NOT drain outstanding global loads
+// (__syncthreads() waits for vmcnt(0), which would expose the latency of a prefetch in flight).
+// Only for phases whose cross-wave communication goes through LDS.
+__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---- one product of a grouped, batched, zero-padded square GEMM ---------------------------
 // C[b] (+)= op(A[b]) * op(B[b]) [+ op(A2[b]) * op(B2[b])], all [n][n] row-major with ld = n.

@@ -28,7 +28,7 @@
 // output channels x a group of (up to) 64 input channels, walks a slice of the patches accumulating in
 // registers (k-steps of 32 pixels streamed across patch boundaries), and writes its partial sums to a
 // workspace; a second kernel adds the slices in a fixed order (bitwise reproducible, no float atomics).
-#include "crw_common.h"
+#include "bf16_mma.h"
 #include "crw_hip_chain.h"
 #include <type_traits>
 #include <cstdlib>
@@ -37,14 +37,6 @@ namespace crw {
 namespace {
 
 constexpr int IMG_W = 10, PAD_W = 12, NPIX = 100, NPAD = 144, MT = 7;  // 7 row tiles of 16 = 112 >= 100
-
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef short s4v __attribute__((ext_vector_type(4)));
-typedef short s8v __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char *lds_cp;
-
-__device__ inline uint16_t f2bf(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-__device__ inline float bf2f(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
 
 // LDS planes: pixel rows are padded by one 16-byte chunk (stride 2C + 16 bytes), so that the 16
 // pixels of an MFMA row tile -- or the 8 pixel rows of a transposed read -- start in different
@@ -109,7 +101,7 @@ __device__ inline void gap_split8(const float *__restrict__ dg8, uint32_t (&gh)[
     const float a0 = gv[2 * w] * (1.0f / NPIX), a1 = gv[2 * w + 1] * (1.0f / NPIX);
     const uint16_t h0 = f2bf(a0), h1 = f2bf(a1);
     gh[w] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-    gl[w] = (uint32_t)f2bf(a0 - bf2f(h0)) | ((uint32_t)f2bf(a1 - bf2f(h1)) << 16);
+    gl[w] = (uint32_t)bf_lo(a0, h0) | ((uint32_t)bf_lo(a1, h1) << 16);
   }
 }
 __device__ inline void gap_mask8(const uint4 &y, const uint32_t (&gh)[4], const uint32_t (&gl)[4], uint4 &oh, uint4 &ol) {
@@ -511,7 +503,7 @@ __device__ __forceinline__ void conv_compute(const ConvIO &a, const ConvTile &t,
             if (a.yh) {
               const uint16_t h = f2bf(v);
               *reinterpret_cast<uint16_t *>(img + pp * RSO + 2 * co) = h;
-              if (SPLIT == 3 && a.yl) *reinterpret_cast<uint16_t *>(img + PLANE + pp * RSO + 2 * co) = f2bf(v - bf2f(h));
+              if (SPLIT == 3 && a.yl) *reinterpret_cast<uint16_t *>(img + PLANE + pp * RSO + 2 * co) = bf_lo(v, h);
             }
           }
         }
@@ -733,23 +725,8 @@ struct WgradArgs {
   int mh, mw, tiles_x, tiles_y;
 };
 
-template <int IMM>
-__device__ inline s4v tr_read(uint32_t lds_addr) {
-  s4v v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(lds_addr), "n"(IMM) : "memory");
-  return v;
-}
-
-// transposed fragment: 8 reduction rows (pixels) x the 16 channels starting at channel C0.  a_lo / a_hi
-// are this lane's LDS byte addresses of its two groups of 4 fragment rows (already including the lane's
-// 8*(pq&1) + 16*(pq>>1) column part); C0 and the plane offset enter as an instruction immediate.
-template <int IMM>
-__device__ inline bf8 tr_frag(uint32_t a_lo, uint32_t a_hi) {
-  const s4v lo = tr_read<IMM>(a_lo);
-  const s4v hi = tr_read<IMM>(a_hi);
-  const s8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf8, v);
-}
+// Transposed fragments here (tr_frag, bf16_mma.h): 8 reduction rows (pixels) x the 16 channels starting at channel C0.  a_lo /
+// a_hi already include the lane's 8*(pq&1) + 16*(pq>>1) column part; C0 and the plane offset enter as the instruction immediate.
 
 // slice (1-D grid; id -> (slice, channel group) mapping below).
 // One workgroup (4 waves) = all 9 taps x WG_NCO output channels x NCI input channels of one patch
@@ -904,10 +881,10 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void conv3x3_wgrad_kernel(WgradArg
         // LDS returns in order: all but the reads just issued (2 ds_read per fragment) have landed
         if (SPLIT == 3) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
       } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lds_reads_landed();
       }
-      __builtin_amdgcn_sched_barrier(0);
       if constexpr (tap == 0) {
         if (bias_wave) {
           const s8v o = {0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80};  // bf16 1.0
@@ -1189,7 +1166,6 @@ __global__ __launch_bounds__(W2_NW * 64, 2) void conv3x3_wgrad2_kernel(WgradArgs
   constexpr int XCH = NCI / 8, XTOT = NPIX * XCH;
   // Global loads go through buffer descriptors rooted at the slice (scalar base + 32-bit per-thread offset: no 64-bit
   // address registers are kept alive across the k-loop, and a row past the end of the stream reads as zero)
-  typedef uint32_t u4v __attribute__((ext_vector_type(4)));
   const long dy_off = (long)p_begin * NPIX * COUT, x_off = (long)p_begin * NPIX * CIN + ci_base;
   const __amdgpu_buffer_rsrc_t dyh_rs = __builtin_amdgcn_make_buffer_rsrc((void *)(a.dyh + dy_off), 0, npx * COUT * 2, 0x00020000);
   const __amdgpu_buffer_rsrc_t dyl_rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -1298,10 +1274,10 @@ __global__ __launch_bounds__(W2_NW * 64, 2) void conv3x3_wgrad2_kernel(WgradArgs
         read_b(std::integral_constant<int, tap + 1>{});
         if (SPLIT == 3) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
       } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lds_reads_landed();
       }
-      __builtin_amdgcn_sched_barrier(0);
       if constexpr (tap == 0) {
         if (bias_wg) {  // one co tile per wave (wave-uniform choice, static fragment index)
           const s8v o = {0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80};  // bf16 1.0
@@ -1460,7 +1436,7 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const float *__restri
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
     const int tap = e % 9, ci = (e / 9) % CI, co = e / (9L * CI);
     const float v = w[e];
-    const uint16_t h = f2bf(v), l = f2bf(v - bf2f(h));
+    const uint16_t h = f2bf(v), l = bf_lo(v, h);
     const long of = frag_index(tap, co, ci, CO, CI), ob = frag_index(8 - tap, ci, co, CI, CO);
     fh[of] = h; bh[ob] = h;
     if (fl) { fl[of] = l; bl[ob] = l; }
@@ -1477,7 +1453,7 @@ __global__ __launch_bounds__(256) void pack_input_kernel(const float *__restrict
     const float v = x[(p * C + c) * npix + i];
     const uint16_t h = f2bf(v);
     xh[e] = h;
-    if (xl) xl[e] = f2bf(v - bf2f(h));
+    if (xl) xl[e] = bf_lo(v, h);
   }
 }
 
@@ -1502,7 +1478,7 @@ __global__ __launch_bounds__(256) void gap_bwd_kernel(const float *__restrict__ 
       const float a0 = (yw[w] & 0x7fffu) ? gv[2 * w] * inv : 0.f, a1 = (yw[w] & 0x7fff0000u) ? gv[2 * w + 1] * inv : 0.f;
       const uint16_t h0 = f2bf(a0), h1 = f2bf(a1);
       h[w] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-      l[w] = (uint32_t)f2bf(a0 - bf2f(h0)) | ((uint32_t)f2bf(a1 - bf2f(h1)) << 16);
+      l[w] = (uint32_t)bf_lo(a0, h0) | ((uint32_t)bf_lo(a1, h1) << 16);
     }
     *reinterpret_cast<uint4 *>(dh + e * 8) = uint4{h[0], h[1], h[2], h[3]};
     if (dl) *reinterpret_cast<uint4 *>(dl + e * 8) = uint4{l[0], l[1], l[2], l[3]};

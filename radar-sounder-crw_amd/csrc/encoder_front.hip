@@ -15,25 +15,12 @@
 //     -> conv2 backward-data (MFMA) -> pool1/ReLU1 backward -> conv1 weight/bias gradient (VALU),
 // one function per phase, shared by the three kernels, accumulating the weight gradients in registers over its slice of
 // patches; slices are added in a fixed order by front_slice_sum_kernel (deterministic).
-#include "crw_common.h"
+#include "bf16_mma.h"
 #include <type_traits>
 #include <cstdlib>
 
 namespace crw {
 namespace {
-
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef short s4v __attribute__((ext_vector_type(4)));
-typedef short s8v __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char *lds_cp;
-
-__device__ inline uint16_t f2bf(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-__device__ inline float bf2f(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
-
-// Workgroup barrier that makes LDS traffic visible but does NOT drain outstanding global loads
-// (__syncthreads() waits for vmcnt(0), which would expose the latency of the next patch's prefetch).
-// Only for phases whose cross-wave communication goes through LDS.
-__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // geometry
 constexpr int XPW = 18;                    // 16x16 input patch, padded by 1
@@ -148,7 +135,7 @@ __device__ inline void pool1(const FwdLds &L, int tid, char *sv = nullptr) {  //
     const int c = e & 7, p = e >> 3, y = p / A1W, x = p % A1W;
     const float *s = L.c1r + map_idx<C1W, PAD>(y, x) * 8 + c;
     const float v = fmaxf(fmaxf(s[0], s[8]), fmaxf(s[ROW], s[ROW + 8]));
-    const uint16_t h = f2bf(v), l = f2bf(v - bf2f(h));
+    const uint16_t h = f2bf(v), l = bf_lo(v, h);
     const int o = ((y + 1) * A1PW + x + 1) * 16 + 2 * c;
     *reinterpret_cast<uint16_t *>(L.a1h + o) = h;
     if (SPLIT == 3) *reinterpret_cast<uint16_t *>(L.a1l + o) = l;
@@ -181,7 +168,7 @@ __device__ inline void pool1_window(const FwdLds &L, int tid, int oy0, int ox0, 
     }
     const uint16_t h = f2bf(v);
     *reinterpret_cast<uint16_t *>(L.a1h + q * 16 + 2 * c) = h;
-    if (SPLIT == 3) *reinterpret_cast<uint16_t *>(L.a1l + q * 16 + 2 * c) = f2bf(v - bf2f(h));
+    if (SPLIT == 3) *reinterpret_cast<uint16_t *>(L.a1l + q * 16 + 2 * c) = bf_lo(v, h);
   }
 }
 
@@ -299,7 +286,7 @@ __global__ __launch_bounds__(NT) void front_fwd_kernel(FrontArgs a) {
       const float v = fmaxf(fmaxf(s[0], s[32]), fmaxf(s[C2W * 32], s[C2W * 32 + 32]));
       const uint16_t h = f2bf(v);
       a.yh[(long)pt * ON * 32 + e] = h;
-      if (SPLIT == 3) a.yl[(long)pt * ON * 32 + e] = f2bf(v - bf2f(h));
+      if (SPLIT == 3) a.yl[(long)pt * ON * 32 + e] = bf_lo(v, h);
       if (sv) sv[SV_OFF_K2 + e] = (char)(argmax4(s[0], s[32], s[C2W * 32], s[C2W * 32 + 32]) | (v > 0.f ? 4 : 0));
     }
     // the next iteration's first barrier orders these c2r reads before conv2_relu overwrites it
@@ -348,7 +335,7 @@ __global__ __launch_bounds__(NT) void front_fwd_map_kernel(FrontMapArgs a) {
         const uint16_t h = f2bf(v);
         const long o = (((long)pt * Ho + oy0 + y) * Wo + ox0 + x) * 32 + c;
         a.f.yh[o] = h;
-        if (SPLIT == 3) a.f.yl[o] = f2bf(v - bf2f(h));
+        if (SPLIT == 3) a.f.yl[o] = bf_lo(v, h);
       }
     }
     // the next iteration's first barrier orders these c2r reads before conv2_relu overwrites it
@@ -365,14 +352,14 @@ __global__ __launch_bounds__(256) void pack_w2_kernel(const float *__restrict__ 
     const float v = tap < 25 ? w[(co * 8 + ci) * 25 + tap] : 0.f;
     const uint16_t h = f2bf(v);
     fh[e] = h;
-    if (fl) fl[e] = f2bf(v - bf2f(h));
+    if (fl) fl[e] = bf_lo(v, h);
   }
   for (int e = blockIdx.x * 256 + threadIdx.x; e < 25 * 8 * 32; e += gridDim.x * 256) {
     const int co = e & 31, ci = (e >> 5) & 7, tap = e >> 8;
     const float v = w[(co * 8 + ci) * 25 + tap];
     const uint16_t h = f2bf(v);
     bh[e] = h;
-    if (bl) bl[e] = f2bf(v - bf2f(h));
+    if (bl) bl[e] = bf_lo(v, h);
   }
 }
 
@@ -399,17 +386,6 @@ struct FrontBwdArgs {
 #else
 #define FRONT_STAMP(k)
 #endif
-
-__device__ inline s4v tr_read0(uint32_t lds_addr) {
-  s4v v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory");
-  return v;
-}
-__device__ inline bf8 tr_pair(uint32_t a_lo, uint32_t a_hi) {
-  const s4v lo = tr_read0(a_lo), hi = tr_read0(a_hi);
-  const s8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf8, v);
-}
 
 // index (0..3) of the first maximum of a 2x2 window in row-major order (torch's max_pool2d tie rule)
 __device__ inline int argmax4(float a, float b, float c, float d) {
@@ -564,7 +540,7 @@ __device__ __forceinline__ void pool2_bwd(const BwdLds &B, int tid, float &db2, 
     const uint16_t h = f2bf(gsum);
     const int o = (co >> 4) * D2HALF + ((y + 4) * D2PW + x + 4) * 32 + 2 * (co & 15);
     *reinterpret_cast<uint16_t *>(B.d2h + o) = h;
-    if (SPLIT == 3) *reinterpret_cast<uint16_t *>(B.d2l + o) = f2bf(gsum - bf2f(h));
+    if (SPLIT == 3) *reinterpret_cast<uint16_t *>(B.d2l + o) = bf_lo(gsum, h);
   }
 }
 
@@ -595,15 +571,14 @@ __device__ __forceinline__ void conv2_wgrad(f32x4 (&wacc)[2], uint32_t d2h_a, ui
         // B: a1 padded plane [pix][8 ci] (16 B rows): fragment columns 0-7 = tap 2nt, 8-15 = tap 2nt+1
         const uint32_t xa_lo = ((y_lo * A1PW + x_lo) + toff) * 16 + 8 * (pq & 1);
         const uint32_t xa_hi = ((y_hi * A1PW + x_hi) + toff) * 16 + 8 * (pq & 1);
-        const bf8 ah = tr_pair(d2h_a + ya_lo + D2HALF * i, d2h_a + ya_hi + D2HALF * i);
-        const bf8 bh = tr_pair(a1h_a + xa_lo, a1h_a + xa_hi);
+        const bf8 ah = tr_frag(d2h_a + ya_lo + D2HALF * i, d2h_a + ya_hi + D2HALF * i);
+        const bf8 bh = tr_frag(a1h_a + xa_lo, a1h_a + xa_hi);
         bf8 al, bl;
         if (SPLIT == 3) {
-          al = tr_pair(d2l_a + ya_lo + D2HALF * i, d2l_a + ya_hi + D2HALF * i);
-          bl = tr_pair(a1l_a + xa_lo, a1l_a + xa_hi);
+          al = tr_frag(d2l_a + ya_lo + D2HALF * i, d2l_a + ya_hi + D2HALF * i);
+          bl = tr_frag(a1l_a + xa_lo, a1l_a + xa_hi);
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        lds_reads_landed();
         if (SPLIT == 3) {
           wacc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, wacc[u], 0, 0, 0);
           wacc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, wacc[u], 0, 0, 0);
@@ -751,8 +726,6 @@ __device__ __forceinline__ void write_partials(const BwdSums &S, float *part, fl
   }
 }
 
-inline __device__ uint32_t lds_addr(const char *p) { return (uint32_t)(uintptr_t)(lds_cp)p; }
-
 // ---- backward with recomputation (tests, CRW_FRONT_RECOMPUTE=1, the phase stamps) ---------------------------------------
 template <int SPLIT>
 __global__ __launch_bounds__(NTH) void front_bwd_kernel(FrontBwdArgs a) {
@@ -773,7 +746,7 @@ __global__ __launch_bounds__(NTH) void front_bwd_kernel(FrontBwdArgs a) {
 
   BwdSums S;
   const int nrp = C1W / cin;  // conv1 weight gradient: row parts of cin pixel rows each
-  const uint32_t d2h_a = lds_addr(B.d2h), d2l_a = lds_addr(B.d2l), a1h_a = lds_addr(L.a1h), a1l_a = lds_addr(L.a1l);
+  const uint32_t d2h_a = lds_addr_of(B.d2h), d2l_a = lds_addr_of(B.d2l), a1h_a = lds_addr_of(L.a1h), a1l_a = lds_addr_of(L.a1l);
 
   const int p_begin = blockIdx.x * a.patches_per_block;
   const int p_end = min(a.f.P, p_begin + a.patches_per_block);
@@ -877,7 +850,7 @@ __global__ __launch_bounds__(NTH) void front_bwd_tile_kernel(FrontBwdArgs a) {
 
   BwdSums S;
   const int nrp = TCW / cin;
-  const uint32_t d2h_a = lds_addr(B.d2h), d2l_a = lds_addr(B.d2l), a1h_a = lds_addr(L.a1h), a1l_a = lds_addr(L.a1l);
+  const uint32_t d2h_a = lds_addr_of(B.d2h), d2l_a = lds_addr_of(B.d2l), a1h_a = lds_addr_of(L.a1h), a1l_a = lds_addr_of(L.a1l);
   const int H = a.H, W = a.W, Ho = H - 6, Wo = W - 6, ntile = a.tiles_x * a.tiles_y;
   const int u_begin = blockIdx.x * a.patches_per_block;
   const int u_end = min(a.f.P * ntile, u_begin + a.patches_per_block);
@@ -969,7 +942,7 @@ __global__ __launch_bounds__(NTH) void front_bwd_saved_kernel(FrontBwdArgs a) {
 
   BwdSums S;
   const int nrp = C1W / cin;
-  const uint32_t d2h_a = lds_addr(B.d2h), d2l_a = lds_addr(B.d2l), a1h_a = lds_addr(L.a1h), a1l_a = lds_addr(L.a1l);
+  const uint32_t d2h_a = lds_addr_of(B.d2h), d2l_a = lds_addr_of(B.d2l), a1h_a = lds_addr_of(L.a1h), a1l_a = lds_addr_of(L.a1l);
   const int p_begin = blockIdx.x * a.patches_per_block;
   const int p_end = min(a.f.P, p_begin + a.patches_per_block);
 
@@ -977,7 +950,6 @@ __global__ __launch_bounds__(NTH) void front_bwd_saved_kernel(FrontBwdArgs a) {
   // chunks 0..337 = a1 hi / lo planes, 338..537 = k2 codes, 538..622 = k1 codes
   constexpr int NA1 = 2 * SV_A1 / 16, NK2 = SV_K2 / 16, NK1 = SV_K1 / 16, NSV = NA1 + NK2 + NK1;
   static_assert(NSV <= NTH && ON * 32 / 4 <= NTH, "one chunk per thread");
-  typedef uint32_t u4v __attribute__((ext_vector_type(4)));
   float4 dy_r;
   float x_r = 0.f;
   u4v sv_r;

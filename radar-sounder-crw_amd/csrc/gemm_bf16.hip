@@ -9,7 +9,7 @@
 // BK = 64, zero-padded square operands [n][n] (n multiple of 128) -> no edge handling.
 // HBM -> LDS goes through LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave-instruction): the LDS
 // image is lane-linear, so the bank swizzle is applied to the per-lane SOURCE address and again on
-// the read.  Two images, both 16 KiB:
+// the read.  Two images (swizzles and fragment reader: bf16_mma.h), both 16 KiB:
 //   KC ("k-contiguous", operand stored [r][k]) : 128 rows x 128 B, chunk' = chunk ^ (row & 7),
 //        fragments by ds_read_b128;
 //   RC ("r-contiguous", operand stored [k][r]) :  64 rows x 256 B, chunk' = chunk ^ (((row&3)<<2)|((row>>2)&3)),
@@ -17,7 +17,7 @@
 //        chain (Lt^T R, Gt^T dLt, ...) never need a transposed copy in HBM.
 // Double-buffered: the DMA of k-tile t+1 is in flight while the MFMAs of tile t run; one barrier
 // per k-tile.  Tiles are 128x128 (4 waves) or 256x256 (8 waves, plain bf16 when the grid still fills the chip).
-#include "crw_common.h"
+#include "bf16_mma.h"
 
 namespace crw {
 namespace {
@@ -27,39 +27,6 @@ namespace {
 // 4-stage BK = 32 ring measured slower than the 2-stage BK = 64 ring (858 vs 940 TFLOP/s: twice the barriers).
 template <int SPLIT, int TB>
 constexpr int tile_bk() { return (TB == 256 && SPLIT == 3) ? 32 : 64; }
-
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef short s4v __attribute__((ext_vector_type(4)));
-typedef short s8v __attribute__((ext_vector_type(8)));
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) char *lds_cp;
-
-// byte offsets inside an image.  KC rows are 2*BK bytes; the chunk swizzle makes the ds_read_b128 lane groups
-// ({0-3,12-15,20-27}, ...) of a fragment read conflict-free: BK = 64: chunk ^ (row & 7); BK = 32 (4 chunks per
-// row, rows r, r+4, r+8, r+12 share their banks): chunk ^ (row & 8 ? 3 : 0)
-template <int BK>
-__device__ inline int kc_sw(int row) { return BK == 64 ? (row & 7) : ((row & 8) ? 3 : 0); }
-template <int BK>
-__device__ inline int kc_off(int row, int chunk) { return row * (2 * BK) + 16 * (chunk ^ kc_sw<BK>(row)); }
-__device__ inline int rc_sw(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-template <int TB>
-__device__ inline int rc_off(int row, int chunk) { return row * (TB * 2) + 16 * (chunk ^ rc_sw(row)); }
-
-__device__ inline void glds16(const uint16_t *g, char *lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                   (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-
-// The transposed LDS read goes through inline asm: given the builtin, hipcc (ROCm 7.2) drains every
-// in-flight LDS-DMA (s_waitcnt vmcnt(0)) in front of it, which serialises the ring.  The caller
-// issues s_waitcnt lgkmcnt(0) + sched_barrier before the MFMAs that consume the result.
-template <int OFF>
-__device__ inline s4v tr_read(uint32_t lds_addr) {  // OFF: image offset inside the stage, an instruction immediate, so
-  s4v v;                                            // the hi and lo planes of an operand share one address register
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(lds_addr), "n"(OFF) : "memory");
-  return v;
-}
-__device__ inline uint32_t lds_addr_of(const char *p) { return (uint32_t)(uintptr_t)(lds_cp)p; }
 
 // stage one image of an operand tile with TB rows (or TB columns): TB/8 pieces of 1 KiB
 //   KC: [TB rows][BK k]   2*BK-byte rows, 512/BK rows per piece
@@ -81,7 +48,7 @@ __device__ inline void stage_image(const uint16_t *__restrict__ X, int ld, int r
     } else {
       constexpr int LPR = TB / 8;  // lanes (16-byte chunks) per row: 16 or 32
       const int row = (64 / LPR) * piece + lane / LPR;
-      const int chunk = (lane % LPR) ^ rc_sw(row);
+      const int chunk = (lane % LPR) ^ rc_sw<TB>(row);
       src = X + (long)(k0 + row) * ld + r0 + 8 * chunk;
     }
     glds16(src, img + piece * 1024);
@@ -107,7 +74,7 @@ __device__ inline void load_image_regs(const uint16_t *__restrict__ X, int ld, i
     } else {
       constexpr int LPR = TB / 8;
       const int row = (64 / LPR) * piece + lane / LPR;
-      const int chunk = (lane % LPR) ^ rc_sw(row);
+      const int chunk = (lane % LPR) ^ rc_sw<TB>(row);
       src = X + (long)(k0 + row) * ld + r0 + 8 * chunk;
     }
     // inline asm: hipcc would wait vmcnt(0) (the younger LDS-DMA included) before the first use of a tracked load; the caller
@@ -122,25 +89,6 @@ __device__ inline void store_image_regs(char *img, int wave, int lane, const u4v
 #pragma unroll
   for (int i = 0; i < PER; ++i)  // inline asm: a plain LDS store makes hipcc drain the in-flight LDS-DMA first
     asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(a), "v"(r[i]), "n"(WAVES * 1024 * i) : "memory");
-}
-
-// fragment of the 16 rows/cols [rb, rb+16) x k-step s (32 deep) of an image
-template <bool KC, int TB, int BK, int OFF>
-__device__ inline bf8 read_frag(const char *stage, int rb, int s, int lane) {  // image at stage + OFF
-  static_assert(OFF >= 0 && OFF < 65536, "image offset must fit the DS offset field");
-  if (KC) {
-    const int row = rb + (lane & 15);
-    return *reinterpret_cast<const bf8 *>(stage + OFF + kc_off<BK>(row, 4 * s + (lane >> 4)));
-  } else {
-    const int g = lane >> 4, t = lane & 15, q = t >> 2, p = t & 3;
-    const int row = 32 * s + 8 * g + q;
-    const int chunk = (rb >> 3) + (p >> 1);
-    const uint32_t base = lds_addr_of(stage);
-    const s4v lo = tr_read<OFF>(base + rc_off<TB>(row, chunk) + 8 * (p & 1));
-    const s4v hi = tr_read<OFF>(base + rc_off<TB>(row + 4, chunk) + 8 * (p & 1));
-    const s8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf8, v);
-  }
 }
 
 struct BfOperand {
@@ -280,10 +228,7 @@ __device__ inline void mainloop(f32x4 (&acc)[Cfg<TB>::FM][Cfg<TB>::FN], BfOperan
             al[i] = dg_al[i];
           }
         }
-        if ((!AKC || !BKC) && diag_reads(DIAG)) {  // inline-asm reads are invisible to the compiler's lgkmcnt bookkeeping
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        if ((!AKC || !BKC) && diag_reads(DIAG)) lds_reads_landed();
         if constexpr (diag_mfma(DIAG)) {
 #pragma unroll
           for (int i = 0; i < AG; ++i)
@@ -365,10 +310,7 @@ __device__ inline void mainloop_ring5(f32x4 (&acc)[Cfg<TB>::FM][Cfg<TB>::FN], Bf
         bf8 a[AG];
 #pragma unroll
         for (int i = 0; i < AG; ++i) a[i] = read_frag<AKC, TB, BKB, 0>(base, wm + 16 * (i0 + i), 0, lane);
-        if (!AKC || !BKC) {  // inline-asm reads are invisible to the compiler's lgkmcnt bookkeeping
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        if (!AKC || !BKC) lds_reads_landed();
         if constexpr (DIAG <= 4) {
 #pragma unroll
           for (int i = 0; i < AG; ++i)
@@ -385,9 +327,6 @@ __device__ inline void mainloop_ring5(f32x4 (&acc)[Cfg<TB>::FM][Cfg<TB>::FN], Bf
   }
   __syncthreads();  // the second product (or the next use of LDS) may restage the ring
 }
-
-__device__ inline uint16_t f2bf(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-__device__ inline float bf2f(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
 
 // One kernel per operand layout (AKC, BKC): a run-time switch over the four main loops costs ~70
 // VGPRs and spills the 256x256 configuration.  The launcher groups products by layout.
@@ -458,7 +397,7 @@ __global__ __launch_bounds__(Cfg<TB>::WAVES * 64) void gemm_pad_bf16_kernel(Gemm
         if (Ch) {
           const uint16_t h = f2bf(v);
           Ch[o] = h;
-          if (Cl) Cl[o] = f2bf(v - bf2f(h));
+          if (Cl) Cl[o] = bf_lo(v, h);
         }
       }
     }
@@ -621,7 +560,7 @@ __global__ __launch_bounds__(256) void split_bf16_kernel(const float *__restrict
     const float v = x[i];
     const uint16_t h = f2bf(v);
     hi[i] = h;
-    if (lo) lo[i] = f2bf(v - bf2f(h));
+    if (lo) lo[i] = bf_lo(v, h);
   }
 }
 

@@ -13,7 +13,7 @@
 //
 // Fragment maps (gfx950, 16x16x4 f32): A lane l -> A[row l&15][k l>>4], B lane l -> B[k l>>4][col l&15],
 // C/D reg r of lane l -> C[row (l>>4)*4 + r][col l&15].
-#include "crw_common.h"
+#include "bf16_mma.h"
 #include <cstdlib>
 
 namespace crw {
@@ -327,18 +327,15 @@ __device__ inline void mfma_block(const float *As, const float *Bs, int wm, int 
 // 2^-24 |a b|, i.e. the result is fp32-grade like the 16x16x4 fp32 MFMA, at 6/16 of its matrix-pipe time (the fp32 MFMA
 // runs at 1/16 of the bf16 rate).  Used by the affinity build and its backward at large node counts, where those two
 // fp32-MFMA kernels were 10 % of the plain-bf16 chain step at N = 4096.
-typedef __bf16 bf8v __attribute__((ext_vector_type(8)));
-__device__ inline uint16_t bf_of(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-__device__ inline float f_of(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
 __device__ inline void split3(float x, uint16_t &h, uint16_t &m, uint16_t &l) {
 #pragma clang fp contract(off)
-  h = bf_of(x);
-  const float r1 = x - f_of(h);
-  m = bf_of(r1);
-  l = bf_of(r1 - f_of(m));
+  h = f2bf(x);
+  const float r1 = x - bf2f(h);
+  m = f2bf(r1);
+  l = bf_lo(r1, m);
 }
 // bf16 operand plane in LDS: [R rows][32 k], 64-byte rows, 16-byte chunks swizzled so that the ds_read_b128 lane groups of
-// a fragment are conflict-free (same scheme as the 32-deep k-tiles of gemm_bf16.hip)
+// a fragment are conflict-free (the scheme of kc_off<32>, bf16_mma.h)
 constexpr int X6K = 32;
 __device__ inline int x6_off(int row, int chunk) { return row * 64 + 16 * (chunk ^ ((row & 8) ? 3 : 0)); }
 // four consecutive k (k0 = 4 kq) of one row -> the three planes (plane stride PL bytes)
@@ -357,20 +354,20 @@ __device__ inline void x6_put4(char *planes, int row, int kq, float4 v) {
 template <int TM, int TN, int PLA, int PLB>
 __device__ inline void x6_block(const char *Ap, const char *Bp, int wm, int wn, int lane, f32x4 (&acc)[TM][TN]) {
   const int r16 = lane & 15, g = lane >> 4;
-  bf8v ah[TM], am[TM], al[TM], bh[TN], bm[TN], bl[TN];
+  bf8 ah[TM], am[TM], al[TM], bh[TN], bm[TN], bl[TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     const char *p = Ap + x6_off(wm + 16 * i + r16, g);
-    ah[i] = *reinterpret_cast<const bf8v *>(p);
-    am[i] = *reinterpret_cast<const bf8v *>(p + PLA);
-    al[i] = *reinterpret_cast<const bf8v *>(p + 2 * PLA);
+    ah[i] = *reinterpret_cast<const bf8 *>(p);
+    am[i] = *reinterpret_cast<const bf8 *>(p + PLA);
+    al[i] = *reinterpret_cast<const bf8 *>(p + 2 * PLA);
   }
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const char *p = Bp + x6_off(wn + 16 * j + r16, g);
-    bh[j] = *reinterpret_cast<const bf8v *>(p);
-    bm[j] = *reinterpret_cast<const bf8v *>(p + PLB);
-    bl[j] = *reinterpret_cast<const bf8v *>(p + 2 * PLB);
+    bh[j] = *reinterpret_cast<const bf8 *>(p);
+    bm[j] = *reinterpret_cast<const bf8 *>(p + PLB);
+    bl[j] = *reinterpret_cast<const bf8 *>(p + 2 * PLB);
   }
 #pragma unroll
   for (int i = 0; i < TM; ++i)

@@ -136,7 +136,6 @@ __global__ __launch_bounds__(256) void labelprop_topk_kernel(const float *__rest
 // scores go to LDS as val[query][candidate] in the reference's candidate order; selection: a wave per PAIR of queries with their candidates in
 // registers (TK_NV per lane and query) -- no workgroup barrier inside the knn rounds --, same rule: highest value, then lowest candidate index.
 constexpr int TK_Q = 16, TK_NV = 32, TK_NT = 512, TK_NW = TK_NT / 64;  // eight waves: two per SIMD cover each other's round trips
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // NCH = 2: the context frames in two halves, one after the other through HALF the score buffer (two workgroups per CU: one's
 // scoring -- matrix cores, loads, LDS scatter -- runs beside the other's selection -- vector compares), the first half's k best
 // carried into the second selection as extra candidates: top-k(A u B) = top-k(top-k(A) u B), and the carried candidates have the
@@ -213,7 +212,7 @@ __global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_k
       } else {
         fetch(item, b);
       }
-      f32x4_t acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};  // even / odd steps: two independent chains
+      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};  // even / odd steps: two independent chains
 #pragma unroll
       for (int j = 0; j < CSTEPS; ++j) {
         acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j].x, b[j].x, acc0, 0, 0, 0);
@@ -594,7 +593,6 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
 //   tail kernel (labelprop_tail_batch_kernel): a workgroup per frame n > cxt, all at once, labels gathered from L in global memory (complete since the prefix).
 // Same operations in the same order per output as the kernels above: bit-identical L and pred.
 constexpr int PX_PF = 16, PX_NT = 512;  // list entries per loader lane and frame (a frame's lists: knn * N <= 64 * PX_PF); threads at most
-__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int KP>
 __global__ __launch_bounds__(PX_NT) void labelprop_prefix_kernel(const float *__restrict__ seed, const float *__restrict__ W,

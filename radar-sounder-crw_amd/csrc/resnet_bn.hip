@@ -7,16 +7,13 @@
 // that feed a matrix-core kernel are bf16 planes (hi, lo) of the same shape; rows of the patches P <= p < Ppad are ZERO in
 // every plane (the GEMM epilogues then need no row predicate and the padded rows add nothing to any statistic).
 // A BatchNorm's coefficients travel as coef[4][C] = (scale = gamma * invstd, shift = beta - mean * scale, mean, invstd).
-#include "crw_common.h"
+#include "bf16_mma.h"
 #include <algorithm>
 #include <atomic>
 #include "resnet.h"
 
 namespace crw {
 namespace {
-
-__device__ inline uint16_t f2bf(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-__device__ inline float bf2f(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
 
 struct Oct {  // eight consecutive channels
   float v[8];
@@ -45,7 +42,7 @@ __device__ inline void store8_planes(uint16_t *hi, uint16_t *lo, const Oct &o) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const uint16_t h0 = f2bf(o.v[2 * i]), h1 = f2bf(o.v[2 * i + 1]);
-    const uint16_t l0 = f2bf(o.v[2 * i] - bf2f(h0)), l1 = f2bf(o.v[2 * i + 1] - bf2f(h1));
+    const uint16_t l0 = bf_lo(o.v[2 * i], h0), l1 = bf_lo(o.v[2 * i + 1], h1);
     hw[i] = (uint32_t)h0 | ((uint32_t)h1 << 16);
     lw[i] = (uint32_t)l0 | ((uint32_t)l1 << 16);
   }
@@ -663,7 +660,7 @@ __global__ __launch_bounds__(256) void rn_stem_apply_kernel(const float *__restr
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       hh[c] = f2bf(v[c]);
-      ll[c] = f2bf(v[c] - bf2f(hh[c]));
+      ll[c] = bf_lo(v[c], hh[c]);
     }
     hh[3] = ll[3] = 0;
     *reinterpret_cast<uint2 *>(m_hi + i * 4) = uint2{(uint32_t)hh[0] | ((uint32_t)hh[1] << 16), (uint32_t)hh[2] | ((uint32_t)hh[3] << 16)};
@@ -756,7 +753,7 @@ __global__ __launch_bounds__(256) void rn_pack_conv_kernel(const float *__restri
     // i indexes the forward plane [co][t][ci] (coalesced stores); the source read is strided
     const int ci = (int)(i % cin), t = (int)((i / cin) % T), co = (int)(i / ((long)cin * T));
     const float v = w[((long)co * cin + ci) * T + t];
-    const uint16_t h = f2bf(v), l = f2bf(v - bf2f(h));
+    const uint16_t h = f2bf(v), l = bf_lo(v, h);
     fh[i] = h;
     fl[i] = l;
     const long j = ((long)ci * T + t) * cout + co;
@@ -795,7 +792,7 @@ __global__ __launch_bounds__(256) void rn_pack_all_kernel(RnPackJobs jobs) {
       const float v0 = pv[r * row + (c8 * 8 + k) * T + t], v1 = pv[r * row + (c8 * 8 + k + 1) * T + t];
       const uint16_t h0 = f2bf(v0), h1 = f2bf(v1);
       h[k / 2] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-      l[k / 2] = (uint32_t)f2bf(v0 - bf2f(h0)) | ((uint32_t)f2bf(v1 - bf2f(h1)) << 16);
+      l[k / 2] = (uint32_t)bf_lo(v0, h0) | ((uint32_t)bf_lo(v1, h1) << 16);
     }
     const long f = ((long)(co0 + r) * T + t) * q.cin + ci0 + c8 * 8;
     *reinterpret_cast<uint4 *>(q.fh + f) = uint4{h[0], h[1], h[2], h[3]};
@@ -809,7 +806,7 @@ __global__ __launch_bounds__(256) void rn_pack_all_kernel(RnPackJobs jobs) {
       const float v0 = pv[k * row + task], v1 = pv[(k + 1) * row + task];
       const uint16_t h0 = f2bf(v0), h1 = f2bf(v1);
       h[k / 2] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-      l[k / 2] = (uint32_t)f2bf(v0 - bf2f(h0)) | ((uint32_t)f2bf(v1 - bf2f(h1)) << 16);
+      l[k / 2] = (uint32_t)bf_lo(v0, h0) | ((uint32_t)bf_lo(v1, h1) << 16);
     }
     const long b = ((long)ci0 * T + task) * q.cout + co0;
     *reinterpret_cast<uint4 *>(q.bh + b) = uint4{h[0], h[1], h[2], h[3]};
@@ -833,7 +830,7 @@ __global__ __launch_bounds__(256) void rn_pack_stem_kernel(const float *__restri
       if (ky < 7 && kx < 7 && c < 3) v = w1[((co * 3 + c) * 7 + ky) * 7 + kx];
       const uint16_t h = f2bf(v);
       fh[i] = h;
-      fl[i] = f2bf(v - bf2f(h));
+      fl[i] = bf_lo(v, h);
     } else {
       const long j = i - nf;
       const int k = (int)(j % ldt), n = (int)((j / ldt) % ncols), iy = (int)(j / ((long)ldt * ncols));
@@ -845,7 +842,7 @@ __global__ __launch_bounds__(256) void rn_pack_stem_kernel(const float *__restri
       if (n < 3 * W0 && oy < H1 && ky >= 0 && ky < 7 && kx >= 0 && kx < 7) v = w1[((co * 3 + c) * 7 + ky) * 7 + kx];
       const uint16_t h = f2bf(v);
       th[j] = h;
-      tl[j] = f2bf(v - bf2f(h));
+      tl[j] = bf_lo(v, h);
     }
   }
 }

@@ -19,63 +19,18 @@
 //       split over patch slices, partial slabs added in a fixed order by rn_wgrad_reduce_kernel (no float atomics).
 //
 // HBM -> LDS by LDS-DMA (global_load_lds_dwordx4) into a ring of lane-linear images with the bank swizzle on the source
-// address, counted vmcnt + raw s_barrier -- the staging scheme of gemm_bf16.hip, here with gathered / strided operands.
+// address, counted vmcnt + raw s_barrier -- the staging scheme of gemm_bf16.hip (images and fragment reader: bf16_mma.h), here
+// with gathered / strided operands.
 #include <algorithm>
 
-#include "crw_common.h"
+#include "bf16_mma.h"
 #include "resnet.h"
 
 namespace crw {
 namespace {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef short s4v __attribute__((ext_vector_type(4)));
-typedef short s8v __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char *lds_cp;
-
-__device__ inline void glds16(const uint16_t *g, char *lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                   (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-__device__ inline uint32_t lds_addr_of(const char *p) { return (uint32_t)(uintptr_t)(lds_cp)p; }
-// inline asm: with the builtin hipcc drains every in-flight LDS-DMA in front of the read (gemm_bf16.hip)
-__device__ inline s4v tr_read(uint32_t lds_addr) {
-  s4v v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory");
-  return v;
-}
-
-// ---- k-contiguous images: [rows][BK], 2*BK-byte rows, fragments by ds_read_b128 ---------------------------------------
-template <int BK>
-__device__ inline int kc_sw(int row) { return BK == 64 ? (row & 7) : ((row & 8) ? 3 : 0); }
-template <int BK>
-__device__ inline int kc_off(int row, int chunk) { return row * (2 * BK) + 16 * (chunk ^ kc_sw<BK>(row)); }
-template <int BK>
-__device__ inline bf8 kc_frag(const char *img, int rb, int s, int lane) {
-  return *reinterpret_cast<const bf8 *>(img + kc_off<BK>(rb + (lane & 15), 4 * s + (lane >> 4)));
-}
-
-// ---- r-contiguous images: [BK k-rows][TB], 2*TB-byte rows, fragments by two ds_read_b64_tr_b16 ------------------------
-// the chunk swizzle keeps the 32-byte windows that the eight k-rows of a half-wave read on distinct banks
-template <int TB>
-__device__ inline int rc_sw(int row) {
-  return TB == 64 ? ((((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1) : (((row & 3) << 2) | ((row >> 2) & 3));
-}
-template <int TB>
-__device__ inline int rc_off(int row, int chunk) { return row * (TB * 2) + 16 * (chunk ^ rc_sw<TB>(row)); }
-template <int TB>
-__device__ inline bf8 rc_frag(const char *img, int rb, int s, int lane) {
-  const int g = lane >> 4, t = lane & 15, q = t >> 2, p = t & 3;
-  const int row = 32 * s + 8 * g + q;
-  const int chunk = (rb >> 3) + (p >> 1);
-  const uint32_t base = lds_addr_of(img);
-  const s4v lo = tr_read(base + rc_off<TB>(row, chunk) + 8 * (p & 1));
-  const s4v hi = tr_read(base + rc_off<TB>(row + 4, chunk) + 8 * (p & 1));
-  const s8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf8, v);
-}
-
-__device__ inline f32x4 mfma(bf8 a, bf8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+// Fragments come from read_frag (bf16_mma.h): read_frag<true, 0, BK> on the k-contiguous images ([rows][BK]) of the NN product,
+// read_frag<false, TB, 0> on the r-contiguous images ([BK k-rows][TB]) of the TN product.
 
 // bijective block -> work remap: blocks b, b+8, b+16, ... run on one XCD (speed only); every XCD gets a contiguous range of
 // the linear work index, so the blocks that share a patch tile (all groups / column tiles of it) meet in one 4 MiB L2
@@ -333,13 +288,13 @@ __global__ __launch_bounds__(TM * 2) void rn_conv_kernel(RnConvArgs a) {  // TM 
       bf8 b[C::FN], bl[C::FN], af[C::FM], al[C::FM];
 #pragma unroll
       for (int j = 0; j < C::FN; ++j) {
-        b[j] = kc_frag<BK>(base + 2 * C::IMG_A, wn + 16 * j, s, lane);
-        bl[j] = kc_frag<BK>(base + 2 * C::IMG_A + C::IMG_B, wn + 16 * j, s, lane);
+        b[j] = read_frag<true, 0, BK>(base + 2 * C::IMG_A, wn + 16 * j, s, lane);
+        bl[j] = read_frag<true, 0, BK>(base + 2 * C::IMG_A + C::IMG_B, wn + 16 * j, s, lane);
       }
 #pragma unroll
       for (int i = 0; i < C::FM; ++i) {
-        af[i] = kc_frag<BK>(base, wm + 16 * i, s, lane);
-        al[i] = kc_frag<BK>(base + C::IMG_A, wm + 16 * i, s, lane);
+        af[i] = read_frag<true, 0, BK>(base, wm + 16 * i, s, lane);
+        al[i] = read_frag<true, 0, BK>(base + C::IMG_A, wm + 16 * i, s, lane);
       }
 #pragma unroll
       for (int i = 0; i < C::FM; ++i)
@@ -507,13 +462,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       bf8 b[C::FN], bl[C::FN], af[C::FM], al[C::FM];
 #pragma unroll
       for (int j = 0; j < C::FN; ++j) {
-        b[j] = kc_frag<BK>(base + 2 * C::IMG_A, wn + 16 * j, s, lane);
-        bl[j] = kc_frag<BK>(base + 2 * C::IMG_A + C::IMG_B, wn + 16 * j, s, lane);
+        b[j] = read_frag<true, 0, BK>(base + 2 * C::IMG_A, wn + 16 * j, s, lane);
+        bl[j] = read_frag<true, 0, BK>(base + 2 * C::IMG_A + C::IMG_B, wn + 16 * j, s, lane);
       }
 #pragma unroll
       for (int i = 0; i < C::FM; ++i) {
-        af[i] = kc_frag<BK>(base, wm + 16 * i, s, lane);
-        al[i] = kc_frag<BK>(base + C::IMG_A, wm + 16 * i, s, lane);
+        af[i] = read_frag<true, 0, BK>(base, wm + 16 * i, s, lane);
+        al[i] = read_frag<true, 0, BK>(base + C::IMG_A, wm + 16 * i, s, lane);
       }
 #pragma unroll
       for (int i = 0; i < C::FM; ++i)
@@ -726,16 +681,15 @@ __global__ __launch_bounds__(256) void rn_wgrad_kernel(RnWgradArgs a) {
       bf8 b[C::FN], bl[C::FN], af[C::FM], al[C::FM];
 #pragma unroll
       for (int j = 0; j < C::FN; ++j) {
-        b[j] = rc_frag<TN>(base + 2 * C::IMG_A, wn + 16 * j, s, lane);
-        bl[j] = rc_frag<TN>(base + 2 * C::IMG_A + C::IMG_B, wn + 16 * j, s, lane);
+        b[j] = read_frag<false, TN, 0>(base + 2 * C::IMG_A, wn + 16 * j, s, lane);
+        bl[j] = read_frag<false, TN, 0>(base + 2 * C::IMG_A + C::IMG_B, wn + 16 * j, s, lane);
       }
 #pragma unroll
       for (int i = 0; i < C::FM; ++i) {
-        af[i] = rc_frag<TM>(base, wm + 16 * i, s, lane);
-        al[i] = rc_frag<TM>(base + C::IMG_A, wm + 16 * i, s, lane);
+        af[i] = read_frag<false, TM, 0>(base, wm + 16 * i, s, lane);
+        al[i] = read_frag<false, TM, 0>(base + C::IMG_A, wm + 16 * i, s, lane);
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // inline-asm reads are invisible to the compiler's bookkeeping
-      __builtin_amdgcn_sched_barrier(0);
+      lds_reads_landed();
 #pragma unroll
       for (int i = 0; i < C::FM; ++i)
 #pragma unroll

@@ -16,33 +16,14 @@
 // 504 MFMAs per patch and pass (6 x 4 x 7 x 3 | 14 x 4 x 3 x 3 | 6 x 14 x 2 x 3), hi / lo operand pairs as everywhere.
 #include <cstdlib>
 
-#include "crw_common.h"
+#include "bf16_mma.h"
 #include "resnet.h"
 
 namespace crw {
 namespace {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef short s4v __attribute__((ext_vector_type(4)));
-typedef short s8v __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char *lds_cp;
-
 constexpr int MAPW = 24, MAP_PLANE = MAPW * MAPW * 8;  // bytes of one plane of the map image
 constexpr int WFRAG_BYTES = 7 * 4 * 2 * 1024;          // weights in fragment order: 7 k-steps x 4 tiles x 2 planes x 1 KB
-
-__device__ inline uint16_t f2bf(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-__device__ inline float bf2f(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
-__device__ inline f32x4 mfma(bf8 a, bf8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-__device__ inline uint32_t lds_addr_of(const char *p) { return (uint32_t)(uintptr_t)(lds_cp)p; }
-__device__ inline s4v tr_read(uint32_t lds_addr) {
-  s4v v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr) : "memory");
-  return v;
-}
-__device__ inline bf8 join(s4v lo, s4v hi) {
-  const s8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf8, v);
-}
 
 struct StemCoef {  // relu0(bn0(fc0(x))) = relu(a[c][0] x0 + a[c][1] x1 + d[c])
   float a[3][2], d[3];
@@ -64,7 +45,7 @@ __device__ inline void stem_pixel(const StemCoef &k, float x0, float x1, uint2 &
   for (int c = 0; c < 3; ++c) {
     const float v = fmaxf(k.a[c][0] * x0 + k.a[c][1] * x1 + k.d[c], 0.f);
     h[c] = f2bf(v);
-    l[c] = f2bf(v - bf2f(h[c]));
+    l[c] = bf_lo(v, h[c]);
   }
   hi = uint2{(uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2]};
   lo = uint2{(uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2]};
@@ -336,8 +317,7 @@ __global__ __launch_bounds__(512) void rn_stem_fwd_band_kernel(const float *__re
 
 // ================================================================================================ weight gradient
 // 8 waves = 4 pairs; a pair shares one patch (map image + dZ1 image) and splits the 14 row tiles of dW^T [224][64].
-constexpr int DZ_PLANE = 96 * 128;  // dZ1 image: 96 rows (81 used, the rest zero) x 64 channels of bf16
-__device__ inline int dz_sw(int row) { return (((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1; }  // = rc_sw<64> of resnet_gemm.hip
+constexpr int DZ_PLANE = 96 * 128;  // dZ1 image: 96 rows (81 used, the rest zero) x 64 channels of bf16; chunk swizzle rc_sw<64> (bf16_mma.h)
 
 template <int CIN>
 __global__ __launch_bounds__(512) void rn_stem_wgrad_kernel(const float *__restrict__ x, const float *__restrict__ stem,
@@ -375,7 +355,7 @@ __global__ __launch_bounds__(512) void rn_stem_wgrad_kernel(const float *__restr
       const long src = (long)p * 81 * 64;
       for (int c = l2; c < 81 * 8; c += 128) {  // 16-byte chunks of the 81 x 64 planes
         const int row = c >> 3, ch = c & 7;
-        const int dst = row * 128 + ((ch ^ dz_sw(row)) << 4);
+        const int dst = row * 128 + ((ch ^ rc_sw<64>(row)) << 4);
         *reinterpret_cast<uint4 *>(dzi + dst) = *reinterpret_cast<const uint4 *>(dz_hi + src + c * 8);
         *reinterpret_cast<uint4 *>(dzi + DZ_PLANE + dst) = *reinterpret_cast<const uint4 *>(dz_lo + src + c * 8);
       }
@@ -390,19 +370,19 @@ __global__ __launch_bounds__(512) void rn_stem_wgrad_kernel(const float *__restr
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int row = 32 * s + 8 * g + q, chunk = 2 * j + (p4 >> 1);
-        const uint32_t o0 = row * 128 + ((chunk ^ dz_sw(row)) << 4) + 8 * (p4 & 1);
-        const uint32_t o1 = (row + 4) * 128 + ((chunk ^ dz_sw(row + 4)) << 4) + 8 * (p4 & 1);
-        b[j] = join(tr_read(dbase + o0), tr_read(dbase + o1));
-        bl[j] = join(tr_read(dbase + DZ_PLANE + o0), tr_read(dbase + DZ_PLANE + o1));
+        const uint32_t o0 = row * 128 + ((chunk ^ rc_sw<64>(row)) << 4) + 8 * (p4 & 1);
+        const uint32_t o1 = (row + 4) * 128 + ((chunk ^ rc_sw<64>(row + 4)) << 4) + 8 * (p4 & 1);
+        // (frag_join of two tr_reads, not tr_frag: each address is computed right in front of its read, which is the schedule measured)
+        b[j] = frag_join(tr_read(dbase + o0), tr_read(dbase + o1));
+        bl[j] = frag_join(tr_read(dbase + DZ_PLANE + o0), tr_read(dbase + DZ_PLANE + o1));
       }
 #pragma unroll
       for (int i = 0; i < 7; ++i) {
         const int mt = 7 * half + i;  // row tile of dW^T: kernel row mt / 2, pixels 4 (mt % 2) .. + 3
         const uint32_t off = (mt >> 1) * (MAPW * 8) + (mt & 1) * 32;
-        const bf8 a = join(tr_read(mbase + pix0 + off), tr_read(mbase + pix1 + off));
-        const bf8 al = join(tr_read(mbase + MAP_PLANE + pix0 + off), tr_read(mbase + MAP_PLANE + pix1 + off));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
+        const bf8 a = frag_join(tr_read(mbase + pix0 + off), tr_read(mbase + pix1 + off));
+        const bf8 al = frag_join(tr_read(mbase + MAP_PLANE + pix0 + off), tr_read(mbase + MAP_PLANE + pix1 + off));
+        lds_reads_landed();
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           acc[i][j] = mfma(al, b[j], acc[i][j]);
@@ -616,7 +596,7 @@ __global__ __launch_bounds__(256) void rn_pack_stem_frag_kernel(const float *__r
     co = 32 * s + 8 * (lane >> 4) + e;
   }
   const float v = (kx < 7 && c < 3) ? w1[((co * 3 + c) * 7 + ky) * 7 + kx] : 0.f;
-  const uint16_t h = f2bf(v), l = f2bf(v - bf2f(h));
+  const uint16_t h = f2bf(v), l = bf_lo(v, h);
   uint16_t *dst = which == 0 ? wf : wt;
   dst[(f * 2 + 0) * 512 + lane * 8 + e] = h;
   dst[(f * 2 + 1) * 512 + lane * 8 + e] = l;

@@ -13,13 +13,10 @@
 //     hi (+ lo) images for the bf16 chains -- no fp32 copies that are only re-read to be converted;
 //   * the backward never reads F / Gt: it recomputes them from A and the statistics (A is half the bytes of F + Gt);
 //   * a wave owns a row and moves 16 bytes per lane; the column kernels give a thread a column (coalesced rows).
-#include "crw_common.h"
+#include "bf16_mma.h"
 
 namespace crw {
 namespace {
-
-__device__ inline uint16_t f2bf(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
-__device__ inline float bf2f(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
 
 // caller's matrix index of internal matrix `mat` ([j][b] -> [b][j])
 __device__ inline long caller_mat(long mat, int B, int Tm1) { return (mat % B) * Tm1 + mat / B; }
@@ -43,7 +40,7 @@ __device__ inline void store_img4(uint16_t *__restrict__ hi, uint16_t *__restric
   const uint16_t h0 = f2bf(v.x), h1 = f2bf(v.y), h2 = f2bf(v.z), h3 = f2bf(v.w);
   *reinterpret_cast<uint2 *>(hi + o) = uint2{(uint32_t)h0 | ((uint32_t)h1 << 16), (uint32_t)h2 | ((uint32_t)h3 << 16)};
   if (lo) {
-    const uint16_t l0 = f2bf(v.x - bf2f(h0)), l1 = f2bf(v.y - bf2f(h1)), l2 = f2bf(v.z - bf2f(h2)), l3 = f2bf(v.w - bf2f(h3));
+    const uint16_t l0 = bf_lo(v.x, h0), l1 = bf_lo(v.y, h1), l2 = bf_lo(v.z, h2), l3 = bf_lo(v.w, h3);
     *reinterpret_cast<uint2 *>(lo + o) = uint2{(uint32_t)l0 | ((uint32_t)l1 << 16), (uint32_t)l2 | ((uint32_t)l3 << 16)};
   }
 }
