@@ -168,6 +168,12 @@ NOVELTY_SIGNATURES = {
     "crw_labelprop_novelty": (_c_int, [_p] + [_c_int] * 7 + [_p, _p, _p, _c_int, _p]),
 }
 
+# include/crw_hip_longmem.h, likewise: the sliding rule with n_long long-term frames, a memory bank (optional: `has_long_memory()`)
+LONGMEM_SIGNATURES = {
+    "crw_labelprop_topk_long": (_c_int, [_p] + [_c_int] * 6 + [_c_f, _c_int, _c_int, _p, _p, _c_int, _c_int, _p]),
+    "crw_labelprop_propagate_long": (_c_int, [_p, _p] + [_c_int] * 7 + [_p, _p, _c_int, _p]),
+}
+
 # include/crw_hip_routes.h, likewise: the route log -- which selector branch launched (optional: `has_routes()`; host pointers)
 ROUTES_SIGNATURES = {
     "crw_routes_clear": (_c_int, []),
@@ -217,6 +223,9 @@ ROUTES_ENTRY_POINTS = tuple(ROUTES_SIGNATURES)
 # likewise: context novelty (`has_novelty()`, `labelprop_novelty`)
 NOVELTY_ENTRY_POINTS = tuple(NOVELTY_SIGNATURES)
 
+# likewise: the sliding rule with a bank of long-term frames (`has_long_memory()`, `labelprop_topk(n_long=)`)
+LONG_MEMORY_ENTRY_POINTS = tuple(LONGMEM_SIGNATURES)
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 ANCHOR_CONTEXTS = ("clamp", "restart")  # what a fully labelled anchor trace does to the frames behind it
 
@@ -227,7 +236,7 @@ OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_E
                          "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS, "joint": JOINT_ENTRY_POINTS,
                          "posterior": POSTERIOR_ENTRY_POINTS, "posterior_batch": POSTERIOR_BATCH_ENTRY_POINTS,
                          "conv_chain": CONV_CHAIN_ENTRY_POINTS, "anchor_restart": ANCHOR_RESTART_ENTRY_POINTS,
-                         "routes": ROUTES_ENTRY_POINTS, "novelty": NOVELTY_ENTRY_POINTS}
+                         "routes": ROUTES_ENTRY_POINTS, "novelty": NOVELTY_ENTRY_POINTS, "long_memory": LONG_MEMORY_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -244,7 +253,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         missing = {n for names in OPTIONAL_ENTRY_POINTS.values() for n in names if not hasattr(handle, n)}
         for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES, **RESTART_SIGNATURES, **ROUTES_SIGNATURES,
-                                   **NOVELTY_SIGNATURES}.items():
+                                   **NOVELTY_SIGNATURES, **LONGMEM_SIGNATURES}.items():
             if name in missing:
                 continue
             fn = getattr(handle, name)
@@ -291,6 +300,7 @@ has_conv_chain, _conv_chain_lib = _optional("conv_chain", "the conv-trunk chain 
 has_anchor_restart, _anchor_restart_lib = _optional("anchor_restart", "the entry points that take a per-frame origin")
 has_routes, _routes_lib = _optional("routes", "the route log's entry points")
 has_novelty, _novelty_lib = _optional("novelty", "the context-novelty entry point")
+has_long_memory, _long_memory_lib = _optional("long_memory", "the entry points that take n_long long-term frames")
 
 MAX_ROUTES = 256  # csrc/crw_common.h
 
@@ -526,13 +536,49 @@ def _topk_origin(ehat, cxt_size, radius, temp, k, first_frame, grid_w, WV, I, ra
     return WV, I
 
 
-def labelprop_topk(ehat, cxt_size, radius, temp, knn, first_frame=1, grid_w=1, origin=None):
+LONG_ROUTES = {"auto": 0, "vector": 1, "matrix": 2}       # `labelprop_topk(n_long=, route=)`; the C codes pass as they are
+LONG_GATHER_ROUTES = {"auto": 0, "general": 1, "ring": 2}  # `labelprop_gather(n_long=, route=)`
+
+
+def check_n_long(n_long, T, first_frame, origin=None, grid_w=1):
+    """what every `n_long=` argument must obey (include/crw_hip_longmem.h) -> int(n_long)"""
+    n_long = int(n_long)
+    if n_long == 1:  # frame 0 alone: nothing is asked that the entry points do not check themselves
+        return 1
+    if not 1 <= n_long <= T - 1:
+        raise ValueError(f"n_long must be in 1 .. T - 1 = {T - 1} (got {n_long})")
+    if not 1 <= int(first_frame) <= T - 1:
+        raise ValueError(f"first_frame must be in 1 .. T - 1 = {T - 1} (got {first_frame})")
+    if origin is not None:
+        raise ValueError("n_long > 1 and origin are not combined: a restart's long-term frame is its origin alone")
+    if grid_w != 1:
+        raise ValueError("n_long > 1 is defined on N x 1 grids only")
+    return n_long
+
+
+def _topk_long(ehat, cxt_size, n_long, radius, temp, k, first_frame, WV, I, raw, route, origin=None, grid_w=1):
+    if origin is not None or grid_w != 1:
+        raise ValueError("route= goes through crw_labelprop_topk_long: N x 1 grids, no origin")
+    T, N, C = ehat.shape
+    _check(_long_memory_lib().crw_labelprop_topk_long(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(n_long), int(radius), float(temp),
+                                                      int(k), int(first_frame), _dev(WV, "WV"), _dev(I, "I", torch.int32), int(raw),
+                                                      LONG_ROUTES.get(route, route), _stream()), "crw_labelprop_topk_long")
+    return WV, I
+
+
+def labelprop_topk(ehat, cxt_size, radius, temp, knn, first_frame=1, grid_w=1, origin=None, n_long=1, route=None):
     """grid_w: the N nodes of a frame form an (N / grid_w) x grid_w grid (1 = a radargram's column of patches).
     origin ([T] int32, `anchor_origins`): frame n scores against frame origin[n] and the frames between it and n only, as frame
-    n - origin[n] of the item that starts there (include/crw_hip_restart.h); None: every frame scores from frame 0."""
+    n - origin[n] of the item that starts there (include/crw_hip_restart.h); None: every frame scores from frame 0.
+    n_long: the first n_long frames of ehat are long-term -- every frame scores against them and the cxt_size frames before it
+    (include/crw_hip_longmem.h, crw_labelprop_topk_long; N x 1 grids, no origin).  1 with route None: frame 0 alone, the call as it
+    has always been.  route (a key of LONG_ROUTES; tests and timing): crw_labelprop_topk_long on that route, at n_long = 1 as well."""
     T, N, C = ehat.shape
+    n_long = check_n_long(n_long, T, first_frame, origin, grid_w)
     W = torch.empty(T - first_frame, knn, N, device=ehat.device, dtype=torch.float32)
     I = torch.empty(T - first_frame, knn, N, device=ehat.device, dtype=torch.int32)
+    if n_long > 1 or route is not None:
+        return _topk_long(ehat, cxt_size, n_long, radius, temp, knn, first_frame, W, I, 0, route or "auto", origin, grid_w)
     if origin is not None:
         return _topk_origin(ehat, cxt_size, radius, temp, knn, first_frame, grid_w, W, I, 0, origin)
     _check(lib().crw_labelprop_topk_grid(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(radius), float(temp), int(knn),
@@ -671,7 +717,7 @@ def _propagate_origin_segmented(seed, W, I, o, T, N, M, knn, first_frame, cxt_si
 
 
 def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_size=None, context="reference", anchors=None,
-                     origin=None):
+                     origin=None, n_long=1, route=None):
     """cxt_size: the context size the lists were made with by `labelprop_topk` (same first_frame) -> crw_labelprop_propagate
     (chained frames in one workgroup, the frames beyond the context bound all at once); None: any lists, one workgroup.
     context='sliding' (needs cxt_size): the indices address the frames they were scored on -- crw_labelprop_propagate_sliding,
@@ -685,9 +731,21 @@ def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_
     origin (needs context='sliding'; [T] int32, `anchor_origins`): the lists are `labelprop_topk(..., origin=origin)`'s and frame n
     reads the rows of the item that starts at origin[n] (include/crw_hip_restart.h) -- ONE crw_labelprop_propagate_origin call,
     anchors marked as above; CRW_ANCHORS_RESTART_SEGMENTED=1 (read per call): crw_labelprop_propagate_sliding once per stretch
-    between origins on the sub-item that starts there, the same bits."""
+    between origins on the sub-item that starts there, the same bits.
+    n_long (needs context='sliding'; no origin): the lists are `labelprop_topk(..., n_long=n_long)`'s, the first n_long frames are
+    long-term (include/crw_hip_longmem.h) -- ONE crw_labelprop_propagate_long call, anchors marked as above.  That entry point takes
+    no seed: with one, its one-hot rows and pred[:, 0] are written here first; the rows of L before first_frame are the caller's.
+    1 with route None: the call is what it was.  route (a key of LONG_GATHER_ROUTES; tests and timing): crw_labelprop_propagate_long
+    on that route, at n_long = 1 as well."""
     knn = W.shape[1]
     check_context(context)
+    n_long = check_n_long(n_long, T, first_frame, origin)
+    long_memory = n_long > 1 or route is not None
+    if long_memory and origin is not None:
+        raise ValueError("route= goes through crw_labelprop_propagate_long: no origin")
+    if long_memory and context != "sliding":
+        raise ValueError("n_long needs context='sliding' (and cxt_size): under the reference rule a late frame never reads a label "
+                         "later than frame cxt_size, so beyond cxt_size + 1 frames it would not read the bank's rows consistently")
     if context == "sliding" and cxt_size is None:
         raise ValueError("context='sliding' needs cxt_size (the context size the lists were made with)")
     if origin is not None:
@@ -705,9 +763,18 @@ def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_
     if pred is None:
         pred = torch.zeros(N, T, device=W.device, dtype=torch.float32)
     if anchors is not None:
-        if origin is None and anchors_segmented():
+        if origin is None and not long_memory and anchors_segmented():
             return _propagate_anchored(seed, W, I, anchors, T, N, M, knn, int(first_frame), cxt_size, L, pred)
         W, I = mark_anchors(W.clone(), I.clone(), anchors, M, int(first_frame))
+    if long_memory:
+        if seed is not None:  # frame 0 from the seed, as the entry points with a seed argument write it
+            L[:N] = (seed[:, None] == torch.arange(M, device=seed.device)).to(L.dtype)
+            pred[:, 0] = seed
+        _check(_long_memory_lib().crw_labelprop_propagate_long(_dev(W, "W"), _dev(I, "I", torch.int32), T, N, M, knn, int(first_frame),
+                                                               int(cxt_size), n_long, _dev(L, "L"), _dev(pred, "pred"),
+                                                               LONG_GATHER_ROUTES.get(route or "auto", route), _stream()),
+               "crw_labelprop_propagate_long")
+        return L, pred
     if origin is not None:
         if anchors_restart_segmented():
             return _propagate_origin_segmented(seed, W, I, o, T, N, M, knn, int(first_frame), cxt_size, L, pred)
@@ -734,11 +801,12 @@ def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_
     return L, pred
 
 
-def labelprop_topk_scores(ehat, cxt_size, radius, temp, kcap, first_frame=1, grid_w=1, out=None, origin=None):
+def labelprop_topk_scores(ehat, cxt_size, radius, temp, kcap, first_frame=1, grid_w=1, out=None, origin=None, n_long=1, route=None):
     """`labelprop_topk` with the selected logits V [T-first_frame, kcap, N] instead of their softmax weights (empty slot -inf), and
     the same I: the lists of every knn <= kcap are their first knn entries (`labelprop_sweep_weights` makes the weights).
-    out: (V, I) tensors of those shapes to write into.  origin: as in `labelprop_topk`."""
+    out: (V, I) tensors of those shapes to write into.  origin, n_long, route: as in `labelprop_topk`."""
     T, N, C = ehat.shape
+    n_long = check_n_long(n_long, T, first_frame, origin, grid_w)
     if out is not None:
         V, I = out
         if tuple(V.shape) != (T - first_frame, kcap, N) or tuple(I.shape) != tuple(V.shape):
@@ -746,6 +814,8 @@ def labelprop_topk_scores(ehat, cxt_size, radius, temp, kcap, first_frame=1, gri
     else:
         V = torch.empty(T - first_frame, kcap, N, device=ehat.device, dtype=torch.float32)
         I = torch.empty(T - first_frame, kcap, N, device=ehat.device, dtype=torch.int32)
+    if n_long > 1 or route is not None:
+        return _topk_long(ehat, cxt_size, n_long, radius, temp, kcap, first_frame, V, I, 1, route or "auto", origin, grid_w)
     if origin is not None:
         return _topk_origin(ehat, cxt_size, radius, temp, kcap, first_frame, grid_w, V, I, 1, origin)
     _check(_sweep_lib().crw_labelprop_topk_scores(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(radius), float(temp), int(kcap),

@@ -14,7 +14,9 @@
 // (crw_labelprop_propagate_sliding) applies them to the frames they were scored on instead; the lists are the same.
 #include "crw_common.h"
 #include "crw_hip_restart.h"
+#include "crw_hip_longmem.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace crw {
 namespace {
@@ -28,17 +30,38 @@ constexpr int MAX_KNN = 64;
 // ORG (crw_labelprop_topk_origin, include/crw_hip_restart.h): frame na is scored as frame n = na - a of the item that starts at its
 // origin a = origin[na] -- the key base moves to frame a, the context arithmetic runs on n, the lists go to frame na's place.
 __device__ inline int frame_origin(const int32_t *origin, int n) { return min(max(origin[n], 0), n - 1); }  // 0 <= a < n whatever it holds
-template <bool ORG>
+// LM (the crw_labelprop_*_long entry points, include/crw_hip_longmem.h): the first K = n_long frames are long-term, where the
+// other instances keep frame 0 alone -- list position p of a truncated list (n > K + cxt) is frame p while p < K, then the window
+// n - cxt .. n - 1.  K = 1 is the other instances' arithmetic; they keep their own text, so their instruction streams stay.
+// The number K travels in the place of the origin pointer, which an LM instance does not have: one 8-byte kernel argument either way,
+// so the other instances keep their argument layout as well (the hidden arguments, blockDim among them, follow the last one).
+struct LongFrames {
+  int n, pad;
+};
+template <bool LM>
+using OriginArg = std::conditional_t<LM, LongFrames, const int32_t *__restrict__>;
+template <bool LM>
+__device__ __forceinline__ int long_frames(OriginArg<LM> a) {
+  if constexpr (LM) return a.n;
+  else return 1;
+}
+template <bool ORG, class Arg>
+__device__ __forceinline__ int origin_at(Arg origin, int n) {
+  if constexpr (ORG) return frame_origin(origin, n);
+  else return 0;
+}
+template <bool ORG, bool LM>
 __global__ __launch_bounds__(256) void labelprop_topk_kernel(const float *__restrict__ ehat, int T, int N, int C,
                                                              int cxt, int radius, float temp, int knn,
                                                              int first_frame, int gw, float *__restrict__ W,
-                                                             int32_t *__restrict__ I, int raw, const int32_t *__restrict__ origin) {
+                                                             int32_t *__restrict__ I, int raw, OriginArg<LM> origin) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int q = blockIdx.x, na = blockIdx.y + first_frame, org = ORG ? frame_origin(origin, na) : 0, n = na - org;
+  const int q = blockIdx.x, na = blockIdx.y + first_frame, org = origin_at<ORG>(origin, na), n = na - org;
   if (ORG) ehat += (long)org * N * C;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const bool trunc = n > cxt + 1;
-  const int nf = trunc ? cxt + 1 : n;
+  const int K = long_frames<LM>(origin);
+  const bool trunc = n > cxt + K;
+  const int nf = trunc ? cxt + K : n;
   const int gh = N / gw, qi = q / gw, qj = q - qi * gw;
   const int lo = max(0, qi - radius + 1), hi = min(gh - 1, qi + radius - 1);        // box rows
   const int lj = max(0, qj - radius + 1), hj = min(gw - 1, qj + radius - 1);        // box columns
@@ -62,7 +85,7 @@ __global__ __launch_bounds__(256) void labelprop_topk_kernel(const float *__rest
     const int p = cand / bw, r = cand - p * bw;
     const int mi = lo + r / bwj, mj = lj + r % bwj, m = mi * gw + mj;
     const bool inside = (mi - qi) * (mi - qi) + (mj - qj) * (mj - qj) < radius * radius;  // (always, on an N x 1 grid)
-    const int frame = trunc ? (p == 0 ? 0 : n - cxt + (p - 1)) : p;
+    const int frame = LM ? ((!trunc || p < K) ? p : n - cxt + (p - K)) : (trunc ? (p == 0 ? 0 : n - cxt + (p - 1)) : p);
     const float *key = ehat + ((long)frame * N + m) * C;
     float d = 0.f;
     if ((C & 3) == 0) {
@@ -144,22 +167,23 @@ constexpr int TK_Q = 16, TK_NV = 32, TK_NT = 512, TK_NW = TK_NT / 64;  // eight 
 // 80 - 100 context frames: 3 888 / 11 781 candidates per query).  The argument holds chunk after chunk -- the k best carried into
 // each selection come from earlier chunks, so they have the lowest indices -- and the chunk size is that of NCH = 2 (pf * max_bi
 // <= 64 * TK_NV / 2 in registers, 64 KiB of scores at 1 024 candidates: two workgroups per CU).
-template <int CSTEPS, int NCH, bool ORG>  // C / 16: float4 per lane and row; ORG: as in labelprop_topk_kernel
+template <int CSTEPS, int NCH, bool ORG, bool LM>  // C / 16: float4 per lane and row; ORG, LM: as in labelprop_topk_kernel
 __global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_kernel(const float *__restrict__ ehat, int T, int N, int cxt, int radius,
                                                                            float temp, int knn, int first_frame, int maxcand, int pf,
                                                                            float *__restrict__ W, int32_t *__restrict__ I, int raw,
-                                                                           const int32_t *__restrict__ origin) {
+                                                                           OriginArg<LM> origin) {
   constexpr int C = 16 * CSTEPS, NV = TK_NV / (NCH == 1 ? 1 : 2);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float *val = smem;  // [TK_Q][maxcand] (maxcand: candidates of ONE chunk)
   __shared__ float sel_v[TK_Q][MAX_KNN];
   __shared__ int sel_i[TK_Q][MAX_KNN];
   const int q0 = blockIdx.x * TK_Q, nq = min(TK_Q, N - q0), na = blockIdx.y + first_frame;
-  const int org = ORG ? frame_origin(origin, na) : 0, n = na - org;
+  const int org = origin_at<ORG>(origin, na), n = na - org;
   if (ORG) ehat += (long)org * N * C;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r16 = lane & 15, g = lane >> 4;
-  const bool trunc = n > cxt + 1;
-  const int nf = trunc ? cxt + 1 : n;
+  const int K = long_frames<LM>(origin);
+  const bool trunc = n > cxt + K;
+  const int nf = trunc ? cxt + K : n;
 
   const int ulo = max(0, q0 - radius + 1), uhi = min(N - 1, q0 + nq - 1 + radius - 1);
   const int kt_lo = ulo >> 4, nkt = (uhi >> 4) - kt_lo + 1;  // item = (context frame p, key tile kt)
@@ -197,7 +221,7 @@ __global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_k
     }
     auto fetch = [&](int item, float4 (&b)[CSTEPS]) {
       const int p = p0 + item / nkt, kt = kt_lo + item % nkt;
-      const int frame = trunc ? (p == 0 ? 0 : n - cxt + (p - 1)) : p;
+      const int frame = LM ? ((!trunc || p < K) ? p : n - cxt + (p - K)) : (trunc ? (p == 0 ? 0 : n - cxt + (p - 1)) : p);
       const float *kp = ehat + ((long)frame * N + min(16 * kt + r16, N - 1)) * C + 4 * g;
 #pragma unroll
       for (int j = 0; j < CSTEPS; ++j) b[j] = *reinterpret_cast<const float4 *>(kp + 16 * j);
@@ -342,30 +366,33 @@ int launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... arg
 
 template <int CSTEPS, int NCH>
 int launch_topk_mfma_n(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int chunkcand, int pf,
-                       float *W, int32_t *I, int raw, const int32_t *origin, hipStream_t s) {
+                       float *W, int32_t *I, int raw, const int32_t *origin, int n_long, hipStream_t s) {
   const dim3 grid((N + TK_Q - 1) / TK_Q, T - first_frame);
   const size_t lds = (size_t)TK_Q * chunkcand * 4;
   if constexpr (NCH == 1) CRW_ROUTE("labelprop.topk_mfma_chunks1");
   else if constexpr (NCH == 2) CRW_ROUTE("labelprop.topk_mfma_chunks2");
   else CRW_ROUTE("labelprop.topk_mfma_long");
+  if (n_long)  // crw_labelprop_topk_long: the LM instance, whatever n_long is (no origins there)
+    return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH, false, true>>(grid, dim3(TK_NT), lds, s, ehat, T, N, cxt, radius, temp, knn,
+                                                                                first_frame, chunkcand, pf, W, I, raw, LongFrames{n_long, 0});
   if (origin)
-    return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH, true>>(grid, dim3(TK_NT), lds, s, ehat, T, N, cxt, radius, temp, knn,
-                                                                         first_frame, chunkcand, pf, W, I, raw, origin);
-  return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH, false>>(grid, dim3(TK_NT), lds, s, ehat, T, N, cxt, radius, temp, knn,
-                                                                        first_frame, chunkcand, pf, W, I, raw, origin);
+    return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH, true, false>>(grid, dim3(TK_NT), lds, s, ehat, T, N, cxt, radius, temp, knn,
+                                                                                first_frame, chunkcand, pf, W, I, raw, origin);
+  return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH, false, false>>(grid, dim3(TK_NT), lds, s, ehat, T, N, cxt, radius, temp, knn,
+                                                                               first_frame, chunkcand, pf, W, I, raw, origin);
 }
 
 // max_nf context frames of max_bi in-band keys: in one piece, or -- when the scores of a 16-query tile fill more than half a CU's LDS --
 // in two halves, so that two workgroups share a CU (CRW_LABELPROP_TOPK_CHUNKS=1: always one piece, A/B)
 template <int CSTEPS>
 int launch_topk_mfma(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int max_nf, int max_bi, float *W,
-                     int32_t *I, int raw, const int32_t *origin, hipStream_t s) {
+                     int32_t *I, int raw, const int32_t *origin, int n_long, hipStream_t s) {
   static const bool one = getenv("CRW_LABELPROP_TOPK_CHUNKS") && getenv("CRW_LABELPROP_TOPK_CHUNKS")[0] == '1';
   const long maxcand = (long)max_nf * max_bi;
   const int pf = (max_nf + 1) / 2;
   if (!one && CSTEPS <= 8 /* 256 channels: past 128 registers */ && (size_t)TK_Q * maxcand * 4 > 76 * 1024 && (long)pf * max_bi <= 64L * (TK_NV / 2))
-    return launch_topk_mfma_n<CSTEPS, 2>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, origin, s);
-  return launch_topk_mfma_n<CSTEPS, 1>(ehat, T, N, cxt, radius, temp, knn, first_frame, (int)maxcand, max_nf, W, I, raw, origin, s);
+    return launch_topk_mfma_n<CSTEPS, 2>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, origin, n_long, s);
+  return launch_topk_mfma_n<CSTEPS, 1>(ehat, T, N, cxt, radius, temp, knn, first_frame, (int)maxcand, max_nf, W, I, raw, origin, n_long, s);
 }
 
 // candidate lists past the two forms above (more than 64 * TK_NV candidates, or a tile's scores over 150 KiB): chunks of pf frames,
@@ -374,12 +401,12 @@ int launch_topk_mfma(const float *ehat, int T, int N, int cxt, int radius, float
 constexpr int TK_LONG_CAND = 64 * (TK_NV / 2);
 template <int CSTEPS>
 int launch_topk_mfma_long(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int max_nf, int max_bi,
-                          float *W, int32_t *I, int raw, const int32_t *origin, hipStream_t s) {
+                          float *W, int32_t *I, int raw, const int32_t *origin, int n_long, hipStream_t s) {
   static_assert(CSTEPS <= 8, "256 channels: past 128 registers");
   int pf = TK_LONG_CAND / max_bi;
   const int nch = (max_nf + pf - 1) / pf;
   pf = (max_nf + nch - 1) / nch;
-  return launch_topk_mfma_n<CSTEPS, 0>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, origin, s);
+  return launch_topk_mfma_n<CSTEPS, 0>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, origin, n_long, s);
 }
 
 __device__ inline float ld_l2(const float *p) {
@@ -396,8 +423,15 @@ __device__ inline void st_l2(float *p, float v) {
 __device__ inline int slide_row(int i, int n, int N, int cxt) { return (i >= N && n > cxt + 1) ? i + (n - cxt - 1) * N : i; }
 // ORG (the crw_labelprop_propagate_origin entry points, include/crw_hip_restart.h): frame n is frame n - a of the item that starts at
 // its origin a = origin[n] -- the same translation on n - a, then a frames further down L.  a = 0: slide_row's value.
-template <bool ORG>
-__device__ inline int slide_row_at(int i, int n, int a, int N, int cxt) {
+// LM (crw_labelprop_propagate_long, include/crw_hip_longmem.h): K long-term frames in front of the window, and the index clamped into
+// the list it addresses first, min(n, K + cxt) * N entries -- what the ring kernel does on every route, so that the routes agree on
+// any list.  K = 1 and an index in range: slide_row's value.
+template <bool ORG, bool LM = false>
+__device__ inline int slide_row_at(int i, int n, int a, int N, int cxt, int K = 1) {
+  if constexpr (LM) {
+    i = min(max(i, 0), min(n, K + cxt) * N - 1);
+    return (i >= K * N && n > cxt + K) ? i + (n - cxt - K) * N : i;
+  }
   return ORG ? a * N + slide_row(i, n - a, N, cxt) : slide_row(i, n, N, cxt);
 }
 // An anchor mark (sliding entry points only, CRW_LABELPROP_ANCHOR_WEIGHT in the header): a slot-0 weight of exactly -inf says that
@@ -455,12 +489,12 @@ __device__ __forceinline__ void init_frame0(const float *seed, float *L, float *
     for (int q = tid; q < N; q += nt) pred[(long)q * T] = seed[q];
 }
 
-template <bool SLIDE, bool ORG>
+template <bool SLIDE, bool ORG, bool LM>
 __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__restrict__ seed,
                                                                 const float *__restrict__ W,
                                                                 const int32_t *__restrict__ I, int T, int N, int M,
                                                                 int knn, int first_frame, float *L,
-                                                                float *__restrict__ pred, int cxt, const int32_t *__restrict__ origin) {
+                                                                float *__restrict__ pred, int cxt, OriginArg<LM> origin) {
   const int tid = threadIdx.x, nt = blockDim.x;
   init_frame0<true, false>(seed, L, pred, nullptr, T, N, M, tid, nt);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -468,13 +502,13 @@ __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__r
   for (int n = first_frame; n < T; ++n) {
     const float *Wn = W + (long)(n - first_frame) * knn * N;
     const int32_t *In = I + (long)(n - first_frame) * knn * N;
-    const int org = ORG ? frame_origin(origin, n) : 0;
+    const int org = origin_at<ORG>(origin, n);
     for (int it = tid; it < N * M; it += nt) {
       const int q = it / M, c = it % M;
       float p = 0.f;
       const bool mk = SLIDE && anchor_mark(Wn[q]);  // an anchored node: its list is not a list -- every read goes to row 0
       for (int j = 0; j < knn; ++j) {
-        const int r = SLIDE ? (mk ? 0 : slide_row_at<ORG>(In[j * N + q], n, org, N, cxt)) : In[j * N + q];
+        const int r = SLIDE ? (mk ? 0 : slide_row_at<ORG, LM>(In[j * N + q], n, org, N, cxt, long_frames<LM>(origin))) : In[j * N + q];
         p += ld_l2(L + (long)r * M + c) * Wn[j * N + q];
       }
       if (mk) p = anchor_onehot(In[q], M, c);  // ... and the sum is dropped for the one-hot of its class
@@ -494,13 +528,14 @@ __global__ __launch_bounds__(1024) void labelprop_gather_kernel(const float *__r
 // same order: bit-identical results.
 constexpr int GATHER_NT = 256, GATHER_PF = 8;  // threads; prefetch registers per thread (knn * N <= 2048)
 constexpr int GATHER_CH = 20;                  // neighbours whose LDS reads are in flight together (KNN = 20: one batch per output; 4: 0.64, 10: 0.61, 20: 0.58 ms per cfg5 pass)
-template <bool SLIDE, bool ORG>  // ORG: a restart frame's long-term frame is an ordinary row of L -- in the ring while it is recent, from L afterwards
+// LM: likewise the long-term frames 1 .. K - 1 (frame 0 has its slot)
+template <bool SLIDE, bool ORG, bool LM>  // ORG: a restart frame's long-term frame is an ordinary row of L -- in the ring while it is recent, from L afterwards
 __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const float *__restrict__ seed,
                                                                          const float *__restrict__ W,
                                                                          const int32_t *__restrict__ I, int T, int N, int M,
                                                                          int knn, int first_frame, float *L,
                                                                          float *__restrict__ pred, int R, int cxt,
-                                                                         const int32_t *__restrict__ origin) {
+                                                                         OriginArg<LM> origin) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, NM = N * M, KN = knn * N;
   float *l0 = sm, *ring = l0 + NM, *wbuf = ring + (long)R * NM;  // [NM], [R][NM], [2][KN]
@@ -514,7 +549,7 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
   const int RNM = R * NM;
   for (int n = first_frame; n < T; ++n) {
     const int cur = n & 1;
-    const int org = ORG ? frame_origin(origin, n) : 0;
+    const int org = origin_at<ORG>(origin, n);
     // next frame's lists: global -> registers now, -> LDS after this frame's arithmetic (unconditional, clamped loads)
     const long nxt = (long)(min(n + 1, T - 1) - first_frame) * KN;
     float pw[GATHER_PF];
@@ -544,7 +579,7 @@ __global__ __launch_bounds__(GATHER_NT) void labelprop_gather_lds_kernel(const f
 #pragma unroll
         for (int u = 0; u < GATHER_CH; ++u) {
           const int jj = min(j0 + u, knn - 1);
-          idx[u] = SLIDE ? (mk ? 0 : slide_row_at<ORG>(in[jj * N + q], n, org, N, cxt)) : in[jj * N + q];
+          idx[u] = SLIDE ? (mk ? 0 : slide_row_at<ORG, LM>(in[jj * N + q], n, org, N, cxt, long_frames<LM>(origin))) : in[jj * N + q];
           w[u] = wn[jj * N + q];
         }
 #pragma unroll
@@ -730,11 +765,18 @@ __global__ __launch_bounds__(PX_NT) void labelprop_prefix_kernel(const float *__
 // time, into the slot that is NOT being read, and the roles flip at the barrier (mb, the slot of the frame whose offsets are made
 // next).  origin[] is copied to LDS once, clamped to [0, n - 1]; a sequence that breaks the chain rule (origin[n] neither origin[n - 1]
 // nor n - 1) reads rows of the wrong frames but never outside the labels in LDS: n' here is counted, at most n.
-template <int KP, bool ORG>
+//
+// LM (crw_labelprop_propagate_long, include/crw_hip_longmem.h): K = n_long long-term frames.  lab is [K][NM] followed by the ring
+// [R][NM]: frame f < K sits at slot f for good (frames first_frame .. K - 1 of the call are computed into their slots like any other),
+// frame f >= K at K + (f - K) % R.  A list position below K * N is its own address; the window's positions take the running shift
+// ((f - cxt - K) % R) * NM once f > K + cxt, wrapped once past the ring's end; the clamp bound is min(f, K + cxt) * N - 1.  Every
+// expression below is written with K, LN = K * N and LNM = K * NM, which are the literals 1, N and NM in the other instances.
+template <int KP, bool ORG, bool LM>
 __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__restrict__ seed, const float *__restrict__ W,
                                                                   const int32_t *__restrict__ I, int T, int N, int M, int knn,
                                                                   int first_frame, int cxt, int R, float *L, float *__restrict__ pred,
-                                                                  int ncw, const int32_t *__restrict__ origin) {
+                                                                  int ncw, OriginArg<LM> origin) {
+  static_assert(!(ORG && LM), "origins and a bank of long-term frames are not combined");
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, NM = N * M, KN = knn * N, last_frame = T - 1;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -747,9 +789,16 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
   // need neither the clamp to the last slot nor the padding test
   constexpr int KLO = KP - 8;
   const int RNM = R * NM;
-  float *lab = sm;                                                                   // [NM] frame 0, [R][NM] the ring
+  // K, K * N and K * NM as expressions the front end folds to the literals 1, N and NM of the other instances' text (a variable that
+  // is 1, or long_frames(), reaches the optimiser as arithmetic: hipcc then groups first_frame - cxt - 1 in the prologue another way
+  // and allocates the KP = 16 instance's registers differently -- tools/isa_diff.py --functions shows it)
+  const int Kl = long_frames<LM>(origin);
+#define K (LM ? Kl : 1)
+#define LN (LM ? Kl * N : N)
+#define LNM (LM ? Kl * NM : NM)
+  float *lab = sm;                                                                   // [NM] frame 0 (LM: [K][NM]), [R][NM] the ring
   // ORG: [NM] the second long-term slot and origin[T] behind the ring, in whole frames (slide_origin_frames(), the launcher's count)
-  const long nlab = ORG ? R + 2 + (T + NM - 1) / NM : R + 1;
+  const long nlab = ORG ? R + 2 + (T + NM - 1) / NM : R + K;
   int2 *pl = reinterpret_cast<int2 *>(lab + ((nlab * NM + 1) & ~1L));  // [2][KNP] (index, weight bits), slot = frame & 1
   int *orgs = reinterpret_cast<int *>(lab + (long)(R + 2) * NM);      // (ORG only)
 
@@ -762,11 +811,13 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
     if (org0 > 0)
       for (int it = tid; it < NM; it += (int)blockDim.x) lab[it] = L[(long)org0 * NM + it];
   }
+  if constexpr (LM)  // the long-term frames 1 .. K - 1 that the caller filled (frame 0: above)
+    for (int it = NM + tid; it < min(K, first_frame) * NM; it += (int)blockDim.x) lab[it] = L[it];
   {
-    const int fl = max(1, first_frame - cxt);
+    const int fl = max(K, first_frame - cxt);
     for (int it = tid; it < (first_frame - fl) * NM; it += (int)blockDim.x) {
       const int f = fl + it / NM, r = it % NM;
-      lab[NM + ((f - 1) % R) * NM + r] = L[(long)f * NM + r];
+      lab[LNM + ((f - K) % R) * NM + r] = L[(long)f * NM + r];
     }
   }
 
@@ -817,7 +868,7 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
   // select on p.  The marked list's offsets stay in range like any other's, so its label reads are harmless and its sum is dropped.
   // ORG: f is the frame's number n' in the item that starts at its origin, mb the offset of its long-term slot (0 or NM + RNM)
   auto to_offsets = [&](int f, int shift, int mb, int (&ix)[KP], float (&ww)[KP], int &mk, int &oh) {
-    const int lim = min(f, cxt + 1) * N - 1;
+    const int lim = min(f, cxt + K) * N - 1;
     mk = anchor_mark(ww[0]) ? -1 : 0;
     oh = __float_as_int(anchor_onehot(ix[0], M, c));
 #pragma unroll
@@ -827,9 +878,9 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
       if constexpr (ORG) {  // two selects, no branch: as an if / else hipcc makes it a divergent branch per neighbour
         const int os = o + shift, ow = os >= NM + RNM ? os - RNM : os;
         o = i >= N ? ow : o + mb;
-      } else if (i >= N) {
+      } else if (i >= LN) {
         o += shift;
-        if (o >= NM + RNM) o -= RNM;
+        if (o >= LNM + RNM) o -= RNM;
       }
       ix[j] = o;
       if (j >= KLO && j >= knn) ww[j] = 0.f;  // padding slot: p + v * 0 = p
@@ -838,8 +889,12 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
   // running offsets (wave-uniform): shift of the frame whose offsets are made next, store slot of the frame computed next
   int shift = first_frame > cxt + 1 ? ((first_frame - cxt - 1) % R) * NM : 0;
   int wslot = NM + ((first_frame - 1) % R) * NM;
+  if constexpr (LM) {  // the same two with K, and a first frame inside the bank
+    shift = first_frame > cxt + K ? ((first_frame - cxt - K) % R) * NM : 0;
+    wslot = first_frame < K ? first_frame * NM : LNM + ((first_frame - K) % R) * NM;
+  }
   auto next_shift = [&](int f) {  // shift of frame f -> shift of frame f + 1
-    if (f + 1 > cxt + 1) {
+    if (f + 1 > cxt + K) {
       shift += NM;
       if (shift == RNM) shift = 0;
     }
@@ -921,13 +976,16 @@ __global__ __launch_bounds__(PX_NT) void labelprop_slide_kernel(const float *__r
     turn = turn + 1 == D ? 0 : turn + 1;
     if constexpr (!ORG) next_shift(f + 1);
     pslot = wslot;
-    wslot = wslot + NM == NM + RNM ? NM : wslot + NM;
+    wslot = wslot + NM == LNM + RNM ? LNM : wslot + NM;  // (LM: a long-term slot's successor is the next slot, the ring's first after K - 1)
     if constexpr (ORG) next_origin(f + 1, o2);
     lds_barrier();
   }
   if (amax) {
     argmax_rows(pred, T, N, M, last_frame, at, 64, lab + pslot, PlainLoad());
   }
+#undef K
+#undef LN
+#undef LNM
 }
 
 // ---- hyper-parameter sweeps (crw_labelprop_sweep_weights, crw_labelprop_propagate_batch) ----------------------------------------
@@ -1148,39 +1206,46 @@ namespace {
 // (crw_labelprop_topk_scores) -- the same kernels, the same selection, another last line of the epilogue
 // origin (crw_labelprop_topk_origin; NULL: every frame scores from frame 0): the route is still chosen from the whole call's
 // arguments -- a restart frame has fewer candidates than the bound the route was chosen for, never more
+// n_long (crw_labelprop_topk_long; 0: frame 0 alone is long-term, the instances the other entry points have always run): the lists
+// hold up to n_long + cxt_size frames, and the routes are chosen for that length.  route: 0 auto, 1 the vector kernel, 2 the
+// matrix-core kernels -- CRW_EINVAL where the forced one does not apply
 int topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int knn, int first_frame, int grid_w, float *W,
-              int32_t *I, int raw, const int32_t *origin, crw_stream_t stream) {
+              int32_t *I, int raw, const int32_t *origin, crw_stream_t stream, int n_long = 0, int route = 0) {
   crw::clear_stale_error();
   if (!ehat || !W || !I || T < 2 || N < 1 || C < 1 || cxt_size < 1 || radius < 1 || knn < 1 || knn > MAX_KNN ||
       !(temp > 0.f) || first_frame < 1 || first_frame >= T || grid_w < 1 || N % grid_w)
     return CRW_EINVAL;
   const long gh = N / grid_w;
-  const long max_nf = (long)(cxt_size + 1 < T - 1 ? cxt_size + 1 : T - 1);
+  const long max_keys = (long)cxt_size + (n_long ? n_long : 1);
+  const long max_nf = max_keys < T - 1 ? max_keys : T - 1;
   const long max_bi = (2L * radius - 1 < gh) ? 2L * radius - 1 : gh, max_bj = (2L * radius - 1 < grid_w) ? 2L * radius - 1 : grid_w;
   const size_t lds = (((size_t)C + 3) & ~(size_t)3) * 4 + (size_t)(max_nf * max_bi * max_bj) * 4;
   // a radargram's patch column with at least one full tile of queries: scores on the fp32 matrix cores (labelprop_topk_mfma_kernel).
   // CRW_LABELPROP_TOPK_VALU=1 keeps the vector kernel (A/B)
   static const bool valu = getenv("CRW_LABELPROP_TOPK_VALU") && getenv("CRW_LABELPROP_TOPK_VALU")[0] == '1';
   const long maxcand = max_nf * max_bi;
-  const bool column = grid_w == 1 && !valu && N >= TK_Q && (((uintptr_t)ehat) & 15) == 0;
+  const bool column = grid_w == 1 && !(route ? route == 1 : valu) && N >= TK_Q && (((uintptr_t)ehat) & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
   if (column && (C == 64 || C == 128 || C == 256) && maxcand <= 64L * TK_NV && (size_t)TK_Q * maxcand * 4 <= 150 * 1024) {
-    if (C == 64) return launch_topk_mfma<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, s);
-    if (C == 128) return launch_topk_mfma<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, s);
-    return launch_topk_mfma<16>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, s);
+    if (C == 64) return launch_topk_mfma<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s);
+    if (C == 128) return launch_topk_mfma<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s);
+    return launch_topk_mfma<16>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s);
   }
   // longer lists (radius 30 / 60 at 80 - 100 context frames): any number of chunks; a single frame's band must fit one chunk
   if (column && (C == 64 || C == 128) && max_bi <= TK_LONG_CAND) {
-    if (C == 64) return launch_topk_mfma_long<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, s);
-    return launch_topk_mfma_long<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, s);
+    if (C == 64) return launch_topk_mfma_long<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s);
+    return launch_topk_mfma_long<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s);
   }
-  if (lds > 60 * 1024) return CRW_EINVAL;
+  if (lds > 60 * 1024 || route == 2) return CRW_EINVAL;
   CRW_ROUTE("labelprop.topk_valu");
-  if (origin)
-    hipLaunchKernelGGL(labelprop_topk_kernel<true>, dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T, N, C, cxt_size,
+  if (n_long)
+    hipLaunchKernelGGL((labelprop_topk_kernel<false, true>), dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T, N, C,
+                       cxt_size, radius, temp, knn, first_frame, grid_w, W, I, raw, LongFrames{n_long, 0});
+  else if (origin)
+    hipLaunchKernelGGL((labelprop_topk_kernel<true, false>), dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T, N, C, cxt_size,
                        radius, temp, knn, first_frame, grid_w, W, I, raw, origin);
   else
-    hipLaunchKernelGGL(labelprop_topk_kernel<false>, dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T,
+    hipLaunchKernelGGL((labelprop_topk_kernel<false, false>), dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T,
                        N, C, cxt_size, radius, temp, knn, first_frame, grid_w, W, I, raw, origin);
   return check_launch();
 }
@@ -1219,17 +1284,20 @@ bool chain_fits(int knn, long NM, long KN, size_t lds) { return knn <= 24 && cha
 // origin (RING only, crw_labelprop_propagate_origin): the slide kernel's ORG instance; NULL: the instance it has always been
 template <int KP, bool RING>
 int launch_chain_kp(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int last, int cxt, int R,
-                    size_t lds, float *L, float *pred, const int32_t *origin, hipStream_t s) {
+                    size_t lds, float *L, float *pred, const int32_t *origin, int n_long, hipStream_t s) {
   const int ncw = chain_ncw((long)N * M);
   const dim3 block((ncw + chain_nld((long)N * M) + 1) * 64);
   if constexpr (RING) {
     if (origin) CRW_ROUTE("labelprop.slide_ring_origin");
     else CRW_ROUTE("labelprop.slide_ring");
+    if (n_long)  // crw_labelprop_propagate_long: the LM instance, whatever n_long is
+      return launch_big_lds<labelprop_slide_kernel<KP, false, true>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, cxt, R, L,
+                                                                     pred, ncw, LongFrames{n_long, 0});
     if (origin)
-      return launch_big_lds<labelprop_slide_kernel<KP, true>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, cxt, R, L, pred,
-                                                              ncw, origin);
-    return launch_big_lds<labelprop_slide_kernel<KP, false>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, cxt, R, L, pred,
-                                                             ncw, origin);
+      return launch_big_lds<labelprop_slide_kernel<KP, true, false>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, cxt, R, L,
+                                                                     pred, ncw, origin);
+    return launch_big_lds<labelprop_slide_kernel<KP, false, false>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, cxt, R, L,
+                                                                    pred, ncw, origin);
   } else {
     CRW_ROUTE("labelprop.propagate_prefix");
     return launch_big_lds<labelprop_prefix_kernel<KP>>(dim3(1), block, lds, s, seed, W, I, T, N, M, knn, first_frame, last, L, pred, ncw);
@@ -1237,10 +1305,10 @@ int launch_chain_kp(const float *seed, const float *W, const int32_t *I, int T, 
 }
 template <bool RING>
 int launch_chain(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int last, int cxt, int R,
-                 size_t lds, float *L, float *pred, const int32_t *origin, hipStream_t s) {
-  if (knn <= 8) return launch_chain_kp<8, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, origin, s);
-  if (knn <= 16) return launch_chain_kp<16, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, origin, s);
-  return launch_chain_kp<24, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, origin, s);
+                 size_t lds, float *L, float *pred, const int32_t *origin, hipStream_t s, int n_long = 0) {
+  if (knn <= 8) return launch_chain_kp<8, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, origin, n_long, s);
+  if (knn <= 16) return launch_chain_kp<16, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, origin, n_long, s);
+  return launch_chain_kp<24, RING>(seed, W, I, T, N, M, knn, first_frame, last, cxt, R, lds, L, pred, origin, n_long, s);
 }
 // frames of LDS the slide kernel's ORG instance keeps beside the two list slots: frame 0's slot, the ring, the second long-term
 // slot, and origin[T] rounded up to whole frames
@@ -1248,13 +1316,17 @@ long slide_origin_frames(long R, long T, long NM) { return R + 2 + (T + NM - 1) 
 
 // the one-workgroup walk over any lists (crw_labelprop_gather; SLIDE: the general route of crw_labelprop_propagate_sliding, the
 // indices translated in the kernel)
-template <bool SLIDE, bool ORG = false>
+// LM (crw_labelprop_propagate_long): n_long long-term frames, the same two selector sites
+template <bool SLIDE, bool ORG = false, bool LM = false>
 int launch_gather(const float *seed, const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int cxt, float *L,
-                  float *pred, crw_stream_t stream, const int32_t *origin = nullptr) {
+                  float *pred, crw_stream_t stream, const int32_t *origin = nullptr, int n_long = 1) {
   crw::clear_stale_error();
   if (bad_propagate_args(W, I, L, pred, T, N, M, knn, first_frame)) return CRW_EINVAL;
   // LDS-resident form when the lists of a frame fit the prefetch registers and at least a few frames fit the ring
   const long NM = (long)N * M, KN = (long)knn * N;
+  OriginArg<LM> origin_arg;
+  if constexpr (LM) origin_arg = LongFrames{n_long, 0};
+  else origin_arg = origin;
   const long budget = 150 * 1024 - 16 * KN;  // bytes left for frame 0 + the ring after the two (weight, index) list copies
   long R = budget > 0 ? budget / (4 * NM) - 1 : 0;
   if (R > T) R = T;
@@ -1264,14 +1336,14 @@ int launch_gather(const float *seed, const float *W, const int32_t *I, int T, in
     if constexpr (ORG) CRW_ROUTE("labelprop.slide_general_origin_lds");
     else if constexpr (SLIDE) CRW_ROUTE("labelprop.slide_general_lds");
     else CRW_ROUTE("labelprop.gather_lds");
-    return launch_big_lds<labelprop_gather_lds_kernel<SLIDE, ORG>>(dim3(1), dim3(GATHER_NT), lds, (hipStream_t)stream, seed, W, I, T, N, M, knn,
-                                                                   first_frame, L, pred, (int)R, cxt, origin);
+    return launch_big_lds<labelprop_gather_lds_kernel<SLIDE, ORG, LM>>(dim3(1), dim3(GATHER_NT), lds, (hipStream_t)stream, seed, W, I, T, N, M,
+                                                                       knn, first_frame, L, pred, (int)R, cxt, origin_arg);
   }
   if constexpr (ORG) CRW_ROUTE("labelprop.slide_general_origin_global");
   else if constexpr (SLIDE) CRW_ROUTE("labelprop.slide_general_global");
   else CRW_ROUTE("labelprop.gather_global");
-  hipLaunchKernelGGL((labelprop_gather_kernel<SLIDE, ORG>), dim3(1), dim3(1024), 0, (hipStream_t)stream, seed, W, I, T, N, M, knn,
-                     first_frame, L, pred, cxt, origin);
+  hipLaunchKernelGGL((labelprop_gather_kernel<SLIDE, ORG, LM>), dim3(1), dim3(1024), 0, (hipStream_t)stream, seed, W, I, T, N, M, knn,
+                     first_frame, L, pred, cxt, origin_arg);
   return check_launch();
 }
 
@@ -1387,6 +1459,31 @@ int crw_labelprop_propagate_origin_batch(const float *seed, const float *W, cons
                                          crw_stream_t stream) {
   if (!origin) return launch_propagate_batch<true>(seed, W, I, i_stride, G, T, N, M, knn, first_frame, cxt_size, L, pred, stream);
   return launch_propagate_batch<true, true>(seed, W, I, i_stride, G, T, N, M, knn, first_frame, cxt_size, L, pred, stream, origin);
+}
+
+// ---- include/crw_hip_longmem.h: n_long long-term frames in place of frame 0 alone (the LM instances of the kernels above) ------
+int crw_labelprop_topk_long(const float *ehat, int T, int N, int C, int cxt_size, int n_long, int radius, float temp, int k, int first_frame,
+                            float *WV, int32_t *I, int raw, int route, crw_stream_t stream) {
+  if ((raw != 0 && raw != 1) || route < 0 || route > 2 || n_long < 1 || n_long > T - 1) return CRW_EINVAL;
+  return topk_grid(ehat, T, N, C, cxt_size, radius, temp, k, first_frame, 1, WV, I, raw, nullptr, stream, n_long, route);
+}
+
+int crw_labelprop_propagate_long(const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int cxt_size, int n_long,
+                                 float *L, float *pred, int route, crw_stream_t stream) {
+  crw::clear_stale_error();
+  if (bad_propagate_args(W, I, L, pred, T, N, M, knn, first_frame) || cxt_size < 1 || n_long < 1 || n_long > T - 1 || route < 0 || route > 2)
+    return CRW_EINVAL;
+  const long NM = (long)N * M, KN = (long)knn * N;
+  // the ring kernel where n_long long-term frames + cxt_size + 1 ring slots fit (the bound does not look at T: one condition per
+  // geometry); it keeps min(cxt_size + 1, T - n_long) ring slots.  The switch of crw_labelprop_propagate_sliding holds for route 0
+  const char *gen = getenv("CRW_LABELPROP_SLIDING_GENERAL");
+  const long R = cxt_size + 1 < T - n_long ? cxt_size + 1 : T - n_long;
+  const bool fits = chain_fits(knn, NM, KN, chain_lds((long)cxt_size + 1 + n_long, NM)) && (long)T * N < (1L << 30) / M;
+  if (route == 2 && !fits) return CRW_EINVAL;
+  const bool ring = route ? route == 2 : fits && !(gen && gen[0] == '1');
+  if (!ring) return launch_gather<true, false, true>(nullptr, W, I, T, N, M, knn, first_frame, cxt_size, L, pred, stream, nullptr, n_long);
+  return launch_chain<true>(nullptr, W, I, T, N, M, knn, first_frame, T - 1, cxt_size, (int)R, chain_lds(R + n_long, NM), L, pred, nullptr,
+                            (hipStream_t)stream, n_long);
 }
 
 int crw_labelprop_sweep_weights(const float *V, int F, int kcap, int N, const int *knns, int nk, float *W, crw_stream_t stream) {

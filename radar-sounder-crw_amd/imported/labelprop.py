@@ -26,6 +26,28 @@ ANCHORS_NEED_SLIDING = ("anchors need CONTEXT 'sliding': under the reference's i
                         "label later than frame CXT_SIZE, so an anchor there would change only itself")
 
 
+MEMORY_NEEDS_SLIDING = ("memory needs CONTEXT 'sliding': under the reference's index quirk a frame beyond CXT_SIZE + 1 never reads a "
+                        "label later than frame CXT_SIZE, so it would not read the bank's rows consistently")
+
+
+def check_memory(memory, N, nclasses, context, anchor_context='clamp'):
+    """The option checks of `memory=` (mem_feats [B, N, C] normalised features, mem_labels [B, N] class ids of B fully labelled
+    traces) -> (mem_feats, mem_labels int64)."""
+    if context != 'sliding':
+        raise ValueError(MEMORY_NEEDS_SLIDING)
+    if anchor_context != 'clamp':
+        raise ValueError("memory and anchor_context='restart' are not combined: a restart drops every long-term frame but its origin")
+    mem_feats, mem_labels = memory
+    if mem_feats.dim() != 3 or mem_feats.shape[0] < 1 or tuple(mem_labels.shape) != tuple(mem_feats.shape[:2]):
+        raise ValueError(f"memory must be (features [B >= 1, N, C], labels [B, N]) (got {tuple(mem_feats.shape)}, {tuple(mem_labels.shape)})")
+    if mem_feats.shape[1] != N:
+        raise ValueError(f"the bank's traces have {mem_feats.shape[1]} nodes, the item's {N}: a bank serves items of its own N")
+    labels = mem_labels.to(torch.int64)
+    if bool(((labels < 0) | (labels >= nclasses)).any()):
+        raise ValueError(f"the bank's traces must be fully labelled with classes in [0, {nclasses})")
+    return mem_feats, labels
+
+
 def restart_origin(anchor_context, anchors, context, T, N, nclasses):
     """The option checks of `anchor_context=` -> the origin array of 'restart' (`crw_hip.anchor_origins`; row 0 of the anchors is
     the seed's and restarts nothing more than frame 0 does), None under 'clamp'."""
@@ -98,9 +120,42 @@ class LabelPropVOS_CRW(object):
         crw_hip.labelprop_gather(None, Wt, It, n + 1, N, M, first_frame=n, L=L, cxt_size=self.cxt_size, context=self.context)
         return L[n * N:].reshape(N, M).t().reshape(1, M, h, w)
 
-    def propagate_all(self, feats, seed, nclasses, grid_w=1, anchors=None, anchor_context='clamp'):
+    def _propagate_memory(self, feats, seed, nclasses, grid_w, anchors, anchor_context, memory):
+        """`propagate_all(memory=)`: the virtual item [bank traces..., item], the bank's B frames (and the item's frame 0 when it is
+        seeded) long-term -- crw_labelprop_topk_long / crw_labelprop_propagate_long through `crw_hip.labelprop_topk(n_long=)` and
+        `labelprop_gather(n_long=)`.  The rows in front are one-hot; the item's part of pred and L is returned."""
+        T, N, C = feats.shape
+        mem_feats, labels = check_memory(memory, N, nclasses, self.context, anchor_context)
+        if grid_w != 1:
+            raise ValueError("memory is defined on N x 1 grids only")
+        B = mem_feats.shape[0]
+        front = labels if seed is None else torch.cat([labels, seed.to(labels.device).long()[None]])
+        K, F = front.shape[0], B + T
+        ehat = torch.cat([mem_feats.to(feats.dtype), feats]).contiguous()
+        self._check_grid(N, 1)
+        Wt, It = crw_hip.labelprop_topk(ehat, self.cxt_size, self.radius, self.temperature, self.topk, first_frame=K, n_long=K, route="auto")
+        if anchors is not None:
+            crw_hip.check_anchors(anchors, T, N, nclasses)
+            shifted = torch.cat([torch.full((B, N), -1, dtype=torch.int8, device=anchors.device), anchors])   # B frames further down
+            crw_hip.mark_anchors(Wt, It, shifted, nclasses, K)
+        L = torch.empty(F * N, nclasses, device=feats.device, dtype=torch.float32)
+        pred = torch.zeros(N, F, device=feats.device, dtype=torch.float32)
+        front = front.to(feats.device)
+        L[:K * N] = (front.reshape(-1, 1) == torch.arange(nclasses, device=feats.device)).to(L.dtype)
+        pred[:, :K] = front.t().to(pred.dtype)
+        crw_hip.labelprop_gather(None, Wt, It, F, N, nclasses, first_frame=K, L=L, pred=pred, cxt_size=self.cxt_size, context='sliding',
+                                 n_long=K, route="auto")
+        return pred[:, B:].contiguous(), L[B * N:]
+
+    def propagate_all(self, feats, seed, nclasses, grid_w=1, anchors=None, anchor_context='clamp', memory=None):
         """feats [T,N,C] (normalised features), seed [N] float class ids of frame 0
         -> (pred [N,T] float class ids, L [T*N, M] soft labels).  grid_w: the N nodes are an (N / grid_w) x grid_w grid.
+        memory (needs CONTEXT 'sliding', anchor_context 'clamp', an N x 1 grid): (mem_feats [B, N, C], mem_labels [B, N]) -- B fully
+        labelled traces from elsewhere (another item, another radargram), normalised features of the same encoder.  They are put in
+        front of the item as long-term frames: every frame scores against them and against its CXT_SIZE predecessors, and reads
+        their labels (include/crw_hip_longmem.h).  With a seed the item's frame 0 is one more long-term frame; seed=None (memory
+        only): the item's frame 0 is predicted from the bank alone and is an ordinary frame afterwards.  Anchors move B frames down
+        with the item.  The item's pred [N,T] and L [T*N, M] are returned, nothing of the bank's.  None: the call is what it was.
         anchor_context 'restart' (needs anchors): a frame whose N nodes are all anchored is as good as a seed -- every frame behind
         it is propagated as a frame of the item that starts there (`crw_hip.anchor_origins`, the `origin=` of `labelprop_topk` and
         `labelprop_gather`); 'clamp': the anchors clamp and the context is what it is without them.
@@ -110,6 +165,10 @@ class LabelPropVOS_CRW(object):
         (`crw_hip.mark_anchors`, no copy) and ONE crw_labelprop_propagate_sliding call follows; CRW_ANCHORS_SEGMENTED=1 (read per call)
         or a library without the marks: one launch per stretch between anchored frames (`crw_hip.labelprop_gather(anchors=)`)."""
         T, N, C = feats.shape
+        if memory is not None:
+            return self._propagate_memory(feats, seed, nclasses, grid_w, anchors, anchor_context, memory)
+        if seed is None:
+            raise ValueError("seed=None needs memory: without a bank nothing labels the item's first frame")
         origin = restart_origin(anchor_context, anchors, self.context, T, N, nclasses)
         if anchors is not None and self.context != 'sliding':
             raise ValueError(ANCHORS_NEED_SLIDING)

@@ -240,7 +240,7 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
 def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap, pos_embed=False,
             correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
             decode='argmax', order=None, posterior=False, floor=crw_hip.POSTERIOR_FLOOR, anchors=None, anchor_context='clamp', suggest=0, suggest_gap=2,
-            suggest_top=None):
+            suggest_top=None, memory=None, seedless=False):
     """dataset: RGDataset (full, overlapping items); seg: reference segmentation [rows, W_rg].
     -> dict(pred [rows, n_rg * rg_len] float labels after the optional reverse merge,
             forward: the forward (+ corrected) map the reference saves as int8 (test_all.py:128),
@@ -295,8 +295,33 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     score -- ``column`` is the frame's first pixel column, which `utils.anchor_nodes` maps back to that frame.  ``anchors`` are
     honoured: under 'restart' the keys start at the origins, and fully labelled frames are not proposed again, so labelling a
     pick and passing it as an anchor gives the next picks.  A pick is a place to look, not a detection: items in which nothing
-    new appears give z as large as a weak onset's.  Every other entry is bit for bit what it is without the option."""
+    new appears give z as large as a weak onset's.  Every other entry is bit for bit what it is without the option.
+    memory: None, a `utils.MemoryBank`, or (annot, cols) -- fully labelled traces from ELSEWHERE (`utils.bank_from_columns` cuts the
+    patch columns that start at the pixel columns ``cols`` of this dataset; a bank may as well come from another radargram or a
+    file).  Needs a label propagation under CONTEXT 'sliding'.  Every item of both passes is propagated with the same bank in front
+    of it as long-term frames (`utils.propagate(memory=)`: the bank's patches go through the encoder with the item); everything
+    downstream takes the soft labels as before.  Not together with anchor_context='restart' or ``suggest``.  The dict gains
+    ``memory_traces`` (the number of bank traces) and ``seedless``.
+    seedless (needs memory; not with ``correction``, which is a re-seed from ``seg``): no item is seeded from ``seg`` -- its first
+    frame is predicted from the bank like any other, and ``seg`` serves the geometry and the evaluation only."""
     _check_anchor_context(anchor_context, anchors)
+    bank = None
+    if seedless and memory is None:
+        raise ValueError("seedless=True needs memory: without a bank nothing labels an item's first frame")
+    if seedless and correction:
+        raise ValueError("seedless=True and correction=True do not combine: the correction is a re-seed from the ground truth")
+    if memory is not None:
+        from utils import MemoryBank, bank_from_columns
+        from imported.labelprop import MEMORY_NEEDS_SLIDING
+        if getattr(lp, 'context', None) != 'sliding' or not hasattr(lp, 'propagate_all'):
+            raise ValueError(MEMORY_NEEDS_SLIDING)
+        if anchor_context != 'clamp':
+            raise ValueError("memory and anchor_context='restart' do not combine: a restart drops every long-term frame but its origin")
+        if suggest:
+            raise ValueError("memory and suggest do not combine: the novelty kernel scores against frame 0 and the window, not the bank")
+        bank = memory if isinstance(memory, MemoryBank) else bank_from_columns(dataset, *memory)
+        if bank.nodes != dataset[0].shape[1]:
+            raise ValueError(f"the bank's traces have {bank.nodes} nodes, the items {dataset[0].shape[1]}: a bank serves items of its own N")
     if int(suggest) < 0 or int(suggest_gap) < 0:
         raise ValueError(f"suggest and suggest_gap must be >= 0 (got {suggest}, {suggest_gap})")
     if suggest and not hasattr(lp, 'novelty'):
@@ -309,6 +334,8 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     extra = dict(decode=decode, order=order) if order else {}
     if posterior:
         extra['floor'] = float(floor)
+    if bank is not None:
+        extra.update(memory_traces=len(bank), seedless=bool(seedless))
     if upsample == 'bilinear':
         kw = dict(soft=True)
 
@@ -329,6 +356,9 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
 
     def run(seq, seg_ref, last, novelty=False, **anch):
         nkw = dict(novelty=True, novelty_top=suggest_top) if novelty else {}
+        if bank is not None:  # the same bank in front of every item of both passes; seedless: `seg` seeds nothing
+            nkw.update(memory=bank)
+            seg_ref = None if seedless else seg_ref
         res = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=last, **kw, **anch, **nkw)
         if novelty:  # taken out again: the writers read the tuple by position
             at = 4 if 'confidence' in kw else 3
@@ -374,7 +404,7 @@ def _suggested(novs, cxt_size, budget, gap, N, nclasses, seq_length, patch_size,
 @torch.no_grad()
 def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size, overlap, pos_embed=False,
                   correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
-                  decode='argmax', order=None, anchors=None, anchor_context='clamp', **posterior_options):
+                  decode='argmax', order=None, anchors=None, anchor_context='clamp', memory=None, **posterior_options):
     """`segment` for every configuration of ``sweep`` (LabelPropSweep, G = len(sweep.configs)) with its control flow run ONCE:
     which items are corrected, at which length (`get_smaller_item` and its permanent shortening of the dataset) and what the
     reverse pass sees depend on the features alone, never on (radius, temp, knn).  Same exception policy in the correction.
@@ -403,7 +433,11 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     anchors: `segment`'s -- None, or (annot, cols), labelled traces inside the radargrams (needs a ``sweep`` under context
     'sliding'); the same anchors in both passes and for all G configurations, the reverse pass mirrored, not together with
     ``correction``; the dict gains ``anchor_cols``.  Slice g stays `segment`'s for ``sweep.configs[g]`` under the same anchors.
-    anchor_context: `segment`'s, one set of origins for the G configurations."""
+    anchor_context: `segment`'s, one set of origins for the G configurations.
+    memory: refused -- a bank of long-term frames is `segment`'s; the batch kernels keep frame 0 alone."""
+    if memory is not None:
+        raise ValueError("memory is not offered in segment_sweep: the batch kernels keep frame 0 alone as the long-term frame; "
+                         "run `segment` per configuration")
     _check_anchor_context(anchor_context, anchors)
     if anchors is not None and correction:
         raise ValueError("anchors and correction=True do not combine: the correction is itself a re-seed (at the change point), and "

@@ -42,7 +42,12 @@ fully labelled anchor trace restarts the propagation context like a seed (``infe
 more line says how many of the anchored traces are such origins, ``--report_json`` gains ``anchor_context``; ``--suggest_anchors K``
 (``--suggest_gap G``, ``--suggest_top R``): a fixed-width table after the report -- item, frame, columns, z, score -- of the K traces
 per radargram whose labelling the context novelty of the forward pass suggests next (``inference.segment(..., suggest=K)``; places to
-look, not detections), ``--report_json`` gains ``suggested_anchors``.  Without these flags the output is what it was.
+look, not detections), ``--report_json`` gains ``suggested_anchors``; ``--memory_cols X [X ...]`` (with ``--context sliding``): a
+memory bank -- the patch columns that start at those pixel columns, fully labelled from the reference map, stand in front of EVERY
+item as long-term frames (``inference.segment(memory=)``; one line says how many traces the bank holds); ``--memory_bank FILE``: a
+bank saved earlier, e.g. from another radargram, ``--save_memory_bank FILE`` writes the one in use; ``--seedless`` (needs a bank):
+no item is seeded from the reference map, which then serves the report alone; ``--report_json`` gains ``memory_traces`` and
+``seedless``.  Without these flags the output is what it was.
 Differences from the scripts:
   * plots are not drawn;
   * true / false flags read true / false (the scripts take any given string as true); ``--patch_size`` takes two numbers;
@@ -140,6 +145,11 @@ def get_args_parser():
     p.add_argument('--suggest_gap', default=None, type=int, metavar='G', help='no two suggestions within G frames of each other (2)')
     p.add_argument('--suggest_top', default=None, type=int, metavar='R',
                    help="a frame's score averages its R most novel nodes (a quarter of the nodes)")
+    p.add_argument('--memory_cols', default=None, nargs='+', type=int, metavar='X',
+                   help='memory bank: the patch columns that start at these pixel columns, labelled from the reference map')
+    p.add_argument('--memory_bank', default=None, metavar='FILE', help='memory bank: one saved with --save_memory_bank')
+    p.add_argument('--save_memory_bank', default=None, metavar='FILE', help='write the memory bank in use (.npz)')
+    p.add_argument('--seedless', action='store_true', help='seed no item from the reference map (needs a memory bank)')
     return p
 
 
@@ -147,6 +157,28 @@ HORIZON_FLAGS = ('horizons', 'min_run', 'tol', 'row_spacing', 'row_unit', 'save_
 POSTERIOR_FLAGS = ('posterior', 'floor', 'save_posterior')
 ANCHOR_FLAGS = ('anchors', 'anchor_every', 'anchor_context')
 SUGGEST_FLAGS = ('suggest_anchors', 'suggest_gap', 'suggest_top')
+MEMORY_FLAGS = ('memory_cols', 'memory_bank', 'save_memory_bank', 'seedless')
+
+
+def check_memory_flags(args):
+    """The flags ``--memory_cols``, ``--memory_bank``, ``--save_memory_bank`` and ``--seedless`` -> is there a bank?"""
+    cols, path = getattr(args, 'memory_cols', None), getattr(args, 'memory_bank', None)
+    if cols is None and path is None:
+        if getattr(args, 'seedless', False) or getattr(args, 'save_memory_bank', None) is not None:
+            raise SystemExit('--seedless and --save_memory_bank need --memory_cols or --memory_bank')
+        return False
+    if cols is not None and path is not None:
+        raise SystemExit('--memory_cols and --memory_bank: one of the two')
+    if args.context != 'sliding':
+        raise SystemExit('--memory_cols / --memory_bank need --context sliding (under the reference rule a late frame never reads a '
+                         "label later than frame cxt_size, so it would not read the bank's rows consistently)")
+    if args.single:
+        raise SystemExit('--memory_cols / --memory_bank are not available with --single')
+    if getattr(args, 'anchor_context', None) == 'restart' or getattr(args, 'suggest_anchors', None) is not None:
+        raise SystemExit('--memory_cols / --memory_bank do not combine with --anchor_context restart or --suggest_anchors')
+    if args.seedless and args.correction:
+        raise SystemExit('--seedless and --correction do not combine: the correction is a re-seed from the reference map')
+    return True
 
 
 def check_suggest_flags(args):
@@ -340,6 +372,9 @@ def main(args):
         hidden += ('anchor_context',)
     if suggest is None:  # likewise
         hidden += SUGGEST_FLAGS
+    banked = check_memory_flags(args)
+    if not banked:  # likewise
+        hidden += MEMORY_FLAGS
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -366,6 +401,13 @@ def main(args):
         anchors = load_anchors(args, seg, rg_len) if anchored else None
         if anchored:
             print('Anchored traces:', len(anchors[1]))
+        bank = None
+        if banked:
+            import utils
+            bank = utils.MemoryBank.load(args.memory_bank) if args.memory_bank else utils.bank_from_columns(dataset, seg.cpu(), args.memory_cols)
+            print('Memory bank traces:', len(bank), '(no item is seeded)' if args.seedless else '')
+            if args.save_memory_bank:
+                bank.save(args.save_memory_bank)
         out = inference.segment(dataset, seg, encoder, lp, nclasses, T, args.patch_size, args.overlap, pos_embed=args.pos_embed,
                                 correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device,
                                 **(dict(confidence=args.confidence, merge=args.merge) if args.confidence else {}),
@@ -374,6 +416,7 @@ def main(args):
                                 **(dict(posterior=True, floor=args.floor) if args.posterior else {}),
                                 **(dict(anchors=anchors) if anchored else {}),
                                 **(dict(anchor_context=anchor_context) if anchor_context else {}),
+                                **(dict(memory=bank, seedless=args.seedless) if banked else {}),
                                 **(dict(suggest=suggest, suggest_gap=args.suggest_gap, suggest_top=args.suggest_top) if suggest else {}))
         if out.get('anchor_context') == 'restart':
             print('Origin traces:', out['origin_traces'], 'of the anchored traces (anchor_context restart)')
@@ -456,6 +499,8 @@ def main(args):
                     d['anchors']['origin_traces'] = out['origin_traces']
         if pcal is not None:
             d['posterior'] = dict(floor=args.floor, calibration=pcal.to_dict(), horizon_bars=bars.to_dict())
+        if banked:
+            d.update(memory_traces=out['memory_traces'], seedless=out['seedless'])
         if suggest:
             d['suggested_anchors'] = dict(per_radargram=suggest, min_gap=args.suggest_gap, top=args.suggest_top,
                                           picks=[dict(p, columns=list(p['columns'])) for picks in out['suggested'] for p in picks])

@@ -94,6 +94,62 @@ def anchor_nodes(annot, cols, rg_len, T, N, rg_h, step_w):
     return out
 
 
+class MemoryBank(object):
+    """Fully labelled traces from elsewhere -- another item, another radargram -- for `propagate(memory=)`: patches [B, N, h, w]
+    float32 (a trace is one patch column, what a frame of an item is) and labels [B, N] int8, one class per node.  `memory_bank`
+    makes one from tensors, `bank_from_columns` cuts one out of an annotated dataset; `save` / `load` keep it in an .npz file."""
+
+    def __init__(self, patches, labels):
+        self.patches, self.labels = patches, labels
+
+    def __len__(self):
+        return self.patches.shape[0]
+
+    @property
+    def nodes(self):
+        return self.patches.shape[1]
+
+    def save(self, path):
+        import numpy as np
+        np.savez(path, patches=self.patches.cpu().numpy(), labels=self.labels.cpu().numpy())
+
+    @staticmethod
+    def load(path):
+        import numpy as np
+        g = np.load(path)
+        return memory_bank(torch.from_numpy(g["patches"]), torch.from_numpy(g["labels"]))
+
+
+def memory_bank(traces, labels):
+    """traces [B, N, h, w] (patch columns as `dataset` cuts them), labels [B, N] int8 -> MemoryBank.  Fully labelled traces only:
+    a negative label is refused (partially labelled traces belong inside their item, as anchors)."""
+    traces, labels = torch.as_tensor(traces), torch.as_tensor(labels)
+    if traces.dim() != 4 or traces.shape[0] < 1 or labels.dtype != torch.int8 or tuple(labels.shape) != tuple(traces.shape[:2]):
+        raise ValueError(f"a memory bank is traces [B >= 1, N, h, w] and labels [B, N] int8 (got {tuple(traces.shape)}, "
+                         f"{labels.dtype} {tuple(labels.shape)})")
+    if bool((labels < 0).any()):
+        raise ValueError("a memory bank holds fully labelled traces only: every node needs a class >= 0")
+    return MemoryBank(traces.float().contiguous(), labels.contiguous())
+
+
+def bank_from_columns(dataset, annot, cols):
+    """The bank of the patch columns that START at the pixel columns `cols` of an RGDataset's radargram (a start is clipped so that
+    the column of patches fits the width), cut as the dataset cuts its frames and labelled from annot [rows, width] at the start
+    column itself by the row rule of `seed_labels`: node n takes annot[floor(n * rg_h / N), x], rg_h the rows the N nodes span."""
+    image, annot = dataset.T, torch.as_tensor(annot)
+    h, w, oh, N, rg_h = dataset.h, dataset.w, dataset.oh, dataset.nh, dataset.nh * (dataset.h - dataset.oh) + dataset.oh
+    width = min(image.shape[-1], annot.shape[-1])
+    xs = [min(max(int(c), 0), width - w) for c in cols]
+    if not xs:
+        raise ValueError("a memory bank needs at least one column")
+    traces = torch.stack([torch.stack([image[n * (h - oh):n * (h - oh) + h, x:x + w] for n in range(N)]) for x in xs])
+    node_rows = torch.div(torch.arange(N) * rg_h, N, rounding_mode='floor')
+    vals = annot[node_rows][:, xs].to(torch.int64).t()
+    if int(vals.max()) > 127:
+        raise ValueError(f"the annotated columns hold class {int(vals.max())}: bank labels are int8")
+    return memory_bank(traces, vals.to(torch.int8))
+
+
 def column_diffs_async(xent):
     """|xent[:, i] - xent[:, i+1]| summed over the nodes (src/utils.py:125), copied to pinned host memory WITHOUT
     blocking: -> (host tensor, event).  Lets the caller queue more GPU work before the host needs the values."""
@@ -127,23 +183,32 @@ def change_point(xent, diffs=None):
         return None
 
 
-def _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last):
+def _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last, memory=None):
     """The front of `propagate` / `propagate_sweep`: ONE encoder call on the whole item (the batch matters for the `Resnet`, whose
-    train-mode BatchNorm statistics are the batch's), normalised features [T,N,C] and the seed labels [N]."""
+    train-mode BatchNorm statistics are the batch's), normalised features [T,N,C] and the seed labels [N].
+    memory (a MemoryBank): its B * N patches go through the SAME encoder call, in front of the item's -- one BatchNorm batch in
+    train mode -- and the result gains the bank's features [B,N,C]; seg_ref None: no seed (None)."""
     T, N, H, W = seq.shape
+    if memory is None and seg_ref is None:
+        raise ValueError("seg_ref=None (no seed) needs memory: without a bank nothing labels the item's first frame")
     if use_last:
         seq = torch.flip(seq, (0,))
+    B = 0 if memory is None else len(memory)
+    if B:
+        seq = torch.cat([memory.patches.to(device=seq.device, dtype=seq.dtype), seq])
     x = seq.reshape(-1, H, W).unsqueeze(1)
     if do_pos_embed:
         x = pos_embed(x)
-    emb = model(x).reshape(T, N, -1).float().contiguous()
+    emb = model(x).reshape(B + T, N, -1).float().contiguous()
     feats = crw_hip.normalize(emb)
-    return feats, seed_labels(seg_ref.to(feats.device), N)
+    if memory is None:
+        return feats, seed_labels(seg_ref.to(feats.device), N)
+    return feats[B:], (None if seg_ref is None else seed_labels(seg_ref.to(feats.device), N)), feats[:B]
 
 
 @torch.no_grad()
 def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False, anchors=None,
-              anchor_context='clamp', novelty=False, novelty_top=None):
+              anchor_context='clamp', novelty=False, novelty_top=None, memory=None):
     """seq [T,N,h,w]; seg_ref [rows, w] class ids of the first (or last) frame; model: encoder;
     lp: LabelPropVOS_CRW  ->  (labels [N,T] float, xent [N,T-1] (CPU), change_idx | None).
 
@@ -163,7 +228,24 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, conf
     device, frames in the pass's own order -- `lp.novelty` on the SAME features (the encoder does not run again), under the pass's
     anchors and anchor_context; column / entry 0 (the seed frame has no keys) is 0.  novelty_top: how many of a frame's largest
     node novelties its score averages (None: max(1, N // 4)).  What `crw_hip.suggest_frames` reads.  The labels do not depend on
-    it."""
+    it.
+    memory: None, or a `MemoryBank` of B fully labelled traces from elsewhere (needs CONTEXT 'sliding', anchor_context 'clamp', no
+    novelty): its patches are encoded in the same encoder call as the item and stand in front of it as long-term frames
+    (``lp.propagate_all(memory=)``).  With a bank ``seg_ref`` may be None: the item has no seed, its first frame is predicted from
+    the bank alone and its confidence is that of any other frame.  Everything returned is the item's, as without a bank."""
+    if memory is not None:
+        if not hasattr(lp, 'propagate_all'):
+            raise ValueError("memory needs a label propagation with `propagate_all` (LabelPropVOS_CRW)")
+        if novelty:
+            raise ValueError("memory and novelty (suggest) are not combined: the novelty kernel scores against frame 0 and the window")
+        if anchor_context != 'clamp':
+            raise ValueError("memory and anchor_context='restart' are not combined: a restart drops every long-term frame but its origin")
+        if getattr(lp, 'context', None) != 'sliding':
+            from imported.labelprop import MEMORY_NEEDS_SLIDING
+            raise ValueError(MEMORY_NEEDS_SLIDING)
+        if memory.nodes != seq.shape[1] or tuple(memory.patches.shape[2:]) != tuple(seq.shape[2:]):
+            raise ValueError(f"the bank's traces are {tuple(memory.patches.shape[1:])} (nodes, h, w), the item's frames "
+                             f"{tuple(seq.shape[1:])}: a bank serves items of its own N and patch size")
     if confidence is not None and confidence not in crw_hip.CONF_KINDS:
         raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
     T, N, H, W = seq.shape
@@ -180,7 +262,14 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, conf
             raise ValueError("novelty needs a label propagation with `propagate_all` and `novelty` (LabelPropVOS_CRW): a foreign "
                              "object's frame-by-frame protocol does not say which keys a frame scores against")
         crw_hip.novelty_top(N, novelty_top)
-    feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
+    mkw = {}
+    if memory is None:
+        feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
+    else:
+        feats, seed, mem_feats = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last, memory)
+        mkw = dict(memory=(mem_feats, memory.labels.to(feats.device)))
+        if T == 1 and seed is None:
+            raise ValueError("a one-frame item without a seed has nothing to propagate from")
     if T == 1:  # a one-frame item (the correction step of test_all.py can ask for it): nothing to propagate, like the reference
         out = (seed[:, None].clone(), torch.zeros(N, 0), None)
         if confidence is not None:
@@ -195,9 +284,9 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, conf
     if anchors is not None:
         a = anchors.to(torch.int8)  # left where it is: from the host (`anchor_nodes`) the frames are found without a device read
         ckw = {} if anchor_context == 'clamp' else dict(anchor_context=anchor_context)
-        pred, L = lp.propagate_all(feats, seed, nclasses, anchors=(torch.flip(a, (0,)) if use_last else a).contiguous(), **ckw)
+        pred, L = lp.propagate_all(feats, seed, nclasses, anchors=(torch.flip(a, (0,)) if use_last else a).contiguous(), **ckw, **mkw)
     elif hasattr(lp, 'propagate_all'):
-        pred, L = lp.propagate_all(feats, seed, nclasses)
+        pred, L = lp.propagate_all(feats, seed, nclasses, **mkw)
     else:  # foreign label-propagation object: reference's frame-by-frame protocol
         pred = torch.zeros(N, T, device=feats.device)
         pred[:, 0] = seed
