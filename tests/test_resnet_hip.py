@@ -350,7 +350,7 @@ def test_resnet_hip_matches_pytorch_modules(hip, monkeypatch, pos_embed, P, path
     path "bf16x3" = the whole pass from native code (crw_rn_train_fwd / _bwd, what training uses), "stepwise" = the same
     kernels launched one by one from Python (resnet_hip.HipResnetFn).  Patch sizes: 16x16 (patch-per-wave stem, 1x1 final map),
     32x32 (the reference's cfg5 encoder input, scripts/test/test_mc1.py:19: gathered stem, 2x2 final map -> the average pool +
-    head as one product over the map), 20x27 (stem rows over two column tiles, 1x1 final map), 40x64 (3x4 final map).
+    head as one product over the map), 20x27 (stem rows over two column tiles, 1x1 final map), 40x64 (2x3 final map: `resnet_hip.final_map(40, 64)`).
 
     Two references.  FREE-RUNNING fp64 modules: features, running statistics, and direction + norm of every gradient (an fp32-grade
     forward and an fp64 one may pick different arg-max pixels / ReLU gates where two candidates differ by less than ~1e-5, which
