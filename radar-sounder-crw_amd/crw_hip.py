@@ -174,6 +174,13 @@ LONGMEM_SIGNATURES = {
     "crw_labelprop_propagate_long": (_c_int, [_p, _p] + [_c_int] * 7 + [_p, _p, _c_int, _p]),
 }
 
+# include/crw_hip_align.h, likewise: a bank aligned to its item -- segment-centred features, a bias on the long-term keys (optional: `has_align()`)
+ALIGN_SIGNATURES = {
+    "crw_center_normalize_ws_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
+    "crw_center_normalize": (_c_int, [_p, _c_int, _c_int, _p, _p, _c_int, _p, _c_sz, _p, _p, _p]),
+    "crw_labelprop_topk_long_bias": (_c_int, [_p] + [_c_int] * 6 + [_c_f, _c_int, _c_int, _p, _p, _c_int, _c_int, _c_f, _p]),
+}
+
 # include/crw_hip_routes.h, likewise: the route log -- which selector branch launched (optional: `has_routes()`; host pointers)
 ROUTES_SIGNATURES = {
     "crw_routes_clear": (_c_int, []),
@@ -226,6 +233,9 @@ NOVELTY_ENTRY_POINTS = tuple(NOVELTY_SIGNATURES)
 # likewise: the sliding rule with a bank of long-term frames (`has_long_memory()`, `labelprop_topk(n_long=)`)
 LONG_MEMORY_ENTRY_POINTS = tuple(LONGMEM_SIGNATURES)
 
+# likewise: segment-centred normalisation and the biased long-memory lists (`has_align()`, `center_normalize`, `labelprop_topk(long_bias=)`)
+ALIGN_ENTRY_POINTS = tuple(ALIGN_SIGNATURES)
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 ANCHOR_CONTEXTS = ("clamp", "restart")  # what a fully labelled anchor trace does to the frames behind it
 
@@ -236,7 +246,8 @@ OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_E
                          "sliding": SLIDING_ENTRY_POINTS, "ordered": ORDERED_ENTRY_POINTS, "joint": JOINT_ENTRY_POINTS,
                          "posterior": POSTERIOR_ENTRY_POINTS, "posterior_batch": POSTERIOR_BATCH_ENTRY_POINTS,
                          "conv_chain": CONV_CHAIN_ENTRY_POINTS, "anchor_restart": ANCHOR_RESTART_ENTRY_POINTS,
-                         "routes": ROUTES_ENTRY_POINTS, "novelty": NOVELTY_ENTRY_POINTS, "long_memory": LONG_MEMORY_ENTRY_POINTS}
+                         "routes": ROUTES_ENTRY_POINTS, "novelty": NOVELTY_ENTRY_POINTS, "long_memory": LONG_MEMORY_ENTRY_POINTS,
+                         "align": ALIGN_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -253,7 +264,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         missing = {n for names in OPTIONAL_ENTRY_POINTS.values() for n in names if not hasattr(handle, n)}
         for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES, **RESTART_SIGNATURES, **ROUTES_SIGNATURES,
-                                   **NOVELTY_SIGNATURES, **LONGMEM_SIGNATURES}.items():
+                                   **NOVELTY_SIGNATURES, **LONGMEM_SIGNATURES, **ALIGN_SIGNATURES}.items():
             if name in missing:
                 continue
             fn = getattr(handle, name)
@@ -301,6 +312,7 @@ has_anchor_restart, _anchor_restart_lib = _optional("anchor_restart", "the entry
 has_routes, _routes_lib = _optional("routes", "the route log's entry points")
 has_novelty, _novelty_lib = _optional("novelty", "the context-novelty entry point")
 has_long_memory, _long_memory_lib = _optional("long_memory", "the entry points that take n_long long-term frames")
+has_align, _align_lib = _optional("align", "the segment-centred normalisation and the biased long-memory lists")
 
 MAX_ROUTES = 256  # csrc/crw_common.h
 
@@ -459,6 +471,60 @@ def normalize(emb):
     return ehat
 
 
+MEMORY_ALIGNS = (None, "center")  # `memory_align=`: how a bank's features are brought to its item's
+
+
+def check_memory_align(memory_align):
+    if memory_align not in MEMORY_ALIGNS:
+        raise ValueError(f"memory_align must be None or 'center' (got {memory_align!r})")
+    return memory_align
+
+
+def check_memory_bias(memory_bias):
+    """`memory_bias=` -> float(memory_bias); a bias that is not finite is refused (include/crw_hip_align.h)"""
+    b = float(memory_bias)
+    if b != b or b in (float("inf"), float("-inf")):
+        raise ValueError(f"memory_bias must be a finite number (got {memory_bias!r})")
+    return b
+
+
+def center_normalize(emb, segments, return_mean=False):
+    """emb [..., C] raw features, rows = emb.numel() / C; segments: the row offsets [0, ..., rows] of S = len - 1 segments of
+    consecutive rows (a sequence of ints: they travel by value, S <= 8; or an int32 tensor on emb's device).  Every segment is
+    centred by its own per-channel mean (fp64 sums, the subtraction rounded once to fp32) and then L2-normalised as `normalize`
+    does -- crw_center_normalize (include/crw_hip_align.h).  A one-row segment becomes the all-zero row.  -> ehat like emb
+    (return_mean: (ehat, mean [S, C] float64)).  CPU tensors: the same definition in torch."""
+    C = emb.shape[-1]
+    rows = emb.numel() // C
+    on_dev = torch.is_tensor(segments)
+    S = (segments.numel() if on_dev else len(segments)) - 1
+    if not emb.is_cuda:
+        b = [int(x) for x in (segments.tolist() if on_dev else segments)]
+        if S < 1 or b[0] != 0 or b[-1] != rows or any(y < x for x, y in zip(b, b[1:])):
+            raise ValueError(f"segments must be row offsets 0 = b_0 <= ... <= b_S = {rows} (got {b})")
+        x = emb.reshape(rows, C).to(torch.float64)
+        mean = torch.zeros(S, C, dtype=torch.float64)
+        y = torch.empty(rows, C, dtype=torch.float32)
+        for s in range(S):
+            if b[s + 1] > b[s]:
+                mean[s] = x[b[s]:b[s + 1]].sum(0) / (b[s + 1] - b[s])
+                y[b[s]:b[s + 1]] = (x[b[s]:b[s + 1]] - mean[s]).to(torch.float32)
+        ehat = (y / y.pow(2).sum(-1, keepdim=True).sqrt().clamp_min(1e-12)).reshape(emb.shape)
+        return (ehat, mean) if return_mean else ehat
+    handle = _align_lib()
+    nbytes = handle.crw_center_normalize_ws_bytes(rows, C, S)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=emb.device)
+    ehat = torch.empty_like(emb)
+    mean = torch.empty(max(S, 1), C, dtype=torch.float64, device=emb.device) if return_mean else None
+    if on_dev:
+        seg_dev, seg_host = _dev(segments, "segments", torch.int32), None
+    else:
+        seg_dev, seg_host = None, (ctypes.c_int32 * (S + 1))(*[int(x) for x in segments])
+    _check(handle.crw_center_normalize(_dev(emb, "emb"), rows, C, seg_dev, seg_host, S, ctypes.c_void_p(ws.data_ptr()), nbytes, _dev(ehat, "ehat"),
+                                       None if mean is None else ctypes.c_void_p(mean.data_ptr()), _stream()), "crw_center_normalize")
+    return (ehat, mean) if return_mean else ehat
+
+
 def check_anchor_context(anchor_context):
     if anchor_context not in ANCHOR_CONTEXTS:
         raise ValueError(f"anchor_context must be one of {ANCHOR_CONTEXTS} (got {anchor_context!r})")
@@ -556,29 +622,37 @@ def check_n_long(n_long, T, first_frame, origin=None, grid_w=1):
     return n_long
 
 
-def _topk_long(ehat, cxt_size, n_long, radius, temp, k, first_frame, WV, I, raw, route, origin=None, grid_w=1):
+def _topk_long(ehat, cxt_size, n_long, radius, temp, k, first_frame, WV, I, raw, route, origin=None, grid_w=1, long_bias=None):
     if origin is not None or grid_w != 1:
         raise ValueError("route= goes through crw_labelprop_topk_long: N x 1 grids, no origin")
     T, N, C = ehat.shape
+    if long_bias is not None:  # include/crw_hip_align.h: the same call with the bias on the long-term keys
+        _check(_align_lib().crw_labelprop_topk_long_bias(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(n_long), int(radius), float(temp),
+                                                         int(k), int(first_frame), _dev(WV, "WV"), _dev(I, "I", torch.int32), int(raw),
+                                                         LONG_ROUTES.get(route, route), check_memory_bias(long_bias), _stream()),
+               "crw_labelprop_topk_long_bias")
+        return WV, I
     _check(_long_memory_lib().crw_labelprop_topk_long(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(n_long), int(radius), float(temp),
                                                       int(k), int(first_frame), _dev(WV, "WV"), _dev(I, "I", torch.int32), int(raw),
                                                       LONG_ROUTES.get(route, route), _stream()), "crw_labelprop_topk_long")
     return WV, I
 
 
-def labelprop_topk(ehat, cxt_size, radius, temp, knn, first_frame=1, grid_w=1, origin=None, n_long=1, route=None):
+def labelprop_topk(ehat, cxt_size, radius, temp, knn, first_frame=1, grid_w=1, origin=None, n_long=1, route=None, long_bias=None):
     """grid_w: the N nodes of a frame form an (N / grid_w) x grid_w grid (1 = a radargram's column of patches).
     origin ([T] int32, `anchor_origins`): frame n scores against frame origin[n] and the frames between it and n only, as frame
     n - origin[n] of the item that starts there (include/crw_hip_restart.h); None: every frame scores from frame 0.
     n_long: the first n_long frames of ehat are long-term -- every frame scores against them and the cxt_size frames before it
     (include/crw_hip_longmem.h, crw_labelprop_topk_long; N x 1 grids, no origin).  1 with route None: frame 0 alone, the call as it
-    has always been.  route (a key of LONG_ROUTES; tests and timing): crw_labelprop_topk_long on that route, at n_long = 1 as well."""
+    has always been.  route (a key of LONG_ROUTES; tests and timing): crw_labelprop_topk_long on that route, at n_long = 1 as well.
+    long_bias (a finite float; None: no such call): crw_labelprop_topk_long_bias (include/crw_hip_align.h) -- the number is added to
+    the cosine of the in-band keys of the long-term frames before the division by temp; 0.0 gives crw_labelprop_topk_long's bits."""
     T, N, C = ehat.shape
     n_long = check_n_long(n_long, T, first_frame, origin, grid_w)
     W = torch.empty(T - first_frame, knn, N, device=ehat.device, dtype=torch.float32)
     I = torch.empty(T - first_frame, knn, N, device=ehat.device, dtype=torch.int32)
-    if n_long > 1 or route is not None:
-        return _topk_long(ehat, cxt_size, n_long, radius, temp, knn, first_frame, W, I, 0, route or "auto", origin, grid_w)
+    if n_long > 1 or route is not None or long_bias is not None:
+        return _topk_long(ehat, cxt_size, n_long, radius, temp, knn, first_frame, W, I, 0, route or "auto", origin, grid_w, long_bias)
     if origin is not None:
         return _topk_origin(ehat, cxt_size, radius, temp, knn, first_frame, grid_w, W, I, 0, origin)
     _check(lib().crw_labelprop_topk_grid(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(radius), float(temp), int(knn),
@@ -801,10 +875,12 @@ def labelprop_gather(seed, W, I, T, N, M, first_frame=1, L=None, pred=None, cxt_
     return L, pred
 
 
-def labelprop_topk_scores(ehat, cxt_size, radius, temp, kcap, first_frame=1, grid_w=1, out=None, origin=None, n_long=1, route=None):
+def labelprop_topk_scores(ehat, cxt_size, radius, temp, kcap, first_frame=1, grid_w=1, out=None, origin=None, n_long=1, route=None,
+                          long_bias=None):
     """`labelprop_topk` with the selected logits V [T-first_frame, kcap, N] instead of their softmax weights (empty slot -inf), and
     the same I: the lists of every knn <= kcap are their first knn entries (`labelprop_sweep_weights` makes the weights).
-    out: (V, I) tensors of those shapes to write into.  origin, n_long, route: as in `labelprop_topk`."""
+    out: (V, I) tensors of those shapes to write into.  origin, n_long, route, long_bias: as in `labelprop_topk` (the logits
+    include the bias)."""
     T, N, C = ehat.shape
     n_long = check_n_long(n_long, T, first_frame, origin, grid_w)
     if out is not None:
@@ -814,8 +890,8 @@ def labelprop_topk_scores(ehat, cxt_size, radius, temp, kcap, first_frame=1, gri
     else:
         V = torch.empty(T - first_frame, kcap, N, device=ehat.device, dtype=torch.float32)
         I = torch.empty(T - first_frame, kcap, N, device=ehat.device, dtype=torch.int32)
-    if n_long > 1 or route is not None:
-        return _topk_long(ehat, cxt_size, n_long, radius, temp, kcap, first_frame, V, I, 1, route or "auto", origin, grid_w)
+    if n_long > 1 or route is not None or long_bias is not None:
+        return _topk_long(ehat, cxt_size, n_long, radius, temp, kcap, first_frame, V, I, 1, route or "auto", origin, grid_w, long_bias)
     if origin is not None:
         return _topk_origin(ehat, cxt_size, radius, temp, kcap, first_frame, grid_w, V, I, 1, origin)
     _check(_sweep_lib().crw_labelprop_topk_scores(_dev(ehat, "ehat"), T, N, C, int(cxt_size), int(radius), float(temp), int(kcap),

@@ -15,6 +15,7 @@
 #include "crw_common.h"
 #include "crw_hip_restart.h"
 #include "crw_hip_longmem.h"
+#include "crw_hip_align.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -35,8 +36,12 @@ __device__ inline int frame_origin(const int32_t *origin, int n) { return min(ma
 // n - cxt .. n - 1.  K = 1 is the other instances' arithmetic; they keep their own text, so their instruction streams stay.
 // The number K travels in the place of the origin pointer, which an LM instance does not have: one 8-byte kernel argument either way,
 // so the other instances keep their argument layout as well (the hidden arguments, blockDim among them, follow the last one).
+// LB (crw_labelprop_topk_long_bias, include/crw_hip_align.h; LM instances only): `bias` is added to the cosine of the in-band keys at
+// list positions p < K -- the long-term part; p < nf <= n, so that is p < min(n, K) -- by one rounded add in front of the division
+// by temp.  It travels in the padding of the same 8-byte argument, which the other instances do not read.
 struct LongFrames {
-  int n, pad;
+  int n;
+  float bias;
 };
 template <bool LM>
 using OriginArg = std::conditional_t<LM, LongFrames, const int32_t *__restrict__>;
@@ -50,7 +55,7 @@ __device__ __forceinline__ int origin_at(Arg origin, int n) {
   if constexpr (ORG) return frame_origin(origin, n);
   else return 0;
 }
-template <bool ORG, bool LM>
+template <bool ORG, bool LM, bool LB = false>
 __global__ __launch_bounds__(256) void labelprop_topk_kernel(const float *__restrict__ ehat, int T, int N, int C,
                                                              int cxt, int radius, float temp, int knn,
                                                              int first_frame, int gw, float *__restrict__ W,
@@ -101,7 +106,12 @@ __global__ __launch_bounds__(256) void labelprop_topk_kernel(const float *__rest
     d += __shfl_xor(d, 4);
     d += __shfl_xor(d, 2);
     d += __shfl_xor(d, 1);
-    if (sub == 0) val[cand] = inside ? d / temp : -INFINITY;
+    if constexpr (LB) {
+      static_assert(LM, "the bias is the long-term keys'");
+      if (sub == 0) val[cand] = inside ? (p < K ? __fadd_rn(d, origin.bias) : d) / temp : -INFINITY;
+    } else {
+      if (sub == 0) val[cand] = inside ? d / temp : -INFINITY;
+    }
   }
   __syncthreads();
 
@@ -167,7 +177,7 @@ constexpr int TK_Q = 16, TK_NV = 32, TK_NT = 512, TK_NW = TK_NT / 64;  // eight 
 // 80 - 100 context frames: 3 888 / 11 781 candidates per query).  The argument holds chunk after chunk -- the k best carried into
 // each selection come from earlier chunks, so they have the lowest indices -- and the chunk size is that of NCH = 2 (pf * max_bi
 // <= 64 * TK_NV / 2 in registers, 64 KiB of scores at 1 024 candidates: two workgroups per CU).
-template <int CSTEPS, int NCH, bool ORG, bool LM>  // C / 16: float4 per lane and row; ORG, LM: as in labelprop_topk_kernel
+template <int CSTEPS, int NCH, bool ORG, bool LM, bool LB = false>  // C / 16: float4 per lane and row; ORG, LM, LB: as in labelprop_topk_kernel
 __global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_kernel(const float *__restrict__ ehat, int T, int N, int cxt, int radius,
                                                                            float temp, int knn, int first_frame, int maxcand, int pf,
                                                                            float *__restrict__ W, int32_t *__restrict__ I, int raw,
@@ -248,7 +258,14 @@ __global__ __launch_bounds__(TK_NT, NCH == 1 ? 2 : 4) void labelprop_topk_mfma_k
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int rr = m - lo_r[r];
-        if (m < N && rr >= 0 && rr < bw_r[r]) val[(4 * g + r) * maxcand + pl * bw_r[r] + rr] = (acc0[r] + acc1[r]) / temp;
+        if constexpr (LB) {
+          static_assert(LM, "the bias is the long-term keys'");
+          const float cs = acc0[r] + acc1[r];
+          if (m < N && rr >= 0 && rr < bw_r[r])
+            val[(4 * g + r) * maxcand + pl * bw_r[r] + rr] = (p0 + pl < K ? __fadd_rn(cs, origin.bias) : cs) / temp;
+        } else {
+          if (m < N && rr >= 0 && rr < bw_r[r]) val[(4 * g + r) * maxcand + pl * bw_r[r] + rr] = (acc0[r] + acc1[r]) / temp;
+        }
       }
       if constexpr (NCH == 1) {
 #pragma unroll
@@ -366,15 +383,19 @@ int launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... arg
 
 template <int CSTEPS, int NCH>
 int launch_topk_mfma_n(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int chunkcand, int pf,
-                       float *W, int32_t *I, int raw, const int32_t *origin, int n_long, hipStream_t s) {
+                       float *W, int32_t *I, int raw, const int32_t *origin, int n_long, hipStream_t s, float long_bias = 0.f) {
   const dim3 grid((N + TK_Q - 1) / TK_Q, T - first_frame);
   const size_t lds = (size_t)TK_Q * chunkcand * 4;
   if constexpr (NCH == 1) CRW_ROUTE("labelprop.topk_mfma_chunks1");
   else if constexpr (NCH == 2) CRW_ROUTE("labelprop.topk_mfma_chunks2");
   else CRW_ROUTE("labelprop.topk_mfma_long");
+  if (n_long && long_bias != 0.f)  // crw_labelprop_topk_long_bias: the LB instance (a zero bias runs the instance below)
+    return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH, false, true, true>>(grid, dim3(TK_NT), lds, s, ehat, T, N, cxt, radius, temp,
+                                                                                      knn, first_frame, chunkcand, pf, W, I, raw,
+                                                                                      LongFrames{n_long, long_bias});
   if (n_long)  // crw_labelprop_topk_long: the LM instance, whatever n_long is (no origins there)
     return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH, false, true>>(grid, dim3(TK_NT), lds, s, ehat, T, N, cxt, radius, temp, knn,
-                                                                                first_frame, chunkcand, pf, W, I, raw, LongFrames{n_long, 0});
+                                                                                first_frame, chunkcand, pf, W, I, raw, LongFrames{n_long, 0.f});
   if (origin)
     return launch_big_lds<labelprop_topk_mfma_kernel<CSTEPS, NCH, true, false>>(grid, dim3(TK_NT), lds, s, ehat, T, N, cxt, radius, temp, knn,
                                                                                 first_frame, chunkcand, pf, W, I, raw, origin);
@@ -386,13 +407,14 @@ int launch_topk_mfma_n(const float *ehat, int T, int N, int cxt, int radius, flo
 // in two halves, so that two workgroups share a CU (CRW_LABELPROP_TOPK_CHUNKS=1: always one piece, A/B)
 template <int CSTEPS>
 int launch_topk_mfma(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int max_nf, int max_bi, float *W,
-                     int32_t *I, int raw, const int32_t *origin, int n_long, hipStream_t s) {
+                     int32_t *I, int raw, const int32_t *origin, int n_long, hipStream_t s, float long_bias = 0.f) {
   static const bool one = getenv("CRW_LABELPROP_TOPK_CHUNKS") && getenv("CRW_LABELPROP_TOPK_CHUNKS")[0] == '1';
   const long maxcand = (long)max_nf * max_bi;
   const int pf = (max_nf + 1) / 2;
   if (!one && CSTEPS <= 8 /* 256 channels: past 128 registers */ && (size_t)TK_Q * maxcand * 4 > 76 * 1024 && (long)pf * max_bi <= 64L * (TK_NV / 2))
-    return launch_topk_mfma_n<CSTEPS, 2>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, origin, n_long, s);
-  return launch_topk_mfma_n<CSTEPS, 1>(ehat, T, N, cxt, radius, temp, knn, first_frame, (int)maxcand, max_nf, W, I, raw, origin, n_long, s);
+    return launch_topk_mfma_n<CSTEPS, 2>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, origin, n_long, s, long_bias);
+  return launch_topk_mfma_n<CSTEPS, 1>(ehat, T, N, cxt, radius, temp, knn, first_frame, (int)maxcand, max_nf, W, I, raw, origin, n_long, s,
+                                       long_bias);
 }
 
 // candidate lists past the two forms above (more than 64 * TK_NV candidates, or a tile's scores over 150 KiB): chunks of pf frames,
@@ -401,12 +423,12 @@ int launch_topk_mfma(const float *ehat, int T, int N, int cxt, int radius, float
 constexpr int TK_LONG_CAND = 64 * (TK_NV / 2);
 template <int CSTEPS>
 int launch_topk_mfma_long(const float *ehat, int T, int N, int cxt, int radius, float temp, int knn, int first_frame, int max_nf, int max_bi,
-                          float *W, int32_t *I, int raw, const int32_t *origin, int n_long, hipStream_t s) {
+                          float *W, int32_t *I, int raw, const int32_t *origin, int n_long, hipStream_t s, float long_bias = 0.f) {
   static_assert(CSTEPS <= 8, "256 channels: past 128 registers");
   int pf = TK_LONG_CAND / max_bi;
   const int nch = (max_nf + pf - 1) / pf;
   pf = (max_nf + nch - 1) / nch;
-  return launch_topk_mfma_n<CSTEPS, 0>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, origin, n_long, s);
+  return launch_topk_mfma_n<CSTEPS, 0>(ehat, T, N, cxt, radius, temp, knn, first_frame, pf * max_bi, pf, W, I, raw, origin, n_long, s, long_bias);
 }
 
 __device__ inline float ld_l2(const float *p) {
@@ -1210,7 +1232,7 @@ namespace {
 // hold up to n_long + cxt_size frames, and the routes are chosen for that length.  route: 0 auto, 1 the vector kernel, 2 the
 // matrix-core kernels -- CRW_EINVAL where the forced one does not apply
 int topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, float temp, int knn, int first_frame, int grid_w, float *W,
-              int32_t *I, int raw, const int32_t *origin, crw_stream_t stream, int n_long = 0, int route = 0) {
+              int32_t *I, int raw, const int32_t *origin, crw_stream_t stream, int n_long = 0, int route = 0, float long_bias = 0.f) {
   crw::clear_stale_error();
   if (!ehat || !W || !I || T < 2 || N < 1 || C < 1 || cxt_size < 1 || radius < 1 || knn < 1 || knn > MAX_KNN ||
       !(temp > 0.f) || first_frame < 1 || first_frame >= T || grid_w < 1 || N % grid_w)
@@ -1227,20 +1249,23 @@ int topk_grid(const float *ehat, int T, int N, int C, int cxt_size, int radius, 
   const bool column = grid_w == 1 && !(route ? route == 1 : valu) && N >= TK_Q && (((uintptr_t)ehat) & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
   if (column && (C == 64 || C == 128 || C == 256) && maxcand <= 64L * TK_NV && (size_t)TK_Q * maxcand * 4 <= 150 * 1024) {
-    if (C == 64) return launch_topk_mfma<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s);
-    if (C == 128) return launch_topk_mfma<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s);
-    return launch_topk_mfma<16>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s);
+    if (C == 64) return launch_topk_mfma<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s, long_bias);
+    if (C == 128) return launch_topk_mfma<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s, long_bias);
+    return launch_topk_mfma<16>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s, long_bias);
   }
   // longer lists (radius 30 / 60 at 80 - 100 context frames): any number of chunks; a single frame's band must fit one chunk
   if (column && (C == 64 || C == 128) && max_bi <= TK_LONG_CAND) {
-    if (C == 64) return launch_topk_mfma_long<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s);
-    return launch_topk_mfma_long<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s);
+    if (C == 64) return launch_topk_mfma_long<4>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s, long_bias);
+    return launch_topk_mfma_long<8>(ehat, T, N, cxt_size, radius, temp, knn, first_frame, (int)max_nf, (int)max_bi, W, I, raw, origin, n_long, s, long_bias);
   }
   if (lds > 60 * 1024 || route == 2) return CRW_EINVAL;
   CRW_ROUTE("labelprop.topk_valu");
-  if (n_long)
+  if (n_long && long_bias != 0.f)
+    hipLaunchKernelGGL((labelprop_topk_kernel<false, true, true>), dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T, N, C,
+                       cxt_size, radius, temp, knn, first_frame, grid_w, W, I, raw, LongFrames{n_long, long_bias});
+  else if (n_long)
     hipLaunchKernelGGL((labelprop_topk_kernel<false, true>), dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T, N, C,
-                       cxt_size, radius, temp, knn, first_frame, grid_w, W, I, raw, LongFrames{n_long, 0});
+                       cxt_size, radius, temp, knn, first_frame, grid_w, W, I, raw, LongFrames{n_long, 0.f});
   else if (origin)
     hipLaunchKernelGGL((labelprop_topk_kernel<true, false>), dim3(N, T - first_frame), dim3(256), lds, (hipStream_t)stream, ehat, T, N, C, cxt_size,
                        radius, temp, knn, first_frame, grid_w, W, I, raw, origin);
@@ -1466,6 +1491,14 @@ int crw_labelprop_topk_long(const float *ehat, int T, int N, int C, int cxt_size
                             float *WV, int32_t *I, int raw, int route, crw_stream_t stream) {
   if ((raw != 0 && raw != 1) || route < 0 || route > 2 || n_long < 1 || n_long > T - 1) return CRW_EINVAL;
   return topk_grid(ehat, T, N, C, cxt_size, radius, temp, k, first_frame, 1, WV, I, raw, nullptr, stream, n_long, route);
+}
+
+// include/crw_hip_align.h: the LB instances of the two top-k kernels; a zero bias is crw_labelprop_topk_long itself
+int crw_labelprop_topk_long_bias(const float *ehat, int T, int N, int C, int cxt_size, int n_long, int radius, float temp, int k,
+                                 int first_frame, float *WV, int32_t *I, int raw, int route, float long_bias, crw_stream_t stream) {
+  if (!(long_bias - long_bias == 0.f)) return CRW_EINVAL;  // NaN, +-inf
+  if ((raw != 0 && raw != 1) || route < 0 || route > 2 || n_long < 1 || n_long > T - 1) return CRW_EINVAL;
+  return topk_grid(ehat, T, N, C, cxt_size, radius, temp, k, first_frame, 1, WV, I, raw, nullptr, stream, n_long, route, long_bias);
 }
 
 int crw_labelprop_propagate_long(const float *W, const int32_t *I, int T, int N, int M, int knn, int first_frame, int cxt_size, int n_long,

@@ -120,11 +120,13 @@ class LabelPropVOS_CRW(object):
         crw_hip.labelprop_gather(None, Wt, It, n + 1, N, M, first_frame=n, L=L, cxt_size=self.cxt_size, context=self.context)
         return L[n * N:].reshape(N, M).t().reshape(1, M, h, w)
 
-    def _propagate_memory(self, feats, seed, nclasses, grid_w, anchors, anchor_context, memory):
+    def _propagate_memory(self, feats, seed, nclasses, grid_w, anchors, anchor_context, memory, memory_bias=0.0):
         """`propagate_all(memory=)`: the virtual item [bank traces..., item], the bank's B frames (and the item's frame 0 when it is
         seeded) long-term -- crw_labelprop_topk_long / crw_labelprop_propagate_long through `crw_hip.labelprop_topk(n_long=)` and
-        `labelprop_gather(n_long=)`.  The rows in front are one-hot; the item's part of pred and L is returned."""
+        `labelprop_gather(n_long=)`.  The rows in front are one-hot; the item's part of pred and L is returned.
+        memory_bias other than 0: the lists are crw_labelprop_topk_long_bias's (`labelprop_topk(long_bias=)`)."""
         T, N, C = feats.shape
+        bias = crw_hip.check_memory_bias(memory_bias)
         mem_feats, labels = check_memory(memory, N, nclasses, self.context, anchor_context)
         if grid_w != 1:
             raise ValueError("memory is defined on N x 1 grids only")
@@ -133,7 +135,8 @@ class LabelPropVOS_CRW(object):
         K, F = front.shape[0], B + T
         ehat = torch.cat([mem_feats.to(feats.dtype), feats]).contiguous()
         self._check_grid(N, 1)
-        Wt, It = crw_hip.labelprop_topk(ehat, self.cxt_size, self.radius, self.temperature, self.topk, first_frame=K, n_long=K, route="auto")
+        bkw = dict(long_bias=bias) if bias != 0.0 else {}   # 0: the call as it is without the option
+        Wt, It = crw_hip.labelprop_topk(ehat, self.cxt_size, self.radius, self.temperature, self.topk, first_frame=K, n_long=K, route="auto", **bkw)
         if anchors is not None:
             crw_hip.check_anchors(anchors, T, N, nclasses)
             shifted = torch.cat([torch.full((B, N), -1, dtype=torch.int8, device=anchors.device), anchors])   # B frames further down
@@ -147,7 +150,7 @@ class LabelPropVOS_CRW(object):
                                  n_long=K, route="auto")
         return pred[:, B:].contiguous(), L[B * N:]
 
-    def propagate_all(self, feats, seed, nclasses, grid_w=1, anchors=None, anchor_context='clamp', memory=None):
+    def propagate_all(self, feats, seed, nclasses, grid_w=1, anchors=None, anchor_context='clamp', memory=None, memory_bias=0.0):
         """feats [T,N,C] (normalised features), seed [N] float class ids of frame 0
         -> (pred [N,T] float class ids, L [T*N, M] soft labels).  grid_w: the N nodes are an (N / grid_w) x grid_w grid.
         memory (needs CONTEXT 'sliding', anchor_context 'clamp', an N x 1 grid): (mem_feats [B, N, C], mem_labels [B, N]) -- B fully
@@ -156,6 +159,9 @@ class LabelPropVOS_CRW(object):
         their labels (include/crw_hip_longmem.h).  With a seed the item's frame 0 is one more long-term frame; seed=None (memory
         only): the item's frame 0 is predicted from the bank alone and is an ordinary frame afterwards.  Anchors move B frames down
         with the item.  The item's pred [N,T] and L [T*N, M] are returned, nothing of the bank's.  None: the call is what it was.
+        memory_bias (needs memory; a finite float, default 0.0: nothing changes): added to the cosine of every in-band key of the
+        long-term frames -- the bank's and, with a seed, the item's frame 0 -- before the division by the temperature
+        (include/crw_hip_align.h), so that a long-term key b closer than it scores wins a slot against a recent key.
         anchor_context 'restart' (needs anchors): a frame whose N nodes are all anchored is as good as a seed -- every frame behind
         it is propagated as a frame of the item that starts there (`crw_hip.anchor_origins`, the `origin=` of `labelprop_topk` and
         `labelprop_gather`); 'clamp': the anchors clamp and the context is what it is without them.
@@ -166,7 +172,9 @@ class LabelPropVOS_CRW(object):
         or a library without the marks: one launch per stretch between anchored frames (`crw_hip.labelprop_gather(anchors=)`)."""
         T, N, C = feats.shape
         if memory is not None:
-            return self._propagate_memory(feats, seed, nclasses, grid_w, anchors, anchor_context, memory)
+            return self._propagate_memory(feats, seed, nclasses, grid_w, anchors, anchor_context, memory, memory_bias)
+        if crw_hip.check_memory_bias(memory_bias) != 0.0:
+            raise ValueError("memory_bias needs memory: without a bank the long-term part of a list is the seed frame alone")
         if seed is None:
             raise ValueError("seed=None needs memory: without a bank nothing labels the item's first frame")
         origin = restart_origin(anchor_context, anchors, self.context, T, N, nclasses)

@@ -240,7 +240,7 @@ def _segment_passes(dataset, seg, seq_length, patch_size, overlap, correction, u
 def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap, pos_embed=False,
             correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
             decode='argmax', order=None, posterior=False, floor=crw_hip.POSTERIOR_FLOOR, anchors=None, anchor_context='clamp', suggest=0, suggest_gap=2,
-            suggest_top=None, memory=None, seedless=False):
+            suggest_top=None, memory=None, seedless=False, memory_align=None, memory_bias=0.0):
     """dataset: RGDataset (full, overlapping items); seg: reference segmentation [rows, W_rg].
     -> dict(pred [rows, n_rg * rg_len] float labels after the optional reverse merge,
             forward: the forward (+ corrected) map the reference saves as int8 (test_all.py:128),
@@ -303,8 +303,15 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     downstream takes the soft labels as before.  Not together with anchor_context='restart' or ``suggest``.  The dict gains
     ``memory_traces`` (the number of bank traces) and ``seedless``.
     seedless (needs memory; not with ``correction``, which is a re-seed from ``seg``): no item is seeded from ``seg`` -- its first
-    frame is predicted from the bank like any other, and ``seg`` serves the geometry and the evaluation only."""
+    frame is predicted from the bank like any other, and ``seg`` serves the geometry and the evaluation only.
+    memory_align (None | 'center'), memory_bias (float, 0.0): how the bank is brought to every item -- `utils.propagate`'s options of
+    those names, the same settings for every item of both passes; they need ``memory``.  With a bank the dict gains ``memory_align``
+    and ``memory_bias``.  At None and 0.0 every entry is bit for bit what it is without them."""
     _check_anchor_context(anchor_context, anchors)
+    crw_hip.check_memory_align(memory_align)
+    memory_bias = crw_hip.check_memory_bias(memory_bias)
+    if memory is None and (memory_align is not None or memory_bias != 0.0):
+        raise ValueError("memory_align and memory_bias need memory: they say how a bank is brought to its item")
     bank = None
     if seedless and memory is None:
         raise ValueError("seedless=True needs memory: without a bank nothing labels an item's first frame")
@@ -335,7 +342,7 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
     if posterior:
         extra['floor'] = float(floor)
     if bank is not None:
-        extra.update(memory_traces=len(bank), seedless=bool(seedless))
+        extra.update(memory_traces=len(bank), seedless=bool(seedless), memory_align=memory_align, memory_bias=memory_bias)
     if upsample == 'bilinear':
         kw = dict(soft=True)
 
@@ -358,6 +365,10 @@ def segment(dataset, seg, encoder, lp, nclasses, seq_length, patch_size, overlap
         nkw = dict(novelty=True, novelty_top=suggest_top) if novelty else {}
         if bank is not None:  # the same bank in front of every item of both passes; seedless: `seg` seeds nothing
             nkw.update(memory=bank)
+            if memory_align is not None:
+                nkw.update(memory_align=memory_align)
+            if memory_bias != 0.0:
+                nkw.update(memory_bias=memory_bias)
             seg_ref = None if seedless else seg_ref
         res = propagate(seq, seg_ref, encoder, lp, nclasses, pos_embed, use_last=last, **kw, **anch, **nkw)
         if novelty:  # taken out again: the writers read the tuple by position
@@ -404,7 +415,8 @@ def _suggested(novs, cxt_size, budget, gap, N, nclasses, seq_length, patch_size,
 @torch.no_grad()
 def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size, overlap, pos_embed=False,
                   correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
-                  decode='argmax', order=None, anchors=None, anchor_context='clamp', memory=None, **posterior_options):
+                  decode='argmax', order=None, anchors=None, anchor_context='clamp', memory=None, memory_align=None, memory_bias=0.0,
+                  **posterior_options):
     """`segment` for every configuration of ``sweep`` (LabelPropSweep, G = len(sweep.configs)) with its control flow run ONCE:
     which items are corrected, at which length (`get_smaller_item` and its permanent shortening of the dataset) and what the
     reverse pass sees depend on the features alone, never on (radius, temp, knn).  Same exception policy in the correction.
@@ -434,8 +446,9 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     'sliding'); the same anchors in both passes and for all G configurations, the reverse pass mirrored, not together with
     ``correction``; the dict gains ``anchor_cols``.  Slice g stays `segment`'s for ``sweep.configs[g]`` under the same anchors.
     anchor_context: `segment`'s, one set of origins for the G configurations.
-    memory: refused -- a bank of long-term frames is `segment`'s; the batch kernels keep frame 0 alone."""
-    if memory is not None:
+    memory (and with it memory_align, memory_bias): refused -- a bank of long-term frames is `segment`'s; the batch kernels keep
+    frame 0 alone."""
+    if memory is not None or memory_align is not None or memory_bias != 0.0:
         raise ValueError("memory is not offered in segment_sweep: the batch kernels keep frame 0 alone as the long-term frame; "
                          "run `segment` per configuration")
     _check_anchor_context(anchor_context, anchors)

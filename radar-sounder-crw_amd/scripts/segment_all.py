@@ -46,8 +46,10 @@ look, not detections), ``--report_json`` gains ``suggested_anchors``; ``--memory
 memory bank -- the patch columns that start at those pixel columns, fully labelled from the reference map, stand in front of EVERY
 item as long-term frames (``inference.segment(memory=)``; one line says how many traces the bank holds); ``--memory_bank FILE``: a
 bank saved earlier, e.g. from another radargram, ``--save_memory_bank FILE`` writes the one in use; ``--seedless`` (needs a bank):
-no item is seeded from the reference map, which then serves the report alone; ``--report_json`` gains ``memory_traces`` and
-``seedless``.  Without these flags the output is what it was.
+no item is seeded from the reference map, which then serves the report alone; ``--memory_align center`` (needs a bank): the bank's
+features and every item's are centred by their own means before the normalisation, ``--memory_bias X`` (needs a bank): X is added
+to the cosine of the long-term keys (``inference.segment(memory_align=, memory_bias=)``); ``--report_json`` gains ``memory_traces``,
+``seedless``, ``memory_align`` and ``memory_bias``.  Without these flags the output is what it was.
 Differences from the scripts:
   * plots are not drawn;
   * true / false flags read true / false (the scripts take any given string as true); ``--patch_size`` takes two numbers;
@@ -150,6 +152,10 @@ def get_args_parser():
     p.add_argument('--memory_bank', default=None, metavar='FILE', help='memory bank: one saved with --save_memory_bank')
     p.add_argument('--save_memory_bank', default=None, metavar='FILE', help='write the memory bank in use (.npz)')
     p.add_argument('--seedless', action='store_true', help='seed no item from the reference map (needs a memory bank)')
+    p.add_argument('--memory_align', default=None, choices=['center'],
+                   help="centre the bank's features and every item's by their own means before the normalisation (needs a memory bank)")
+    p.add_argument('--memory_bias', default=None, type=float, metavar='X',
+                   help='add X to the cosine of the long-term keys (needs a memory bank; 0)')
     return p
 
 
@@ -157,13 +163,19 @@ HORIZON_FLAGS = ('horizons', 'min_run', 'tol', 'row_spacing', 'row_unit', 'save_
 POSTERIOR_FLAGS = ('posterior', 'floor', 'save_posterior')
 ANCHOR_FLAGS = ('anchors', 'anchor_every', 'anchor_context')
 SUGGEST_FLAGS = ('suggest_anchors', 'suggest_gap', 'suggest_top')
-MEMORY_FLAGS = ('memory_cols', 'memory_bank', 'save_memory_bank', 'seedless')
+MEMORY_FLAGS = ('memory_cols', 'memory_bank', 'save_memory_bank', 'seedless', 'memory_align', 'memory_bias')
 
 
 def check_memory_flags(args):
-    """The flags ``--memory_cols``, ``--memory_bank``, ``--save_memory_bank`` and ``--seedless`` -> is there a bank?"""
+    """The flags ``--memory_cols``, ``--memory_bank``, ``--save_memory_bank``, ``--seedless``, ``--memory_align`` and
+    ``--memory_bias`` -> is there a bank?"""
     cols, path = getattr(args, 'memory_cols', None), getattr(args, 'memory_bank', None)
+    bias = getattr(args, 'memory_bias', None)
+    if bias is not None and (bias != bias or bias in (float('inf'), float('-inf'))):
+        raise SystemExit('--memory_bias must be a finite number')
     if cols is None and path is None:
+        if getattr(args, 'memory_align', None) is not None or bias is not None:
+            raise SystemExit('--memory_align and --memory_bias need --memory_cols or --memory_bank')
         if getattr(args, 'seedless', False) or getattr(args, 'save_memory_bank', None) is not None:
             raise SystemExit('--seedless and --save_memory_bank need --memory_cols or --memory_bank')
         return False
@@ -375,6 +387,8 @@ def main(args):
     banked = check_memory_flags(args)
     if not banked:  # likewise
         hidden += MEMORY_FLAGS
+    elif args.memory_align is None and args.memory_bias is None:  # likewise: a bank as it is without the two
+        hidden += ('memory_align', 'memory_bias')
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -417,6 +431,8 @@ def main(args):
                                 **(dict(anchors=anchors) if anchored else {}),
                                 **(dict(anchor_context=anchor_context) if anchor_context else {}),
                                 **(dict(memory=bank, seedless=args.seedless) if banked else {}),
+                                **(dict(memory_align=args.memory_align) if banked and args.memory_align else {}),
+                                **(dict(memory_bias=args.memory_bias) if banked and args.memory_bias is not None else {}),
                                 **(dict(suggest=suggest, suggest_gap=args.suggest_gap, suggest_top=args.suggest_top) if suggest else {}))
         if out.get('anchor_context') == 'restart':
             print('Origin traces:', out['origin_traces'], 'of the anchored traces (anchor_context restart)')
@@ -500,7 +516,8 @@ def main(args):
         if pcal is not None:
             d['posterior'] = dict(floor=args.floor, calibration=pcal.to_dict(), horizon_bars=bars.to_dict())
         if banked:
-            d.update(memory_traces=out['memory_traces'], seedless=out['seedless'])
+            d.update(memory_traces=out['memory_traces'], seedless=out['seedless'], memory_align=out['memory_align'],
+                     memory_bias=out['memory_bias'])
         if suggest:
             d['suggested_anchors'] = dict(per_radargram=suggest, min_gap=args.suggest_gap, top=args.suggest_top,
                                           picks=[dict(p, columns=list(p['columns'])) for picks in out['suggested'] for p in picks])

@@ -183,11 +183,13 @@ def change_point(xent, diffs=None):
         return None
 
 
-def _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last, memory=None):
+def _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last, memory=None, memory_align=None):
     """The front of `propagate` / `propagate_sweep`: ONE encoder call on the whole item (the batch matters for the `Resnet`, whose
     train-mode BatchNorm statistics are the batch's), normalised features [T,N,C] and the seed labels [N].
     memory (a MemoryBank): its B * N patches go through the SAME encoder call, in front of the item's -- one BatchNorm batch in
-    train mode -- and the result gains the bank's features [B,N,C]; seg_ref None: no seed (None)."""
+    train mode -- and the result gains the bank's features [B,N,C]; seg_ref None: no seed (None).
+    memory_align 'center' (with a bank): the raw features are two segments, the bank's B * N rows and the item's T * N rows; each is
+    centred by its own per-channel mean before the normalisation (`crw_hip.center_normalize`, crw_center_normalize)."""
     T, N, H, W = seq.shape
     if memory is None and seg_ref is None:
         raise ValueError("seg_ref=None (no seed) needs memory: without a bank nothing labels the item's first frame")
@@ -200,7 +202,10 @@ def _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last, memory=None)
     if do_pos_embed:
         x = pos_embed(x)
     emb = model(x).reshape(B + T, N, -1).float().contiguous()
-    feats = crw_hip.normalize(emb)
+    if B and memory_align == 'center':
+        feats = crw_hip.center_normalize(emb, [0, B * N, (B + T) * N])
+    else:
+        feats = crw_hip.normalize(emb)
     if memory is None:
         return feats, seed_labels(seg_ref.to(feats.device), N)
     return feats[B:], (None if seg_ref is None else seed_labels(seg_ref.to(feats.device), N)), feats[:B]
@@ -208,7 +213,7 @@ def _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last, memory=None)
 
 @torch.no_grad()
 def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False, anchors=None,
-              anchor_context='clamp', novelty=False, novelty_top=None, memory=None):
+              anchor_context='clamp', novelty=False, novelty_top=None, memory=None, memory_align=None, memory_bias=0.0):
     """seq [T,N,h,w]; seg_ref [rows, w] class ids of the first (or last) frame; model: encoder;
     lp: LabelPropVOS_CRW  ->  (labels [N,T] float, xent [N,T-1] (CPU), change_idx | None).
 
@@ -232,7 +237,15 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, conf
     memory: None, or a `MemoryBank` of B fully labelled traces from elsewhere (needs CONTEXT 'sliding', anchor_context 'clamp', no
     novelty): its patches are encoded in the same encoder call as the item and stand in front of it as long-term frames
     (``lp.propagate_all(memory=)``).  With a bank ``seg_ref`` may be None: the item has no seed, its first frame is predicted from
-    the bank alone and its confidence is that of any other frame.  Everything returned is the item's, as without a bank."""
+    the bank alone and its confidence is that of any other frame.  Everything returned is the item's, as without a bank.
+    memory_align (needs memory): None, or 'center' -- the bank's features and the item's are each centred by their own mean over
+    all their nodes before the L2 normalisation (the item's seed frame included), which removes an appearance offset between the
+    labelled radargram and this one.  memory_bias (needs memory; float, default 0.0): ``lp.propagate_all(memory_bias=)``, a bonus
+    on the cosine of the long-term keys.  With None and 0.0 the call is bit for bit what it is without them."""
+    crw_hip.check_memory_align(memory_align)
+    memory_bias = crw_hip.check_memory_bias(memory_bias)
+    if memory is None and (memory_align is not None or memory_bias != 0.0):
+        raise ValueError("memory_align and memory_bias need memory: they say how a bank is brought to its item")
     if memory is not None:
         if not hasattr(lp, 'propagate_all'):
             raise ValueError("memory needs a label propagation with `propagate_all` (LabelPropVOS_CRW)")
@@ -266,8 +279,10 @@ def propagate(seq, seg_ref, model, lp, nclasses, do_pos_embed, use_last, *, conf
     if memory is None:
         feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
     else:
-        feats, seed, mem_feats = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last, memory)
+        feats, seed, mem_feats = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last, memory, memory_align)
         mkw = dict(memory=(mem_feats, memory.labels.to(feats.device)))
+        if memory_bias != 0.0:
+            mkw.update(memory_bias=memory_bias)
         if T == 1 and seed is None:
             raise ValueError("a one-frame item without a seed has nothing to propagate from")
     if T == 1:  # a one-frame item (the correction step of test_all.py can ask for it): nothing to propagate, like the reference
