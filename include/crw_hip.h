@@ -51,6 +51,18 @@
  *     side stream PER DEVICE (created on first use, with its event pool) -- at most one host thread per device may be inside them
  *     at a time; and the crw_rn_timing_* diagnostic (one global record list).  Everything they enqueue on the side stream is joined
  *     back into the caller's stream before they return, on error paths too.
+ *
+ * Non-finite values (NaN, +inf, -inf; never told apart: the hi/lo bf16 split turns inf into NaN) on the training path -- the
+ * encoders, crw_normalize, crw_affinity_fwd / _bwd, crw_walk_fwd / _bwd, crw_adam_step -- behave as in the reference's PyTorch ops
+ * (relu, max_pool2d, clamp_min, softmax propagate them); DESIGN.md section 3e, tests/test_nonfinite_gpu.py:
+ *   - no laundering: wherever the reference's output is non-finite, ours is (features, ehat, norm, A, At_out, loss, dA, demb,
+ *     parameter gradients, BatchNorm running statistics, Adam's p / m / v); for A, the loss and the encoder features the masks are
+ *     EQUAL (no spurious NaN either; a poison in the last frame, whose logits feed no cycle, leaves the loss finite); a row or
+ *     column of A that holds a non-finite logit has a non-finite sum in the `stats` of crw_affinity_fwd;
+ *   - no contamination: what the reference keeps bit-equal to its clean run stays bit-equal to OUR clean run -- the other patches
+ *     of the CNN and of the eval-mode Resnet, the other batch items' A / At_out / dA / demb, the other elements of Adam's buffers;
+ *   - finite inputs give the bits they always gave.
+ * Label propagation on non-finite features is outside this contract.
  */
 #ifndef CRW_HIP_H
 #define CRW_HIP_H

@@ -76,6 +76,15 @@ __device__ inline float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+// ---- maxima that keep a NaN (include/crw_hip.h, "Non-finite values") -----------------------
+// fmaxf is IEEE maxNum: fmaxf(NaN, 0) = 0, so a ReLU or a max-pool written with it hands a finite activation on where the
+// PyTorch ops of the reference (relu, max_pool2d, clamp_min) hand on the NaN.  max_nan is IEEE 754-2019 `maximum`: NaN if
+// either operand is, otherwise the bits fmaxf gives (-0 < +0 in both).  One v_maximum3_f32 on gfx950, where fmaxf is one
+// v_max_f32: the instruction count of an epilogue does not change (profiles/nonfinite_isa.log).
+__device__ inline float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ inline float relu_nan(float v) { return max_nan(v, 0.f); }
+__device__ inline float max4_nan(float a, float b, float c, float d) { return max_nan(max_nan(a, b), max_nan(c, d)); }
+
 // Workgroup barrier that makes LDS traffic visible but does NOT drain outstanding global loads
 // (__syncthreads() waits for vmcnt(0), which would expose the latency of a prefetch in flight).
 // Only for phases whose cross-wave communication goes through LDS.

@@ -489,7 +489,7 @@ __device__ __forceinline__ void conv_compute(const ConvIO &a, const ConvTile &t,
           if (valid) {
             float v = acc[k][j][r];
             if (MODE == 0) {
-              v = fmaxf(v + bias_r[j], 0.f);
+              v = relu_nan(v + bias_r[j]);
               if (!MAP || (ty0 + i / IMG_W < a.mh && tx0 + i % IMG_W < a.mw)) gsum[j] += v;
             }
             if (a.yf) {

@@ -122,7 +122,7 @@ __device__ inline void conv1_relu(const FwdLds &L, int cin, int tid) {
         acc.w = fmaf(v, wv.w, acc.w);
       }
     }
-    *reinterpret_cast<float4 *>(L.c1r + map_idx<CW, PAD>(y, xx) * 8 + c0) = float4{fmaxf(acc.x, 0.f), fmaxf(acc.y, 0.f), fmaxf(acc.z, 0.f), fmaxf(acc.w, 0.f)};
+    *reinterpret_cast<float4 *>(L.c1r + map_idx<CW, PAD>(y, xx) * 8 + c0) = float4{relu_nan(acc.x), relu_nan(acc.y), relu_nan(acc.z), relu_nan(acc.w)};
   }
 }
 
@@ -134,7 +134,7 @@ __device__ inline void pool1(const FwdLds &L, int tid, char *sv = nullptr) {  //
   for (int e = tid; e < A1W * A1W * 8; e += NT) {
     const int c = e & 7, p = e >> 3, y = p / A1W, x = p % A1W;
     const float *s = L.c1r + map_idx<C1W, PAD>(y, x) * 8 + c;
-    const float v = fmaxf(fmaxf(s[0], s[8]), fmaxf(s[ROW], s[ROW + 8]));
+    const float v = max4_nan(s[0], s[8], s[ROW], s[ROW + 8]);
     const uint16_t h = f2bf(v), l = bf_lo(v, h);
     const int o = ((y + 1) * A1PW + x + 1) * 16 + 2 * c;
     *reinterpret_cast<uint16_t *>(L.a1h + o) = h;
@@ -164,7 +164,7 @@ __device__ inline void pool1_window(const FwdLds &L, int tid, int oy0, int ox0, 
     float v = 0.f;
     if (ay >= 0 && ay < H - 3 && ax >= 0 && ax < W - 3) {
       const float *s1 = L.c1r + map_idx<MC1W, PAD>(r, cc) * 8 + c;
-      v = fmaxf(fmaxf(s1[0], s1[8]), fmaxf(s1[ROW], s1[ROW + 8]));
+      v = max4_nan(s1[0], s1[8], s1[ROW], s1[ROW + 8]);
     }
     const uint16_t h = f2bf(v);
     *reinterpret_cast<uint16_t *>(L.a1h + q * 16 + 2 * c) = h;
@@ -225,7 +225,7 @@ __device__ inline void conv2_relu(const FwdLds &L, float bias, int tid) {  // bi
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = 16 * ((wave + NW * u) >> 1) + 4 * g + r;
-      if (i < C2N) L.c2r[map_idx<C2W, PAD>(i / C2W, i % C2W) * 32 + co] = fmaxf(acc[u][r] + b, 0.f);
+      if (i < C2N) L.c2r[map_idx<C2W, PAD>(i / C2W, i % C2W) * 32 + co] = relu_nan(acc[u][r] + b);
     }
 }
 
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(NT) void front_fwd_kernel(FrontArgs a) {
     for (int e = tid; e < ON * 32; e += NT) {
       const int c = e & 31, q = e >> 5, y = q / OW, x = q % OW;
       const float *s = L.c2r + (y * C2W + x) * 32 + c;
-      const float v = fmaxf(fmaxf(s[0], s[32]), fmaxf(s[C2W * 32], s[C2W * 32 + 32]));
+      const float v = max4_nan(s[0], s[32], s[C2W * 32], s[C2W * 32 + 32]);
       const uint16_t h = f2bf(v);
       a.yh[(long)pt * ON * 32 + e] = h;
       if (SPLIT == 3) a.yl[(long)pt * ON * 32 + e] = bf_lo(v, h);
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(NT) void front_fwd_map_kernel(FrontMapArgs a) {
       const int c = e & 31, q = e >> 5, y = q / OW, x = q % OW;
       if (oy0 + y < Ho && ox0 + x < Wo) {
         const float *s2 = L.c2r + (y * C2W + x) * 32 + c;
-        const float v = fmaxf(fmaxf(s2[0], s2[32]), fmaxf(s2[C2W * 32], s2[C2W * 32 + 32]));
+        const float v = max4_nan(s2[0], s2[32], s2[C2W * 32], s2[C2W * 32 + 32]);
         const uint16_t h = f2bf(v);
         const long o = (((long)pt * Ho + oy0 + y) * Wo + ox0 + x) * 32 + c;
         a.f.yh[o] = h;

@@ -612,7 +612,8 @@ __global__ __launch_bounds__(256) void affinity_tile_kernel(const float *__restr
   const float *pp = (rows ? rpart : cpart) + idx * 2;
   const float ma = pp[0], sa = pp[1], mb = pp[TS * 2], sb = pp[TS * 2 + 1];
   const float m = fmaxf(ma, mb);
-  const float sum = (sa > 0.f ? sa * expf(ma - m) : 0.f) + (sb > 0.f ? sb * expf(mb - m) : 0.f);
+  // (an empty half has s = 0 and m = -inf: its exp(-inf + inf) must not count; a NaN sum must)
+  const float sum = (sa == 0.f ? 0.f : sa * expf(ma - m)) + (sb == 0.f ? 0.f : sb * expf(mb - m));
   const int gi = (rows ? m0 : n0) + idx;
   if (gi < N) {
     const long nmat = gridDim.y;

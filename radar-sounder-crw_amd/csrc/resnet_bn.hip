@@ -274,7 +274,7 @@ __global__ __launch_bounds__(256) void rn_bn_apply_kernel(const float *__restric
       }
       if (relu)
 #pragma unroll
-        for (int k = 0; k < 8; ++k) y.v[k] = fmaxf(y.v[k], 0.f);
+        for (int k = 0; k < 8; ++k) y.v[k] = relu_nan(y.v[k]);
     } else {
 #pragma unroll
       for (int k = 0; k < 8; ++k) y.v[k] = 0.f;
@@ -314,8 +314,8 @@ __global__ __launch_bounds__(256) void rn_bn_pool_kernel(const float *__restrict
           const Oct z = load8(Z + ((p * H + iy) * W + ix) * C + c);
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
-            const float v = fmaxf(z.v[k] * s.v[k] + t.v[k], 0.f);
-            if (v > y.v[k]) {
+            const float v = relu_nan(z.v[k] * s.v[k] + t.v[k]);
+            if (v > y.v[k] || v != v) {  // ATen's rule again: a NaN takes the window and keeps it
               y.v[k] = v;
               am[k] = ky * 3 + kx;
             }
@@ -504,7 +504,7 @@ __device__ inline Oct pool_grad8(const float *__restrict__ d1, const float *__re
       g.v[k] += (ok[w] && a == code[w]) ? d[w].v[k] : 0.f;
     }
 #pragma unroll
-  for (int k = 0; k < 8; ++k) g.v[k] = (z.v[k] * scale.v[k] + shift.v[k]) > 0.f ? g.v[k] : 0.f;
+  for (int k = 0; k < 8; ++k) g.v[k] = (z.v[k] * scale.v[k] + shift.v[k]) <= 0.f ? 0.f : g.v[k];  // (a NaN activation passes, as ATen's relu backward)
   return g;
 }
 
@@ -654,7 +654,7 @@ __global__ __launch_bounds__(256) void rn_stem_apply_kernel(const float *__restr
       if (y0 >= 1 && y0 <= h && x0 >= 1 && x0 <= w)
         for (int k = 0; k < cin; ++k) xi[k] = x[((p * cin + k) * h + (y0 - 1)) * w + (x0 - 1)];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = fmaxf(stem[12 + 2 * c] * xi[0] + stem[13 + 2 * c] * xi[1] + stem[18 + c], 0.f);
+      for (int c = 0; c < 3; ++c) v[c] = relu_nan(stem[12 + 2 * c] * xi[0] + stem[13 + 2 * c] * xi[1] + stem[18 + c]);
     }
     uint16_t hh[4], ll[4];
 #pragma unroll
@@ -692,7 +692,7 @@ __global__ __launch_bounds__(256) void rn_stem_bwd_reduce_kernel(const float *__
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float y = stem[12 + 2 * c] * xi[0] + stem[13 + 2 * c] * xi[1] + stem[18 + c];
-      const float g = y > 0.f ? dX0[(p * H0 + y0) * ldx + x0 * 3 + c] : 0.f;
+      const float g = y <= 0.f ? 0.f : dX0[(p * H0 + y0) * ldx + x0 * 3 + c];  // (a NaN activation passes, as ATen's relu backward)
       float pre = b0[c];
       for (int k = 0; k < cin; ++k) pre += w0[c * cin + k] * xi[k];
       const float xh = (pre - stem[6 + c]) * stem[9 + c];

@@ -43,7 +43,7 @@ __device__ inline void stem_pixel(const StemCoef &k, float x0, float x1, uint2 &
   uint16_t h[3], l[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const float v = fmaxf(k.a[c][0] * x0 + k.a[c][1] * x1 + k.d[c], 0.f);
+    const float v = relu_nan(k.a[c][0] * x0 + k.a[c][1] * x1 + k.d[c]);
     h[c] = f2bf(v);
     l[c] = bf_lo(v, h[c]);
   }
@@ -548,7 +548,7 @@ __global__ __launch_bounds__(512) void rn_stem_bwd_kernel(const float *__restric
           if (CIN == 2) xi1 = xp[256 + (iy - 1) * 16 + ix - 1];
         }
         const float y = a0 * xi0 + a1 * xi1 + dd;
-        const float gsel = y > 0.f ? ((iy & 1) ? dxo[iy >> 1] : dxe[iy >> 1]) : 0.f;
+        const float gsel = y <= 0.f ? 0.f : ((iy & 1) ? dxo[iy >> 1] : dxe[iy >> 1]);  // (a NaN activation passes, as ATen's relu backward)
         const float xh = (w_0 * xi0 + w_1 * xi1 + bb - mm) * is;
         S[0] += gsel;
         S[1] += gsel * xh;

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void normalize_kernel(const float *__restrict_
   float ss = 0.f;
   for (int c = lane; c < C; c += 64) ss += x[c] * x[c];
   ss = wave_sum(ss);
-  const float d = fmaxf(sqrtf(ss), EPS_NORM);
+  const float d = max_nan(sqrtf(ss), EPS_NORM);  // clamp_min keeps a NaN norm
   for (int c = lane; c < C; c += 64) ehat[row * C + c] = x[c] / d;
   if (lane == 0 && norm) norm[row] = d;
 }
