@@ -181,6 +181,12 @@ ALIGN_SIGNATURES = {
     "crw_labelprop_topk_long_bias": (_c_int, [_p] + [_c_int] * 6 + [_c_f, _c_int, _c_int, _p, _p, _c_int, _c_int, _c_f, _p]),
 }
 
+# include/crw_hip_reach.h, likewise: one confusion matrix per group of columns -- accuracy against distance (optional: `has_reach()`)
+REACH_SIGNATURES = {
+    "crw_confusion_grouped_ws_bytes": (_c_sz, [_c_int, _c_int, _c_int, _c_int]),
+    "crw_confusion_grouped": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_sz, _p] + [_c_int] * 5 + [_p, _p, _p, _p, _c_sz, _p]),
+}
+
 # include/crw_hip_routes.h, likewise: the route log -- which selector branch launched (optional: `has_routes()`; host pointers)
 ROUTES_SIGNATURES = {
     "crw_routes_clear": (_c_int, []),
@@ -236,6 +242,9 @@ LONG_MEMORY_ENTRY_POINTS = tuple(LONGMEM_SIGNATURES)
 # likewise: segment-centred normalisation and the biased long-memory lists (`has_align()`, `center_normalize`, `labelprop_topk(long_bias=)`)
 ALIGN_ENTRY_POINTS = tuple(ALIGN_SIGNATURES)
 
+# likewise: the grouped confusion matrix (`has_reach()`, `confusion_grouped`)
+REACH_ENTRY_POINTS = tuple(REACH_SIGNATURES)
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 ANCHOR_CONTEXTS = ("clamp", "restart")  # what a fully labelled anchor trace does to the frames behind it
 
@@ -247,7 +256,7 @@ OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_E
                          "posterior": POSTERIOR_ENTRY_POINTS, "posterior_batch": POSTERIOR_BATCH_ENTRY_POINTS,
                          "conv_chain": CONV_CHAIN_ENTRY_POINTS, "anchor_restart": ANCHOR_RESTART_ENTRY_POINTS,
                          "routes": ROUTES_ENTRY_POINTS, "novelty": NOVELTY_ENTRY_POINTS, "long_memory": LONG_MEMORY_ENTRY_POINTS,
-                         "align": ALIGN_ENTRY_POINTS}
+                         "align": ALIGN_ENTRY_POINTS, "reach": REACH_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -264,7 +273,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         missing = {n for names in OPTIONAL_ENTRY_POINTS.values() for n in names if not hasattr(handle, n)}
         for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES, **RESTART_SIGNATURES, **ROUTES_SIGNATURES,
-                                   **NOVELTY_SIGNATURES, **LONGMEM_SIGNATURES, **ALIGN_SIGNATURES}.items():
+                                   **NOVELTY_SIGNATURES, **LONGMEM_SIGNATURES, **ALIGN_SIGNATURES, **REACH_SIGNATURES}.items():
             if name in missing:
                 continue
             fn = getattr(handle, name)
@@ -313,6 +322,7 @@ has_routes, _routes_lib = _optional("routes", "the route log's entry points")
 has_novelty, _novelty_lib = _optional("novelty", "the context-novelty entry point")
 has_long_memory, _long_memory_lib = _optional("long_memory", "the entry points that take n_long long-term frames")
 has_align, _align_lib = _optional("align", "the segment-centred normalisation and the biased long-memory lists")
+has_reach, _reach_lib = _optional("reach", "the grouped confusion matrix's entry points")
 
 MAX_ROUTES = 256  # csrc/crw_common.h
 
@@ -1425,6 +1435,137 @@ def _calibration_cpu(gt, pred, c, K, bins, aux, ignore_gt, ignore_pred, ignore_a
     ok = torch.bincount(row, weights=(binned & (g == p)).to(torch.float64), minlength=bins + 3).to(torch.int64)
     s = torch.bincount(row, weights=torch.where(binned, c.to(torch.float64), torch.zeros(1, dtype=torch.float64)), minlength=bins + 3)
     return torch.stack([n[:bins], ok[:bins]], 1), s[:bins], n[bins:]
+
+
+# ------------------------------------------------------------------------------ accuracy against distance
+REACH_MAX_GROUPS = 64
+REACH_EDGES = (1, 2, 3, 5, 9, 17, 33, 65, 129, 257)  # frame distances {0} {1} {2} {3-4} {5-8} ... {129-256} {257-}
+REACH_DIRECTIONS = ("both", "forward", "backward")
+
+
+def column_groups(cols, labelled, step, edges=None, segments=None, direction="both"):
+    """How far is every column of a map from a labelled one?  -> (group uint8 [cols], frames int64 [cols]); host work, no GPU.
+    The pixel distance of column c is min |c - l| over the labelled columns l of c's own segment (``segments``: offsets 0 = b_0 <
+    ... < b_S = cols, default one segment: an item never reads another item's labels); ``direction`` 'forward' admits only
+    l <= c, 'backward' only l >= c.  The frame distance is ceil(pixel distance / step), and the group is the number of ``edges``
+    (strictly increasing integers >= 1; default `REACH_EDGES`: the groups {0} {1} {2} {3-4} {5-8} ...) that are <= it.  A column
+    with no admissible labelled column has frames = -1 and the last group, len(edges) + 1: len(edges) + 2 groups in all."""
+    cols, step = int(cols), int(step)
+    if cols < 0:
+        raise ValueError(f"cols must be at least 0 (got {cols})")
+    if step < 1:
+        raise ValueError(f"step must be at least 1 pixel column per frame (got {step})")
+    if direction not in REACH_DIRECTIONS:
+        raise ValueError(f"direction must be one of {REACH_DIRECTIONS} (got {direction!r})")
+    edges = list(REACH_EDGES if edges is None else edges)
+    if any(int(e) != e for e in edges) or any(e < 1 for e in edges) or any(b <= a for a, b in zip(edges, edges[1:])):
+        raise ValueError(f"edges must be strictly increasing integers >= 1 (got {edges})")
+    if len(edges) + 2 > REACH_MAX_GROUPS:
+        raise ValueError(f"at most {REACH_MAX_GROUPS - 2} edges: {REACH_MAX_GROUPS} groups with the unreached one (got {len(edges)})")
+    segments = [0, cols] if segments is None else [int(b) for b in segments]
+    if cols and (len(segments) < 2 or segments[0] != 0 or segments[-1] != cols or any(b <= a for a, b in zip(segments, segments[1:]))):
+        raise ValueError(f"segments must be offsets 0 = b_0 < ... < b_S = {cols} (got {segments})")
+    if any(int(l) != l for l in labelled):
+        raise ValueError("labelled columns must be integers")
+    lab = sorted({int(l) for l in labelled})
+    if lab and not 0 <= lab[0] <= lab[-1] < cols:
+        raise ValueError(f"labelled columns {lab[0]} .. {lab[-1]} lie outside the map's {cols} columns")
+    far = torch.iinfo(torch.int64).max
+    dist = torch.full((cols,), far, dtype=torch.int64)
+    at = torch.tensor(lab, dtype=torch.int64)
+    for a, b in zip(segments, segments[1:]):
+        own = at[(at >= a) & (at < b)]
+        if not own.numel():
+            continue
+        c = torch.arange(a, b, dtype=torch.int64)
+        nxt = torch.searchsorted(own, c)                               # the first labelled column >= c
+        ahead = torch.where(nxt < own.numel(), own[nxt.clamp(max=own.numel() - 1)] - c, far)
+        prv = torch.searchsorted(own, c, right=True) - 1               # the last labelled column <= c
+        behind = torch.where(prv >= 0, c - own[prv.clamp(min=0)], far)
+        dist[a:b] = behind if direction == "forward" else ahead if direction == "backward" else torch.minimum(ahead, behind)
+    reached = dist != far
+    frames = torch.where(reached, (dist + (step - 1)) // step, -1)
+    group = torch.bucketize(frames, torch.tensor(edges, dtype=torch.int64), right=True)
+    group = torch.where(reached, group, len(edges) + 1).to(torch.uint8)
+    return group, frames
+
+
+def confusion_grouped(gt, pred, K, col_group, groups, conf=None, aux=None, ignore_gt=-1, ignore_pred=-1, ignore_aux=-1):
+    """`confusion` per group of columns of [rows, cols] maps (or ``[rows, a:b]`` column windows of wider ones) -> (counts [groups,
+    K, K] int64, conf_sum [groups] float64 or None without ``conf``, dropped [4] int64) on the inputs' device.  ``col_group``: uint8
+    [cols], the group of every column (`column_groups`); a pixel of a column whose entry is >= ``groups`` is counted in dropped[3]
+    and examined no further.  Then `confusion`'s mask (dropped[0]) and validity (dropped[1]) rules; with ``conf``, a float map of
+    the same shape, `calibration`'s test: NaN or a value outside [0, 1] is counted in dropped[2].  Every other pixel adds 1 to
+    counts[g, gt, pred] and its confidence to conf_sum[g].  Device tensors: one pass of crw_confusion_grouped with a workspace of
+    its own, nothing synchronises; windows that share one pitch are read where they lie.  CPU tensors: the same integers from
+    torch.bincount, conf_sum in float64."""
+    K, groups = _report_args(K, aux, ignore_gt, ignore_pred, ignore_aux), int(groups)
+    if not 1 <= groups <= REACH_MAX_GROUPS:
+        raise ValueError(f"groups must be in 1 ... {REACH_MAX_GROUPS} (got {groups})")
+    if gt.dim() != 2:
+        raise ValueError(f"gt must be a [rows, cols] map (got shape {tuple(gt.shape)})")
+    maps = (gt, pred) if conf is None else (gt, pred, conf)
+    _report_operands("gt, pred" + (", conf" if conf is not None else ""), maps, aux, lambda t: tuple(t.shape), "pixels")
+    rows, cols = gt.shape
+    if conf is not None and not conf.is_floating_point():
+        raise ValueError(f"conf must be a floating-point map (got {conf.dtype})")
+    if col_group.dtype != torch.uint8 or tuple(col_group.shape) != (cols,):
+        raise ValueError(f"col_group must be uint8 [{cols}] (got {col_group.dtype} {tuple(col_group.shape)})")
+    if not gt.is_cuda:
+        return _confusion_grouped_cpu(gt, pred, K, col_group.cpu(), groups, conf, aux, ignore_gt, ignore_pred, ignore_aux)
+    # rows stay where they are when the dtype is one of the kernel's and the window's rows are contiguous
+    ops = [_kernel_dtype(gt), _kernel_dtype(pred)] + ([conf.to(torch.float32)] if conf is not None else [])
+    ops += [_kernel_dtype(aux)] if aux is not None else []
+    pitches = [_pitch(t) for t in ops]
+    if rows * cols == 0:
+        ld = cols
+    elif None in pitches or len(set(pitches)) > 1:
+        ops, ld = [t.contiguous() for t in ops], cols
+    else:
+        ld = pitches[0]
+    g, p = ops[0], ops[1]
+    c = ops[2] if conf is not None else None
+    a = ops[-1] if aux is not None else None
+    if rows * cols == 0:  # an empty tensor has no address: nothing to mask
+        a, ignore_aux = None, -1
+    grp = col_group.to(gt.device).contiguous()
+    n = groups * K * K
+    out = torch.empty(n + groups + 4, dtype=torch.int64, device=gt.device)  # counts | conf_sum (as bits) | dropped [4]
+    L = _reach_lib()
+    nbytes = L.crw_confusion_grouped_ws_bytes(rows, cols, K, groups)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=gt.device)
+    base = out.data_ptr()
+    _check(L.crw_confusion_grouped(_ptr(g), _dt(g), _ptr(p), _dt(p), _ptr(a), _dt(a), _ptr(c) if c is not None else None, rows, cols, ld,
+                                   _ptr(grp), groups, K, int(ignore_gt), int(ignore_pred), int(ignore_aux), ctypes.c_void_p(base),
+                                   ctypes.c_void_p(base + 8 * n) if c is not None else None, ctypes.c_void_p(base + 8 * (n + groups)),
+                                   _ptr(ws), nbytes, _stream()), "crw_confusion_grouped")
+    return out[:n].view(groups, K, K), out[n:n + groups].view(torch.float64) if c is not None else None, out[n + groups:]
+
+
+def _confusion_grouped_cpu(gt, pred, K, col_group, groups, conf, aux, ignore_gt, ignore_pred, ignore_aux):
+    rows, cols = gt.shape
+    g, p = gt.reshape(-1).to(torch.float64), pred.reshape(-1).to(torch.float64)
+    grp = col_group.to(torch.int64)[None].expand(rows, cols).reshape(-1)
+    excluded = grp >= groups
+    masked, valid = _mask_valid(g, p, aux, K, ignore_gt, ignore_pred, ignore_aux)
+    masked, invalid = masked & ~excluded, ~masked & ~valid & ~excluded
+    keep = ~excluded & ~masked & ~invalid
+    n = groups * K * K
+    if conf is not None:
+        c = conf.reshape(-1).to(torch.float32)
+        bad = keep & ~((c >= 0) & (c <= 1))
+        keep = keep & ~bad
+    # the dropped pixels go to four extra bins, like the kernel's: no boolean-indexed copy of the maps
+    idx = torch.where(keep, (grp * K + g) * K + p, torch.where(masked, float(n), torch.where(invalid, float(n + 1), float(n + 3))))
+    if conf is not None:
+        idx = torch.where(bad, float(n + 2), idx)
+    idx = idx.to(torch.int64)
+    out = torch.bincount(idx, minlength=n + 4)
+    conf_sum = None
+    if conf is not None:
+        zero = torch.zeros(1, dtype=torch.float64)
+        conf_sum = torch.bincount(torch.where(keep, grp, 0), weights=torch.where(keep, c.to(torch.float64), zero), minlength=groups)[:groups]
+    return out[:n].view(groups, K, K), conf_sum, out[n:]
 
 
 # ------------------------------------------------------------------------------ dense label maps

@@ -716,6 +716,97 @@ def horizons_sweep(pred, seg, dataset_id, remove_unc=True, unc_seg=None, nclasse
     return [_horizons_of(row, K, pred.shape[1:], min_run, tol, row_spacing, unit) for row in host]
 
 
+def labelled_columns(n_cols, seq_length, patch_size, overlap, use_last, anchor_cols=(), seeds=True):
+    """Which pixel columns of `segment`'s map were labelled, by `_segment_passes`'s arithmetic -> (labelled, segments, direction,
+    step) for `label_reach`.  ``n_cols``: the reference map's columns (the result map has the whole items' n_rg * rg_len of them:
+    segments[-1]).  Every item (rg_len = T * (W - ow) + ow columns, one segment) is seeded from the W pixel columns of its first
+    frame; with ``use_last`` the reverse pass seeds it from those of its last frame as well and the labels travel in both
+    directions ('both'), otherwise 'forward'; an anchored pixel column labels every pixel column of its frame
+    (`utils.anchor_nodes`: frame min(x mod rg_len // (W - ow), T - 1)).  step = W - ow pixel columns per frame.  The traces of a
+    memory bank are labelled elsewhere and are no positions in this map: for a ``seedless`` run pass seeds=False, which leaves the
+    anchors alone -- an item without any then falls into the unreached group."""
+    T, (H, W), (oh, ow) = int(seq_length), patch_size, overlap
+    step = W - ow
+    rg_len = T * step + ow
+    n_rg = int(n_cols) // rg_len
+    if n_rg < 1:
+        raise ValueError(f"{n_cols} columns hold no item of {rg_len} columns")
+    labelled = set()
+    for t in range(n_rg if seeds else 0):
+        labelled.update(range(rg_len * t, rg_len * t + W))
+        if use_last:
+            labelled.update(range(rg_len * (t + 1) - W, rg_len * (t + 1)))
+    for x in sorted(int(c) for c in anchor_cols):
+        if not 0 <= x < n_rg * rg_len:
+            raise ValueError(f"anchored column {x} lies outside the {n_rg} item(s) of {rg_len} columns")
+        a = x // rg_len * rg_len + min(x % rg_len // step, T - 1) * step
+        labelled.update(range(a, a + W))
+    return sorted(labelled), [rg_len * t for t in range(n_rg + 1)], 'both' if use_last else 'forward', step
+
+
+def _reach_groups(pred, labelled, step, segments, direction, edges):
+    """The column groups of `label_reach` for maps of pred's width -> (group map on pred's device, number of groups, edges, the
+    largest frame distance of every group's columns: -1 for a group without columns)."""
+    group, frames = crw_hip.column_groups(pred.shape[-1], labelled, step, edges=edges, segments=segments, direction=direction)
+    edges = list(crw_hip.REACH_EDGES if edges is None else edges)
+    groups = len(edges) + 2
+    last = torch.full((groups,), -1, dtype=torch.int64).scatter_reduce(0, group.to(torch.int64), frames, 'amax', include_self=True)
+    return group.to(pred.device), groups, edges, last
+
+
+def _reach_of(row, groups, K, has_conf, edges, last):
+    """A host row of `crw_hip.confusion_grouped`'s outputs (counts [groups, K, K], the bit pattern of conf_sum [groups] when there
+    is a confidence map, dropped [4])."""
+    from metrics import Reach
+    n = groups * K * K
+    conf_sum = row[n:n + groups].view(torch.float64) if has_conf else None
+    return Reach(row[:n].view(groups, K, K), conf_sum, _dropped(row[n + groups * has_conf:], K), edges=edges, last_frame=last)
+
+
+def _reach_maps(pred, seg, conf, mask):
+    if pred.dim() != 2:
+        raise ValueError(f'pred must be a [rows, cols] map (got shape {tuple(pred.shape)})')
+    if conf is not None and conf.numel() != pred.numel():
+        raise ValueError(f'conf {tuple(conf.shape)} and pred {tuple(pred.shape)} must cover the same pixels')
+    mask = {k: (_map2d(v, pred) if torch.is_tensor(v) else v) for k, v in mask.items()}
+    return _map2d(seg, pred), None if conf is None else _map2d(conf.to(pred.device), pred), mask
+
+
+def label_reach(pred, seg, dataset_id, labelled, step, segments=None, direction='both', edges=None, conf=None, remove_unc=True,
+                unc_seg=None, nclasses=None):
+    """How far do the labels travel?  The accuracy of the label map ``pred`` ([rows, cols]) against ``seg``, binned by the distance
+    of every column, in frames of ``step`` pixel columns, from the nearest labelled column of its own item -> ``metrics.Reach``.
+    ``labelled``, ``segments``, ``direction``, ``step``: what `labelled_columns` returns for a `segment` call, or a caller's own
+    (`crw_hip.column_groups` has the definition and ``edges``).  ``conf``: the map's confidences, for the mean confidence per
+    group.  `evaluate`'s arguments and mask rules, passed through as arguments of the one ``crw_hip.confusion_grouped`` call: the
+    pixels it counts are the pixels `evaluate` counts.  A surviving label outside 0 ... K-1 raises ``crw_hip.LabelError``; a
+    surviving confidence that is NaN or outside [0, 1] is counted in ``dropped[2]`` and in no group."""
+    K, seg, mask = _report_rules(pred, seg, dataset_id, remove_unc, unc_seg, nclasses)
+    seg, conf, mask = _reach_maps(pred, seg, conf, mask)
+    group, groups, edges, last = _reach_groups(pred, labelled, step, segments, direction, edges)
+    counts, conf_sum, dropped = crw_hip.confusion_grouped(seg, pred, K, group, groups, conf=conf, **mask)
+    parts = [counts.reshape(-1)] + ([conf_sum.view(torch.int64)] if conf is not None else []) + [dropped]
+    return _reach_of(torch.cat(parts).cpu(), groups, K, conf is not None, edges, last)  # the one copy
+
+
+def label_reach_sweep(pred, seg, dataset_id, labelled, step, segments=None, direction='both', edges=None, conf=None, remove_unc=True,
+                      unc_seg=None, nclasses=None):
+    """`label_reach` for the G maps of `segment_sweep` (pred [G, rows, cols], conf [G, rows, cols] or None) -> G ``metrics.Reach``:
+    one group map, G `crw_hip.confusion_grouped` calls queued back to back, ONE copy of all counts to the host at the end, like
+    `evaluate_sweep`.  Same mask rules; a label outside 0 ... K-1 that survives the mask in any map raises ``crw_hip.LabelError``."""
+    if pred.dim() != 3 or pred[0].numel() != seg.numel():
+        raise ValueError(f'pred {tuple(pred.shape)} must be G [rows, cols] maps covering the pixels of seg {tuple(seg.shape)}')
+    if conf is not None and (conf.shape[0] != pred.shape[0] or conf.numel() != pred.numel()):
+        raise ValueError(f'conf {tuple(conf.shape)} and pred {tuple(pred.shape)} must cover the same pixels')
+    K, seg, mask = _report_rules(pred[0], seg, dataset_id, remove_unc, unc_seg, nclasses)
+    seg, _, mask = _reach_maps(pred[0], seg, None, mask)
+    group, groups, edges, last = _reach_groups(pred, labelled, step, segments, direction, edges)
+    confs = [None] * pred.shape[0] if conf is None else conf.to(pred.device)
+    outs = [crw_hip.confusion_grouped(seg, p, K, group, groups, conf=c, **mask) for p, c in zip(pred, confs)]
+    host = _host_rows([(n,) + ((s.view(torch.int64),) if s is not None else ()) + (d,) for n, s, d in outs])
+    return [_reach_of(row, groups, K, conf is not None, edges, last) for row in host]
+
+
 # the reference's three per-dataset drivers (scripts/test/test_mc1.py:19-30, test_mc3.py:19-33, test_sharad.py:19-32): argparse
 # defaults, the class count and encoder they hard-code, and the change points test_mc3 / test_sharad set by hand before correcting
 DRIVERS = {

@@ -298,6 +298,97 @@ class Horizons:
         return text
 
 
+class Reach:
+    """How far do the labels travel?  Accuracy against the distance, in frames, from the nearest labelled trace: one confusion
+    matrix per group of columns, from the [groups, K, K] counts, the [groups] confidence sums (None without a confidence map) and
+    the dropped quadruple of ``crw_hip.confusion_grouped`` under the column groups of ``crw_hip.column_groups`` (``edges``: its
+    edges; group 0 is the labelled columns themselves, group len(edges) + 1 the columns no labelled column reaches).
+
+    ``last_frame`` [groups]: the largest frame distance among each group's columns (-1: the group has no column), so that a
+    group the map only partly fills is reported up to the distance it holds.  Per group g: frames[g] = (first, last) frame distance
+    (None for the unreached group), pixels / correct [groups] int64, accuracy / mean_iou / mean_confidence [groups] float64 -- NaN
+    for an empty group, mean_iou over the classes present in the group, mean_confidence NaN throughout without confidences.
+    dropped = (masked, invalid label, invalid confidence, excluded column) or None."""
+
+    def __init__(self, counts, conf_sum=None, dropped=None, edges=crw_hip.REACH_EDGES, last_frame=None):
+        host = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        counts = np.asarray(host(counts), dtype=np.int64)
+        self.edges = [int(e) for e in edges]
+        if counts.ndim != 3 or counts.shape[1] != counts.shape[2] or counts.shape[0] != len(self.edges) + 2:
+            raise ValueError(f"counts must be [len(edges) + 2, K, K] (got shape {counts.shape} for {len(self.edges)} edges)")
+        if (counts < 0).any():
+            raise ValueError("counts must be non-negative")
+        self.counts, self.groups, self.K = counts, counts.shape[0], counts.shape[1]
+        self.unreached = self.groups - 1
+        self.dropped = None if dropped is None else tuple(int(v) for v in host(dropped))
+        self.conf_sum = None if conf_sum is None else np.asarray(host(conf_sum), dtype=np.float64).reshape(-1)
+        if self.conf_sum is not None and self.conf_sum.shape[0] != self.groups:
+            raise ValueError(f"conf_sum must hold one sum per group (got {self.conf_sum.shape[0]} for {self.groups} groups)")
+        first = [0] + self.edges
+        nominal = [e - 1 for e in self.edges] + [None]
+        held = [None] * self.groups if last_frame is None else [int(v) for v in host(last_frame)]
+        if len(held) != self.groups:
+            raise ValueError(f"last_frame must hold one distance per group (got {len(held)} for {self.groups} groups)")
+        self.frames = []
+        for g in range(self.groups - 1):
+            last = nominal[g] if held[g] is None or held[g] < 0 else held[g]
+            if last is not None and not first[g] <= last <= (last if nominal[g] is None else nominal[g]):
+                raise ValueError(f"group {g} holds frame distances {first[g]} ... {nominal[g]} (last_frame says {last})")
+            self.frames.append((first[g], last))
+        self.frames.append(None)
+        self.pixels = counts.sum((1, 2))
+        self.correct = np.trace(counts, axis1=1, axis2=2)
+        filled = self.pixels > 0
+        nan = np.full(self.groups, np.nan)
+        self.accuracy, self.mean_confidence = nan.copy(), nan.copy()
+        np.divide(self.correct, self.pixels, out=self.accuracy, where=filled)
+        if self.conf_sum is not None:
+            np.divide(self.conf_sum, self.pixels, out=self.mean_confidence, where=filled)
+        self.mean_iou = np.array([Report(counts[g]).mean_iou if filled[g] else np.nan for g in range(self.groups)])
+        self.total = int(self.pixels.sum())
+
+    def report(self, g):
+        """``metrics.Report`` of group g: the per-class scores of its pixels."""
+        return Report(self.counts[g], None if self.dropped is None else self.dropped[:2])
+
+    def reach_at(self, accuracy):
+        """The last frame distance of the longest unbroken run of groups, from group {1} on, that each have at least ``accuracy``;
+        empty groups are skipped, the unreached group is never counted, and the result is 0 when the first filled group fails."""
+        reach = 0
+        for g in range(1, self.unreached):
+            if not self.pixels[g]:
+                continue
+            if not self.accuracy[g] >= accuracy:
+                break
+            reach = self.frames[g][1] if self.frames[g][1] is not None else self.frames[g][0]
+        return int(reach)
+
+    def _name(self, g):
+        if g == self.unreached:
+            return "unreached"
+        a, b = self.frames[g]
+        return "{}-".format(a) if b is None else str(a) if a == b else "{}-{}".format(a, b)
+
+    def to_dict(self):
+        lst = lambda a: [float(v) for v in a]
+        ints = lambda a: [int(v) for v in a]
+        d = dict(groups=self.groups, K=self.K, edges=list(self.edges), frames=[None if f is None else list(f) for f in self.frames],
+                 pixels=ints(self.pixels), correct=ints(self.correct), accuracy=lst(self.accuracy), mean_iou=lst(self.mean_iou),
+                 mean_confidence=lst(self.mean_confidence), total=self.total)
+        if self.dropped is not None:
+            d["dropped"] = dict(masked=self.dropped[0], invalid=self.dropped[1], invalid_confidence=self.dropped[2],
+                                excluded=self.dropped[3])
+        return d
+
+    def __str__(self, digits=4):
+        num = lambda v: "{:>10}".format("-") if v != v else "{:>10.{d}f}".format(v, d=digits)
+        text = "{:>13} {:>12} {:>12} {:>10} {:>10} {:>10}\n\n".format("frames", "pixels", "correct", "accuracy", "mean IoU", "mean conf")
+        for g in range(self.groups):
+            text += "{:>13} {:>12} {:>12} {} {} {}\n".format(self._name(g), int(self.pixels[g]), int(self.correct[g]), num(self.accuracy[g]),
+                                                            num(self.mean_iou[g]), num(self.mean_confidence[g]))
+        return text
+
+
 class HorizonBars:
     """Error bars of the ordered decode's horizon picks against a reference (``inference.horizon_bars``), per boundary k = 1 ...
     S-1 over the ``n`` columns in which the reference has the boundary: ``mae`` of the pick, ``mean_bar`` (the mean error bar,

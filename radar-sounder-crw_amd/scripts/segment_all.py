@@ -61,6 +61,11 @@ Differences from the scripts:
     radargram only, encoder in eval mode (test.py:42), forward seed ``seg[:rg_h, :W]``, ``change_idx = seq_length - 2`` when none
     is found, no ``try`` around the correction.  test.py saves and scores nothing; here the map is saved and scored like
     test_all's (``--remove_unc`` applies), against the reference map's first ``rg_len`` columns.
+
+``--reach`` (not with ``--single`` or ``--correction true``): after the other tables, the accuracy against the distance, in frames, from
+the nearest labelled trace (``inference.label_reach`` under ``inference.labelled_columns``; ``--reach_edges E ...``: the first frame
+distance of every group behind {0}; ``--reach_accuracy A``, default 0.9: the accuracy of the printed reach); ``--report_json`` gains a
+``reach`` key.
 """
 import argparse
 import json
@@ -156,6 +161,11 @@ def get_args_parser():
                    help="centre the bank's features and every item's by their own means before the normalisation (needs a memory bank)")
     p.add_argument('--memory_bias', default=None, type=float, metavar='X',
                    help='add X to the cosine of the long-term keys (needs a memory bank; 0)')
+    p.add_argument('--reach', action='store_true',
+                   help='also print the accuracy against the distance, in frames, from the nearest labelled trace')
+    p.add_argument('--reach_edges', default=None, nargs='+', type=int, metavar='E',
+                   help='first frame distance of every group behind {0} (1 2 3 5 9 17 33 65 129 257)')
+    p.add_argument('--reach_accuracy', default=None, type=float, metavar='A', help='the accuracy of the printed reach (0.9)')
     return p
 
 
@@ -163,6 +173,7 @@ HORIZON_FLAGS = ('horizons', 'min_run', 'tol', 'row_spacing', 'row_unit', 'save_
 POSTERIOR_FLAGS = ('posterior', 'floor', 'save_posterior')
 ANCHOR_FLAGS = ('anchors', 'anchor_every', 'anchor_context')
 SUGGEST_FLAGS = ('suggest_anchors', 'suggest_gap', 'suggest_top')
+REACH_FLAGS = ('reach', 'reach_edges', 'reach_accuracy')
 MEMORY_FLAGS = ('memory_cols', 'memory_bank', 'save_memory_bank', 'seedless', 'memory_align', 'memory_bias')
 
 
@@ -190,6 +201,27 @@ def check_memory_flags(args):
         raise SystemExit('--memory_cols / --memory_bank do not combine with --anchor_context restart or --suggest_anchors')
     if args.seedless and args.correction:
         raise SystemExit('--seedless and --correction do not combine: the correction is a re-seed from the reference map')
+    return True
+
+
+def check_reach_flags(args):
+    """The flags ``--reach``, ``--reach_edges`` and ``--reach_accuracy`` (a namespace from before them has none) -> whether the
+    table is asked for."""
+    reach = getattr(args, 'reach', False)
+    edges, accuracy = getattr(args, 'reach_edges', None), getattr(args, 'reach_accuracy', None)
+    if not reach:
+        if edges is not None or accuracy is not None:
+            raise SystemExit('--reach_edges and --reach_accuracy need --reach')
+        return False
+    if args.single:
+        raise SystemExit('--reach is not available with --single')
+    if args.correction:
+        raise SystemExit('--reach and --correction true do not combine: whether a correction re-seeded an item is not in the result')
+    if edges is not None and (any(e < 1 for e in edges) or any(b <= a for a, b in zip(edges, edges[1:])) or len(edges) > 62):
+        raise SystemExit(f'--reach_edges {edges}: at most 62 strictly increasing integers >= 1')
+    if accuracy is not None and not 0 <= accuracy <= 1:
+        raise SystemExit(f'--reach_accuracy {accuracy}: 0 ... 1')
+    args.reach_accuracy = 0.9 if accuracy is None else accuracy
     return True
 
 
@@ -389,6 +421,9 @@ def main(args):
         hidden += MEMORY_FLAGS
     elif args.memory_align is None and args.memory_bias is None:  # likewise: a bank as it is without the two
         hidden += ('memory_align', 'memory_bias')
+    reach = check_reach_flags(args)
+    if not reach:  # likewise
+        hidden += REACH_FLAGS
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -489,6 +524,18 @@ def main(args):
     if suggest:
         print('')
         print(suggested_table(out['suggested']))
+    rch = None
+    if reach:
+        # a seedless item is labelled by its anchors alone: the bank's traces are no positions in this map
+        labelled, segments, direction, step = inference.labelled_columns(cols, T, args.patch_size, args.overlap, args.use_last,
+                                                                         out.get('anchor_cols', ()), seeds=not (banked and args.seedless))
+        rch = inference.label_reach(final, seg[:, :cols], args.dataset, labelled, step, segments=segments, direction=direction,
+                                    edges=args.reach_edges, conf=out.get('conf'), remove_unc=args.remove_unc,
+                                    unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses)
+        print('')
+        print(f'Accuracy against the distance from the nearest labelled trace (frames of {step} columns, {direction}):')
+        print(rch)
+        print(f'Reach at accuracy {args.reach_accuracy:g}: {rch.reach_at(args.reach_accuracy)} frames')
     t_all = time.time() - tim
     print('\nTime elapsed (inference + metrics):', t_all)
     if args.report_json:
@@ -518,6 +565,9 @@ def main(args):
         if banked:
             d.update(memory_traces=out['memory_traces'], seedless=out['seedless'], memory_align=out['memory_align'],
                      memory_bias=out['memory_bias'])
+        if rch is not None:
+            d['reach'] = dict(rch.to_dict(), step=step, direction=direction, at_accuracy=args.reach_accuracy,
+                              reach=rch.reach_at(args.reach_accuracy))
         if suggest:
             d['suggested_anchors'] = dict(per_radargram=suggest, min_gap=args.suggest_gap, top=args.suggest_top,
                                           picks=[dict(p, columns=list(p['columns'])) for picks in out['suggested'] for p in picks])

@@ -35,7 +35,12 @@ before them.
 the same anchors for every configuration (``inference.segment_sweep(..., anchors=(map, columns))``); one line says how many traces
 are anchored and ``--report_json`` gains ``anchors``; ``--anchor_context restart``: ``segment_all.py``'s, one set of origins for
 every configuration.  Without them the output is what it was.
-CRW_SWEEP_PER_CONFIG=1: the label propagation as a loop over the configurations (same maps; the A/B arm)."""
+CRW_SWEEP_PER_CONFIG=1: the label propagation as a loop over the configurations (same maps; the A/B arm).
+
+``--reach``: one more column, how many frames the labels of every configuration travel at ``--reach_accuracy`` (default 0.9;
+``inference.label_reach_sweep``), the best configuration's table after the others, a ``reach`` entry per configuration in
+``--report_json``, and ``--select reach`` (offered only with ``--reach``) -- the LARGEST wins, ties go to the first in grid order.
+"""
 import argparse
 import json
 import os
@@ -63,11 +68,13 @@ SELECT_HORIZON = {'horizon_mae': lambda h: h.mean_mae('top')}
 # scores of the posterior map's calibration (``--posterior``): lower is better
 SELECT_POST = {'post_ece': lambda c: c.ece, 'post_aurc': lambda c: c.aurc}
 POSTERIOR_FLAGS = ('posterior', 'floor')
+# score of the reach table (``--reach``): frames, the LARGEST wins
+SELECT_REACH = ('reach',)
 
 
-def get_args_parser(horizons=False, posterior=False):
+def get_args_parser(horizons=False, posterior=False, reach=False):
     """``horizons``: whether ``--horizons`` is on the command line -- only then is there a horizon score to select by, and only
-    then does ``--select`` offer ``horizon_mae``.  ``posterior``: likewise for ``--posterior`` and ``post_ece`` / ``post_aurc``."""
+    then does ``--select`` offer ``horizon_mae``.  ``posterior``: likewise for ``--posterior`` and ``post_ece`` / ``post_aurc``, and ``reach`` for ``--reach`` and ``reach``."""
     p = argparse.ArgumentParser('CRW label-propagation sweep (launch_test_batch.sh over test_all.py)', add_help=True)
     p.add_argument('--model', default=None, type=int, help='0=CNN,1=Resnet18')
     p.add_argument('--dataset', default=None, type=int, help='0=MCORDS1,1=Miguel,3=SHARAD')
@@ -93,9 +100,9 @@ def get_args_parser(horizons=False, posterior=False):
     p.add_argument('--unc_seg_path', default=None, help="dataset 0's map with the uncertain class 4 (the reference's dataset id 2)")
     p.add_argument('--synthetic', default=None, nargs=2, type=int, metavar=('H', 'W'))
     p.add_argument('--select', default='macro_f1', choices=sorted(SELECT) + sorted(SELECT_CAL) + (sorted(SELECT_HORIZON) if horizons else [])
-                   + (sorted(SELECT_POST) if posterior else []),
+                   + (sorted(SELECT_POST) if posterior else []) + (list(SELECT_REACH) if reach else []),
                    help='the score the best configuration is picked by (ece, aurc: the lowest, need --confidence; horizon_mae: the '
-                        'lowest, needs --horizons; post_ece, post_aurc: the lowest, need --posterior)')
+                        'lowest, needs --horizons; post_ece, post_aurc: the lowest, need --posterior; reach: the largest, needs --reach)')
     p.add_argument('--reports', action='store_true', help='print the full report of every configuration')
     p.add_argument('--report_json', default=None, metavar='FILE')
     p.add_argument('--save_maps', action='store_true', help='save every predicted_map_r{r}_t{t}_k{k}.pt (int8)')
@@ -124,6 +131,11 @@ def get_args_parser(horizons=False, posterior=False):
                    help="evaluation: the reference map's column at the first pixel of every K-th frame as anchors (needs --context sliding)")
     p.add_argument('--anchor_context', default=None, choices=('clamp', 'restart'),
                    help='restart: a fully labelled anchor trace restarts the propagation context, like a seed (needs anchors; clamp)')
+    p.add_argument('--reach', action='store_true',
+                   help='how many frames the labels of every configuration travel at --reach_accuracy (a column)')
+    p.add_argument('--reach_edges', default=None, nargs='+', type=int, metavar='E',
+                   help='first frame distance of every group behind {0} (1 2 3 5 9 17 33 65 129 257)')
+    p.add_argument('--reach_accuracy', default=None, type=float, metavar='A', help='the accuracy of the reach (0.9)')
     return p
 
 
@@ -137,6 +149,8 @@ def check_confidence_flags(args):
         raise SystemExit(f'--bins {args.bins}: 1 ... 64')
     if not args.horizons and args.select in SELECT_HORIZON:
         raise SystemExit(f'--select {args.select} needs --horizons')
+    if not getattr(args, 'reach', False) and args.select in SELECT_REACH:
+        raise SystemExit(f'--select {args.select} needs --reach')
     if args.horizons and (args.min_run < 1 or args.tol < 0):
         raise SystemExit('--min_run is at least 1, --tol at least 0')
     return check_posterior_flags(segment_all.check_decode_flags(args))
@@ -197,6 +211,9 @@ def main(args):
     anchor_context = getattr(args, 'anchor_context', None)
     if anchor_context is None:  # likewise
         hidden += ('anchor_context',)
+    reach = segment_all.check_reach_flags(args)
+    if not reach:  # likewise
+        hidden += segment_all.REACH_FLAGS
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -255,20 +272,31 @@ def main(args):
         pcals = inference.calibration_sweep(final, out['post'], seg[:, :cols], args.dataset, remove_unc=args.remove_unc,
                                             unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses, bins=args.bins)
         bars = inference.horizon_bars_sweep(out['horizon'], seg[:, :cols], out['order'])
+    rchs = None
+    if reach:
+        labelled, segments, direction, step = inference.labelled_columns(cols, T, args.patch_size, args.overlap, args.use_last,
+                                                                         out.get('anchor_cols', ()))
+        rchs = inference.label_reach_sweep(final, seg[:, :cols], args.dataset, labelled, step, segments=segments, direction=direction,
+                                           edges=args.reach_edges, conf=out.get('conf'), remove_unc=args.remove_unc,
+                                           unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses)
     print('{:>6} {:>7} {:>4} {:>9} {:>9} {:>11} {:>9}'.format('radius', 'temp', 'knn', 'accuracy', 'macro f1', 'weighted f1', 'mean iou')
           + (' {:>8} {:>8}'.format('ece', 'aurc') if cals else '') + (' {:>11}'.format('horizon mae') if hzs else '')
-          + (' {:>8} {:>9}'.format('post ece', 'bar cover') if pcals else ''))
+          + (' {:>8} {:>9}'.format('post ece', 'bar cover') if pcals else '') + (' {:>6}'.format('reach') if rchs else ''))
     for g, (cfg, r) in enumerate(zip(sweep.configs, reports)):
         print('{:>6} {:>7g} {:>4} {:>9.4f} {:>9.4f} {:>11.4f} {:>9.4f}'.format(cfg['RADIUS'], cfg['TEMP'], cfg['KNN'], r.accuracy,
                                                                                r.macro['f1'], r.weighted['f1'], r.mean_iou)
               + (' {:>8.4f} {:>8.4f}'.format(cals[g].ece, cals[g].aurc) if cals else '')
               + (' {:>11.4f}'.format(hzs[g].mean_mae('top')) if hzs else '')
-              + (' {:>8.4f} {:>9.4f}'.format(pcals[g].ece, bars[g].mean_coverage) if pcals else ''))
+              + (' {:>8.4f} {:>9.4f}'.format(pcals[g].ece, bars[g].mean_coverage) if pcals else '')
+              + (' {:>6}'.format(rchs[g].reach_at(args.reach_accuracy)) if rchs else ''))
         if args.reports:
             print(r)
             print(r.matrix_str())
             print('')
-    if args.select in SELECT_POST:
+    if args.select in SELECT_REACH:  # frames: the largest wins, ties go to the first in grid order
+        scores = [float(r.reach_at(args.reach_accuracy)) for r in rchs]
+        best = pick_best(scores)
+    elif args.select in SELECT_POST:
         scores = [float(SELECT_POST[args.select](c)) for c in pcals]
         best = pick_best(scores, lower_is_better=True)
     elif args.select in SELECT_HORIZON:
@@ -296,6 +324,10 @@ def main(args):
         print(f'Calibration (posterior of the ordered decode, floor {args.floor:g}):')
         print(pcals[best])
         print(bars[best])
+    if rchs:
+        print('')
+        print(f'Accuracy against the distance from the nearest labelled trace (frames of {step} columns, {direction}):')
+        print(rchs[best])
     t_all = time.time() - tim
     print('\nTime elapsed (inference + metrics):', t_all)
     if args.report_json:
@@ -316,6 +348,10 @@ def main(args):
             for c, cal, b in zip(d['configs'], pcals, bars):
                 c['posterior'] = dict(calibration=cal.to_dict(), horizon_bars=b.to_dict())
             d['floor'] = args.floor
+        if rchs:
+            for c, r in zip(d['configs'], rchs):
+                c['reach'] = dict(r.to_dict(), reach=r.reach_at(args.reach_accuracy))
+            d['reach'] = dict(step=step, direction=direction, at_accuracy=args.reach_accuracy)
         if args.upsample != 'nearest':
             d['upsample'] = args.upsample
         if args.context != 'reference':
@@ -336,4 +372,5 @@ def main(args):
 
 if __name__ == '__main__':
     torch.manual_seed(11)  # the scripts seed at import (test_all.py:14)
-    main(get_args_parser(horizons='--horizons' in sys.argv[1:], posterior='--posterior' in sys.argv[1:]).parse_args())
+    main(get_args_parser(horizons='--horizons' in sys.argv[1:], posterior='--posterior' in sys.argv[1:],
+                         reach='--reach' in sys.argv[1:]).parse_args())
