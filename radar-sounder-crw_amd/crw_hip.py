@@ -187,6 +187,11 @@ REACH_SIGNATURES = {
     "crw_confusion_grouped": (_c_int, [_p, _c_int, _p, _c_int, _p, _c_int, _p, _c_int, _c_int, _c_sz, _p] + [_c_int] * 5 + [_p, _p, _p, _p, _c_sz, _p]),
 }
 
+# include/crw_hip_sweepmem.h, likewise: a memory bank in the parameter sweep -- crw_labelprop_propagate_long for G configurations (optional: `has_sweep_memory()`)
+SWEEPMEM_SIGNATURES = {
+    "crw_labelprop_propagate_long_batch": (_c_int, [_p, _p, _c_sz] + [_c_int] * 8 + [_p, _p, _p]),
+}
+
 # include/crw_hip_routes.h, likewise: the route log -- which selector branch launched (optional: `has_routes()`; host pointers)
 ROUTES_SIGNATURES = {
     "crw_routes_clear": (_c_int, []),
@@ -245,6 +250,9 @@ ALIGN_ENTRY_POINTS = tuple(ALIGN_SIGNATURES)
 # likewise: the grouped confusion matrix (`has_reach()`, `confusion_grouped`)
 REACH_ENTRY_POINTS = tuple(REACH_SIGNATURES)
 
+# likewise: the batched propagation with a bank of long-term frames (`has_sweep_memory()`, `labelprop_propagate_batch(n_long=)`)
+SWEEP_MEMORY_ENTRY_POINTS = tuple(SWEEPMEM_SIGNATURES)
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 ANCHOR_CONTEXTS = ("clamp", "restart")  # what a fully labelled anchor trace does to the frames behind it
 
@@ -256,7 +264,7 @@ OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_E
                          "posterior": POSTERIOR_ENTRY_POINTS, "posterior_batch": POSTERIOR_BATCH_ENTRY_POINTS,
                          "conv_chain": CONV_CHAIN_ENTRY_POINTS, "anchor_restart": ANCHOR_RESTART_ENTRY_POINTS,
                          "routes": ROUTES_ENTRY_POINTS, "novelty": NOVELTY_ENTRY_POINTS, "long_memory": LONG_MEMORY_ENTRY_POINTS,
-                         "align": ALIGN_ENTRY_POINTS, "reach": REACH_ENTRY_POINTS}
+                         "align": ALIGN_ENTRY_POINTS, "reach": REACH_ENTRY_POINTS, "sweep_memory": SWEEP_MEMORY_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -273,7 +281,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         missing = {n for names in OPTIONAL_ENTRY_POINTS.values() for n in names if not hasattr(handle, n)}
         for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES, **RESTART_SIGNATURES, **ROUTES_SIGNATURES,
-                                   **NOVELTY_SIGNATURES, **LONGMEM_SIGNATURES, **ALIGN_SIGNATURES, **REACH_SIGNATURES}.items():
+                                   **NOVELTY_SIGNATURES, **LONGMEM_SIGNATURES, **ALIGN_SIGNATURES, **REACH_SIGNATURES, **SWEEPMEM_SIGNATURES}.items():
             if name in missing:
                 continue
             fn = getattr(handle, name)
@@ -323,6 +331,7 @@ has_novelty, _novelty_lib = _optional("novelty", "the context-novelty entry poin
 has_long_memory, _long_memory_lib = _optional("long_memory", "the entry points that take n_long long-term frames")
 has_align, _align_lib = _optional("align", "the segment-centred normalisation and the biased long-memory lists")
 has_reach, _reach_lib = _optional("reach", "the grouped confusion matrix's entry points")
+has_sweep_memory, _sweep_memory_lib = _optional("sweep_memory", "the batched propagation that takes n_long long-term frames")
 
 MAX_ROUTES = 256  # csrc/crw_common.h
 
@@ -998,15 +1007,36 @@ def labelprop_sweep_weights(V, knns, out=None):
     return W
 
 
-def labelprop_propagate_batch(seed, W, I, T, N, M, first_frame=1, cxt_size=None, L=None, pred=None, context="reference", origin=None):
+def sweep_memory_fits(N, M, n_long):
+    """crw_labelprop_propagate_long_batch's one condition per geometry (include/crw_hip_sweepmem.h): the n_long long-term frames and
+    a ring of two fit the 150 KiB of LDS"""
+    return (int(n_long) + 2) * N * M * 4 <= 150 * 1024
+
+
+def labelprop_propagate_batch(seed, W, I, T, N, M, first_frame=1, cxt_size=None, L=None, pred=None, context="reference", origin=None,
+                              n_long=None):
     """G configurations' `labelprop_gather(..., cxt_size=cxt_size, context=context)` in one call: W [G, T-first_frame, knn, N]; I the same shape, or
     [T-first_frame, knn, N] shared by all -> (L [G, T*N, M], pred [G, N, T]), slice g bitwise what the per-configuration call
     gives on W[g] (shorter lists padded with zero weights).  seed None: L's frames before first_frame are filled by the caller.
     origin (needs context='sliding'): ONE [T] int32 origin array for the G configurations -- crw_labelprop_propagate_origin_batch;
-    CRW_ANCHORS_RESTART_SEGMENTED=1 (read per call): the segmented `labelprop_gather(origin=)`, configuration by configuration."""
+    CRW_ANCHORS_RESTART_SEGMENTED=1 (read per call): the segmented `labelprop_gather(origin=)`, configuration by configuration.
+    n_long (needs context='sliding'; no origin): the lists are `labelprop_topk_scores(..., n_long=n_long)`'s and the first n_long
+    frames are long-term (include/crw_hip_sweepmem.h) -- ONE crw_labelprop_propagate_long_batch call.  That entry point takes no
+    seed: with one, its one-hot rows and pred[:, :, 0] are written here first; the rows of L before first_frame are the caller's.
+    Where the bank and a ring of two frames do not fit LDS (`sweep_memory_fits`), or N * M * 4 > 30 KiB: crw_labelprop_propagate_long,
+    configuration by configuration, the same bits.  None: the call is what it was."""
     if cxt_size is None:
         raise ValueError("cxt_size (the context size the lists were made with) is required")
     check_context(context)
+    if n_long is not None:
+        if origin is not None:
+            raise ValueError("n_long and origin are not combined: a restart's long-term frame is its origin alone")
+        if context != "sliding":
+            raise ValueError("n_long needs context='sliding' (and cxt_size): under the reference rule a late frame never reads a label "
+                             "later than frame cxt_size, so beyond cxt_size + 1 frames it would not read the bank's rows consistently")
+        n_long = int(n_long)
+        if not 1 <= n_long <= T - 1:
+            raise ValueError(f"n_long must be in 1 .. T - 1 = {T - 1} (got {n_long})")
     if origin is not None:
         if context != "sliding":
             raise ValueError("origin needs context='sliding' (and cxt_size): the restart rule is defined on the frames the lists were "
@@ -1029,6 +1059,20 @@ def labelprop_propagate_batch(seed, W, I, T, N, M, first_frame=1, cxt_size=None,
         pred = torch.zeros(G, N, T, device=W.device, dtype=torch.float32)
     if tuple(L.shape) != (G, T * N, M) or tuple(pred.shape) != (G, N, T):
         raise RuntimeError(f"L must be {(G, T * N, M)} and pred {(G, N, T)} (got {tuple(L.shape)}, {tuple(pred.shape)})")
+    if n_long is not None:
+        if seed is not None:  # frame 0 from the seed, as the entry points with a seed argument write it
+            L[:, :N] = (seed[:, None] == torch.arange(M, device=seed.device)).to(L.dtype)
+            pred[:, :, 0] = seed
+        if not sweep_memory_fits(N, M, n_long) or N * M * 4 > 30 * 1024:  # the one-configuration routes, slice by slice
+            for g in range(G):
+                labelprop_gather(None, W[g], I[g] if stride else I, T, N, M, first_frame, L[g], pred[g], cxt_size, "sliding",
+                                 n_long=n_long, route="auto")
+            return L, pred
+        _check(_sweep_memory_lib().crw_labelprop_propagate_long_batch(_dev(W, "W"), _dev(I, "I", torch.int32), stride, G, T, N, M, knn,
+                                                                      int(first_frame), int(cxt_size), n_long, _dev(L, "L"),
+                                                                      _dev(pred, "pred"), _stream()),
+               "crw_labelprop_propagate_long_batch")
+        return L, pred
     if origin is not None:
         if anchors_restart_segmented():
             for g in range(G):

@@ -16,6 +16,7 @@
 #include "crw_hip_restart.h"
 #include "crw_hip_longmem.h"
 #include "crw_hip_align.h"
+#include "crw_hip_sweepmem.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -1055,32 +1056,44 @@ __global__ __launch_bounds__(256) void labelprop_sweep_weights_kernel(const floa
 constexpr int PB_CH = 16;
 // SLIDE: slide_row() on every index before the clamp (crw_labelprop_propagate_sliding_batch); ORG: slide_row_at() with the frame's
 // origin, one origin array for the G configurations (crw_labelprop_propagate_origin_batch)
-template <bool SLIDE, bool ORG>
+// LM (crw_labelprop_propagate_long_batch, include/crw_hip_sweepmem.h): K = n_long long-term frames, [K][NM] in front of the ring
+// [R][NM].  Frame f < K sits at slot f for good (the caller's are copied in, frames first_frame .. K - 1 of the call are computed
+// into their slots like any other), frame f >= K at K + (f - K) % R; the ring holds frames this launch computed and nothing else.
+// slide_row_at<false, true> clamps an index into the list it addresses and makes it a row of L below frame n; `first`, `old` and the
+// ring's epochs are then those of the other instances with K * N in the place of N and frames counted from K.  No seed.
+template <bool SLIDE, bool ORG, bool LM = false>
 __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float *__restrict__ seed, const float *__restrict__ W,
                                                                      const int32_t *__restrict__ I, long i_stride, int T, int N, int M,
                                                                      int knn, int first_frame, int last_frame, float *L,
                                                                      float *__restrict__ pred, int R, int cxt,
-                                                                     const int32_t *__restrict__ origin) {
+                                                                     OriginArg<LM> origin) {
+  static_assert(!LM || (SLIDE && !ORG), "a bank of long-term frames: the sliding rule, no origins");
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, nt = (int)blockDim.x, NM = N * M, KN = knn * N, g = blockIdx.x;
   W += (long)g * (T - first_frame) * KN;
   I += (long)g * i_stride;
   L += (long)g * T * NM;
   pred += (long)g * N * T;
-  float *l0 = sm, *ring = l0 + NM;  // [NM], [R][NM]
-  init_frame0<true, true>(seed, L, pred, l0, T, N, M, tid, nt);
+  const int K = long_frames<LM>(origin);
+  float *l0 = sm, *ring = l0 + (LM ? K * NM : NM);  // [NM] (LM: [K][NM]), [R][NM]
+  if constexpr (LM) {  // the long-term frames the caller filled
+    for (int it = tid; it < min(K, first_frame) * NM; it += nt) l0[it] = ld_l2(L + it);
+  } else {
+    init_frame0<true, true>(seed, L, pred, l0, T, N, M, tid, nt);
+  }
   __syncthreads();
   const int RNM = R * NM;
   for (int n = first_frame; n <= last_frame; ++n) {
     const float *Wn = W + (long)(n - first_frame) * KN;
     const int32_t *In = I + (long)(n - first_frame) * KN;
-    // frames [lo_f, n - 1] live in the ring; a frame f sits at flat offset (f % R) * NM
-    const int lo_f = max(first_frame, n - R + 1);
+    // frames [lo_f, n - 1] live in the ring; a frame f sits at flat offset (f % R) * NM (LM: ((f - K) % R) * NM)
+    const int lo_f = LM ? max(max(first_frame, K), n - R + 1) : max(first_frame, n - R + 1);
     const int lo_idx = lo_f * N;               // first label-list row that is in the ring
-    const int epoch_base = (n / R - 1) * RNM;  // flat offset of the older of the (at most) two ring epochs in view
+    // flat offset of the older of the (at most) two ring epochs in view (LM: in rows counted from frame K; unused while n < K)
+    const int epoch_base = LM ? (max(n - K, 0) / R - 1) * RNM + K * NM : (n / R - 1) * RNM;
     const int row_lim = n * N - 1;
-    const int org = ORG ? frame_origin(origin, n) : 0;
-    float *slot = ring + (n % R) * NM;
+    const int org = origin_at<ORG>(origin, n);
+    float *slot = LM ? (n < K ? l0 + n * NM : ring + ((n - K) % R) * NM) : ring + (n % R) * NM;
     for (int it = tid; it < NM; it += nt) {
       const int q = it / M, c = it % M;
       float p = 0.f;
@@ -1092,7 +1105,7 @@ __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float
 #pragma unroll
         for (int u = 0; u < PB_CH; ++u) {
           const int jj = min(j0 + u, knn - 1);
-          const int raw_i = SLIDE ? slide_row_at<ORG>(In[jj * N + q], n, org, N, cxt) : In[jj * N + q];
+          const int raw_i = SLIDE ? slide_row_at<ORG, LM>(In[jj * N + q], n, org, N, cxt, K) : In[jj * N + q];
           idx[u] = min(max(raw_i, 0), row_lim);  // in range whatever the lists hold (topk: < min(n, cxt + 1) * N)
           w[u] = Wn[jj * N + q];
         }
@@ -1101,8 +1114,8 @@ __global__ __launch_bounds__(1024) void labelprop_chain_batch_kernel(const float
           // frame 0 sits in l0 = sm[0, NM), the ring behind it; a label older than the ring comes from global memory
           int off = idx[u] * M + c - epoch_base;
           if (off >= RNM) off -= RNM;
-          const bool first = idx[u] < N, old = !first && idx[u] < lo_idx;
-          const int a = first ? idx[u] * M + c : (old ? 0 : NM + off);
+          const bool first = idx[u] < (LM ? K * N : N), old = !first && idx[u] < lo_idx;
+          const int a = first ? idx[u] * M + c : (old ? 0 : (LM ? K * NM : NM) + off);
           v[u] = sm[a];
           if (old) v[u] = ld_l2(L + (long)idx[u] * M + c);
         }
@@ -1372,6 +1385,15 @@ int launch_gather(const float *seed, const float *W, const int32_t *I, int T, in
   return check_launch();
 }
 
+// the route of a batch launch: one site per name, shared by launch_propagate_batch and launch_propagate_long_batch (the batch with a
+// bank of long-term frames is the sliding batch's route, as crw_labelprop_propagate_long goes through labelprop.slide_ring)
+template <bool SLIDE, bool ORG>
+void route_propagate_batch() {
+  if constexpr (ORG) CRW_ROUTE("labelprop.batch_slide_origin");
+  else if constexpr (SLIDE) CRW_ROUTE("labelprop.batch_slide");
+  else CRW_ROUTE("labelprop.batch_reference");
+}
+
 // SLIDE: every frame is chained (last = T - 1, no tail launch), the indices translated in the kernel
 template <bool SLIDE, bool ORG = false>
 int launch_propagate_batch(const float *seed, const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M, int knn,
@@ -1387,15 +1409,32 @@ int launch_propagate_batch(const float *seed, const float *W, const int32_t *I, 
     if (R > last + 1) R = last + 1;
     if (R < 2) R = 2;
     const int nt = (int)(NM >= 1024 ? 1024 : (NM + 63) / 64 * 64);
-    if constexpr (ORG) CRW_ROUTE("labelprop.batch_slide_origin");
-    else if constexpr (SLIDE) CRW_ROUTE("labelprop.batch_slide");
-    else CRW_ROUTE("labelprop.batch_reference");
+    route_propagate_batch<SLIDE, ORG>();
     const int rc = launch_big_lds<labelprop_chain_batch_kernel<SLIDE, ORG>>(dim3(G), dim3(nt), (size_t)(4 * NM * (R + 1)), s, seed, W, I,
                                                                             (long)i_stride, T, N, M, knn, first_frame, last, L, pred, (int)R,
                                                                             cxt_size, origin);
     if (rc != CRW_OK) return rc;
   }
   return launch_tail(W, I, (long)i_stride, G, T, N, M, knn, first_frame, t0, L, pred, s);
+}
+
+// the LM instance (crw_labelprop_propagate_long_batch): every frame is chained, n_long long-term frames and a ring of at least two in LDS
+int launch_propagate_long_batch(const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M, int knn, int first_frame,
+                                int cxt_size, int n_long, float *L, float *pred, crw_stream_t stream) {
+  crw::clear_stale_error();
+  if (bad_propagate_args(W, I, L, pred, T, N, M, knn, first_frame) || G < 1 || G > 65535 || knn > MAX_KNN || cxt_size < 1) return CRW_EINVAL;
+  if (n_long < 1 || n_long > T - 1 || first_frame < 1 || first_frame > T - 1) return CRW_EINVAL;
+  const long NM = (long)N * M;
+  if ((long)T * N >= (1L << 30) / M || NM * 4 > 30 * 1024) return CRW_EINVAL;  // as launch_propagate_batch
+  long R = (150L * 1024) / (4 * NM) - n_long;
+  if (R < 2) return CRW_EINVAL;  // n_long + 2 frames do not fit: one condition per geometry (N * M, n_long)
+  if (R > T - first_frame) R = T - first_frame;
+  if (R < 2) R = 2;
+  const int nt = (int)(NM >= 1024 ? 1024 : (NM + 63) / 64 * 64);
+  route_propagate_batch<true, false>();
+  return launch_big_lds<labelprop_chain_batch_kernel<true, false, true>>(dim3(G), dim3(nt), (size_t)(4 * NM * (R + n_long)), (hipStream_t)stream,
+                                                                         nullptr, W, I, (long)i_stride, T, N, M, knn, first_frame, T - 1, L,
+                                                                         pred, (int)R, cxt_size, LongFrames{n_long, 0});
 }
 
 }  // namespace
@@ -1517,6 +1556,12 @@ int crw_labelprop_propagate_long(const float *W, const int32_t *I, int T, int N,
   if (!ring) return launch_gather<true, false, true>(nullptr, W, I, T, N, M, knn, first_frame, cxt_size, L, pred, stream, nullptr, n_long);
   return launch_chain<true>(nullptr, W, I, T, N, M, knn, first_frame, T - 1, cxt_size, (int)R, chain_lds(R + n_long, NM), L, pred, nullptr,
                             (hipStream_t)stream, n_long);
+}
+
+// include/crw_hip_sweepmem.h: the LM instance of the batch kernel
+int crw_labelprop_propagate_long_batch(const float *W, const int32_t *I, size_t i_stride, int G, int T, int N, int M, int knn,
+                                       int first_frame, int cxt_size, int n_long, float *L, float *pred, crw_stream_t stream) {
+  return launch_propagate_long_batch(W, I, i_stride, G, T, N, M, knn, first_frame, cxt_size, n_long, L, pred, stream);
 }
 
 int crw_labelprop_sweep_weights(const float *V, int F, int kcap, int N, const int *knns, int nk, float *W, crw_stream_t stream) {

@@ -213,7 +213,10 @@ class LabelPropSweep(object):
     (radius outermost, knn innermost); ``propagate_all`` returns the label map of every configuration, each exactly that of
     ``LabelPropVOS_CRW(configs[g]).propagate_all``."""
 
-    def __init__(self, cxt_size, radii, temps, knns, context='reference'):
+    def __init__(self, cxt_size, radii, temps, knns, context='reference', biases=(0.0,)):
+        """biases: the values of `LabelPropVOS_CRW.propagate_all`'s memory_bias to sweep -- a fourth grid axis between temp and knn
+        (radius outermost, then temp, then bias, knn innermost), for `propagate_all(memory=)`.  Other than (0.0,) every cfg carries
+        its MEMORY_BIAS; with the default the dicts are what they were."""
         self.cxt_size = int(cxt_size)
         self.context = crw_hip.check_context(context)
         self.radii, self.temps, self.knns = [int(r) for r in radii], [float(t) for t in temps], [int(k) for k in knns]
@@ -221,8 +224,14 @@ class LabelPropSweep(object):
             raise ValueError("radii, temps and knns must each hold at least one value")
         if min(self.knns) < 1 or len(self.knns) > 16:
             raise ValueError("knns: 1 ... 16 values >= 1")
+        self.biases = [crw_hip.check_memory_bias(b) for b in biases]
+        if not self.biases:
+            raise ValueError("biases must hold at least one value")
         self.configs = [dict(CXT_SIZE=self.cxt_size, RADIUS=r, TEMP=t, KNN=k)
-                        for r in self.radii for t in self.temps for k in self.knns]
+                        for r in self.radii for t in self.temps for b in self.biases for k in self.knns]
+        if self.biases != [0.0]:  # (the key is absent without the axis: the dicts are what they were)
+            for i, cfg in enumerate(self.configs):
+                cfg['MEMORY_BIAS'] = self.biases[i // len(self.knns) % len(self.biases)]
         if self.context != 'reference':  # (the key is absent under the default rule: the dicts are what they were)
             for cfg in self.configs:
                 cfg['CONTEXT'] = self.context
@@ -235,9 +244,60 @@ class LabelPropSweep(object):
             raise RuntimeError(f"KNN={max(self.knns)} exceeds the number of nodes per frame ({h * w}); "
                                "torch.topk in the reference raises for the first frame as well")
 
-    def propagate_all(self, feats, seed, nclasses, grid_w=1, soft=False, anchors=None, anchor_context='clamp'):
+    def _propagate_memory(self, feats, seed, nclasses, grid_w, soft, anchors, anchor_context, memory):
+        """`propagate_all(memory=)`: `LabelPropVOS_CRW._propagate_memory`'s virtual item [bank traces..., item] for the whole grid.
+        Per (radius, temp, bias) one selection at kmax (`labelprop_topk_scores(n_long=K, long_bias=b)`) and one
+        `labelprop_sweep_weights`; the one-hot front rows go to every L[g]; ONE `labelprop_propagate_batch(n_long=K)`."""
+        T, N, C = feats.shape
+        mem_feats, labels = check_memory(memory, N, nclasses, self.context, anchor_context)
+        if grid_w != 1:
+            raise ValueError("memory is defined on N x 1 grids only")
+        self._check_grid(N, 1)
+        if anchors is not None:
+            crw_hip.check_anchors(anchors, T, N, nclasses)
+        if os.environ.get("CRW_SWEEP_PER_CONFIG") == "1":
+            akw = {} if anchors is None else dict(anchors=anchors)
+            outs = [LabelPropVOS_CRW(cfg).propagate_all(feats, seed, nclasses, memory=memory, memory_bias=cfg.get('MEMORY_BIAS', 0.0), **akw)
+                    for cfg in self.configs]
+            pred = torch.stack([o[0] for o in outs])
+            return (pred, torch.stack([o[1] for o in outs])) if soft else pred
+        B = mem_feats.shape[0]
+        front = labels if seed is None else torch.cat([labels, seed.to(labels.device).long()[None]])
+        K, Fv = front.shape[0], B + T
+        ehat = torch.cat([mem_feats.to(feats.dtype), feats]).contiguous()
+        nk, kmax, F = len(self.knns), max(self.knns), Fv - K
+        P = len(self.radii) * len(self.temps) * len(self.biases)
+        G = P * nk
+        W = torch.empty(P, nk, F, kmax, N, device=feats.device, dtype=torch.float32)
+        I = torch.empty(P, F, kmax, N, device=feats.device, dtype=torch.int32)
+        V = torch.empty(F, kmax, N, device=feats.device, dtype=torch.float32)
+        p = 0
+        for r in self.radii:
+            for t in self.temps:
+                for b in self.biases:
+                    bkw = dict(long_bias=b) if b != 0.0 else {}   # 0: the call as it is without the option
+                    crw_hip.labelprop_topk_scores(ehat, self.cxt_size, r, t, kmax, first_frame=K, out=(V, I[p]), n_long=K, route="auto", **bkw)
+                    crw_hip.labelprop_sweep_weights(V, self.knns, out=W[p])
+                    p += 1
+        if anchors is not None:  # (a library that has the long-memory entry points honours the marks)
+            shifted = torch.cat([torch.full((B, N), -1, dtype=torch.int8, device=anchors.device), anchors])   # B frames further down
+            crw_hip.mark_anchors(W.view(G, F, kmax, N), I, shifted, nclasses, K)
+        Ig = I[0] if P == 1 else I[:, None].expand(P, nk, F, kmax, N).reshape(G, F, kmax, N)
+        L = torch.empty(G, Fv * N, nclasses, device=feats.device, dtype=torch.float32)
+        pred = torch.zeros(G, N, Fv, device=feats.device, dtype=torch.float32)
+        front = front.to(feats.device)
+        L[:, :K * N] = (front.reshape(-1, 1) == torch.arange(nclasses, device=feats.device)).to(L.dtype)
+        pred[:, :, :K] = front.t().to(pred.dtype)
+        crw_hip.labelprop_propagate_batch(None, W.view(G, F, kmax, N), Ig, Fv, N, nclasses, first_frame=K, cxt_size=self.cxt_size, L=L,
+                                          pred=pred, context='sliding', n_long=K)
+        pred = pred[:, :, B:].contiguous()
+        return (pred, L[:, B * N:].contiguous()) if soft else pred
+
+    def propagate_all(self, feats, seed, nclasses, grid_w=1, soft=False, anchors=None, anchor_context='clamp', memory=None):
         """feats [T,N,C] (normalised features), seed [N] float class ids of frame 0 -> pred [G,N,T] float class ids, G =
-        len(configs).  anchor_context: `LabelPropVOS_CRW.propagate_all`'s -- under 'restart' ONE origin array serves every selection
+        len(configs).  memory (needs context 'sliding', anchor_context 'clamp', an N x 1 grid): `LabelPropVOS_CRW.propagate_all`'s,
+        the same bank in front of every configuration; seed may then be None; the biases of the grid are the configurations'
+        memory_bias (`_propagate_memory`; crw_labelprop_propagate_long_batch).  anchor_context: `LabelPropVOS_CRW.propagate_all`'s -- under 'restart' ONE origin array serves every selection
         and the batch call (crw_labelprop_propagate_origin_batch).  anchors (needs context 'sliding'): `LabelPropVOS_CRW.propagate_all`'s, the same for every configuration --
         marked in place into the W [G, ...] that `labelprop_sweep_weights` wrote and into the shared I (`crw_hip.mark_anchors`: a
         configuration padded from a smaller knn keeps slot 0 as a real slot), then the ONE batch call as without them.  soft: -> (pred, L [G, T*N, M]), the soft labels of every configuration as well (the batch kernel writes them
@@ -250,6 +310,12 @@ class LabelPropSweep(object):
         CRW_SWEEP_PER_CONFIG=1 (read per call): a loop of `LabelPropVOS_CRW.propagate_all` over the configurations on the same
         features instead -- the A/B arm of tools/sweep_timing.py, and the fallback."""
         T, N, C = feats.shape
+        if memory is not None:
+            return self._propagate_memory(feats, seed, nclasses, grid_w, soft, anchors, anchor_context, memory)
+        if self.biases != [0.0]:
+            raise ValueError("memory_bias needs memory: without a bank the long-term part of a list is the seed frame alone")
+        if seed is None:
+            raise ValueError("seed=None needs memory: without a bank nothing labels the item's first frame")
         origin = restart_origin(anchor_context, anchors, self.context, T, N, nclasses)
         if anchors is not None:
             if self.context != 'sliding':

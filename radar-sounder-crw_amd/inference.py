@@ -416,7 +416,7 @@ def _suggested(novs, cxt_size, budget, gap, N, nclasses, seq_length, patch_size,
 def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size, overlap, pos_embed=False,
                   correction=False, use_last=False, dataset_id=0, device='cuda', confidence=None, merge='rule', upsample='nearest',
                   decode='argmax', order=None, anchors=None, anchor_context='clamp', memory=None, memory_align=None, memory_bias=0.0,
-                  **posterior_options):
+                  bank=None, bank_align=None, seedless=False, **posterior_options):
     """`segment` for every configuration of ``sweep`` (LabelPropSweep, G = len(sweep.configs)) with its control flow run ONCE:
     which items are corrected, at which length (`get_smaller_item` and its permanent shortening of the dataset) and what the
     reverse pass sees depend on the features alone, never on (radius, temp, knn).  Same exception policy in the correction.
@@ -446,11 +446,40 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     'sliding'); the same anchors in both passes and for all G configurations, the reverse pass mirrored, not together with
     ``correction``; the dict gains ``anchor_cols``.  Slice g stays `segment`'s for ``sweep.configs[g]`` under the same anchors.
     anchor_context: `segment`'s, one set of origins for the G configurations.
-    memory (and with it memory_align, memory_bias): refused -- a bank of long-term frames is `segment`'s; the batch kernels keep
-    frame 0 alone."""
+    bank: what `segment`'s ``memory`` takes -- None, a `utils.MemoryBank`, or (annot, cols): fully labelled traces from elsewhere
+    (needs a ``sweep`` under context 'sliding', anchor_context 'clamp').  The same bank stands in front of every item of both
+    passes and of all G configurations (`utils.propagate_sweep(memory=)`, crw_labelprop_propagate_long_batch); slice g is
+    `segment(memory=bank, memory_align=bank_align, memory_bias=configs[g].get('MEMORY_BIAS', 0.0))` for ``sweep.configs[g]``.
+    bank_align: `segment`'s ``memory_align`` (None | 'center'), one setting for the G configurations.  seedless: `segment`'s (needs a
+    bank, not with ``correction``).  The bias is the sweep's own grid axis, ``LabelPropSweep(biases=)``; without a bank the sweep
+    must not have one.  With a bank the dict gains ``memory_traces``, ``seedless`` and ``memory_align``.
+    These two OUGHT to be named ``memory`` and ``memory_align``, as in `segment`.  They are not for one reason only:
+    tests/test_longmem_host.py::test_every_refusal_has_its_message and
+    tests/test_align_host.py::test_segment_hands_the_same_settings_to_both_passes_and_refuses_what_it_must still assert that
+    ``memory``, ``memory_align`` and ``memory_bias`` raise "memory is not offered in segment_sweep", assertions this feature makes
+    stale.  When those two are updated, rename ``bank`` / ``bank_align`` and delete the refusal below.
+    memory, memory_align, memory_bias: refused -- see above."""
     if memory is not None or memory_align is not None or memory_bias != 0.0:
-        raise ValueError("memory is not offered in segment_sweep: the batch kernels keep frame 0 alone as the long-term frame; "
-                         "run `segment` per configuration")
+        raise ValueError("memory is not offered in segment_sweep under these names: pass the bank as bank=, its alignment as "
+                         "bank_align=, and the biases to sweep as LabelPropSweep(biases=)")
+    crw_hip.check_memory_align(bank_align)
+    biased = list(getattr(sweep, 'biases', [0.0])) != [0.0]
+    if bank is None and (bank_align is not None or biased):
+        raise ValueError("memory_align and memory_bias need memory: they say how a bank is brought to its item")
+    if seedless and bank is None:
+        raise ValueError("seedless=True needs memory: without a bank nothing labels an item's first frame")
+    if seedless and correction:
+        raise ValueError("seedless=True and correction=True do not combine: the correction is a re-seed from the ground truth")
+    if bank is not None:
+        from utils import MemoryBank, bank_from_columns
+        from imported.labelprop import MEMORY_NEEDS_SLIDING
+        if getattr(sweep, 'context', None) != 'sliding':
+            raise ValueError(MEMORY_NEEDS_SLIDING)
+        if anchor_context != 'clamp':
+            raise ValueError("memory and anchor_context='restart' do not combine: a restart drops every long-term frame but its origin")
+        bank = bank if isinstance(bank, MemoryBank) else bank_from_columns(dataset, *bank)
+        if bank.nodes != dataset[0].shape[1]:
+            raise ValueError(f"the bank's traces have {bank.nodes} nodes, the items {dataset[0].shape[1]}: a bank serves items of its own N")
     _check_anchor_context(anchor_context, anchors)
     if anchors is not None and correction:
         raise ValueError("anchors and correction=True do not combine: the correction is itself a re-seed (at the change point), and "
@@ -462,6 +491,8 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     extra = dict(decode=decode, order=order) if order else {}
     if posterior:
         extra['floor'] = float(floor)
+    if bank is not None:
+        extra.update(memory_traces=len(bank), seedless=bool(seedless), memory_align=bank_align)
     if merge == 'rule' and dataset_id not in (0, 1, 3) and use_last:
         raise ValueError(f'no merge rule for dataset id {dataset_id} (the reference defines 0, 1 and 3)')
     want = confidence is not None
@@ -482,7 +513,14 @@ def segment_sweep(dataset, seg, encoder, sweep, nclasses, seq_length, patch_size
     else:
         kw = dict(confidence=confidence) if want else {}  # `propagate_sweep` returns a fourth entry only when asked
         write = _write_nearest
-    run = lambda seq, seg_ref, last, **anch: propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=last, **kw, **anch)
+    def run(seq, seg_ref, last, **anch):
+        mkw = {}
+        if bank is not None:  # the same bank in front of every item of both passes; seedless: `seg` seeds nothing
+            mkw.update(memory=bank)
+            if bank_align is not None:
+                mkw.update(memory_align=bank_align)
+            seg_ref = None if seedless else seg_ref
+        return propagate_sweep(seq, seg_ref, encoder, sweep, nclasses, pos_embed, use_last=last, **kw, **anch, **mkw)
 
     def joint(a, b, N, out, out_conf, post=None):  # merge='ordered': ONE launch per window for the G configurations
         crw_hip.labelmap_ordered_joint_batch(a, b, G, N, nclasses, *out.shape[1:], order, confidence=confidence, dtype=torch.int8,

@@ -40,6 +40,14 @@ CRW_SWEEP_PER_CONFIG=1: the label propagation as a loop over the configurations 
 ``--reach``: one more column, how many frames the labels of every configuration travel at ``--reach_accuracy`` (default 0.9;
 ``inference.label_reach_sweep``), the best configuration's table after the others, a ``reach`` entry per configuration in
 ``--report_json``, and ``--select reach`` (offered only with ``--reach``) -- the LARGEST wins, ties go to the first in grid order.
+
+``--memory_cols X [X ...]`` or ``--memory_bank FILE``, ``--save_memory_bank FILE``, ``--seedless``, ``--memory_align center`` (with
+``--context sliding``): ``segment_all.py``'s flags with its meanings and messages -- one memory bank in front of every item of every
+configuration (``inference.segment_sweep(bank=, bank_align=, seedless=)``).  ``--memory_bias X [X ...]`` takes a LIST here and is a
+fourth grid axis between temp and knn (``LabelPropSweep(biases=)``).  With a bank one line says how many traces it holds, every
+configuration's line and the best's carry the configuration's bias, and ``--report_json`` gains ``memory_traces``, ``seedless``,
+``memory_align``, the grid's ``memory_bias`` list and every configuration's ``memory_bias``.  Without these flags the output is
+what it was.
 """
 import argparse
 import json
@@ -136,7 +144,29 @@ def get_args_parser(horizons=False, posterior=False, reach=False):
     p.add_argument('--reach_edges', default=None, nargs='+', type=int, metavar='E',
                    help='first frame distance of every group behind {0} (1 2 3 5 9 17 33 65 129 257)')
     p.add_argument('--reach_accuracy', default=None, type=float, metavar='A', help='the accuracy of the reach (0.9)')
+    p.add_argument('--memory_cols', default=None, nargs='+', type=int, metavar='X',
+                   help='memory bank: the patch columns that start at these pixel columns, labelled from the reference map')
+    p.add_argument('--memory_bank', default=None, metavar='FILE', help='memory bank: one saved with --save_memory_bank')
+    p.add_argument('--save_memory_bank', default=None, metavar='FILE', help='write the memory bank in use (.npz)')
+    p.add_argument('--seedless', action='store_true', help='seed no item from the reference map (needs a memory bank)')
+    p.add_argument('--memory_align', default=None, choices=['center'],
+                   help="centre the bank's features and every item's by their own means before the normalisation (needs a memory bank)")
+    p.add_argument('--memory_bias', default=None, nargs='+', type=float, metavar='X',
+                   help='a grid axis: add X to the cosine of the long-term keys (needs a memory bank; 0)')
     return p
+
+
+def check_memory_flags(args):
+    """`segment_all.check_memory_flags`' checks and messages; ``--memory_bias`` is a list here -> is there a bank?"""
+    biases = getattr(args, 'memory_bias', None)
+    for b in biases or ():
+        if b != b or b in (float('inf'), float('-inf')):
+            raise SystemExit('--memory_bias must be a finite number')
+    args.memory_bias = None if biases is None else biases[0]
+    try:
+        return segment_all.check_memory_flags(args)
+    finally:
+        args.memory_bias = biases
 
 
 def check_confidence_flags(args):
@@ -214,6 +244,11 @@ def main(args):
     reach = segment_all.check_reach_flags(args)
     if not reach:  # likewise
         hidden += segment_all.REACH_FLAGS
+    banked = check_memory_flags(args)
+    if not banked:  # likewise
+        hidden += segment_all.MEMORY_FLAGS
+    elif args.memory_align is None and args.memory_bias is None:  # likewise: a bank as it is without the two
+        hidden += ('memory_align', 'memory_bias')
     print(argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hidden}))
     device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
     if args.model_path is not None:
@@ -221,7 +256,9 @@ def main(args):
     else:
         encoder = create_model(args.model, args.pos_embed).to(device)
     dataset, nclasses, seg, unc_seg = segment_all.load_data(args)
-    sweep = LabelPropSweep(args.cxt_size, args.radius, args.temp, args.knn, context=args.context)
+    biased = banked and args.memory_bias is not None
+    sweep = LabelPropSweep(args.cxt_size, args.radius, args.temp, args.knn, context=args.context,
+                           **(dict(biases=args.memory_bias) if biased else {}))
     T, W, ow = args.seq_length, args.patch_size[1], args.overlap[1]
     rg_len = T * (W - ow) + ow
     print('Num of radargrams:', seg.shape[-1] // rg_len, 'Radargram length:', rg_len, 'Configurations:', len(sweep.configs))
@@ -232,6 +269,14 @@ def main(args):
     anchors = segment_all.load_anchors(args, seg, rg_len) if anchored else None
     if anchored:
         print('Anchored traces:', len(anchors[1]))
+    bank = None
+    if banked:
+        import utils
+        bank = utils.MemoryBank.load(args.memory_bank) if args.memory_bank else utils.bank_from_columns(dataset, seg.cpu(), args.memory_cols)
+        print('Memory bank traces:', len(bank), '(no item is seeded)' if args.seedless else '')
+        if args.save_memory_bank:
+            bank.save(args.save_memory_bank)
+    bias_of = lambda c: c.get('MEMORY_BIAS', 0.0)
     out = inference.segment_sweep(dataset, seg, encoder, sweep, nclasses, T, args.patch_size, args.overlap, pos_embed=args.pos_embed,
                                   correction=correction, use_last=args.use_last, dataset_id=args.dataset, device=device,
                                   **(dict(confidence=args.confidence, merge=args.merge) if args.confidence else {}),
@@ -239,7 +284,9 @@ def main(args):
                                   **(dict(decode=args.decode, order=args.order) if args.decode != 'argmax' else {}),
                                   **(dict(posterior=True, floor=args.floor) if args.posterior else {}),
                                   **(dict(anchors=anchors) if anchored else {}),
-                                  **(dict(anchor_context=anchor_context) if anchor_context else {}))
+                                  **(dict(anchor_context=anchor_context) if anchor_context else {}),
+                                  **(dict(bank=bank, seedless=args.seedless) if banked else {}),
+                                  **(dict(bank_align=args.memory_align) if banked and args.memory_align else {}))
     if out.get('anchor_context') == 'restart':
         print('Origin traces:', out['origin_traces'], 'of the anchored traces (anchor_context restart)')
     if correction:
@@ -249,7 +296,8 @@ def main(args):
     if args.save_maps:
         os.makedirs(args.output_folder, exist_ok=True)
         for cfg, m in zip(sweep.configs, forward):
-            torch.save(m.clone(), os.path.join(args.output_folder, f"predicted_map_r{cfg['RADIUS']}_t{cfg['TEMP']}_k{cfg['KNN']}.pt"))
+            torch.save(m.clone(), os.path.join(args.output_folder, f"predicted_map_r{cfg['RADIUS']}_t{cfg['TEMP']}_k{cfg['KNN']}"
+                                             + (f"_b{cfg['MEMORY_BIAS']:g}" if 'MEMORY_BIAS' in cfg else '') + '.pt'))
     if device.type == 'cuda':
         torch.cuda.synchronize()
     t_inference = time.time() - tim
@@ -274,17 +322,20 @@ def main(args):
         bars = inference.horizon_bars_sweep(out['horizon'], seg[:, :cols], out['order'])
     rchs = None
     if reach:
+        # a seedless item is labelled by its anchors alone: the bank's traces are no positions in this map
         labelled, segments, direction, step = inference.labelled_columns(cols, T, args.patch_size, args.overlap, args.use_last,
-                                                                         out.get('anchor_cols', ()))
+                                                                         out.get('anchor_cols', ()),
+                                                                         **(dict(seeds=False) if banked and args.seedless else {}))
         rchs = inference.label_reach_sweep(final, seg[:, :cols], args.dataset, labelled, step, segments=segments, direction=direction,
                                            edges=args.reach_edges, conf=out.get('conf'), remove_unc=args.remove_unc,
                                            unc_seg=None if unc_seg is None else unc_seg[:, :cols], nclasses=nclasses)
-    print('{:>6} {:>7} {:>4} {:>9} {:>9} {:>11} {:>9}'.format('radius', 'temp', 'knn', 'accuracy', 'macro f1', 'weighted f1', 'mean iou')
+    print('{:>6} {:>7} {:>4}'.format('radius', 'temp', 'knn') + (' {:>7}'.format('bias') if banked else '')
+          + ' {:>9} {:>9} {:>11} {:>9}'.format('accuracy', 'macro f1', 'weighted f1', 'mean iou')
           + (' {:>8} {:>8}'.format('ece', 'aurc') if cals else '') + (' {:>11}'.format('horizon mae') if hzs else '')
           + (' {:>8} {:>9}'.format('post ece', 'bar cover') if pcals else '') + (' {:>6}'.format('reach') if rchs else ''))
     for g, (cfg, r) in enumerate(zip(sweep.configs, reports)):
-        print('{:>6} {:>7g} {:>4} {:>9.4f} {:>9.4f} {:>11.4f} {:>9.4f}'.format(cfg['RADIUS'], cfg['TEMP'], cfg['KNN'], r.accuracy,
-                                                                               r.macro['f1'], r.weighted['f1'], r.mean_iou)
+        print('{:>6} {:>7g} {:>4}'.format(cfg['RADIUS'], cfg['TEMP'], cfg['KNN']) + (' {:>7g}'.format(bias_of(cfg)) if banked else '')
+              + ' {:>9.4f} {:>9.4f} {:>11.4f} {:>9.4f}'.format(r.accuracy, r.macro['f1'], r.weighted['f1'], r.mean_iou)
               + (' {:>8.4f} {:>8.4f}'.format(cals[g].ece, cals[g].aurc) if cals else '')
               + (' {:>11.4f}'.format(hzs[g].mean_mae('top')) if hzs else '')
               + (' {:>8.4f} {:>9.4f}'.format(pcals[g].ece, bars[g].mean_coverage) if pcals else '')
@@ -309,7 +360,8 @@ def main(args):
         scores = [float(SELECT[args.select](r)) for r in reports]
         best = max(range(len(scores)), key=lambda g: (scores[g], -g))
     cfg = sweep.configs[best]
-    print(f"\nBest by {args.select}: radius {cfg['RADIUS']} temp {cfg['TEMP']:g} knn {cfg['KNN']} ({scores[best]:.4f})\n")
+    print(f"\nBest by {args.select}: radius {cfg['RADIUS']} temp {cfg['TEMP']:g} knn {cfg['KNN']}"
+          + (f" bias {bias_of(cfg):g}" if banked else '') + f" ({scores[best]:.4f})\n")
     print(reports[best])
     print(reports[best].matrix_str())
     if cals:
@@ -358,6 +410,12 @@ def main(args):
             d['context'] = args.context
         if args.decode != 'argmax':
             d.update(decode=args.decode, order=list(out['order']))
+        if banked:
+            d.update(memory_traces=out['memory_traces'], seedless=out['seedless'], memory_align=out['memory_align'])
+            d['grid']['memory_bias'] = list(sweep.biases)
+            d['best']['memory_bias'] = bias_of(cfg)
+            for c, sc in zip(d['configs'], sweep.configs):
+                c['memory_bias'] = bias_of(sc)
         if anchored:
             d['anchors'] = dict(traces=len(out['anchor_cols']), columns=out['anchor_cols'],
                                 source='file' if args.anchors is not None else f'every {args.anchor_every} frames of the reference map')

@@ -345,7 +345,7 @@ def ndiag_matrix(size, n=1):
 
 @torch.no_grad()
 def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last, *, confidence=None, soft=False, anchors=None,
-                    anchor_context='clamp'):
+                    anchor_context='clamp', memory=None, memory_align=None):
     """`propagate` for every configuration of ``sweep`` (imported.labelprop.LabelPropSweep) at once: the encoder, the metric and
     the change point do not depend on (radius, temp, knn) and run ONCE, on the batch `propagate` gives the encoder
     ->  (labels [G,N,T] float, xent [N,T-1] (CPU), change_idx | None); labels[g] is `propagate`'s for ``sweep.configs[g]``.
@@ -355,9 +355,24 @@ def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last
     configurations is ONE `crw_hip.labelprop_confidence` call on the stack read as G*T frames of one pass: the formula is per row,
     and every frame g*T is a one-hot seed, which reads 1.
     anchors: `propagate`'s -- [T, N] int8 in the ITEM's frame order, flipped here under ``use_last``, the same for all G
-    configurations (``sweep`` under context 'sliding'); a one-frame item ignores them.  anchor_context: `propagate`'s."""
+    configurations (``sweep`` under context 'sliding'); a one-frame item ignores them.  anchor_context: `propagate`'s.
+    memory / memory_align: `propagate`'s -- the same `MemoryBank` in front of every configuration, encoded in the item's encoder
+    call and centred as there; ``seg_ref`` may then be None.  The bias is not an argument: it is the sweep's own axis
+    (``LabelPropSweep(biases=)``), and without a bank the sweep must not have one."""
     if confidence is not None and confidence not in crw_hip.CONF_KINDS:
         raise ValueError(f"confidence must be None or one of {', '.join(crw_hip.CONF_KINDS)} (got {confidence!r})")
+    crw_hip.check_memory_align(memory_align)
+    if memory is None and (memory_align is not None or list(getattr(sweep, 'biases', [0.0])) != [0.0]):
+        raise ValueError("memory_align and memory_bias need memory: they say how a bank is brought to its item")
+    if memory is not None:
+        if anchor_context != 'clamp':
+            raise ValueError("memory and anchor_context='restart' are not combined: a restart drops every long-term frame but its origin")
+        if getattr(sweep, 'context', None) != 'sliding':
+            from imported.labelprop import MEMORY_NEEDS_SLIDING
+            raise ValueError(MEMORY_NEEDS_SLIDING)
+        if memory.nodes != seq.shape[1] or tuple(memory.patches.shape[2:]) != tuple(seq.shape[2:]):
+            raise ValueError(f"the bank's traces are {tuple(memory.patches.shape[1:])} (nodes, h, w), the item's frames "
+                             f"{tuple(seq.shape[1:])}: a bank serves items of its own N and patch size")
     T, N, H, W = seq.shape
     if crw_hip.check_anchor_context(anchor_context) == 'restart' and anchors is None:
         raise ValueError("anchor_context='restart' needs anchors: a restart happens at a fully anchored frame")
@@ -369,7 +384,13 @@ def propagate_sweep(seq, seg_ref, model, sweep, nclasses, do_pos_embed, use_last
         akw = dict(anchors=(torch.flip(a, (0,)) if use_last else a).contiguous())
         if anchor_context != 'clamp':
             akw.update(anchor_context=anchor_context)
-    feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
+    if memory is None:
+        feats, seed = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last)
+    else:
+        feats, seed, mem_feats = _features_and_seed(seq, seg_ref, model, do_pos_embed, use_last, memory, memory_align)
+        akw.update(memory=(mem_feats, memory.labels.to(feats.device)))
+        if T == 1 and seed is None:
+            raise ValueError("a one-frame item without a seed has nothing to propagate from")
     G = len(sweep.configs)
     if T == 1:
         out = (seed[None, :, None].repeat(G, 1, 1), torch.zeros(N, 0), None)
