@@ -192,6 +192,12 @@ SWEEPMEM_SIGNATURES = {
     "crw_labelprop_propagate_long_batch": (_c_int, [_p, _p, _c_sz] + [_c_int] * 8 + [_p, _p, _p]),
 }
 
+# include/crw_hip_guard.h, likewise: the guarded Adam step -- refuse a non-finite gradient, clip by the norm, on the device (optional: `has_guard()`)
+GUARD_SIGNATURES = {
+    "crw_adam_guard_ws_bytes": (_c_sz, [ctypes.c_long]),
+    "crw_adam_step_guarded": (_c_int, [_p, _p, _p, _p, ctypes.c_long, _c_f, _c_f, _c_f, _c_f, _c_int, _c_f, _p, _p, _c_sz, _p]),
+}
+
 # include/crw_hip_routes.h, likewise: the route log -- which selector branch launched (optional: `has_routes()`; host pointers)
 ROUTES_SIGNATURES = {
     "crw_routes_clear": (_c_int, []),
@@ -253,6 +259,9 @@ REACH_ENTRY_POINTS = tuple(REACH_SIGNATURES)
 # likewise: the batched propagation with a bank of long-term frames (`has_sweep_memory()`, `labelprop_propagate_batch(n_long=)`)
 SWEEP_MEMORY_ENTRY_POINTS = tuple(SWEEPMEM_SIGNATURES)
 
+# likewise: the guarded Adam step (`has_guard()`, `adam_step_guarded`)
+GUARD_ENTRY_POINTS = tuple(GUARD_SIGNATURES)
+
 CONTEXTS = ("reference", "sliding")  # which frames the indices of a late frame address
 ANCHOR_CONTEXTS = ("clamp", "restart")  # what a fully labelled anchor trace does to the frames behind it
 
@@ -264,7 +273,8 @@ OPTIONAL_ENTRY_POINTS = {"sweep": SWEEP_ENTRY_POINTS, "confidence": CONFIDENCE_E
                          "posterior": POSTERIOR_ENTRY_POINTS, "posterior_batch": POSTERIOR_BATCH_ENTRY_POINTS,
                          "conv_chain": CONV_CHAIN_ENTRY_POINTS, "anchor_restart": ANCHOR_RESTART_ENTRY_POINTS,
                          "routes": ROUTES_ENTRY_POINTS, "novelty": NOVELTY_ENTRY_POINTS, "long_memory": LONG_MEMORY_ENTRY_POINTS,
-                         "align": ALIGN_ENTRY_POINTS, "reach": REACH_ENTRY_POINTS, "sweep_memory": SWEEP_MEMORY_ENTRY_POINTS}
+                         "align": ALIGN_ENTRY_POINTS, "reach": REACH_ENTRY_POINTS, "sweep_memory": SWEEP_MEMORY_ENTRY_POINTS,
+                         "guard": GUARD_ENTRY_POINTS}
 
 _lib = None
 _present = {}  # group -> the loaded library exports every one of its entry points (filled by lib())
@@ -281,7 +291,8 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         missing = {n for names in OPTIONAL_ENTRY_POINTS.values() for n in names if not hasattr(handle, n)}
         for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES, **RESTART_SIGNATURES, **ROUTES_SIGNATURES,
-                                   **NOVELTY_SIGNATURES, **LONGMEM_SIGNATURES, **ALIGN_SIGNATURES, **REACH_SIGNATURES, **SWEEPMEM_SIGNATURES}.items():
+                                   **NOVELTY_SIGNATURES, **LONGMEM_SIGNATURES, **ALIGN_SIGNATURES, **REACH_SIGNATURES, **SWEEPMEM_SIGNATURES,
+                                   **GUARD_SIGNATURES}.items():
             if name in missing:
                 continue
             fn = getattr(handle, name)
@@ -332,6 +343,7 @@ has_long_memory, _long_memory_lib = _optional("long_memory", "the entry points t
 has_align, _align_lib = _optional("align", "the segment-centred normalisation and the biased long-memory lists")
 has_reach, _reach_lib = _optional("reach", "the grouped confusion matrix's entry points")
 has_sweep_memory, _sweep_memory_lib = _optional("sweep_memory", "the batched propagation that takes n_long long-term frames")
+has_guard, _guard_lib = _optional("guard", "the guarded Adam step's entry points")
 
 MAX_ROUTES = 256  # csrc/crw_common.h
 
@@ -2271,6 +2283,46 @@ def adam_step(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8):
     """One Adam step in place on the flat fp32 buffers p (parameters), m, v with the flat gradient g (torch.optim.Adam defaults)."""
     _check(lib().crw_adam_step(_dev(p, "p"), _dev(g, "g"), _dev(m, "m"), _dev(v, "v"), p.numel(), float(lr), float(beta1),
                                float(beta2), float(eps), int(step), _stream()), "crw_adam_step")
+
+
+# the control block of crw_adam_step_guarded (include/crw_hip_guard.h): 64 bytes of device memory, zeroed once by the caller
+GUARD_CTL_BYTES = 64
+GUARD_CTL_FORMAT = "<qqdfi"  # int64 applied; int64 skipped; double norm; float scale; int32 last_applied; the rest is reserved
+GUARD_CTL_FIELDS = ("applied", "skipped", "norm", "scale", "last_applied")
+
+
+def adam_guard_ws_bytes(n):
+    """bytes of the workspace crw_adam_step_guarded wants for n elements (the per-block fp64 partials and the decision record)"""
+    return _guard_lib().crw_adam_guard_ws_bytes(int(n))
+
+
+def check_max_norm(max_norm):
+    """`max_grad_norm=` -> float (None -> 0.0, no clip); a negative or NaN bound is refused (include/crw_hip_guard.h)"""
+    x = 0.0 if max_norm is None else float(max_norm)
+    if not x >= 0.0:
+        raise ValueError(f"max_grad_norm must be None or a number >= 0 (got {max_norm!r})")
+    return x
+
+
+def guard_ctl_unpack(ctl):
+    """the 64 bytes of a control block (a uint8 tensor anywhere, or bytes) -> {field: value} in GUARD_CTL_FIELDS' order"""
+    import struct
+    raw = bytes(ctl.detach().cpu().contiguous().view(torch.uint8).tolist()) if isinstance(ctl, torch.Tensor) else bytes(ctl)
+    if len(raw) != GUARD_CTL_BYTES:
+        raise ValueError(f"a control block is {GUARD_CTL_BYTES} bytes (got {len(raw)})")
+    return dict(zip(GUARD_CTL_FIELDS, struct.unpack_from(GUARD_CTL_FORMAT, raw)))
+
+
+def adam_step_guarded(p, g, m, v, step, lr, ctl, ws, beta1=0.9, beta2=0.999, eps=1e-8, max_norm=None):
+    """crw_adam_step_guarded (include/crw_hip_guard.h): the Adam step of `adam_step`, refused on the device when g holds a NaN or an
+    infinity and scaled when its norm exceeds max_norm (None / 0: no clip).  ctl: the 64-byte control block (uint8, on the device,
+    zeroed once), ws: at least `adam_guard_ws_bytes(p.numel())` bytes (uint8, on the device).  Nothing is read back."""
+    max_norm = check_max_norm(max_norm)
+    if ctl.numel() != GUARD_CTL_BYTES:
+        raise ValueError(f"ctl must hold {GUARD_CTL_BYTES} bytes (got {ctl.numel()})")
+    _check(_guard_lib().crw_adam_step_guarded(_dev(p, "p"), _dev(g, "g"), _dev(m, "m"), _dev(v, "v"), p.numel(), float(lr), float(beta1),
+                                              float(beta2), float(eps), int(step), max_norm, _dev(ctl, "ctl", torch.uint8),
+                                              _dev(ws, "ws", torch.uint8), ws.numel(), _stream()), "crw_adam_step_guarded")
 
 
 def enc_pack_input_map(x, split):

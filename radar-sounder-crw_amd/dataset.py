@@ -92,6 +92,16 @@ class RGDataset(Dataset):
         patches = block.unfold(0, self.h, self.h - self.oh).unfold(1, self.w, self.w - self.ow)  # [N, Tc, h, w]
         return patches.permute(1, 0, 2, 3).float()
 
+    def finite_items(self):
+        """bool [len(self)], on the radargram's device: item ``i`` is finite when its pixel block -- rows ``[0, pxh)``, columns
+        ``[(w-ow)*i, (w-ow)*i + pxw)`` -- holds no NaN and no infinity (no-data columns, ``log10`` of zero power).  One
+        per-column ``isfinite`` reduction and one prefix sum over the columns, not a pass per item."""
+        bad = (~torch.isfinite(self.T[:self.pxh])).any(dim=0)
+        before = torch.zeros(bad.numel() + 1, dtype=torch.int64, device=bad.device)      # before[c] = bad columns in [0, c)
+        torch.cumsum(bad, 0, out=before[1:])
+        first = torch.arange(len(self), device=bad.device) * (self.w - self.ow)
+        return before[first + self.pxw] == before[first]
+
     def get_smaller_item(self, index, small_length):
         # like the reference this permanently shortens the item length of the dataset
         self.small_pxw = self.pxw = small_length * self.w - self.ow * (small_length - 1)
